@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- fused audio-visual lip-biometric embedding throughput on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -20,10 +20,19 @@ One "step" = one pass of the hot path over one batch of synthetic A+V pairs PER 
 Inputs and weights are synthetic (name-keyed generator, seed 1), already resident in HBM when the
 timed region starts.  Rank 0 prints ONE JSON line.  metric = lip-clips/sec (whole job).
 
+A plain run measures the headline and nothing else: set-up, W warm-up steps, ONE timed region of exactly
+K steps (value, ms_per_step), the outputs if --dump-outputs is given, the line.  --full adds everything
+else this file measures and checks: the in-run PMC passes, three timed regions (value = the median one),
+per-kernel figures (HIP events, in-kernel spans), the H2D-inclusive leg, the other arithmetic mode, the
+BASELINE configurations and entry points (C2..C5, F2, E1..E3), the CPU baseline with parity against it,
+and a scaling run's per-rank self-check; the --no-* options below leave parts of that out.
+--dump-outputs DIR writes what the timed path returned in its last timed step -- the fused [N*B, 1024]
+rows every rank receives -- as DIR/fused_av_embedding.npy (float32; a fixed, seeded row sample above 64 MB).
+
 Arithmetic modes (--precision): "f16x3" (default) evaluates every conv/linear product of fp32
 values as hi*hi + hi*lo + lo*hi on the f16 matrix core with fp32 accumulation (fp32-grade: measured
-~1e-6 vs the CPU reference, bar 1e-4); "f32" is the exact fp32-MFMA path.  Both are timed in one
-run; the other one is reported under "alt_mode".
+~1e-6 vs the CPU reference, bar 1e-4); "f32" is the exact fp32-MFMA path.  With --full both are timed
+in one run; the other one is reported under "alt_mode".
 
 roofline: the path is a dense contraction (MFMA-bound).  `achieved` is for the dominant kernel (the
 implicit-GEMM conv instance that carries most FLOPs): ALGORITHMIC FLOPs (2*M*N*K) of its launches
@@ -61,11 +70,13 @@ LIVE_PMC = None       # {"kernels": pmc.summarise(...), "steps": n, "seconds": s
 def _live_pmc_passes(argv):
     """`roofline.traffic` measured IN THIS RUN: two short rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE: separate passes, as the guide
     prescribes) of this very command, run as CHILD processes NOW -- before this process has touched the GPU -- on 5 + 2 replayed steps
-    each.  Single process only (N = 1 outside a job); --no-pmc skips them; any failure leaves the committed collection
+    each.  Single process only (N = 1 outside a job), --full runs only; --no-pmc skips them; any failure leaves the committed collection
     (profiles/traffic_latest.json, sha-stamped) as the source, and the line says which it was."""
     import shutil
     import subprocess
     import tempfile
+    if "--full" not in argv:
+        return None
     if "--pmc-child" in argv or "--no-pmc" in argv or "--dry-launch" in argv or "--eager" in argv:
         return {"skipped": "disabled for this invocation"}
     # Never from inside a profiler: under `rocprofv3 ... -- python3 bench.py` the tool's preloaded library may already have initialised
@@ -88,7 +99,7 @@ def _live_pmc_passes(argv):
             d = tempfile.mkdtemp(prefix="dlip_pmc_")
             dirs.append(d)
             cmd = [exe, "--pmc", counter, "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__), "--steps", str(steps),
-                   "--warmup", str(warm), "--no-cpu-baseline", "--single-mode", "--no-configs", "--no-kernel-events", "--no-h2d", "--no-spans",
+                   "--warmup", str(warm), "--full", "--no-cpu-baseline", "--single-mode", "--no-configs", "--no-kernel-events", "--no-h2d", "--no-spans",
                    "--pmc-child"] + passthrough
             env = dict(os.environ, TMPDIR="/tmp")
             r = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=180)
@@ -274,6 +285,22 @@ def cpu_baseline(sds, audio_dim, budget_s=12.0, sample=8):
             "kind": "port",
             "sample": f"{iters} passes of the oracle fused A+V embed on {sample} clips [{sample},1,29,88,88] + "
                       f"[{sample},{audio_dim},300] (torch-CPU fp32, {best_n} of {cores} usable cores, {el:.1f}s)"}, ref, xv, xa
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array as path/<name>.npy in float32.  Above DUMP_LIMIT_BYTES in all, every array keeps a fixed, seeded
+    sample of its rows (sorted, the same for the same shapes), so that two builds run with the same arguments compare row for row."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.size * 4 for a in arrays.values())
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, int(a.shape[0] * DUMP_LIMIT_BYTES // total))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def _timed_replay(run, steps, warmup, sync):
@@ -777,8 +804,10 @@ def dry_launch(args, world, rank):
     return 0
 
 
-def main():
-    ap = argparse.ArgumentParser()
+def parse_args(argv=None):
+    """The command line -> args, a plain run's choices applied.  No abbreviated options: whether the PMC passes at the top of this
+    file run is decided from the literal spellings in argv, and every other decision has to agree with it."""
+    ap = argparse.ArgumentParser(allow_abbrev=False)
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
@@ -786,6 +815,10 @@ def main():
     ap.add_argument("--audio-dim", type=int, default=80, help="mel bins F of the [B,1,F,300] audio input")
     ap.add_argument("--precision", default="f16x3", choices=["f32", "f16x3"],
                     help="implicit-GEMM arithmetic: exact fp32 MFMA, or split fp16 pairs (3 f16 MFMAs per product)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline (see the top of this file); a plain run times K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the fused rows of the last timed step as DIR/fused_av_embedding.npy (float32)")
     ap.add_argument("--single-mode", action="store_true", help="do not also time the other arithmetic mode")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--audio-stream", action="store_true",
@@ -816,7 +849,23 @@ def main():
     ap.add_argument("--dry-fail-rank", type=int, default=-1, help="with --dry-launch: this rank exits 3 (tests return-code propagation)")
     ap.add_argument("--dry-hang-rank", type=int, default=-1, help="with --dry-launch --dp-leg: this rank never comes back from the last leg "
                     "(tests the watchdog: the line is printed without the leg, every rank ends with code 0)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.dry_launch and args.dump_outputs:
+        ap.error("--dump-outputs: a --dry-launch computes nothing to write")
+    if not args.full:
+        # a plain run: the headline alone (the PMC passes at the top of this file are --full only as well)
+        args.single_mode = args.no_cpu_baseline = args.no_configs = args.no_entry_points = args.no_kernel_events = True
+        args.spans = args.h2d = False
+    return args
+
+
+def timed_regions(args):
+    """Timed regions of exactly K steps each: one in a plain run (and --eager); REGIONS with --full, the line reporting the median."""
+    return REGIONS if (args.full and not args.eager) else 1
+
+
+def main():
+    args = parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -925,8 +974,9 @@ def main():
             # line reports the MEDIAN region (value, ms_per_step, the in-kernel spans: all of that one region) with the fastest and
             # slowest beside it (value_min / value_max, roofline.frac_regions): the boxes of this pool differ by +-4-7 %, and within one
             # box the chip's clock moves with temperature -- one sample said little (BENCH r02 -> r03 -> r04: 15 951 / 15 083 / 16 072).
-            n_regions = 1 if args.eager else REGIONS
+            n_regions = timed_regions(args)
             regions = []
+            last_out = None
             for _r in range(n_regions):
                 if plan is not None and args.spans:
                     plan.span_summary()             # reset: only this region's replays count
@@ -936,10 +986,12 @@ def main():
                 t0 = time.perf_counter()
                 ev0.record()
                 for _ in range(args.steps):
-                    run_step()
+                    out = run_step()
                 ev1.record()
                 sync_all()
                 el = time.perf_counter() - t0
+                if args.dump_outputs and _r == n_regions - 1:
+                    last_out = out.detach().float().cpu().numpy()      # the last timed step's rows (a replay overwrites them)
                 # what the REPLAYED launches of the region measured about themselves (in-kernel 100 MHz clock, first workgroup
                 # in -> last workgroup out, per launch; dlip_span_scope_*)
                 rep = plan.span_summary() if (plan is not None and args.spans) else None
@@ -958,7 +1010,7 @@ def main():
             value = world * B * args.steps / elapsed
             ranks = None
             n1_alone = None
-            if dist_on:
+            if dist_on and args.full:
                 # self-check of a scaling run: what every rank saw (RCCL's own world size, its wall time over the same K
                 # steps, the all-gather of [B,1024] rows timed on its own)
                 fused_probe = torch.zeros((B, 1024), device=device)
@@ -1106,7 +1158,7 @@ def main():
                   "value_regions": [round(v, 2) for v in region_values],
                   "step_frac_regions": [round(v / world * GFLOP_PER_FUSED_CLIP / 1e3 / peak, 4) for v in region_values],
                   "dtype": DTYPE_NAME[precision], "dtype_note": DTYPE_NOTE[precision], "gpu_ms_per_step_hip_events": round(gpu_ms / args.steps, 4),
-                  "roofline": roof, "ranks": ranks, "n1_alone": n1_alone, "h2d": h2d, "peak": peak}
+                  "roofline": roof, "ranks": ranks, "n1_alone": n1_alone, "h2d": h2d, "peak": peak, "last_out": last_out}
         return fields, video, audio, sds
 
     def parity(precision, video, audio, ref, cxv, cxa):
@@ -1120,6 +1172,8 @@ def main():
                 "tolerance": 1e-4}
 
     main_fields, video, audio, sds = measure(args.precision)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"fused_av_embedding": main_fields.pop("last_out")})
     configs = None
     if rank == 0 and not args.no_configs:
         configs = extra_configs(args, device, video, audio, xv, xa, main_fields["peak"], StepPlan, {"pending": True} if dist_on else None)

@@ -35,7 +35,7 @@ def test_dist_api_on_rccl_one_rank():
 
 
 def test_bench_scaling_protocol_on_rccl_one_rank():
-    rc, js, lines = _run("bench.py", ["--gpus", "1", "--steps", "5", "--warmup", "2", "--no-configs", "--single-mode", "--no-h2d"])
+    rc, js, lines = _run("bench.py", ["--gpus", "1", "--steps", "5", "--warmup", "2", "--full", "--no-configs", "--single-mode", "--no-h2d"])
     assert rc == 0, "".join(lines)[-2000:]
     assert len(js) == 1
     r = js[0]
@@ -50,7 +50,7 @@ def test_bench_dp_training_leg_on_rccl_one_rank(monkeypatch):
     all-reduced INSIDE its recorded step on the capture group) as a one-rank job, with the first-replay verification forced on: the
     line says the recorded step ran, was checked against an eager step from the same state, and what the check measured."""
     monkeypatch.setenv("DLIP_VERIFY_GRAPH", "1")
-    rc, js, lines = _run("bench.py", ["--gpus", "1", "--steps", "5", "--warmup", "2", "--no-configs", "--single-mode", "--no-h2d", "--dp-leg"])
+    rc, js, lines = _run("bench.py", ["--gpus", "1", "--steps", "5", "--warmup", "2", "--full", "--no-configs", "--single-mode", "--no-h2d", "--dp-leg"])
     assert rc == 0, "".join(lines)[-2000:]
     c5 = js[-1]["configs"]["C5_fusion_train_step"]
     assert "error" not in c5, c5
@@ -62,7 +62,7 @@ def test_bench_watchdog_prints_the_line_when_the_dp_leg_hangs(monkeypatch):
     """The DP training leg runs LAST and under a watchdog: a rank that hangs in it (here: by a test hook) must not cost the scaling
     record -- after --dp-leg-timeout seconds the line is printed as it stands, with the leg marked, and the job ends with code 0."""
     monkeypatch.setenv("DLIP_BENCH_DP_HANG", "1")
-    rc, js, lines = _run("bench.py", ["--gpus", "1", "--steps", "5", "--warmup", "2", "--no-configs", "--single-mode", "--no-h2d", "--dp-leg",
+    rc, js, lines = _run("bench.py", ["--gpus", "1", "--steps", "5", "--warmup", "2", "--full", "--no-configs", "--single-mode", "--no-h2d", "--dp-leg",
                                       "--dp-leg-timeout", "5"])
     assert rc == 0, "".join(lines)[-2000:]
     assert len(js) == 1 and js[0]["value"] > 1000

@@ -10,7 +10,7 @@ for i in 1 2 3; do
 done
 for i in 1 2; do
   for v in "--dbg 9=0" ""; do
-    python3 $R/bench.py --no-cpu-baseline --single-mode $v 2>/dev/null | python3 -c "
+    python3 $R/bench.py --full --no-cpu-baseline --single-mode $v 2>/dev/null | python3 -c "
 import json, sys
 b = json.loads(sys.stdin.read().strip().splitlines()[-1]); c = b['configs']['C3_audio_embed']
 print('C3 [$v]:', c['value'], c['ms_per_step'], c['step_frac'], c['dominant_kernel'], 'headline', b['value'], b['roofline']['frac'], 'F2', b['configs']['F2_train_video_step'].get('value'), b['configs']['F2_train_audio_step'].get('value'))"

@@ -7,7 +7,7 @@ for i in 1 2 3; do for L in A B; do
 done; done
 for L in A B; do
   if [ $L = A ]; then export DLIP_LIB_PATH=$R/deeplip_amd/lib/libdeeplip_hip_A.so; else unset DLIP_LIB_PATH; fi
-  python3 $R/bench.py --no-cpu-baseline --single-mode --no-configs 2>/dev/null | python3 -c "
+  python3 $R/bench.py --full --no-cpu-baseline --single-mode --no-configs 2>/dev/null | python3 -c "
 import json,sys
 b=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('lib $L headline', b['value'], b['roofline']['frac'], b['roofline']['kernels']['conv_rows_f16x3_kernel<160,256>'])"
 done
