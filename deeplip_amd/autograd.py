@@ -315,7 +315,7 @@ def _bn_rows_bwd_sums(dy2, x2, gamma, beta, mean, invstd, slope, act_first, ms=N
     dg = torch.empty_like(mean)
     db = torch.empty_like(mean)
     lift = torch.empty((LIFT_WORDS,), device=x2.device, dtype=torch.float32)
-    parts = torch.empty((2 * ((C_ + 63) // 64) * int(lib().dlip_bn_rows_chunks(M)),), device=x2.device, dtype=torch.float32)
+    parts = torch.empty((2 * C_ * (int(lib().dlip_bn_rows_chunks(M)) + 1),), device=x2.device, dtype=torch.float32)   # (per part and channel; ABI 50)
     check(lib().dlip_bn_rows_train_bwd_sums_f32(ptr(dy2), ptr(x2), ptr(gamma), ptr(beta), ptr(mean), ptr(invstd), ptr(dg), ptr(db),
                                                 ptr(_ws(M, C_, x2.device)), ptr(parts), M, C_, slope, int(act_first), ptr(lift), ptr(ms_c),
                                                 int(ms_T), stream_handle()), "dlip_bn_rows_train_bwd_sums_f32")

@@ -116,7 +116,8 @@ struct ColFin {
   float* running_var;
   long long* nbt;                    // MODE 0 (nullable): num_batches_tracked += 1
   float momentum, eps;
-  unsigned* amax_parts = nullptr;    // MODE 1 (nullable): per workgroup (max |g|, max |xhat|) as bit patterns, 2 words each (dlip_bn_rows_train_bwd_sums_f32)
+  unsigned* amax_parts = nullptr;    // MODE 1 (nullable): per (part, channel) (max |g|, max |xhat|) as bit patterns, 2 words each, then the
+                                     // same per channel over all parts (the last workgroup of its block writes those; dlip_bn_rows_train_bwd_sums_f32)
   MsSrc ms;                          // MODE 1, act_first == 0: dy formed on load from a pooled gradient (dlip_bn_rows_train_bwd_ms_f32)
 };
 
@@ -168,7 +169,21 @@ __device__ __forceinline__ void col_finish(double* part, int parts, int M, int C
   const int col = threadIdx.x & 63, grp = threadIdx.x >> 6;
   const int cc = c0 + col;
   double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+  float gm = 0.f, hm = 0.f;                          // MODE 1 with amax_parts: the channel's max |g|, max |xhat| over the parts
   if (cc < C) {
+    if (MODE == 1 && fin.amax_parts != nullptr) {   // (four loads in flight, as the sums below)
+      typedef unsigned u2 __attribute__((ext_vector_type(2)));
+      const u2* q = reinterpret_cast<const u2*>(fin.amax_parts) + cc;
+      int i = grp;
+      for (; i + 12 < parts; i += 16) {
+        u2 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = q[(size_t)(i + 4 * u) * C];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { gm = fmaxf(gm, __uint_as_float(v[u][0])); hm = fmaxf(hm, __uint_as_float(v[u][1])); }
+      }
+      for (; i < parts; i += 4) { const u2 v = q[(size_t)i * C]; gm = fmaxf(gm, __uint_as_float(v[0])); hm = fmaxf(hm, __uint_as_float(v[1])); }
+    }
     typedef double d2 __attribute__((ext_vector_type(2)));
     const double* pa = part + (long long)cc * 2;
     const double* pb = pa + (long long)parts * C * 2;
@@ -192,8 +207,16 @@ __device__ __forceinline__ void col_finish(double* part, int parts, int M, int C
   __syncthreads();                                   // (red is free: every thread passed last_arrival's barriers)
   red[grp][col][0] = a0; red[grp][col][1] = a1;
   if (MODE == 3) red[grp][col][2] = a2;
+  if (MODE == 1) { red[4 + grp][col][0] = gm; red[4 + grp][col][1] = hm; }
   __syncthreads();
   if (grp != 0 || cc >= C) return;
+  if (MODE == 1 && fin.amax_parts != nullptr) {
+    float g = 0.f, h = 0.f;
+#pragma unroll
+    for (int i = 4; i < 8; ++i) { g = fmaxf(g, (float)red[i][col][0]); h = fmaxf(h, (float)red[i][col][1]); }
+    unsigned* q = fin.amax_parts + ((size_t)parts * C + cc) * 2;
+    q[0] = __float_as_uint(g); q[1] = __float_as_uint(h);
+  }
   double s = 0.0, q = 0.0, t = 0.0;
 #pragma unroll
   for (int i = 0; i < 4; ++i) { s += red[i][col][0]; q += red[i][col][1]; if (MODE == 3) t += red[i][col][2]; }
@@ -219,7 +242,8 @@ __global__ __launch_bounds__(256) void col_partial_kernel(const float* __restric
   const int c = c0 + lx * 4;
   const int r0 = chunk * rows_per_part, r1 = min(M, r0 + rows_per_part);
   double s0[4] = {0, 0, 0, 0}, s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
-  float gmax = 0.f, hmax = 0.f;      // MODE 1: the largest |g| and |xhat| this lane saw (fin.amax_parts: the bound behind the fused backward's lift)
+  float gmax[4] = {0.f, 0.f, 0.f, 0.f}, hmax[4] = {0.f, 0.f, 0.f, 0.f};   // MODE 1: the largest |g| and |xhat| per channel this lane saw
+                                                                             // (fin.amax_parts: the bound behind the fused backward's lift)
   if (c < C) {   // C % 4 == 0
     f32x4 mu = {0, 0, 0, 0}, is = {0, 0, 0, 0}, ga = {0, 0, 0, 0}, be = {0, 0, 0, 0}, sl = {0, 0, 0, 0};
     if (MODE == 1 || MODE == 3) {
@@ -248,7 +272,7 @@ __global__ __launch_bounds__(256) void col_partial_kernel(const float* __restric
           float g = gv[k];
           if (!act_first) g *= (xh * ga[k] + be[k]) >= 0.f ? 1.f : slope;
           s0[k] += (double)g; s1[k] += (double)g * (double)xh;
-          gmax = fmaxf(gmax, fabsf(g)); hmax = fmaxf(hmax, fabsf(xh));
+          gmax[k] = fmaxf(gmax[k], fabsf(g)); hmax[k] = fmaxf(hmax[k], fabsf(xh));
         }
       } else if (MODE == 3) {
 #pragma unroll
@@ -306,45 +330,78 @@ __global__ __launch_bounds__(256) void col_partial_kernel(const float* __restric
       publish(p2, a2); publish(p2 + 1, 0.0);
     }
   }
-  if (MODE == 1 && fin.amax_parts != nullptr) {       // (workgroup-uniform)
-    __shared__ float mx[4][2];
+  if (MODE == 1 && fin.amax_parts != nullptr) {       // (workgroup-uniform) per channel: the four row groups of a wave by shuffles, then the waves
+    __shared__ float mx[4][64][2];
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { gmax = fmaxf(gmax, __shfl_xor(gmax, off)); hmax = fmaxf(hmax, __shfl_xor(hmax, off)); }
-    if ((threadIdx.x & 63) == 0) { mx[threadIdx.x >> 6][0] = gmax; mx[threadIdx.x >> 6][1] = hmax; }
+    for (int k = 0; k < 4; ++k) {
+#pragma unroll
+      for (int off = 16; off < 64; off <<= 1) { gmax[k] = fmaxf(gmax[k], __shfl_xor(gmax[k], off)); hmax[k] = fmaxf(hmax[k], __shfl_xor(hmax[k], off)); }
+    }
+    if ((threadIdx.x & 63) < 16) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) { mx[threadIdx.x >> 6][lx * 4 + k][0] = gmax[k]; mx[threadIdx.x >> 6][lx * 4 + k][1] = hmax[k]; }
+    }
     __syncthreads();
-    if (threadIdx.x < 2) {
-      float m = fmaxf(fmaxf(mx[0][threadIdx.x], mx[1][threadIdx.x]), fmaxf(mx[2][threadIdx.x], mx[3][threadIdx.x]));
+    if (threadIdx.x < 128 && c0 + (int)(threadIdx.x & 63) < C) {
+      const int cl = threadIdx.x & 63, w = threadIdx.x >> 6;
+      float m = fmaxf(fmaxf(mx[0][cl][w], mx[1][cl][w]), fmaxf(mx[2][cl][w], mx[3][cl][w]));
       if (!(m == m)) m = 3.4e38f;
-      publish(fin.amax_parts + 2 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x) + threadIdx.x, __float_as_uint(m));
+      publish(fin.amax_parts + ((size_t)chunk * C + c0 + cl) * 2 + w, __float_as_uint(m));
     }
   }
   col_finish<MODE>(part, parts, M, C, c0, fin, red);
 }
 
-// The lift of a BatchNorm backward's dx WITHOUT dx: |dx| = |gamma invstd (g - mean(g) - xhat mean(g xhat))| <= gamma invstd max|g| (2 + max|xhat|)
-// (|mean(g xhat)| <= sqrt(mean g^2) sqrt(mean xhat^2) <= max|g|: the batch statistics make mean xhat^2 = 1).  parts: n pairs
-// (max |g|, max |xhat|) from col_partial_kernel<1>.  out: a DLIP_LIFT_WORDS buffer as pow2_finalize_parts writes it, the exponent chosen
-// so that the BOUND sits at `target`: the true maximum then lies up to (2 + max|xhat|) -- an order of magnitude -- below it, well inside
-// the split format (a power-of-two lift is exact: another exponent, the same gradients).
-__global__ __launch_bounds__(256) void bn_bwd_lift_bound_kernel(const unsigned* __restrict__ parts, int n, const float* __restrict__ gamma,
-                                                                const float* __restrict__ invstd, int C, float* __restrict__ out, float target) {
-  __shared__ float red[4][3];
-  float g = 0.f, h = 0.f, gi = 0.f;
-  for (int i = threadIdx.x; i < n; i += 256) { g = fmaxf(g, __uint_as_float(parts[2 * i])); h = fmaxf(h, __uint_as_float(parts[2 * i + 1])); }
-  for (int c = threadIdx.x; c < C; c += 256) gi = fmaxf(gi, fabsf(gamma[c] * invstd[c]));
+// The lift of a BatchNorm backward's dx WITHOUT dx.  Per channel, dx = gamma invstd (g - dbeta / M - xhat dgamma / M) (times the activation's
+// slope behind it when act_first: `post` = max(1, |slope|)), so |dx_c| <= |gamma_c invstd_c| (G_c + |dbeta_c| / M + H_c |dgamma_c| / M) with
+// G_c, H_c the channel's max |g|, max |xhat| -- the triangle bound, taken per channel before the max over channels: maxima of the three
+// factors taken over all channels on their own paired a dead channel's invstd (1 / sqrt(eps)) with another channel's g and an outlier row's
+// xhat and put the bound up to 2^18 above the true max|dx| (tests/test_bn_conditioning_gpu.py).  gh: [C] pairs (G_c, H_c) as bit patterns
+// (col_finish / amax_chan_kernel); dgamma / dbeta finished on this stream.  out: a DLIP_LIFT_WORDS buffer as pow2_finalize_parts writes
+// it, the exponent chosen so that the BOUND sits in (target / 2, target] (a power-of-two lift is exact: another exponent, the same
+// gradients; the bound is raised by 2^-10 against the fp32 rounding of its own terms and of dx).
+__global__ __launch_bounds__(256) void bn_bwd_lift_bound_kernel(const unsigned* __restrict__ gh, const float* __restrict__ gamma,
+                                                                const float* __restrict__ invstd, const float* __restrict__ dgamma,
+                                                                const float* __restrict__ dbeta, int M, int C, float post,
+                                                                float* __restrict__ out, float target) {
+  __shared__ float red[4];
+  float b = 0.f;
+  const float inv_m = 1.f / (float)M;
+  for (int c = threadIdx.x; c < C; c += 256) {
+    const float G = __uint_as_float(gh[2 * c]), H = __uint_as_float(gh[2 * c + 1]);
+    float bc = fabsf(gamma[c] * invstd[c]) * (G + fabsf(dbeta[c]) * inv_m + H * (fabsf(dgamma[c]) * inv_m));
+    if (!(bc == bc)) bc = 3.4e38f;
+    b = fmaxf(b, bc);
+  }
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) { g = fmaxf(g, __shfl_xor(g, off)); h = fmaxf(h, __shfl_xor(h, off)); gi = fmaxf(gi, __shfl_xor(gi, off)); }
-  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = g; red[threadIdx.x >> 6][1] = h; red[threadIdx.x >> 6][2] = gi; }
+  for (int off = 32; off > 0; off >>= 1) b = fmaxf(b, __shfl_xor(b, off));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = b;
   __syncthreads();
-  g = fmaxf(fmaxf(red[0][0], red[1][0]), fmaxf(red[2][0], red[3][0]));
-  h = fmaxf(fmaxf(red[0][1], red[1][1]), fmaxf(red[2][1], red[3][1]));
-  gi = fmaxf(fmaxf(red[0][2], red[1][2]), fmaxf(red[2][2], red[3][2]));
-  const float bound = gi * g * (2.f + h);
+  const float bound = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])) * post * (1.f + 0x1p-10f);
   float s = 1.f;
   if (bound > 0.f && bound < 3.0e38f) s = exp2f(floorf(log2f(target / bound)));
   if (!(s > 0.f) || s > 1.0e30f) s = 1.0e30f;
   if (threadIdx.x == 0) { out[0] = s; out[1] = 1.f / s; }
   for (int i = threadIdx.x; i < DLIP_LIFT_BCAST; i += 256) out[2 + i] = 1.f / s;
+}
+
+// (no ticket words: the separate finalize launches) the per-channel maxima over the parts that col_finish forms otherwise: amax_parts
+// [parts][C] pairs -> the [C] pairs behind them.
+__global__ __launch_bounds__(256) void amax_chan_kernel(unsigned* __restrict__ amax_parts, int C, int parts) {
+  __shared__ float red[4][64][2];
+  const int col = threadIdx.x & 63, grp = threadIdx.x >> 6, c = blockIdx.x * 64 + col;
+  float g = 0.f, h = 0.f;
+  if (c < C)
+    for (int i = grp; i < parts; i += 4) {
+      g = fmaxf(g, __uint_as_float(amax_parts[((size_t)i * C + c) * 2])); h = fmaxf(h, __uint_as_float(amax_parts[((size_t)i * C + c) * 2 + 1]));
+    }
+  red[grp][col][0] = g; red[grp][col][1] = h;
+  __syncthreads();
+  if (grp != 0 || c >= C) return;
+  g = fmaxf(fmaxf(red[0][col][0], red[1][col][0]), fmaxf(red[2][col][0], red[3][col][0]));
+  h = fmaxf(fmaxf(red[0][col][1], red[1][col][1]), fmaxf(red[2][col][1], red[3][col][1]));
+  amax_parts[((size_t)parts * C + c) * 2] = __float_as_uint(g);
+  amax_parts[((size_t)parts * C + c) * 2 + 1] = __float_as_uint(h);
 }
 
 // The BatchNorm + PReLU backward sums (col_partial_kernel<3>) BEHIND A MAX-POOL, taken over the POOLED rows: the gradient behind
@@ -1495,9 +1552,13 @@ extern "C" int dlip_bn_rows_train_bwd_sums_f32(const float* dy, const float* x, 
   if (ms_coef != nullptr) { fin.ms.coef = ms_coef; fin.ms.T = ms_T; fin.ms.div_T = dlip_fastdiv((uint32_t)ms_T); }
   hipLaunchKernelGGL(col_partial_kernel<1>, dim3((C + 63) / 64, chunks), dim3(256), 0, st, x, dy, save_mean, save_invstd, gamma, beta, workspace, M,
                      C, slope, act_first, nullptr, rpp, fin);
-  if (!tickets) hipLaunchKernelGGL(col_finalize_kernel, dim3((C + 15) / 16), dim3(256), 0, st, workspace, dbeta, dgamma, C, chunks);
-  hipLaunchKernelGGL(bn_bwd_lift_bound_kernel, dim3(1), dim3(256), 0, st, reinterpret_cast<const unsigned*>(amax_parts), ((C + 63) / 64) * chunks,
-                     gamma, save_invstd, C, dx_lift2, 1024.0f);
+  if (!tickets) {
+    hipLaunchKernelGGL(col_finalize_kernel, dim3((C + 15) / 16), dim3(256), 0, st, workspace, dbeta, dgamma, C, chunks);
+    hipLaunchKernelGGL(amax_chan_kernel, dim3((C + 63) / 64), dim3(256), 0, st, fin.amax_parts, C, chunks);
+  }
+  const float post = act_first ? fmaxf(1.f, fabsf(slope)) : 1.f;     // (act_first: dz = lrelu'(z) dx of the activated value)
+  hipLaunchKernelGGL(bn_bwd_lift_bound_kernel, dim3(1), dim3(256), 0, st, fin.amax_parts + (size_t)2 * C * chunks, gamma, save_invstd, dgamma,
+                     dbeta, M, C, post, dx_lift2, 1024.0f);
   return dlip_launch_status();
 }
 

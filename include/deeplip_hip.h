@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define DLIP_ABI_VERSION 49
+#define DLIP_ABI_VERSION 50
 #define DLIP_LIFT_WORDS 4098   /* a gradient's power-of-two lift: (2^e, 2^-e), then 2^-e repeated 2048 times (the post_scale vector of
                                   the convolution that consumes the lifted gradient); while it is formed the words behind the pair
                                   hold one maximum per workgroup of the producing pass */
@@ -665,8 +665,9 @@ int dlip_wgrad_chwn_bn_f32(const float* x, float* out, int64_t N, int32_t H, int
                            float* nhwc_split_out, dlip_stream_t stream);
 /* (ABI 47) The BACKWARD of a train-mode BatchNorm (+ LeakyReLU) applied ON LOAD, in two parts: (1) dlip_bn_rows_train_bwd_sums_f32 = the first
  * half of dlip_bn_rows_train_bwd_f32 -- dgamma, dbeta -- plus the power-of-two lift of a dx that is never written: from the largest |g| and
- * |xhat| the sums pass sees (amax_parts: 2 * ceil(C / 64) * dlip_bn_rows_chunks(M) floats of scratch) and max gamma invstd, the bound
- * |dx| <= gamma invstd max|g| (2 + max|xhat|) is put at 1024 (a lift is exact: another exponent, the same gradients); (2) the two operand
+ * |xhat| the sums pass sees PER CHANNEL (ABI 50; amax_parts: 2 * C * (dlip_bn_rows_chunks(M) + 1) floats of scratch) and the finished sums,
+ * the bound |dx| <= max_c |gamma_c invstd_c| (max|g_c| + |dbeta_c| / M + max|xhat_c| |dgamma_c| / M) is put at 1024 (a lift is exact: another
+ * exponent, the same gradients; ABI 47 - 49 took the three maxima over all channels apart and could sit 2^18 above max|dx|); (2) the two operand
  * producers read dy and z and form dx = gamma invstd (g - dbeta / M - xhat dgamma / M) per loaded value (the apply pass's expression, the
  * same bits), times lift[0], straight into the weight gradient's image and the data gradient's split operand (nhwc_split_out, nullable).
  * The convolution in front of a BatchNorm (tdnn.py:35-43 under loss.backward(), train_audio.py:189-191) needs the BatchNorm's input
