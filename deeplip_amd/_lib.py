@@ -13,7 +13,7 @@ import torch  # must be imported first: the library binds to the HIP runtime tor
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DLIP_LIB_PATH") or os.path.join(_PKG, "lib", "libdeeplip_hip.so")  # env override: A/B builds
-ABI_VERSION = 50
+ABI_VERSION = 51
 LIFT_WORDS = 4098
 LIFT_BCAST = 2048
 
@@ -164,6 +164,9 @@ SIGNATURES = {
     "dlip_margin_ce_bwd_f32": [c_f, c_f, c_f, c_i32, c_i32, C.c_float, C.c_float, C.c_float, c_f, c_stream],
     "dlip_l2_normalize_bwd_f32": [c_f, c_f, c_f, c_i32, c_i32, C.c_float, c_stream],
     "dlip_gemm_small_f32": [c_f, c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_i32, c_stream],
+    "dlip_shuffle_stem24_f32": [c_f, c_f, c_f, c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_stream],
+    "dlip_shuffle_dwpw_f32": [c_f, c_f, c_f, c_f, c_f, c_f, c_f] + [c_i32] * 12 + [c_stream],
+    "dlip_avgpool3_nhwc_f32": [c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_stream],
 }
 
 

@@ -367,6 +367,85 @@ def stem3d_pool(x_bthw: Tensor, w_img: Tensor, bias: Tensor, slope: Optional[Ten
     return y
 
 
+def shuffle_stem24(x_bthw: Tensor, w_248x32: Tensor, bias: Tensor, slope: Optional[Tensor]) -> Tensor:
+    """x [B,T,H,W] -> [(B*T), H/2, W/2, 24]: the ShuffleNet lip-clip stem, Conv3d(1->24, 5x7x7) + folded BN + PReLU/ReLU in exact
+    fp32 (dlip_shuffle_stem24_f32; weights of deeplip_amd.shufflenet.pack_stem24)."""
+    for t, n in ((x_bthw, "x"), (w_248x32, "w"), (bias, "bias"), (slope, "slope")):
+        _req(t, n)
+    B, T, H, W = x_bthw.shape
+    if tuple(w_248x32.shape) != (248, 32) or bias.numel() != 24 or (slope is not None and slope.numel() != 24):
+        raise ValueError("shuffle_stem24: weights [248, 32], bias and slope [24]")
+    y = _empty((B * T, H // 2, W // 2, 24), x_bthw.device)
+    hook = LAUNCH_HOOK
+    if hook is not None:
+        tok = hook.begin("shuffle_stem24_f32_kernel", 2.0 * B * T * (H // 2) * (W // 2) * 24 * 245)
+    check(lib().dlip_shuffle_stem24_f32(ptr(x_bthw), ptr(w_248x32), ptr(bias), ptr(slope), ptr(y), B, T, H, W, stream_handle()),
+          "dlip_shuffle_stem24_f32")
+    if hook is not None:
+        hook.end(tok)
+    return y
+
+
+def shuffle_dwpw(x: Tensor, w: Tensor, bias: Tensor, *, dw_w: Optional[Tensor] = None, dw_b: Optional[Tensor] = None,
+                 stride: int = 1, in_channels: Optional[int] = None, in_channel_offset: int = 0, out: Optional[Tensor] = None,
+                 hp: int = 0, par: int = 0, passthrough: Optional[Tensor] = None) -> Tensor:
+    """ReLU(w^T A + bias) per pixel (dlip_shuffle_dwpw_f32), A = the channel slice [in_channel_offset : +in_channels] of x
+    [N,H,W,Cx] (NHWC) or, with ``dw_w`` [9, Cin] / ``dw_b`` [Cin], its depthwise 3x3 (pad 1, ``stride``) computed on load.
+    ``w`` [Cp, Kp] k-major (Cp = Cin rounded up to 32, Kp a multiple of 64), ``bias`` [K].
+
+    ``hp`` = 0: y [N,Ho,Wo,K] (or channels [0, K) of ``out``).  ``hp`` > 0: output channel j lands at logical channel 2j + ``par``
+    of a 2K-channel InvertedResidual output stored as two halves padded to ``hp`` channels (``out`` [N,Ho,Wo,>= 2hp]:
+    deeplip_amd.shufflenet.phys_map); ``par`` = 1 also zeroes the padding channels.  ``passthrough`` [N,H,W,*] (stride 1):
+    its channels [0, K) -- a unit's x1 -- go to the other parity in the same launch."""
+    for t, n in ((x, "x"), (w, "w"), (bias, "bias"), (dw_w, "dw_w"), (dw_b, "dw_b"), (out, "out"), (passthrough, "passthrough")):
+        _req(t, n)
+    N, H, W, Cx = x.shape
+    Cin = Cx - in_channel_offset if in_channels is None else in_channels
+    K = bias.numel()
+    Cp, Kp = w.shape
+    if in_channel_offset + Cin > Cx or Cin % 4 or Cx % 4 or in_channel_offset % 4:
+        raise ValueError(f"shuffle_dwpw: input slice [{in_channel_offset}:+{Cin}] of {Cx} channels (multiples of 4)")
+    if Cp != (Cin + 31) // 32 * 32 or Kp % 64 or Kp < K:
+        raise ValueError(f"shuffle_dwpw: weights {tuple(w.shape)} for Cin={Cin}, K={K}")
+    if (dw_w is None) != (dw_b is None) or (dw_w is not None and (tuple(dw_w.shape) != (9, Cin) or dw_b.numel() != Cin)):
+        raise ValueError("shuffle_dwpw: depthwise weights [9, Cin] and bias [Cin] go together")
+    if stride not in (1, 2) or (stride == 2 and dw_w is None):
+        raise ValueError("shuffle_dwpw: stride 2 needs the depthwise stage")
+    Ho, Wo = (H, W) if stride == 1 else ((H - 1) // 2 + 1, (W - 1) // 2 + 1)
+    Ky = 2 * hp if hp else K
+    if out is None:
+        out = _empty((N, Ho, Wo, Ky), x.device)
+    if tuple(out.shape[:3]) != (N, Ho, Wo) or out.shape[3] < Ky or (hp and hp < K):
+        raise ValueError(f"shuffle_dwpw: output {tuple(out.shape)} for {(N, Ho, Wo, Ky)} (hp={hp}, K={K})")
+    ldp = 0
+    if passthrough is not None:
+        if not hp or stride != 1 or tuple(passthrough.shape[:3]) != (N, H, W) or passthrough.shape[3] < K:
+            raise ValueError("shuffle_dwpw: passthrough needs a shuffled stride-1 output and >= K channels per pixel")
+        ldp = passthrough.shape[3]
+    hook = LAUNCH_HOOK
+    if hook is not None:
+        tok = hook.begin("shuffle_dwpw_f32_kernel", 2.0 * N * Ho * Wo * K * Cin + (18.0 * N * Ho * Wo * Cin if dw_w is not None else 0.0))
+    check(lib().dlip_shuffle_dwpw_f32(x.data_ptr() + 4 * in_channel_offset, ptr(dw_w), ptr(dw_b), ptr(w), ptr(bias), ptr(passthrough),
+                                      ptr(out), N, H, W, stride, Cin, K, Kp, Cx, ldp, out.shape[3], hp, par, stream_handle()),
+          "dlip_shuffle_dwpw_f32")
+    if hook is not None:
+        hook.end(tok)
+    return out
+
+
+def avgpool3(x: Tensor) -> Tensor:
+    """AvgPool2d(3) of x [N,H,W,C] -> [N,C]: the mean of the top-left 3x3 window (stride 3, no padding: a 3..5 pixel map gives
+    exactly one output pixel, dlip_avgpool3_nhwc_f32).  Other map sizes raise ValueError (the reference cannot view them as
+    [-1, C] per frame either)."""
+    _req(x, "x")
+    N, H, W, Cc = x.shape
+    if not (3 <= H <= 5 and 3 <= W <= 5):
+        raise ValueError(f"avgpool3: AvgPool2d(3) of a {H}x{W} map does not give one pixel per frame")
+    y = _empty((N, Cc), x.device)
+    check(lib().dlip_avgpool3_nhwc_f32(ptr(x), ptr(y), N, H, W, Cc, stream_handle()), "dlip_avgpool3_nhwc_f32")
+    return y
+
+
 def center_crop_origin(size: int, crop: int) -> int:
     """CenterCrop's offset (models/video_models/preprocess.py:89-90): ``int(round(w - tw) / 2.)`` -- the round() is of the
     integer margin (a no-op), the division's result is truncated: FLOOR of half the margin, as dlip_crop_normalize_u8 does.

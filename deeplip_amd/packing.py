@@ -205,7 +205,9 @@ def state_version(module: torch.nn.Module, device) -> tuple:
     v = 7919 * module.__dict__.get("_dlip_exp_ver", 0)     # the activation exponents folded into the f16x3 pack (set_act_exponents)
     for t in c[1]:
         v += t._version + (t.data_ptr() & 0xFFFFFFFF)     # in-place updates bump _version; `p.data = other` moves data_ptr
-    return (gen, device, PRECISION, v)
+    # a model that packs in ONE arithmetic whatever the mode (the ShuffleNet lip-clip encoder: exact f32) names it here, so its pack
+    # cache and the plans recorded with it do not depend on the mode current at the call
+    return (gen, device, module.__dict__.get("_dlip_precision", PRECISION), v)
 
 
 # ---- activation exponents of the f16x3 packs -------------------------------------------------------------------------------------

@@ -500,9 +500,16 @@ class Lipreading(nn.Module):
             self.backend_out = 512
             self.trunk = ResNet(BasicBlock, [2, 2, 2, 2], relu_type=relu_type)
         elif backbone_type == "shufflenet":
+            # model.py:72-78: ShuffleNetV2's features + conv_last + globalpool (conv1 / maxpool / classifier are built and dropped);
+            # eval mode only, exact fp32 under every arithmetic mode (deeplip_amd/shufflenet.py)
+            from .shufflenet import ShuffleNetV2, ShuffleTrunk
             assert width_mult in [0.5, 1.0, 1.5, 2.0], "Width multiplier not correct"
-            raise NotImplementedError("shufflenet backbone is out of scope: both shipped configs select resnet "
-                                      "(conf/video_config.json:2, conf/fusion_config.yaml:75)")
+            shufflenet = ShuffleNetV2(input_size=96, width_mult=width_mult)
+            self.trunk = ShuffleTrunk(shufflenet.features, shufflenet.conv_last, shufflenet.globalpool)
+            self.frontend_nout = 24
+            self.backend_out = 1024 if width_mult != 2.0 else 2048
+            self.stage_out_channels = shufflenet.stage_out_channels[-1]
+            self.__dict__["_dlip_precision"] = "f32"      # packing.state_version: its packs are f32 under every mode
         else:
             raise NotImplementedError(backbone_type)
         frontend_relu = PReLUParams(self.frontend_nout) if relu_type == "prelu" else Marker("ReLU")
@@ -520,6 +527,10 @@ class Lipreading(nn.Module):
         return self.trunk.exponent_groups()
 
     def _pack(self, device):
+        if self.backbone_type == "shufflenet":
+            from .shufflenet import pack_stem24
+            return {"stem": pack_stem24(self.frontend3D[0], self.frontend3D[1], _slope(self.frontend3D[2], 24, device), device),
+                    "trunk": self.trunk.pack(device), "tcn": self.tcn.pack(device)}
         # activation exponents of the f16x3 pack (packing.act_exponents: all zero unless a calibration set them): "in" the float
         # clip, "stem" the pooled stem output, "h<i>" / "o<i>" the trunk's block tensors
         e = packing.act_exponents(self) if packing.PRECISION == "f16x3" else {}
@@ -577,8 +588,13 @@ class Lipreading(nn.Module):
         (``lengths``, model.py:16-17) instead feeds the padding frames through the net as they are and only masks the
         consensus mean, and so does this method without ``ragged``.  ``clip_params``: per-clip crop / flip of uint8 frames."""
         if self.training:
+            if self.backbone_type == "shufflenet":
+                raise NotImplementedError("Lipreading(backbone_type='shufflenet'): training is not supported (eval-mode forward, "
+                                          "classifier_features and embed only); call .eval()")
             return self._forward_train(x, lengths)
-        _lib.check_range()      # an overflow reported by an earlier f16x3 launch surfaces here (host read, no sync)
+        _lib.check_range()
+        if self.backbone_type == "shufflenet":
+            return self._forward_shufflenet(x, lengths, taps, pooled, ragged, clip_params)      # an overflow reported by an earlier f16x3 launch surfaces here (host read, no sync)
         if x.dtype == torch.uint8:
             return self._forward_u8(x, lengths, taps, pooled, ragged, clip_params)
         B, C, T, H, W = x.size()
@@ -615,6 +631,43 @@ class Lipreading(nn.Module):
             return self.trunk.run(y, p["trunk"], None, x_split=split, pool_frames=T, pool_lengths=ragged)
         y = self._descale(self.trunk.run(y, p["trunk"], taps, x_split=split, owner=self), p).view(B, T, self.backend_out)
         return y if self.extract_feats else self.tcn.run(y, lengths, p["tcn"])
+
+    def _exact(self):
+        """The ShuffleNet path packs and runs in exact fp32 whatever the arithmetic mode (nothing of it leaves a range, so the auto
+        mode has nothing to re-run); the ResNet path keeps the mode's packs."""
+        return arith.exact() if self.backbone_type == "shufflenet" else contextlib.nullcontext()
+
+    def _forward_shufflenet(self, x: Tensor, lengths, taps, pooled: bool, ragged: Optional[Tensor], clip_params):
+        """Eval-mode forward of the ShuffleNet backbone (model.py:72-78,80-90): 24-channel stem + max pool, 16 InvertedResidual
+        units, conv_last + AvgPool2d(3), then (extract_feats False) the MS-TCN head.  uint8 frames go through VideoFrontend."""
+        if pooled:
+            raise ValueError("pooled partial sums are the ResNet f16x3 path's")
+        if x.dtype == torch.uint8:
+            if x.dim() not in (4, 5) or (x.dim() == 5 and x.shape[2] != 3):
+                raise ValueError("Lipreading: uint8 input must be [B,T,H,W] (gray) or [B,T,3,H,W] (RGB)")
+            if clip_params is not None:
+                raise NotImplementedError("per-clip crop / flip of uint8 frames lives in the ResNet f16x3 stem's pre-pass")
+            from .frontend import VideoFrontend
+            x = VideoFrontend(88)(x)
+        B, C, T, H, W = x.size()
+        if C != 1:
+            raise ValueError("Lipreading expects grayscale clips [B,1,T,H,W] (model.py:82); use "
+                             "deeplip_amd.ops.ingest_rgb_u8 for [B,T,3,H,W] uint8 RGB")
+        from .shufflenet import check_input_size
+        check_input_size(H, W)
+        with arith.exact():
+            p = _cached_pack(self, x.device, self._pack)
+            x = x.contiguous().float()
+            if ragged is not None:
+                x = ops.mask_frames(x.view(B, T, H * W), ragged).view(B, 1, T, H, W)     # padding frames -> zeros
+            y = ops.shuffle_stem24(x.view(B, T, H, W), p["stem"].w, p["stem"].b, p["stem"].slope)   # [(B*T),H/2,W/2,24]
+            if taps is not None:
+                taps["stem_act"] = y
+            y = ops.maxpool3x3s2(y)
+            if taps is not None:
+                taps["stem"] = y
+            y = self.trunk.run(y, p["trunk"], taps).view(B, T, self.backend_out)
+            return y if self.extract_feats else self.tcn.run(y, lengths, p["tcn"])
 
     @staticmethod
     def _descale(y: Tensor, p) -> Tensor:
@@ -659,7 +712,8 @@ class Lipreading(nn.Module):
             feats = self.forward(x, lengths)
         finally:
             self.extract_feats = ef
-        return self.tcn.pooled(feats, lengths, _cached_pack(self, x.device, self._pack)["tcn"])
+        with self._exact():
+            return self.tcn.pooled(feats, lengths, _cached_pack(self, x.device, self._pack)["tcn"])
 
     @arith.guarded_eval
     @_lib.scoped_eval
@@ -690,7 +744,9 @@ class Lipreading(nn.Module):
 
     def _can_pool(self, x: Tensor) -> bool:
         """The pooled epilogue serves the f16x3 packing when a clip's T*Ho*Wo output pixels of the last convolution
-        are at least one workgroup tile (so a tile holds at most one clip boundary)."""
+        are at least one workgroup tile (so a tile holds at most one clip boundary).  Never for the ShuffleNet backbone."""
+        if self.backbone_type == "shufflenet":
+            return False
         p = _cached_pack(self, x.device, self._pack)
         if not self.trunk.wants_split(p["trunk"]) or p["stem"].wscale is None:
             return False

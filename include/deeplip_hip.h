@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define DLIP_ABI_VERSION 50
+#define DLIP_ABI_VERSION 51
 #define DLIP_LIFT_WORDS 4098   /* a gradient's power-of-two lift: (2^e, 2^-e), then 2^-e repeated 2048 times (the post_scale vector of
                                   the convolution that consumes the lifted gradient); while it is formed the words behind the pair
                                   hold one maximum per workgroup of the producing pass */
@@ -849,6 +849,35 @@ int dlip_range_scope_end(dlip_stream_t stream);
  * 9 the rows kernel's short last round (0 = off: every tile the full height);
  * value -1 restores the built-in choice. */
 int dlip_debug_set(int32_t key, int32_t value);
+
+/* ------------------------------------------------------------------------------------------
+ * ShuffleNetV2 lip-clip trunk, eval mode, exact fp32 (Lipreading(backbone_type='shufflenet'); deeplip_amd/shufflenet.py).
+ *
+ * dlip_shuffle_stem24_f32: Conv3d(1->24, 5x7x7, stride (1,2,2), pad (2,3,3)) + folded BatchNorm3d + PReLU|ReLU (slope[k]: PReLU
+ * weight or 0; NULL = identity), replacing models/video_models/model.py:81-83 for frontend_nout = 24 (model.py:76).  x [B,T,H,W],
+ * w = [248][32] k-major (245 taps + 3 zero rows; channels 24..31 zero), y [(B*T),H/2,W/2,24].  H, W even, W <= 128.
+ *
+ * dlip_shuffle_dwpw_f32: one branch tail of an InvertedResidual unit (shufflenetv2.py:42-105):
+ *   y = ReLU(W * A + bias), A = x (dw_w == NULL: plain 1x1) or A = dw3x3(x) + dw_b (pad 1, stride 1|2, groups = channels,
+ *   no activation; computed on load and never stored), folded BatchNorms in both.  x [N,H,W,*] at pixel pitch ldx (Cin
+ *   channels from the pointer on), dw_w [9][Cin] tap-major, dw_b [Cin], w [Cp][Kp] k-major (Cp = Cin rounded up to 32 with
+ *   zero rows, Kp a multiple of 64 >= K), bias [K].  Output pixel m, channel j goes to y[m*ldy + j] (hp == 0) or, hp > 0, to
+ *   the unit's shuffled position (channel_shuffle(cat(.,.), 2), shufflenetv2.py:27-40,96-105): logical channel L = 2j + par
+ *   of the 2K-channel unit output, stored at L (L < K) or hp + L - K (L >= K), hp >= K the padded half, ldy >= 2hp; the launch with
+ *   par == 1 also writes zeros to the padding channels [K, hp) and [hp + K, 2hp).  xp != NULL (stride 1, hp > 0): the
+ *   passthrough half x1 (shufflenetv2.py:98-100) -- channel j < K of xp at pitch ldp goes to logical 2j + 1 - par.
+ *   Cin, ldx multiples of 4; x, dw_w, dw_b 16-byte aligned.
+ *
+ * dlip_avgpool3_nhwc_f32: AvgPool2d(3) (stride 3, no padding; the `globalpool` of model.py:75 with input_size 96) of an
+ * [N,H,W,C] map with 3 <= H, W <= 5 -- the one output pixel is the mean of the TOP-LEFT 3x3 window -- to y [N,C].
+ * ------------------------------------------------------------------------------------------ */
+int dlip_shuffle_stem24_f32(const float* x, const float* w_248x32, const float* bias, const float* slope, float* y,
+                            int32_t B, int32_t T, int32_t H, int32_t W, dlip_stream_t stream);
+int dlip_shuffle_dwpw_f32(const float* x, const float* dw_w, const float* dw_b, const float* w, const float* bias,
+                          const float* xp, float* y, int32_t N, int32_t H, int32_t W, int32_t stride, int32_t Cin,
+                          int32_t K, int32_t Kp, int32_t ldx, int32_t ldp, int32_t ldy, int32_t hp, int32_t par,
+                          dlip_stream_t stream);
+int dlip_avgpool3_nhwc_f32(const float* x, float* y, int32_t N, int32_t H, int32_t W, int32_t C, dlip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Step plans.  The reference drives its encoders from a Python loop, one utterance and one torch.nn layer
