@@ -1197,5 +1197,42 @@ def dropout(x, p: float, training: bool = True):
     return DropoutFn.apply(x, u, p)
 
 
+class DepthwiseTemporalConvFn(Function):
+    """The depthwise Conv1d of the dwpw TCN heads (groups = channels, bias=False, padding (k-1)d on both sides; tcn.py:33-34,158-159,
+    169-170) on channels-last x [B,T,C], for every branch that reads x in one launch: z_r [B, T + (k_r-1)d, C] (the BatchNorm behind
+    takes its statistics over that full length, tcn.py:35-38).  Backward: the data gradients of all branches summed in one launch,
+    the weight gradients in two (fp64 chunk sums, fixed-order reduction: deterministic).  Weights keep the reference layout [C,1,k];
+    the kernels read them tap-major [k,C]."""
+
+    @staticmethod
+    def forward(ctx, x, d, *weights):
+        x = x.contiguous()
+        B, T, C_ = x.shape
+        ks = [int(w.shape[2]) for w in weights]
+        wt = [_permute3(w.detach().contiguous(), (2, 1, 0)).view(k, C_) for w, k in zip(weights, ks)]
+        pads = [(k - 1) * d for k in ks]
+        zs = ops.tcn_dw(x, wt, d, pads=pads, t_outs=[T + p for p in pads])
+        ctx.save_for_backward(x, *wt)
+        ctx.cfg = (d, ks, pads)
+        return tuple(zs)
+
+    @staticmethod
+    def backward(ctx, *dzs):
+        x, *wt = ctx.saved_tensors
+        d, ks, pads = ctx.cfg
+        dzs = [g.contiguous() for g in dzs]
+        C_ = x.shape[2]
+        dx = ops.tcn_dw_dgrad(dzs, wt, d, pads=pads, T=x.shape[1]) if ctx.needs_input_grad[0] else None
+        dws = [None] * len(wt)
+        if any(ctx.needs_input_grad[2:]):
+            dws = [_permute3(g.view(k, 1, C_), (2, 1, 0)) for g, k in zip(ops.tcn_dw_wgrad(x, dzs, ks, d, pads=pads), ks)]
+        return (dx, None) + tuple(dws)
+
+
+def depthwise_temporal_conv(x, weights, dilation: int):
+    """[z_r] = depthwise Conv1d(x; weights[r] [C,1,k_r], dilation, padding (k_r-1)d) of channels-last x [B,T,C] (DepthwiseTemporalConvFn)."""
+    return list(DepthwiseTemporalConvFn.apply(x, int(dilation), *weights))
+
+
 def stem_conv(x_bthw, weight):
     return StemConvTrainFn.apply(x_bthw, weight)

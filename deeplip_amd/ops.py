@@ -433,6 +433,111 @@ def shuffle_dwpw(x: Tensor, w: Tensor, bias: Tensor, *, dw_w: Optional[Tensor] =
     return out
 
 
+def _dw_geometry(what: str, x_shape, ws, k_list, pads, t_outs, d: int):
+    B, T, Cc = x_shape
+    if Cc % 4:
+        raise ValueError(f"{what}: C = {Cc} must be a multiple of 4")
+    if not 1 <= len(ws) <= 4 or not (len(ws) == len(k_list) == len(pads) == len(t_outs)):
+        raise ValueError(f"{what}: 1..4 branches with one weight, k, pad and output length each")
+    if d < 1:
+        raise ValueError(f"{what}: dilation {d} < 1")
+    for w, k, P, To in zip(ws, k_list, pads, t_outs):
+        if tuple(w.shape) != (k, Cc):
+            raise ValueError(f"{what}: depthwise weights {tuple(w.shape)}, expected tap-major [k={k}, C={Cc}]")
+        if k < 1 or k > 64 or P < 0 or To < 1:
+            raise ValueError(f"{what}: k = {k}, pad = {P}, output length {To}")
+
+
+def _arr(ctype, vals):
+    return (ctype * len(vals))(*vals)
+
+
+def tcn_dw(x: Tensor, ws: Sequence[Tensor], d: int, *, pads: Sequence[int], t_outs: Sequence[int],
+           biases: Optional[Sequence[Tensor]] = None, slopes: Optional[Sequence[Tensor]] = None) -> list:
+    """Depthwise dilated temporal convolution (dlip_tcn_dw_fwd_f32), one launch for every branch: x [B,T,C] channels-last,
+    ws[r] [k_r, C] tap-major -> [act(z_r + bias_r)] with z_r[b,t,c] = sum_j ws[r][j,c] x[b, t - pads[r] + j d, c], t < t_outs[r].
+    Eval: pads = (k-1)d/2, t_outs = T, folded BatchNorm in ws / biases, slopes = PReLU weights or zeros (ReLU).  Train: pads =
+    (k-1)d, t_outs = T + (k-1)d, no bias or slope (raw z)."""
+    _req(x, "x")
+    ks = [int(w.shape[0]) for w in ws]
+    for i, w in enumerate(ws):
+        _req(w, f"ws[{i}]")
+    for grp, n in ((biases, "biases"), (slopes, "slopes")):
+        if grp is not None:
+            if len(grp) != len(ws):
+                raise ValueError(f"tcn_dw: {len(grp)} {n} for {len(ws)} branches")
+            for t in grp:
+                _req(t, n)
+                if t.numel() != x.shape[2]:
+                    raise ValueError(f"tcn_dw: {n} entries must have C = {x.shape[2]} elements")
+    _dw_geometry("tcn_dw", x.shape, ws, ks, pads, t_outs, d)
+    B, T, Cc = x.shape
+    ys = [_empty((B, int(To), Cc), x.device) for To in t_outs]
+    n = len(ws)
+    check(lib().dlip_tcn_dw_fwd_f32(ptr(x), n, _arr(C.c_void_p, [w.data_ptr() for w in ws]),
+                                    _arr(C.c_void_p, [b.data_ptr() for b in biases]) if biases is not None else None,
+                                    _arr(C.c_void_p, [s.data_ptr() for s in slopes]) if slopes is not None else None,
+                                    _arr(C.c_void_p, [y.data_ptr() for y in ys]), _arr(C.c_int32, ks), _arr(C.c_int32, list(pads)),
+                                    _arr(C.c_int32, list(t_outs)), B, T, Cc, int(d), stream_handle()), "dlip_tcn_dw_fwd_f32")
+    return ys
+
+
+def tcn_dw_dgrad(dzs: Sequence[Tensor], ws: Sequence[Tensor], d: int, *, pads: Sequence[int], T: int) -> Tensor:
+    """The data gradient of tcn_dw over every branch at once: dx [B,T,C] = sum_r sum_j ws[r][j,c] dzs[r][b, s + pads[r] - j d, c]
+    (dlip_tcn_dw_dgrad_f32; dzs[r] [B, T_out_r, C])."""
+    for i, (g, w) in enumerate(zip(dzs, ws)):
+        _req(g, f"dzs[{i}]")
+        _req(w, f"ws[{i}]")
+    if len(dzs) != len(ws) or not dzs:
+        raise ValueError("tcn_dw_dgrad: one gradient per branch weight")
+    B, _, Cc = dzs[0].shape
+    ks = [int(w.shape[0]) for w in ws]
+    t_outs = [int(g.shape[1]) for g in dzs]
+    if any(g.dim() != 3 or g.shape[0] != B or g.shape[2] != Cc for g in dzs):
+        raise ValueError("tcn_dw_dgrad: gradients [B, T_out, C] with one B and C")
+    _dw_geometry("tcn_dw_dgrad", (B, T, Cc), ws, ks, pads, t_outs, d)
+    dx = _empty((B, T, Cc), dzs[0].device)
+    check(lib().dlip_tcn_dw_dgrad_f32(_arr(C.c_void_p, [g.data_ptr() for g in dzs]), len(dzs), _arr(C.c_void_p, [w.data_ptr() for w in ws]),
+                                      _arr(C.c_int32, ks), _arr(C.c_int32, list(pads)), _arr(C.c_int32, t_outs), ptr(dx), B, T, Cc,
+                                      int(d), stream_handle()), "dlip_tcn_dw_dgrad_f32")
+    return dx
+
+
+def tcn_dw_wgrad(x: Tensor, dzs: Sequence[Tensor], ks: Sequence[int], d: int, *, pads: Sequence[int]) -> list:
+    """The weight gradients of tcn_dw: [dw_r [k_r, C]], dw_r[j,c] = sum_{b,t} dzs[r][b,t,c] x[b, t - pads[r] + j d, c]
+    (dlip_tcn_dw_wgrad_f32: fp64 chunk sums, then a fixed-order sum of the chunks -- deterministic, two launches)."""
+    _req(x, "x")
+    for i, g in enumerate(dzs):
+        _req(g, f"dzs[{i}]")
+    B, T, Cc = x.shape
+    t_outs = [int(g.shape[1]) for g in dzs]
+    if any(g.dim() != 3 or g.shape[0] != B or g.shape[2] != Cc for g in dzs):
+        raise ValueError("tcn_dw_wgrad: gradients [B, T_out, C] matching x [B, T, C]")
+    dws = [_empty((int(k), Cc), x.device) for k in ks]
+    _dw_geometry("tcn_dw_wgrad", x.shape, dws, list(ks), pads, t_outs, d)
+    n_ws = sum(int(lib().dlip_tcn_dw_wgrad_chunks(B * To)) * int(k) * Cc for k, To in zip(ks, t_outs))
+    ws = _empty((n_ws,), x.device, torch.float64)
+    check(lib().dlip_tcn_dw_wgrad_f32(ptr(x), len(dzs), _arr(C.c_void_p, [g.data_ptr() for g in dzs]),
+                                      _arr(C.c_void_p, [w.data_ptr() for w in dws]), _arr(C.c_int32, [int(k) for k in ks]),
+                                      _arr(C.c_int32, list(pads)), _arr(C.c_int32, t_outs), B, T, Cc, int(d), ptr(ws), n_ws,
+                                      stream_handle()), "dlip_tcn_dw_wgrad_f32")
+    return dws
+
+
+def add_prelu(a: Tensor, b: Tensor, slope: Tensor) -> Tensor:
+    """prelu(a + b) with per-channel slopes (dlip_add_prelu_rows_fwd_f32): an identity residual's end of block in eval mode."""
+    for t, n in ((a, "a"), (b, "b"), (slope, "slope")):
+        _req(t, n)
+    if a.shape != b.shape or a.shape[-1] % 4 or slope.numel() != a.shape[-1]:
+        raise ValueError(f"add_prelu: a {tuple(a.shape)}, b {tuple(b.shape)}, slope {slope.numel()} (channels a multiple of 4)")
+    Cc = a.shape[-1]
+    s_ = _empty(a.shape, a.device)
+    y = _empty(a.shape, a.device)
+    check(lib().dlip_add_prelu_rows_fwd_f32(ptr(a), ptr(b), ptr(slope), ptr(s_), ptr(y), a.numel() // Cc, Cc, stream_handle()),
+          "dlip_add_prelu_rows_fwd_f32")
+    return y
+
+
 def avgpool3(x: Tensor) -> Tensor:
     """AvgPool2d(3) of x [N,H,W,C] -> [N,C]: the mean of the top-left 3x3 window (stride 3, no padding: a 3..5 pixel map gives
     exactly one output pixel, dlip_avgpool3_nhwc_f32).  Other map sizes raise ValueError (the reference cannot view them as

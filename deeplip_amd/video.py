@@ -259,7 +259,7 @@ class ResNet(nn.Module):
 
 
 # ------------------------------------------------------------------------------------------
-# tcn.py (multibranch MS-TCN head; the single-branch TCN is on no shipped config)
+# tcn.py (multibranch MS-TCN head, single-branch TCN head; dense or depthwise-separable (dwpw) convolutions)
 # ------------------------------------------------------------------------------------------
 class Chomp1d(Marker):
     """tcn.py:12-25.  Symmetric chomp of a (k-1)d-padded conv == 'same' padding (k-1)d/2, which is
@@ -273,23 +273,51 @@ class Chomp1d(Marker):
 
 
 class ConvBatchChompRelu(nn.Module):
-    """tcn.py:28-59 (dwpw=False)."""
+    """tcn.py:28-59.  dwpw=False: conv / batchnorm / chomp / non_lin.  dwpw=True: ``conv`` = Sequential(depthwise Conv1d (groups =
+    n_inputs, no bias), BatchNorm1d, Chomp1d, act, pointwise Conv1d (no bias), BatchNorm1d, act) -- keys conv.{0,1,3,4,5,6}."""
 
     def __init__(self, n_inputs, n_outputs, kernel_size, stride, dilation, padding, relu_type, dwpw=False):
         super().__init__()
-        if dwpw:
-            raise NotImplementedError("depthwise-separable TCN (tcn_dwpw) is off in every shipped config")
         assert stride == 1
         self.kernel_size, self.dilation, self.padding = kernel_size, dilation, padding
-        self.n_outputs = n_outputs
+        self.n_inputs, self.n_outputs = n_inputs, n_outputs
+        self.dwpw = dwpw
+        if dwpw:
+            self.conv = _dwpw_pair(n_inputs, n_outputs, kernel_size, padding, relu_type)
+            return
         self.conv = ConvParams(n_inputs, n_outputs, (kernel_size,), bias=True)
         self.batchnorm = BatchNormParams(n_outputs)
         self.chomp = Chomp1d(padding, True)
         self.non_lin = _act_holder(relu_type, n_outputs)
 
     def pack(self, device):
+        if self.dwpw:
+            return _pack_dwpw(self.conv, 0, device)
         return packing.pack_conv1d(self.conv.weight, self.conv.bias, self.batchnorm, device,
                                    _slope(self.non_lin, self.n_outputs, device))
+
+
+def _dwpw_pair(n_inputs, n_outputs, kernel_size, padding, relu_type) -> nn.Sequential:
+    """The seven modules of one depthwise-separable conv set (tcn.py:33-42 / :156-164): depthwise Conv1d (groups = channels,
+    bias=False), BatchNorm1d, Chomp1d (symmetric), act, pointwise Conv1d (bias=False), BatchNorm1d, act."""
+    return nn.Sequential(ConvParams(1, n_inputs, (kernel_size,), bias=False), BatchNormParams(n_inputs), Chomp1d(padding, True),
+                         _act_holder(relu_type, n_inputs), ConvParams(n_inputs, n_outputs, (1,), bias=False),
+                         BatchNormParams(n_outputs), _act_holder(relu_type, n_outputs))
+
+
+def _pack_dwpw(seq, i: int, device) -> dict:
+    """Eval pack of the conv set at seq[i : i + 7]: the depthwise taps with the BatchNorm folded in, tap-major [k, C] fp32 (exact under
+    every arithmetic mode), its shift and slopes; the pointwise 1x1 + BatchNorm + act in the pack's precision (packing.pack_conv1d)."""
+    dw, bn, act, pw, bn2, act2 = seq[i], seq[i + 1], seq[i + 3], seq[i + 4], seq[i + 5], seq[i + 6]
+    C = dw.out_channels
+    scale, shift = packing.bn_scale_shift(bn)
+    taps = (dw.weight.detach().double().cpu()[:, 0, :] * scale.view(C, 1)).t().contiguous()      # [k, C]
+    return {"dw_w": packing._dev(taps, device), "dw_b": packing._dev(shift, device), "dw_slope": _slope(act, C, device),
+            "pw": packing.pack_conv1d(pw.weight, None, bn2, device, _slope(act2, pw.out_channels, device))}
+
+
+def _run_pw(a: Tensor, pk: packing.Packed, **kw) -> Tensor:
+    return ops.conv1d_ntc(a, pk.w, pk.b, slope=pk.slope, w_scale=pk.wscale, **kw)
 
 
 class MultibranchTemporalBlock(nn.Module):
@@ -316,6 +344,7 @@ class MultibranchTemporalBlock(nn.Module):
         # the shipped config and every block owns a 1x1 projection.
         self.downsample = ConvParams(n_inputs, n_outputs, (1,), bias=True) if (n_inputs // self.num_kernels) != n_outputs else None
         self.relu_final = _act_holder(relu_type, n_outputs)
+        self.dwpw = dwpw
 
     def pack(self, device):
         p = {f"cbcr{s}_{j}": getattr(self, f"cbcr{s}_{j}").pack(device) for s in (0, 1) for j in range(self.num_kernels)}
@@ -325,19 +354,28 @@ class MultibranchTemporalBlock(nn.Module):
         return p
 
     def run(self, x: Tensor, p) -> Tensor:
-        """x [B,T,Cin] -> [B,T,n_outputs]; branches write channel slices of one buffer (no concat)."""
+        """x [B,T,Cin] -> [B,T,n_outputs]; branches write channel slices of one buffer (no concat).  dwpw: the depthwise stages of
+        all branches in one launch (they read the same input), then one pointwise GEMM per branch into its channel slice."""
         B, T, _ = x.shape
         nb = self.n_outputs_branch
         cur = x
         for s in (0, 1):
             out = ops._empty((B, T, self.n_outputs), x.device)
-            for j, k in enumerate(self.kernel_sizes):
-                pk = p[f"cbcr{s}_{j}"]
-                ops.conv1d_ntc(cur, pk.w, pk.b, dilation=self.dilation, pad=(k - 1) * self.dilation // 2,
-                               slope=pk.slope, out=out, out_channel_offset=j * nb, w_scale=pk.wscale)
+            pks = [p[f"cbcr{s}_{j}"] for j in range(self.num_kernels)]
+            if self.dwpw:
+                dws = ops.tcn_dw(cur, [q["dw_w"] for q in pks], self.dilation, pads=[(k - 1) * self.dilation // 2 for k in self.kernel_sizes],
+                                 t_outs=[T] * self.num_kernels, biases=[q["dw_b"] for q in pks], slopes=[q["dw_slope"] for q in pks])
+                for j, (a, q) in enumerate(zip(dws, pks)):
+                    _run_pw(a, q["pw"], out=out, out_channel_offset=j * nb)
+            else:
+                for j, k in enumerate(self.kernel_sizes):
+                    pk = pks[j]
+                    ops.conv1d_ntc(cur, pk.w, pk.b, dilation=self.dilation, pad=(k - 1) * self.dilation // 2,
+                                   slope=pk.slope, out=out, out_channel_offset=j * nb, w_scale=pk.wscale)
             cur = out  # dropout: identity in eval
         if self.downsample is not None:
             return ops.conv1d_ntc(x, p["down"].w, p["down"].b, residual=cur, slope=p["final_slope"], w_scale=p["down"].wscale)
+        # (n_inputs == num_kernels * n_outputs: the reference itself cannot add the n_inputs-channel x to out1, tcn.py:113-116)
         raise NotImplementedError("identity-residual multibranch block never occurs (tcn.py:87)")
 
 
@@ -445,14 +483,197 @@ class MultiscaleMultibranchTCN(nn.Module):
         _require_eval(self)
         return self.run(x.contiguous(), lengths, _cached_pack(self, x.device, self.pack))
 
+    def forward_train(self, y: Tensor, lengths, p_drop: float) -> Tensor:
+        """The head under model.train() on channels-last features y [B,T,C_in] (Lipreading._forward_train): logits, differentiable."""
+        from . import autograd as ag
+        for blk in self.mb_ms_tcn.network:
+            y = (_tcn_dwpw_block_train if blk.dwpw else _tcn_block_train)(blk, y, p_drop)
+        return ag.linear(_time_mean_train(y, lengths), self.tcn_output.weight, self.tcn_output.bias)
+
+
+class TemporalBlock(nn.Module):
+    """tcn.py:145-216, the block of the single-branch TCN head.  dwpw=False registers conv1 .. relu2 as attributes AND inside ``net``
+    (tcn.py:205-206), so the state dict holds each of their tensors twice (``conv1.weight`` and ``net.0.weight``; both load and name
+    the same Parameter).  dwpw=True: ``net`` = two depthwise-separable conv sets with a Dropout after each (keys
+    net.{0,1,3,4,5,6,8,9,11,12,13,14}).  The residual is projected only when n_inputs != n_outputs (tcn.py:208); otherwise the
+    block ends in relu(out + x)."""
+
+    def __init__(self, n_inputs, n_outputs, kernel_size, stride, dilation, padding, dropout=0.2,
+                 symm_chomp=False, no_padding=False, relu_type="relu", dwpw=False):
+        super().__init__()
+        if no_padding:
+            raise NotImplementedError("TemporalBlock(no_padding=True) is reachable only by building the block directly "
+                                      "(TemporalConvNet and Lipreading never ask for it)")
+        if not dwpw and not symm_chomp:
+            raise NotImplementedError("TemporalBlock(symm_chomp=False) (a causal chomp) is reachable only by building the block "
+                                      "directly (TemporalConvNet and Lipreading always chomp symmetrically)")
+        assert stride == 1
+        self.no_padding = no_padding
+        self.n_inputs, self.n_outputs = n_inputs, n_outputs
+        self.kernel_size, self.dilation, self.padding = kernel_size, dilation, padding
+        self.dwpw = dwpw
+        if dwpw:
+            a, b = _dwpw_pair(n_inputs, n_outputs, kernel_size, padding, relu_type), _dwpw_pair(n_outputs, n_outputs, kernel_size, padding, relu_type)
+            self.net = nn.Sequential(*a, Marker(f"Dropout({dropout})"), *b, Marker(f"Dropout({dropout})"))
+        else:
+            self.conv1 = ConvParams(n_inputs, n_outputs, (kernel_size,), bias=True)
+            self.batchnorm1 = BatchNormParams(n_outputs)
+            self.chomp1 = Chomp1d(padding, symm_chomp)
+            self.relu1 = _act_holder(relu_type, n_outputs)
+            self.dropout1 = Marker(f"Dropout({dropout})")
+            self.conv2 = ConvParams(n_outputs, n_outputs, (kernel_size,), bias=True)
+            self.batchnorm2 = BatchNormParams(n_outputs)
+            self.chomp2 = Chomp1d(padding, symm_chomp)
+            self.relu2 = _act_holder(relu_type, n_outputs)
+            self.dropout2 = Marker(f"Dropout({dropout})")
+            self.net = nn.Sequential(self.conv1, self.batchnorm1, self.chomp1, self.relu1, self.dropout1,
+                                     self.conv2, self.batchnorm2, self.chomp2, self.relu2, self.dropout2)
+        self.downsample = ConvParams(n_inputs, n_outputs, (1,), bias=True) if n_inputs != n_outputs else None
+        self.relu = _act_holder(relu_type, n_outputs)
+
+    def pack(self, device):
+        if self.dwpw:
+            p = {"set0": _pack_dwpw(self.net, 0, device), "set1": _pack_dwpw(self.net, 8, device)}
+        else:
+            p = {"conv1": packing.pack_conv1d(self.conv1.weight, self.conv1.bias, self.batchnorm1, device,
+                                              _slope(self.relu1, self.n_outputs, device)),
+                 "conv2": packing.pack_conv1d(self.conv2.weight, self.conv2.bias, self.batchnorm2, device,
+                                              _slope(self.relu2, self.n_outputs, device))}
+        if self.downsample is not None:
+            p["down"] = packing.pack_conv1d(self.downsample.weight, self.downsample.bias, None, device)
+        p["final_slope"] = _slope(self.relu, self.n_outputs, device)
+        return p
+
+    def run(self, x: Tensor, p) -> Tensor:
+        """x [B,T,n_inputs] -> [B,T,n_outputs] (eval: dropout is the identity, the symmetric chomp is 'same' padding (k-1)d/2)."""
+        T = x.shape[1]
+        d, pad = self.dilation, (self.kernel_size - 1) * self.dilation // 2
+        if self.dwpw:
+            cur = x
+            for st in ("set0", "set1"):
+                q = p[st]
+                a = ops.tcn_dw(cur, [q["dw_w"]], d, pads=[pad], t_outs=[T], biases=[q["dw_b"]], slopes=[q["dw_slope"]])[0]
+                cur = _run_pw(a, q["pw"])
+        else:
+            h = _run_pw(x, p["conv1"], dilation=d, pad=pad)
+            cur = _run_pw(h, p["conv2"], dilation=d, pad=pad)
+        if self.downsample is not None:
+            return ops.conv1d_ntc(x, p["down"].w, p["down"].b, residual=cur, slope=p["final_slope"], w_scale=p["down"].wscale)
+        return ops.add_prelu(cur, x, p["final_slope"])          # identity residual: relu(relu2(...) + x), tcn.py:211-216
+
+
+class TemporalConvNet(nn.Module):
+    """tcn.py:219-237."""
+
+    def __init__(self, num_inputs, num_channels, tcn_options, dropout=0.2, relu_type="relu", dwpw=False):
+        super().__init__()
+        ks = tcn_options["kernel_size"]
+        self.ksize = ks[0] if isinstance(ks, list) else ks
+        layers = []
+        for i in range(len(num_channels)):
+            d = 2 ** i
+            cin = num_inputs if i == 0 else num_channels[i - 1]
+            layers.append(TemporalBlock(cin, num_channels[i], self.ksize, stride=1, dilation=d, padding=(self.ksize - 1) * d,
+                                        dropout=dropout, symm_chomp=True, no_padding=False, relu_type=relu_type, dwpw=dwpw))
+        self.network = nn.Sequential(*layers)
+
 
 class TCN(nn.Module):
-    """model.py:40-58 single-branch head: selected only when len(kernel_size) == 1, which no
-    shipped config does (conf/video_config.json:6-10, conf/fusion_config.yaml:80)."""
+    """model.py:40-58: the single-branch head, selected by Lipreading when len(kernel_size) == 1.  Same pack / run / pooled / forward
+    surface as MultiscaleMultibranchTCN."""
 
-    def __init__(self, *a, **k):
+    def __init__(self, input_size, num_channels, num_classes, tcn_options, dropout, relu_type, dwpw=False):
         super().__init__()
-        raise NotImplementedError("single-branch TCN head is out of scope (no shipped config selects it)")
+        self.tcn_trunk = TemporalConvNet(input_size, num_channels, dropout=dropout, tcn_options=tcn_options, relu_type=relu_type, dwpw=dwpw)
+        self.tcn_output = LinearParams(num_channels[-1], num_classes)
+        self.has_aux_losses = False
+
+    def pack(self, device):
+        return {"blocks": [b.pack(device) for b in self.tcn_trunk.network],
+                "out": packing.pack_linear(self.tcn_output.weight, self.tcn_output.bias, None, device)}
+
+    def pooled(self, x: Tensor, lengths, p) -> Tensor:
+        """x [B,T,C_in] -> consensus features [B, num_channels[-1]] = _average_batch(tcn_trunk(x)) (model.py:16-17,54-57)."""
+        for b, bp in zip(self.tcn_trunk.network, p["blocks"]):
+            x = b.run(x, bp)
+        return ops.time_mean(x, _lengths_i32(lengths, x.device))
+
+    def run(self, x: Tensor, lengths, p) -> Tensor:
+        return ops.linear(self.pooled(x, lengths, p), p["out"].w, p["out"].b, w_scale=p["out"].wscale)   # tcn_output, model.py:47,58
+
+    def forward(self, x, lengths, B):
+        _require_eval(self)
+        return self.run(x.contiguous(), lengths, _cached_pack(self, x.device, self.pack))
+
+    def forward_train(self, y: Tensor, lengths, p_drop: float) -> Tensor:
+        """The head under model.train() on channels-last features y [B,T,C_in] (Lipreading._forward_train): logits, differentiable."""
+        from . import autograd as ag
+        for blk in self.tcn_trunk.network:
+            y = _temporal_block_train(blk, y, p_drop)
+        return ag.linear(_time_mean_train(y, lengths), self.tcn_output.weight, self.tcn_output.bias)
+
+
+def _time_mean_train(y: Tensor, lengths) -> Tensor:
+    from . import autograd_video as av
+    return av.time_mean(y, _lengths_i32(lengths, y.device))
+
+
+def _dwpw_set_train(seq, i: int, x: Tensor, dilation: int) -> Tensor:
+    """One depthwise-separable conv set (seq[i : i + 7], tcn.py:33-42 / :156-164) under model.train(): the depthwise convolution over
+    the padded length (pad (k-1)d on both sides), BatchNorm with the statistics of that FULL length, the symmetric chomp and the act,
+    then the pointwise 1x1 + BatchNorm + act.  x [B,T,C] -> [B,T,n_outputs]."""
+    from . import autograd_video as av
+    B, T, _ = x.shape
+    dw = seq[i]
+    z = av.depthwise_temporal_conv(x, [dw.weight], dilation)[0]              # [B, T + (k-1)d, C]
+    a = av.batchnorm_prelu(z, seq[i + 1], seq[i + 3])
+    a = av.chomp_concat([a.view(B, 1, z.shape[1], z.shape[2])], T)           # the element-wise act commutes with the chomp
+    h = av.conv(a.view(B, 1, T, a.shape[2]), seq[i + 4].weight, None)
+    return av.batchnorm_prelu(h, seq[i + 5], seq[i + 6]).view(B, T, seq[i + 4].out_channels)
+
+
+def _temporal_block_train(b: "TemporalBlock", x: Tensor, p_drop: float) -> Tensor:
+    """TemporalBlock.forward under model.train() (tcn.py:211-216): batch-statistics BatchNorm over the padded length, then the chomp
+    (as in _tcn_block_train), dropout after each conv set, the projected or identity residual and the final act."""
+    from . import autograd_video as av
+    B, T, _ = x.shape
+    d = b.dilation
+    if b.dwpw:
+        cur = av.dropout(_dwpw_set_train(b.net, 0, x, d), p_drop)
+        cur = av.dropout(_dwpw_set_train(b.net, 8, cur, d), p_drop)
+    else:
+        cur = x
+        pad = (b.kernel_size - 1) * d
+        for conv, bn, act in ((b.conv1, b.batchnorm1, b.relu1), (b.conv2, b.batchnorm2, b.relu2)):
+            z = av.conv(cur.reshape(B, 1, T, cur.shape[2]), conv.weight, conv.bias, pad=(0, pad), dil=(1, d))
+            cur = av.dropout(av.chomp_concat([av.batchnorm_prelu(z, bn, act)], T), p_drop)
+    res = x
+    if b.downsample is not None:
+        res = av.conv(x.reshape(B, 1, T, x.shape[2]), b.downsample.weight, b.downsample.bias).view(B, T, b.n_outputs)
+    return av.add_prelu(cur, res, b.relu)
+
+
+def _tcn_dwpw_block_train(b: "MultibranchTemporalBlock", x: Tensor, p_drop: float) -> Tensor:
+    """MultibranchTemporalBlock.forward with dwpw=True under model.train(): per stage ONE depthwise launch for every branch (forward,
+    data gradient and weight gradient), then each branch's BatchNorm + chomp + act and its pointwise 1x1 + BatchNorm + act; the
+    branch outputs concatenated along channels, dropout, the projection (tcn.py:87) and the final act."""
+    from . import autograd_video as av
+    B, T, _ = x.shape
+    d = b.dilation
+    cur = x
+    for s in (0, 1):
+        ms = [getattr(b, f"cbcr{s}_{j}").conv for j in range(b.num_kernels)]
+        zs = av.depthwise_temporal_conv(cur, [m[0].weight for m in ms], d)
+        outs = []
+        for m, z in zip(ms, zs):
+            a = av.chomp_concat([av.batchnorm_prelu(z, m[1], m[3]).view(B, 1, z.shape[1], z.shape[2])], T)
+            h = av.conv(a.view(B, 1, T, a.shape[2]), m[4].weight, None)
+            outs.append(av.batchnorm_prelu(h, m[5], m[6]))                    # [B,1,T,nb]
+        cur = av.dropout(av.chomp_concat(outs, T), p_drop)                      # (pad 0: the concatenation alone)
+    if b.downsample is None:
+        raise NotImplementedError("identity-residual multibranch block never occurs (tcn.py:87)")
+    res = av.conv(x.reshape(B, 1, T, x.shape[2]), b.downsample.weight, b.downsample.bias).view(B, T, b.n_outputs)
+    return av.add_prelu(cur, res, b.relu_final)
 
 
 # ------------------------------------------------------------------------------------------
@@ -559,7 +780,7 @@ class Lipreading(nn.Module):
         """forward() under model.train() (train_video.py:129,140-146): the whole encoder differentiable, every
         forward and backward step a dlip_* launch (deeplip_amd/autograd_video.py); BatchNorm uses batch
         statistics and updates its running buffers, Dropout draws a fresh keep-mask."""
-        from . import autograd as ag, autograd_video as av
+        from . import autograd_video as av
         B, C, T, H, W = x.size()
         if C != 1:
             raise ValueError("Lipreading expects grayscale clips [B,1,T,H,W] (model.py:82)")
@@ -573,9 +794,7 @@ class Lipreading(nn.Module):
         y = av.avgpool(y).view(B, T, self.backend_out)
         if self.extract_feats:
             return y
-        for blk in self.tcn.mb_ms_tcn.network:
-            y = _tcn_block_train(blk, y, self.tcn_dropout)
-        return ag.linear(av.time_mean(y, _lengths_i32(lengths, x.device)), self.tcn.tcn_output.weight, self.tcn.tcn_output.bias)
+        return self.tcn.forward_train(y, lengths, self.tcn_dropout)
 
     @arith.guarded_eval
     @_lib.scoped_eval

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define DLIP_ABI_VERSION 51
+#define DLIP_ABI_VERSION 52
 #define DLIP_LIFT_WORDS 4098   /* a gradient's power-of-two lift: (2^e, 2^-e), then 2^-e repeated 2048 times (the post_scale vector of
                                   the convolution that consumes the lifted gradient); while it is formed the words behind the pair
                                   hold one maximum per workgroup of the producing pass */
@@ -878,6 +878,33 @@ int dlip_shuffle_dwpw_f32(const float* x, const float* dw_w, const float* dw_b, 
                           int32_t K, int32_t Kp, int32_t ldx, int32_t ldp, int32_t ldy, int32_t hp, int32_t par,
                           dlip_stream_t stream);
 int dlip_avgpool3_nhwc_f32(const float* x, float* y, int32_t N, int32_t H, int32_t W, int32_t C, dlip_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 52) Depthwise dilated temporal convolution of the depthwise-separable TCN heads (tcn_dwpw): the grouped Conv1d
+ * (groups = channels, bias=False) of models/video_models/tcn.py:33-34 (ConvBatchChompRelu, dwpw MS-TCN) and :158-159,169-170
+ * (TemporalBlock), exact fp32.  Channels-last x [B,T,C] fp32, C % 4 == 0, 16-byte aligned tensors; weights tap-major [k][C].
+ * One call serves 1 <= n <= 4 branches that read the same x (the kernel sizes of one dwpw MS-TCN stage); w, bias, slope, y, dz,
+ * dw, k, pad, t_out are HOST arrays of n entries.  Branch r:
+ *   z_r[b,t,c] = sum_j w_r[j,c] x[b, t - pad_r + j d, c] (zeros outside [0, T)),  t in [0, t_out_r).
+ * Eval (deeplip_amd.video): pad = (k-1)d/2, t_out = T (the symmetric chomp folded into "same" padding), the BatchNorm folded into
+ * w and bias, y = act(z + bias) with slope[c] the PReLU weight or 0 (ReLU); bias / slope NULL (or a NULL entry) = none.
+ * Train: pad = (k-1)d, t_out = T + (k-1)d, raw z (tcn.py:35-38: the BatchNorm's batch statistics cover the padded length).
+ *
+ * dlip_tcn_dw_dgrad_f32: dx[b,s,c] = sum_r sum_j w_r[j,c] dz_r[b, s + pad_r - j d, c] (zeros outside [0, t_out_r)); every branch's
+ *   gradient summed into one dx [B,T,C] in a fixed order.
+ * dlip_tcn_dw_wgrad_f32: dw_r[j,c] = sum_{b,t} dz_r[b,t,c] x[b, t - pad_r + j d, c]: fp64 partial sums over chunks of rows, then a
+ *   fixed-order fp64 sum of the chunks rounded once to fp32 -- two launches, no atomics, the same bits on every run.  workspace:
+ *   sum_r dlip_tcn_dw_wgrad_chunks(B * t_out_r) * k_r * C doubles (workspace_len = its size in doubles).
+ * ------------------------------------------------------------------------------------------ */
+int dlip_tcn_dw_fwd_f32(const float* x, int32_t n, const float* const* w, const float* const* bias, const float* const* slope,
+                        float* const* y, const int32_t* k, const int32_t* pad, const int32_t* t_out, int32_t B, int32_t T,
+                        int32_t C, int32_t d, dlip_stream_t stream);
+int dlip_tcn_dw_dgrad_f32(const float* const* dz, int32_t n, const float* const* w, const int32_t* k, const int32_t* pad,
+                          const int32_t* t_out, float* dx, int32_t B, int32_t T, int32_t C, int32_t d, dlip_stream_t stream);
+int dlip_tcn_dw_wgrad_chunks(int32_t rows);
+int dlip_tcn_dw_wgrad_f32(const float* x, int32_t n, const float* const* dz, float* const* dw, const int32_t* k, const int32_t* pad,
+                          const int32_t* t_out, int32_t B, int32_t T, int32_t C, int32_t d, double* workspace,
+                          int64_t workspace_len, dlip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Step plans.  The reference drives its encoders from a Python loop, one utterance and one torch.nn layer

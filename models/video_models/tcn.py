@@ -1,3 +1,3 @@
-"""Drop-in for the reference's models/video_models/tcn.py (multibranch MS-TCN)."""
+"""Drop-in for the reference's models/video_models/tcn.py (multibranch MS-TCN, single-branch TCN)."""
 from deeplip_amd.video import (Chomp1d, ConvBatchChompRelu, MultibranchTemporalBlock,  # noqa: F401
-                               MultibranchTemporalConvNet)
+                               MultibranchTemporalConvNet, TemporalBlock, TemporalConvNet)
