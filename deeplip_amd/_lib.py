@@ -13,7 +13,7 @@ import torch  # must be imported first: the library binds to the HIP runtime tor
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DLIP_LIB_PATH") or os.path.join(_PKG, "lib", "libdeeplip_hip.so")  # env override: A/B builds
-ABI_VERSION = 52
+ABI_VERSION = 53
 LIFT_WORDS = 4098
 LIFT_BCAST = 2048
 
@@ -174,6 +174,9 @@ SIGNATURES = {
     "dlip_tcn_dw_wgrad_f32": [c_f, c_i32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                               C.POINTER(C.c_int32), c_i32, c_i32, c_i32, c_i32, c_f, c_i64, c_stream],
     "dlip_avgpool3_nhwc_f32": [c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_stream],
+    "dlip_triplet_mine_f32": [c_f, c_f, C.c_float, c_i32, c_f, c_f, c_f, c_f, c_i32, c_i32, c_stream],
+    "dlip_triplet_loss_f32": [c_f, c_f, c_f, c_f, C.c_float, c_i32, c_f, c_f, c_f, c_f, c_f, c_i32, c_stream],
+    "dlip_triplet_loss_bwd_f32": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i32, c_i32, c_stream],
 }
 
 

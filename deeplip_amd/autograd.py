@@ -172,6 +172,35 @@ class MarginCELossFn(Function):
         return g, None, None, None
 
 
+class TripletLossFn(Function):
+    """OnlineTriplet (loss.py:18-31) with the mining on the device: forward = dlip_triplet_mine_f32 + dlip_triplet_loss_f32,
+    backward = dlip_triplet_loss_bwd_f32 (deeplip_amd/triplet.py).  Returns (loss, n_triplets): 0-dim fp32 and 0-dim int32 device
+    tensors, nothing is read back.  ``mine_margin`` is the selector's margin, ``margin`` the criterion's; ``u``: the draws of the
+    random / semi-hard modes (None otherwise)."""
+
+    @staticmethod
+    def forward(ctx, embeddings, labels, margin, mine_margin, mode, u):
+        from . import triplet as tp
+        x = embeddings.contiguous()
+        m = tp.mine(x, labels, mine_margin, mode, u)
+        loss, n, wcount = tp.loss_forward(m, margin)
+        ctx.save_for_backward(x, m.g, m.rownorm, wcount, n)
+        ctx.mark_non_differentiable(n)
+        return loss, n
+
+    @staticmethod
+    def backward(ctx, dloss, _dn):
+        from . import triplet as tp
+        x, g, rownorm, wcount, n = ctx.saved_tensors
+        dl = dloss.reshape(1).to(torch.float32).contiguous()       # stays on the device: no host read-back per step
+        dx = tp.loss_backward(x, tp.Mined(g, rownorm, None, None, 0), wcount, n, dl)
+        return dx, None, None, None, None, None
+
+
+def triplet_loss(embeddings, labels, margin, mine_margin, mode, u=None):
+    return TripletLossFn.apply(embeddings, labels, float(margin), float(mine_margin), int(mode), u)
+
+
 class AAMMarginFn(Function):
     """cos(theta) -> cos(theta + m) on the target column of cosine logits (ArcFace / AAM-softmax)."""
 

@@ -1,5 +1,5 @@
 """Speaker-classification criteria on the HIP engine: mirror of the reference's
-``models/audio_models/loss.py`` (LMCL = CosFace / AM-softmax, CrossEntropy).
+``models/audio_models/loss.py`` (LMCL = CosFace / AM-softmax, CrossEntropy, OnlineTriplet).
 
 ``forward(embeddings, labels) -> (loss, logits)`` exactly as the reference; both values come from
 ``dlip_logits_argmax_f32`` + ``dlip_margin_ce_loss_f32``.  ``predict`` adds the first-max argmax
@@ -102,6 +102,40 @@ class CrossEntropy(nn.Module):
             return ag.margin_ce_loss(logits, labels, 1.0, 0.0), logits
         loss, logits, _ = self.predict(embeddings, labels)
         return loss, logits
+
+
+class OnlineTriplet(nn.Module):
+    """loss.py:18-31: ``forward(embeddings, labels) -> (loss, n_triplets)`` with ``triplet_selector`` one of
+    deeplip_amd.triplet's selectors (the reference's names and constructors).  The selector names the mining mode; mining, loss and
+    backward are dlip_triplet_* launches that never leave the device, so a recorded training step can contain the criterion:
+    ``loss`` is a 0-dim fp32 device tensor (mean over the triplets of relu(cos(a,n) - cos(a,p) + margin)), ``n_triplets`` a 0-dim int32
+    device tensor (``int(n)`` is the reference's ``len(triplets)``; it synchronises, keep it out of a step).  With grad enabled the
+    call goes through ``autograd.TripletLossFn``; under ``torch.no_grad()`` the same forward launches run.
+
+    Zero triplets (no label twice in the batch, one label only, or no pair with a candidate): the reference's selector builds a
+    ragged array and fails (utils.py:114-118); here loss = 0, n_triplets = 0 and the gradient is all zeros -- no division by zero.
+    No parameters.  CPU tensors are refused (DeepLipHipError); E % 4 != 0, B > 1024 and float labels raise ValueError before any
+    launch."""
+
+    def __init__(self, margin, triplet_selector):
+        super().__init__()
+        from . import triplet as tp
+        if not isinstance(triplet_selector, tp.TripletSelector) or triplet_selector.mode is None:
+            raise TypeError("OnlineTriplet: triplet_selector must be one of deeplip_amd.triplet's selectors (AllTripletSelector, "
+                            "HardestNegativeTripletSelector, RandomNegativeTripletSelector, SemihardNegativeTripletSelector)")
+        self.margin = margin
+        self.triplet_selector = triplet_selector
+
+    def forward(self, embeddings, labels, u=None):
+        from . import autograd as ag, triplet as tp
+        tp.check_inputs(embeddings, labels)
+        sel = self.triplet_selector
+        if u is None:
+            u = sel.draws(embeddings)
+        if torch.is_grad_enabled() and embeddings.requires_grad:
+            return ag.triplet_loss(embeddings, labels, self.margin, sel.margin, sel.mode, u)
+        loss, n, _ = tp.loss_forward(tp.mine(embeddings, labels, sel.margin, sel.mode, u), float(self.margin))
+        return loss, n
 
 
 class _Stub(nn.Module):

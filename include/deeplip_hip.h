@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define DLIP_ABI_VERSION 52
+#define DLIP_ABI_VERSION 53
 #define DLIP_LIFT_WORDS 4098   /* a gradient's power-of-two lift: (2^e, 2^-e), then 2^-e repeated 2048 times (the post_scale vector of
                                   the convolution that consumes the lifted gradient); while it is formed the words behind the pair
                                   hold one maximum per workgroup of the producing pass */
@@ -905,6 +905,36 @@ int dlip_tcn_dw_wgrad_chunks(int32_t rows);
 int dlip_tcn_dw_wgrad_f32(const float* x, int32_t n, const float* const* dz, float* const* dw, const int32_t* k, const int32_t* pad,
                           const int32_t* t_out, int32_t B, int32_t T, int32_t C, int32_t d, double* workspace,
                           int64_t workspace_len, dlip_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 53) Online triplet loss with negative mining on the device: OnlineTriplet (models/audio_models/loss.py:18-31) and the
+ * triplet selectors (models/audio_models/utils.py:18-142: FunctionNegativeTripletSelector.get_triplets copies the embeddings to
+ * the host and runs one tensor index + one numpy call per anchor-positive pair; AllTripletSelector builds a Python list of every
+ * triplet).  Exact fp32, x [B,E] row-major, 1 <= B <= 1024, E % 4 == 0, 16-byte aligned; labels device int32 [B].  Shapes depend on
+ * B and E alone, nothing is read back, every sum has a fixed order (no float atomics): a replayed launch repeats the bits.
+ * mode: 0 = all triplets, 1 = hardest negative, 2 = random hard negative, 3 = semi-hard negative.
+ *
+ * dlip_triplet_mine_f32 (replaces utils.py:89-113): g [B,B] = x x^T, the RAW dot products the reference mines on (utils.py:93),
+ *   rownorm [B] = max(|x_i|, 1e-8) (F.cosine_similarity's clamp), and for mode != 0 the dense neg [B,B]: for an anchor-positive
+ *   pair a < p of equal label, neg[a,p] = the chosen n of another label, by v_n = (g[a,n] + margin) - g[a,p]:
+ *   hardest = argmax_n v_n (lowest index on ties) if that v > 0; random = candidate number floor(u[a,p] * count) in index order of
+ *   {n : v_n > 0}; semi-hard = the same of {n : 0 < v_n < margin}; -1 where the set is empty and everywhere else.  u [B,B]: uniform
+ *   draws in [0,1) (modes 2, 3; NULL otherwise).  mode 0 writes g and rownorm only (neg may be NULL).
+ * dlip_triplet_loss_f32 (replaces loss.py:28-31): loss[0] = mean over the triplets of relu(cos(a,n) - cos(a,p) + margin), cos(i,j) =
+ *   g[i,j] / (rownorm[i] rownorm[j]); n_triplets[0] = their number N.  N == 0: loss = 0 (the reference fails there, utils.py:114-118).
+ *   Scratch the caller owns: rowsum [B] fp64, rowcnt [B]; wcount [B,B] = per anchor row the signed count of ACTIVE triplets
+ *   (+1 per triplet in which column j is the negative, -1 per triplet in which it is the positive), kept for the backward pass.
+ * dlip_triplet_loss_bwd_f32: dx [B,E] = gscale[0] * d loss / d x (gscale NULL = 1): with S = wcount + wcount^T (the transposed half is
+ *   read, not scattered), M_ij = S_ij gscale / (N rownorm_i rownorm_j), M_ii = -sum_j M_ij g_ij / rownorm_i^2, dx = M x.  mw: scratch
+ *   of B * (B rounded up to 16) floats, 16-byte aligned.  N == 0: dx = 0.
+ * ------------------------------------------------------------------------------------------ */
+int dlip_triplet_mine_f32(const float* x, const int32_t* labels, float margin, int32_t mode, const float* u, float* g,
+                          float* rownorm, int32_t* neg, int32_t B, int32_t E, dlip_stream_t stream);
+int dlip_triplet_loss_f32(const float* g, const float* rownorm, const int32_t* labels, const int32_t* neg, float margin,
+                          int32_t mode, double* rowsum, int32_t* rowcnt, int32_t* wcount, float* loss, int32_t* n_triplets,
+                          int32_t B, dlip_stream_t stream);
+int dlip_triplet_loss_bwd_f32(const float* x, const float* g, const float* rownorm, const int32_t* wcount, const int32_t* n_triplets,
+                              const float* gscale, float* mw, float* dx, int32_t B, int32_t E, dlip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Step plans.  The reference drives its encoders from a Python loop, one utterance and one torch.nn layer

@@ -9,6 +9,9 @@ available as ``eer_cos`` / ``score_fusion`` / ``feature_fusion_scores``."""
 from deeplip_amd.scoring import (EmbeddingTable, cosine_scores, eer_cos, eer_from_scores,  # noqa: F401
                                  feature_fusion_scores, read_trial_list, roc_curve, score_fusion)
 from deeplip_amd.scoring_entry import AUDIO_DEFAULTS as _DEFAULTS, make_entry_points as _make, set_paths  # noqa: F401
+from deeplip_amd.triplet import (AllTripletSelector, FunctionNegativeTripletSelector, HardestNegativeTripletSelector,  # noqa: F401
+                                 RandomNegativeTripletSelector, SemihardNegativeTripletSelector, TripletSelector, hardest_negative,
+                                 random_hard_negative, semihard_negative)      # utils.py:18-142, mined on the device
 import numpy as np
 
 

@@ -40,7 +40,30 @@ sys.path.insert(0, ROOT)
 from deeplip_amd import _lib, arith, dist as ddist, ops, scoring, weightgen as wg  # noqa: E402
 from deeplip_amd.synthetic import SyntheticAVSet, synthetic_trials  # noqa: E402
 from models.audio_models import tdnn  # noqa: E402
-from models.audio_models.loss import AAMSoftmax, LMCL, CrossEntropy  # noqa: E402
+from models.audio_models.loss import AAMSoftmax, LMCL, CrossEntropy, OnlineTriplet  # noqa: E402
+
+
+def build_criterion(train_opts, embedding_dim, n_spk):
+    """The criterion ``train.loss`` names (train_audio.py:90-97; host-side construction, no GPU needed).  ``LMCL`` and ``AAMSoftmax``
+    start at ``train.margin[0]``; ``Triplet`` (conf/audio_config.yaml:130 lists it, the reference's trainer never builds it) is
+    OnlineTriplet on the build-owned block ``train.triplet: {margin: 0.2, selector: hardest | semihard | random | all}`` (absent
+    block or key: those defaults; one margin for mining and loss); every other value is CrossEntropy, as upstream."""
+    kind = train_opts["loss"]
+    if kind == "LMCL":
+        return LMCL(embedding_dim, n_spk, train_opts["scale"], train_opts["margin"][0])
+    if kind == "AAMSoftmax":                                            # a stub upstream (loss.py:62-67); ArcFace here
+        return AAMSoftmax(embedding_dim, n_spk, train_opts["scale"], train_opts["margin"][0])
+    if kind == "Triplet":
+        from deeplip_amd.triplet import make_selector
+        t = train_opts.get("triplet") or {}
+        unknown = sorted(set(t) - {"margin", "selector"})
+        if unknown:
+            raise ValueError(f"train.triplet: unknown key(s) {unknown}; expected margin, selector")
+        if train_opts.get("freeze_encoder", False):
+            raise ValueError("train.loss: Triplet has no parameters of its own: train.freeze_encoder would leave nothing to train")
+        margin = float(t.get("margin", 0.2))
+        return OnlineTriplet(margin, make_selector(str(t.get("selector", "hardest")), margin))
+    return CrossEntropy(embedding_dim, n_spk)
 
 
 class Trainer(object):
@@ -87,18 +110,16 @@ class Trainer(object):
         self.model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
         self.model.eval().to(self.device)
         E = self.model_opts[arch]["embedding_dim"]
-        if self.train_opts["loss"] == "LMCL":
+        self.criterion = build_criterion(self.train_opts, E, d["n_spk"]).to(self.device)
+        if isinstance(self.criterion, (LMCL, AAMSoftmax)):
             self.init_margin, self.end_margin = self.train_opts["margin"]
-            self.criterion = LMCL(E, d["n_spk"], self.train_opts["scale"], self.init_margin).to(self.device)
-        elif self.train_opts["loss"] == "AAMSoftmax":                       # a stub upstream (loss.py:62-67); ArcFace here
-            self.init_margin, self.end_margin = self.train_opts["margin"]
-            self.criterion = AAMSoftmax(E, d["n_spk"], self.train_opts["scale"], self.init_margin).to(self.device)
-        else:
-            self.criterion = CrossEntropy(E, d["n_spk"]).to(self.device)
+        self.triplet = isinstance(self.criterion, OnlineTriplet)
         o = self.train_opts["sgd"]
         self.freeze_encoder = bool(self.train_opts.get("freeze_encoder", False))
         groups = [{"params": self.criterion.parameters()}] if self.freeze_encoder else \
                  [{"params": self.model.parameters()}, {"params": self.criterion.parameters()}]   # train_audio.py:112
+        if self.triplet:
+            groups = groups[:1]         # OnlineTriplet has no parameters: the optimiser gets the model's alone
         # train.graph_step (default on): the optimisation step is recorded once per crop length and replayed as one HIP graph
         # (deeplip_amd/train_plan.py); a recorded step reads its learning rate from a device tensor, which MultiStepLR updates in
         # place, and takes the fused SGD kernel.  train.graph_step: false keeps the loop of eager launches.
@@ -223,7 +244,8 @@ class Trainer(object):
             else:
                 loss, logits = self._one_step(x, lab)
             acc[0] += loss.detach().double() * x.shape[0]
-            acc[1] += (torch.max(logits.detach(), dim=1)[1] == lab).sum()
+            # (OnlineTriplet returns the number of triplets, a device scalar, where the classifiers return logits)
+            acc[1] += logits.detach().double() if self.triplet else (torch.max(logits.detach(), dim=1)[1] == lab).sum()
             acc[2] += x.shape[0]
             staged = stage(i + 1) if i + 1 < steps else None
         if recorded:
@@ -232,7 +254,9 @@ class Trainer(object):
         _lib.check_range(sync=True)                       # f16x3 packing: an overflow in this epoch is an error, not a NaN
         dt = time.perf_counter() - t0
         tot, correct, n = ddist.allreduce_metrics([tot, correct, n], self.device)
-        self.last_epoch_stats = {"loss": tot / n, "acc": correct / n, "utt_per_s": n / dt, "steps": steps, "bs": bs * self.world,
+        # Triplet: there are no logits, hence no accuracy; the statistics carry the mean number of triplets per step (and rank) instead
+        quality = {"triplets": correct / max(steps * self.world, 1)} if self.triplet else {"acc": correct / n}
+        self.last_epoch_stats = {"loss": tot / n, **quality, "utt_per_s": n / dt, "steps": steps, "bs": bs * self.world,
                                  "step_mode": (self._steps.mode if recorded else "eager"), "crop_ladder": [int(t) for t in ladder]}
         self.model.eval()
         return tot / n
@@ -243,8 +267,9 @@ class Trainer(object):
             self._adjust_margin()
             loss = self._train_epoch()
             st = self.last_epoch_stats
-            print("Epoch {} loss {:.4f} acc {:.3f} ({:.0f} utt/s, {} steps of {})".format(epoch, loss, st["acc"], st["utt_per_s"],
-                                                                                     st["steps"], st["bs"]), flush=True)
+            quality = "triplets/step {:.0f}".format(st["triplets"]) if self.triplet else "acc {:.3f}".format(st["acc"])
+            print("Epoch {} loss {:.4f} {} ({:.0f} utt/s, {} steps of {})".format(epoch, loss, quality, st["utt_per_s"],
+                                                                              st["steps"], st["bs"]), flush=True)
             self.lr_scheduler.step()
             self.save()
             if ddist.active():
