@@ -201,6 +201,33 @@ def triplet_loss(embeddings, labels, margin, mine_margin, mode, u=None):
     return TripletLossFn.apply(embeddings, labels, float(margin), float(mine_margin), int(mode), u)
 
 
+class BilinearPoolFn(Function):
+    """z = mean over k of (e1 U) * (e2 V) (deeplip_amd.fusion.BNBilinear; csrc/bilinear_ops.hip).  The forward keeps P = e1 U and
+    Q = e2 V (2 B k o floats) instead of computing them again in the backward; dU / dV come from one launch that forms dP, dQ on load,
+    de1 / de2 from a second launch that is made only when an embedding asks for its gradient (train_fusion freezes the encoders)."""
+
+    @staticmethod
+    def forward(ctx, e1, e2, U, V, k):
+        e1, e2, U, V = e1.contiguous(), e2.contiguous(), U.contiguous(), V.contiguous()
+        z, P, Q = ops.bilinear_pool(e1, e2, U, V, k, save=True)
+        ctx.save_for_backward(e1, e2, U, V, P, Q)
+        ctx.k = int(k)
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        e1, e2, U, V, P, Q = ctx.saved_tensors
+        dz = dz.contiguous()
+        need = ctx.needs_input_grad
+        de1, de2 = ops.bilinear_pool_bwd_x(P, Q, dz, U, V, ctx.k, need[0], need[1]) if (need[0] or need[1]) else (None, None)
+        dU, dV = ops.bilinear_pool_bwd_w(e1, e2, P, Q, dz, ctx.k) if (need[2] or need[3]) else (None, None)
+        return de1, de2, dU if need[2] else None, dV if need[3] else None, None
+
+
+def bilinear_pool(e1, e2, U, V, k):
+    return BilinearPoolFn.apply(e1, e2, U, V, int(k))
+
+
 class AAMMarginFn(Function):
     """cos(theta) -> cos(theta + m) on the target column of cosine logits (ArcFace / AAM-softmax)."""
 

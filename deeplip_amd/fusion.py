@@ -1,5 +1,5 @@
 """Fusion heads on the HIP engine: mirror of ``models/fusion_models/model_fusion.py`` (Linearfusion)
-and ``models/fusion_models/LBP.py`` (LowFER), plus the test-time fusion the reference actually
+and ``models/fusion_models/LBP.py`` (LowFER, and the BNBilinear head its trainer asks for), plus the test-time fusion the reference actually
 uses for scoring: per-modality z-norm + concat (train_fusion.py:233-238,353-358)."""
 from __future__ import annotations
 
@@ -67,6 +67,48 @@ class LowFER(nn.Module):
 
     def forward(self, e1, e2):
         return ops.lowfer_cat(e1.contiguous(), e2.contiguous())
+
+
+class BNBilinear(nn.Module):
+    """``LBP.BNBilinear(d1, d2, o)``: the head the reference's train_fusion.py:84 builds and its LBP.py does not define.  Build-owned
+    (there is nothing upstream to pin it to); it follows the live and commented lines of LBP.py:38-44 in their order, without the
+    signed square root of :42 (its derivative is unbounded at 0):
+
+        P = e1 @ U, Q = e2 @ V                      U [d1, k o], V [d2, k o]: LowFER's names, shapes and uniform(-1, 1) start
+        z = (P * Q).view(-1, o, k).mean(-1)         low-rank bilinear pooling
+        out = bn1(F.normalize(z, p=2, dim=-1))      BatchNorm1d(o): batch statistics in train mode, folded in eval mode
+
+    The product runs on csrc/bilinear_ops.hip (exact fp32 MFMA under every arithmetic mode, hence the f32 pack precision below);
+    train mode composes autograd.bilinear_pool with the engine's L2-normalise and BatchNorm Functions."""
+
+    def __init__(self, d1, d2, o, k=30):
+        super().__init__()
+        d1, d2, o, k = int(d1), int(d2), int(o), int(k)
+        if d1 < 4 or d2 < 4 or d1 % 4 or d2 % 4:
+            raise ValueError(f"BNBilinear: embedding widths ({d1}, {d2}) must be positive multiples of 4")
+        if o < 1 or k < 1:
+            raise ValueError(f"BNBilinear: o = {o} and k = {k} must be positive")
+        self.U = nn.Parameter(torch.tensor(np.random.uniform(-1, 1, (d1, k * o)), dtype=torch.float))
+        self.V = nn.Parameter(torch.tensor(np.random.uniform(-1, 1, (d2, k * o)), dtype=torch.float))
+        self.bn1 = BatchNormParams(o)
+        self.d1, self.d2, self.k, self.o = d1, d2, k, o
+        self.__dict__["_dlip_precision"] = "f32"      # packing.state_version: its pack is the same under every mode
+
+    def _pack(self, device):
+        scale, shift = packing.bn_scale_shift(self.bn1)
+        return {"scale": packing._dev(scale, device), "shift": packing._dev(shift, device)}
+
+    def forward(self, e1, e2):
+        e1, e2 = e1.contiguous(), e2.contiguous()
+        U, V = self.U.contiguous(), self.V.contiguous()
+        ops.bilinear_check(e1, e2, U.detach(), V.detach(), self.k)
+        if self.training:
+            if e1.shape[0] < 2:
+                raise ValueError("BNBilinear: train mode needs at least two rows (BatchNorm1d's batch statistics)")
+            from . import autograd as ag
+            return ag.bn_act_train(ag.l2_normalize(ag.bilinear_pool(e1, e2, U, V, self.k), 1e-12), self.bn1, 1.0)
+        p = _cached_pack(self, e1.device, self._pack)
+        return ops.bilinear_finish(ops.bilinear_pool(e1, e2, U.detach(), V.detach(), self.k), p["scale"], p["shift"], 1e-12)
 
 
 def feature_normalize(data: torch.Tensor) -> torch.Tensor:

@@ -830,3 +830,69 @@ def lowfer_cat(e1: Tensor, e2: Tensor) -> Tensor:
     y = _empty((B, 3 * D), e1.device)
     check(lib().dlip_lowfer_cat_f32(ptr(e1), ptr(e2), ptr(y), B, D, stream_handle()), "dlip_lowfer_cat_f32")
     return y
+
+
+# ---- low-rank bilinear pooling (csrc/bilinear_ops.hip, ABI 54): the product of deeplip_amd.fusion.BNBilinear ----
+def bilinear_check(e1: Tensor, e2: Tensor, U: Tensor, V: Tensor, k: int):
+    """The kernels' limits, refused on the host before any launch: fp32 contiguous device tensors, e1 [B,d1], e2 [B,d2] of one
+    batch size, U [d1, k o], V [d2, k o], d1 % 4 == 0, d2 % 4 == 0 (16-byte loads along the embeddings).  Returns (B, d1, d2, o)."""
+    for t, name in ((e1, "e1"), (e2, "e2"), (U, "U"), (V, "V")):
+        if not isinstance(t, Tensor) or not t.is_cuda:
+            raise _lib.DeepLipHipError(f"{name}: expected a CUDA (ROCm) tensor; deeplip_amd has no CPU path")
+        if t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous():
+            raise ValueError(f"{name}: expected a contiguous float32 matrix, got {t.dtype} {tuple(t.shape)}")
+    (B, d1), (B2, d2) = e1.shape, e2.shape
+    if B != B2:
+        raise ValueError(f"bilinear pooling: e1 has {B} rows, e2 {B2}")
+    if B < 1 or d1 < 4 or d2 < 4 or d1 % 4 or d2 % 4:
+        raise ValueError(f"bilinear pooling: embedding widths ({d1}, {d2}) must be positive multiples of 4 and the batch non-empty")
+    k = int(k)
+    if k < 1 or U.shape[0] != d1 or V.shape[0] != d2 or U.shape[1] != V.shape[1] or U.shape[1] % k or U.shape[1] == 0:
+        raise ValueError(f"bilinear pooling: U {tuple(U.shape)} / V {tuple(V.shape)} do not fit e1 [*,{d1}], e2 [*,{d2}] and k = {k}")
+    return B, d1, d2, U.shape[1] // k
+
+
+def bilinear_pool(e1: Tensor, e2: Tensor, U: Tensor, V: Tensor, k: int, save: bool = False):
+    """z [B,o] = mean over k of (e1 U) * (e2 V) in one launch.  ``save``: also returns P = e1 U and Q = e2 V [B, k o]."""
+    B, d1, d2, o = bilinear_check(e1, e2, U, V, k)
+    z = _empty((B, o), e1.device)
+    P = _empty((B, k * o), e1.device) if save else None
+    Q = _empty((B, k * o), e1.device) if save else None
+    check(lib().dlip_bilinear_pool_f32(ptr(e1), ptr(e2), ptr(U), ptr(V), ptr(z), ptr(P), ptr(Q), B, d1, d2, o, int(k), stream_handle()),
+          "dlip_bilinear_pool_f32")
+    return (z, P, Q) if save else z
+
+
+def bilinear_pool_bwd_w(e1: Tensor, e2: Tensor, P: Tensor, Q: Tensor, dz: Tensor, k: int):
+    """(dU [d1, k o], dV [d2, k o]) of bilinear_pool."""
+    B, d1 = e1.shape
+    d2, o = e2.shape[1], dz.shape[1]
+    _req(dz, "dz")
+    dU = _empty((d1, k * o), e1.device)
+    dV = _empty((d2, k * o), e1.device)
+    check(lib().dlip_bilinear_pool_bwd_w_f32(ptr(e1), ptr(e2), ptr(P), ptr(Q), ptr(dz), ptr(dU), ptr(dV), B, d1, d2, o, int(k),
+                                             stream_handle()), "dlip_bilinear_pool_bwd_w_f32")
+    return dU, dV
+
+
+def bilinear_pool_bwd_x(P: Tensor, Q: Tensor, dz: Tensor, U: Tensor, V: Tensor, k: int, want1: bool = True, want2: bool = True):
+    """(de1 [B,d1], de2 [B,d2]) of bilinear_pool; an output that is not wanted is None and not computed."""
+    B, o = dz.shape
+    d1, d2 = U.shape[0], V.shape[0]
+    _req(dz, "dz")
+    de1 = _empty((B, d1), dz.device) if want1 else None
+    de2 = _empty((B, d2), dz.device) if want2 else None
+    if want1 or want2:
+        check(lib().dlip_bilinear_pool_bwd_x_f32(ptr(P), ptr(Q), ptr(dz), ptr(U), ptr(V), ptr(de1), ptr(de2), B, d1, d2, o, int(k),
+                                                 stream_handle()), "dlip_bilinear_pool_bwd_x_f32")
+    return de1, de2
+
+
+def bilinear_finish(z: Tensor, scale: Tensor, shift: Tensor, eps: float = 1e-12) -> Tensor:
+    """F.normalize(z) * scale + shift on [B,o]: the row norm and the folded eval-mode BatchNorm1d in one launch."""
+    _req(z, "z"); _req(scale, "scale"); _req(shift, "shift")
+    B, o = z.shape
+    out = _empty((B, o), z.device)
+    check(lib().dlip_bilinear_finish_f32(ptr(z), ptr(scale), ptr(shift), ptr(out), B, o, float(eps), stream_handle()),
+          "dlip_bilinear_finish_f32")
+    return out

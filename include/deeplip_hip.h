@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define DLIP_ABI_VERSION 53
+#define DLIP_ABI_VERSION 54
 #define DLIP_LIFT_WORDS 4098   /* a gradient's power-of-two lift: (2^e, 2^-e), then 2^-e repeated 2048 times (the post_scale vector of
                                   the convolution that consumes the lifted gradient); while it is formed the words behind the pair
                                   hold one maximum per workgroup of the producing pass */
@@ -935,6 +935,30 @@ int dlip_triplet_loss_f32(const float* g, const float* rownorm, const int32_t* l
                           int32_t B, dlip_stream_t stream);
 int dlip_triplet_loss_bwd_f32(const float* x, const float* g, const float* rownorm, const int32_t* wcount, const int32_t* n_triplets,
                               const float* gscale, float* mw, float* dx, int32_t B, int32_t E, dlip_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 54) Low-rank bilinear pooling, the product of deeplip_amd.fusion.BNBilinear (the head train_fusion.py:84 of the reference
+ * names and LBP.py does not define; LBP.py:38-44 without the signed square root).  e1 [B,d1], e2 [B,d2], u [d1, k o], v [d2, k o],
+ * all fp32 row-major and 16-byte aligned; d1 % 4 == 0, d2 % 4 == 0, any k >= 1, o >= 1, B >= 1.  Exact fp32 on the fp32 MFMA under
+ * every arithmetic mode; every sum has a fixed order (no reduction split over workgroups, no float atomics): a replayed launch
+ * repeats the bits.
+ *
+ * dlip_bilinear_pool_f32: z[b,j] = (1/k) sum_{i<k} P[b, j k + i] Q[b, j k + i] with P = e1 u, Q = e2 v, one launch.  p, q
+ *   (both NULL, or both [B, k o]): P and Q are also written, for the backward pass.
+ * dlip_bilinear_pool_bwd_w_f32: du [d1, k o] = e1^T dP, dv [d2, k o] = e2^T dQ, where dP[b,n] = dz[b, n / k] / k * q[b,n] and dQ
+ *   likewise with p are formed on load.  One workgroup owns a 64-column stripe of both and reduces over B by itself.
+ * dlip_bilinear_pool_bwd_x_f32: de1 [B,d1] = dP u^T, de2 [B,d2] = dQ v^T; either output may be NULL (not both).
+ * dlip_bilinear_finish_f32: out[b,j] = z[b,j] / max(|z_b|_2, eps) * scale[j] + shift[j] on [B,o]: F.normalize followed by an
+ *   eval-mode BatchNorm1d folded into scale and shift.
+ * ------------------------------------------------------------------------------------------ */
+int dlip_bilinear_pool_f32(const float* e1, const float* e2, const float* u, const float* v, float* z, float* p, float* q, int32_t B,
+                           int32_t d1, int32_t d2, int32_t o, int32_t k, dlip_stream_t stream);
+int dlip_bilinear_pool_bwd_w_f32(const float* e1, const float* e2, const float* p, const float* q, const float* dz, float* du, float* dv,
+                                 int32_t B, int32_t d1, int32_t d2, int32_t o, int32_t k, dlip_stream_t stream);
+int dlip_bilinear_pool_bwd_x_f32(const float* p, const float* q, const float* dz, const float* u, const float* v, float* de1, float* de2,
+                                 int32_t B, int32_t d1, int32_t d2, int32_t o, int32_t k, dlip_stream_t stream);
+int dlip_bilinear_finish_f32(const float* z, const float* scale, const float* shift, float* out, int32_t B, int32_t o, float eps,
+                             dlip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Step plans.  The reference drives its encoders from a Python loop, one utterance and one torch.nn layer

@@ -133,6 +133,10 @@ class Trainer(object):
         elif kind == "lowfer":    # LBP.LowFER as shipped: cat[e1, sigmoid(e2), sigmoid(e2)*e1]
             self.model_fusion = LBP.LowFER(self.embedding_dim, self.embedding_dim, 512)
             fused_dim = 3 * self.embedding_dim
+        elif kind == "bilinear":  # the head upstream's train_fusion.py:84 asks for: low-rank bilinear pooling + L2 norm + BatchNorm
+            b = self.model_opts.get("bilinear") or {}
+            fused_dim = int(b.get("out_dim", 512))
+            self.model_fusion = LBP.BNBilinear(self.embedding_dim, self.embedding_dim, fused_dim, k=int(b.get("rank", 30)))
         elif kind == "concat":
             self.model_fusion = torch.nn.Identity()
             fused_dim = 2 * self.embedding_dim
@@ -230,7 +234,7 @@ class Trainer(object):
         return xv_audio, em_video
 
     def _fuse(self, xv_audio, em_video):
-        if self.fusion_kind == "lowfer":
+        if self.fusion_kind in ("lowfer", "bilinear"):      # the two-input heads take the embeddings apart
             return self.model_fusion(xv_audio, em_video)
         return self.model_fusion(torch.cat([xv_audio, em_video], dim=1).contiguous())
 
