@@ -228,6 +228,36 @@ def bilinear_pool(e1, e2, U, V, k):
     return BilinearPoolFn.apply(e1, e2, U, V, int(k))
 
 
+class CompactBilinearFn(Function):
+    """cbp = D * (count sketch of x1) circularly convolved with (count sketch of x2) (deeplip_amd.fusion.CompactBilinearPooling;
+    csrc/compact_bilinear_ops.hip).  The forward keeps psi1 and psi2 only when an input asks for its gradient; the sketches are
+    constants (``p1``, ``p2``: ops.compact_bilinear_pack), so with frozen inputs there is no backward launch at all."""
+
+    @staticmethod
+    def forward(ctx, x1, x2, p1, p2, sum_pool):
+        need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        ctx.p1, ctx.p2, ctx.sum_pool, ctx.shapes = p1, p2, bool(sum_pool), (tuple(x1.shape), tuple(x2.shape))
+        if not need:
+            return ops.compact_bilinear(x1, x2, p1, p2, sum_pool)
+        out, psi1, psi2 = ops.compact_bilinear(x1, x2, p1, p2, sum_pool, save=True)
+        ctx.save_for_backward(psi1, psi2)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        need = ctx.needs_input_grad
+        if not (need[0] or need[1]):
+            return None, None, None, None, None
+        psi1, psi2 = ctx.saved_tensors
+        dx1, dx2 = ops.compact_bilinear_bwd(g.contiguous(), psi1, psi2, ctx.p1, ctx.p2, ctx.shapes[0], ctx.shapes[1], ctx.sum_pool,
+                                            need[0], need[1])
+        return dx1, dx2, None, None, None
+
+
+def compact_bilinear(x1, x2, p1, p2, sum_pool=True):
+    return CompactBilinearFn.apply(x1, x2, p1, p2, bool(sum_pool))
+
+
 class AAMMarginFn(Function):
     """cos(theta) -> cos(theta + m) on the target column of cosine logits (ArcFace / AAM-softmax)."""
 

@@ -1,5 +1,6 @@
 """Fusion heads on the HIP engine: mirror of ``models/fusion_models/model_fusion.py`` (Linearfusion)
-and ``models/fusion_models/LBP.py`` (LowFER, and the BNBilinear head its trainer asks for), plus the test-time fusion the reference actually
+and ``models/fusion_models/LBP.py`` (LowFER, and the BNBilinear head its trainer asks for) and of the lost
+``models/fusion_models/compact_bilinear_pooling.py`` (CompactBilinearPooling), plus the test-time fusion the reference actually
 uses for scoring: per-modality z-norm + concat (train_fusion.py:233-238,353-358)."""
 from __future__ import annotations
 
@@ -109,6 +110,89 @@ class BNBilinear(nn.Module):
             return ag.bn_act_train(ag.l2_normalize(ag.bilinear_pool(e1, e2, U, V, self.k), 1e-12), self.bn1, 1.0)
         p = _cached_pack(self, e1.device, self._pack)
         return ops.bilinear_finish(ops.bilinear_pool(e1, e2, U.detach(), V.detach(), self.k), p["scale"], p["shift"], 1e-12)
+
+
+class CompactBilinearPooling(nn.Module):
+    """``CompactBilinearPooling(in_channels1, in_channels2, out_channels, sum_pool=True)``: the head the reference's
+    train_fusion.py:31-32,83 imports and builds; upstream ships no source for it any more.  Constructor, attribute names and
+    state-dict keys are upstream's:
+
+        tensor_sketch1 [C1, D], tensor_sketch2 [C2, D]      count sketches, requires_grad=False: row i is s[i] = +-1 at column h[i]
+        psi1 = x1.permute(0,2,3,1) @ tensor_sketch1, psi2 likewise
+        cbp  = irfft(rfft(psi1) * rfft(psi2), n=D) * D      = D * (psi1 circularly convolved with psi2)
+        return cbp.sum(dim=[1,2]) if sum_pool else cbp      [B,D] or [B,H,W,D]
+
+    The hashes come from torch's global generator in the order h1, s1, h2, s2 (h: randint(D, (C,)), s: 2 randint(2, (C,)) - 1), so
+    torch.manual_seed reproduces a head and a checkpoint carries its hashes.  The kernels (csrc/compact_bilinear_ops.hip) never
+    touch the dense matrices: the pack is h, s and their bin-sorted lists, re-read from the parameters whenever these change
+    (load_state_dict); a sketch that is not one +-1 per row is refused there.  [B,C] inputs are taken as one position (build-owned:
+    upstream's permute needs 4-D)."""
+
+    def __init__(self, in_channels1, in_channels2, out_channels, sum_pool=True):
+        super().__init__()
+        c1, c2, d = int(in_channels1), int(in_channels2), int(out_channels)
+        if c1 < 1 or c2 < 1 or not 1 <= d <= ops.CBP_MAX_D:
+            raise ValueError(f"CompactBilinearPooling: channels ({c1}, {c2}) must be positive and out_channels = {d} in 1 .. {ops.CBP_MAX_D}")
+        self.in_channels1, self.in_channels2, self.out_channels, self.sum_pool = c1, c2, d, bool(sum_pool)
+        h1, s1 = self._draw(c1, d)
+        h2, s2 = self._draw(c2, d)
+        self.tensor_sketch1 = nn.Parameter(self.generate_tensor_sketch(h1, s1, d), requires_grad=False)
+        self.tensor_sketch2 = nn.Parameter(self.generate_tensor_sketch(h2, s2, d), requires_grad=False)
+        self.__dict__["_dlip_precision"] = "f32"      # packing.state_version: its pack is the same under every mode
+
+    @staticmethod
+    def _draw(c, d):
+        h = torch.randint(d, (c,))
+        s = 2 * torch.randint(2, (c,), dtype=torch.float32) - 1
+        return h, s
+
+    @staticmethod
+    def generate_tensor_sketch(rand_h, rand_s, out_channels):
+        sketch = torch.zeros(rand_h.numel(), int(out_channels), dtype=torch.float32)
+        sketch[torch.arange(rand_h.numel()), rand_h.long()] = rand_s.float()
+        return sketch
+
+    def _pack(self, device):
+        return {"s1": ops.compact_bilinear_pack(packing._dev(self.tensor_sketch1, device), "tensor_sketch1"),
+                "s2": ops.compact_bilinear_pack(packing._dev(self.tensor_sketch2, device), "tensor_sketch2")}
+
+    def forward(self, x1, x2):
+        for t, name in ((x1, "x1"), (x2, "x2")):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise ops._lib.DeepLipHipError(f"{name}: expected a CUDA (ROCm) tensor; deeplip_amd has no CPU path")
+        p = _cached_pack(self, x1.device, self._pack)
+        ops.compact_bilinear_check(x1, x2, p["s1"], p["s2"])
+        from . import autograd as ag
+        return ag.compact_bilinear(x1, x2, p["s1"], p["s2"], self.sum_pool)
+
+
+class BNCompactBilinear(nn.Module):
+    """The trainer's compact bilinear head (``model.fusion: compact_bilinear``): bn1(F.normalize(cbp(e1, e2))), the tail of
+    BNBilinear behind CompactBilinearPooling(d1, d2, o).  The raw layer's outputs scale with D |e1| |e2|; the row norm and the
+    BatchNorm1d(o) are what make them usable in front of CrossEntropy / LMCL.  The signed square root that usually precedes the
+    norm is not built, for BNBilinear's reason (its derivative is unbounded at 0).  Build-owned; trains only bn1 (the sketches are
+    constants)."""
+
+    def __init__(self, d1, d2, o):
+        super().__init__()
+        self.cbp = CompactBilinearPooling(d1, d2, o)
+        self.bn1 = BatchNormParams(int(o))
+        self.d1, self.d2, self.o = int(d1), int(d2), int(o)
+        self.__dict__["_dlip_precision"] = "f32"
+
+    def _pack(self, device):
+        scale, shift = packing.bn_scale_shift(self.bn1)
+        return {"scale": packing._dev(scale, device), "shift": packing._dev(shift, device)}
+
+    def forward(self, e1, e2):
+        if self.training:
+            if isinstance(e1, torch.Tensor) and e1.is_cuda and e1.shape[0] < 2:
+                raise ValueError("BNCompactBilinear: train mode needs at least two rows (BatchNorm1d's batch statistics)")
+            from . import autograd as ag
+            return ag.bn_act_train(ag.l2_normalize(self.cbp(e1, e2), 1e-12), self.bn1, 1.0)
+        z = self.cbp(e1, e2)
+        p = _cached_pack(self, e1.device, self._pack)
+        return ops.bilinear_finish(z, p["scale"], p["shift"], 1e-12)
 
 
 def feature_normalize(data: torch.Tensor) -> torch.Tensor:

@@ -896,3 +896,82 @@ def bilinear_finish(z: Tensor, scale: Tensor, shift: Tensor, eps: float = 1e-12)
     check(lib().dlip_bilinear_finish_f32(ptr(z), ptr(scale), ptr(shift), ptr(out), B, o, float(eps), stream_handle()),
           "dlip_bilinear_finish_f32")
     return out
+
+
+# ---- compact bilinear pooling (csrc/compact_bilinear_ops.hip, ABI 55): deeplip_amd.fusion.CompactBilinearPooling ----
+CBP_MAX_D = 4096
+
+
+def compact_bilinear_pack(sketch: Tensor, name: str = "tensor_sketch") -> dict:
+    """What the kernels read instead of the dense count sketch [C, D]: h [C] (the column of row i's nonzero) and s [C] (its sign), and
+    the same sorted by bin: rowptr [D+1], idx [C] (ascending within a bin), sgn [C] = s[idx].  Built on the sketch's own device at
+    pack time.  A sketch that is not exactly one +-1 per row (a loaded checkpoint, say) raises ValueError naming the first such row:
+    there is no dense fallback."""
+    S = sketch.detach()
+    if S.dim() != 2 or S.dtype != torch.float32 or S.shape[0] < 1 or not 1 <= S.shape[1] <= CBP_MAX_D:
+        raise ValueError(f"{name}: expected a float32 count sketch [C >= 1, 1 <= D <= {CBP_MAX_D}], got {S.dtype} {tuple(S.shape)}")
+    C, D = S.shape
+    nz = (S != 0).sum(dim=1)
+    h = S.abs().argmax(dim=1)
+    s = S.gather(1, h[:, None])[:, 0]
+    bad = ((nz != 1) | (s.abs() != 1)).nonzero()
+    if bad.numel():
+        i = int(bad[0])
+        raise ValueError(f"{name}: row {i} holds {int(nz[i])} nonzero(s), largest {float(s[i])}; a count sketch row is a single +1 or -1")
+    idx = torch.sort(h, stable=True).indices
+    rowptr = torch.zeros(D + 1, dtype=torch.int64, device=S.device)
+    rowptr[1:] = torch.cumsum(torch.bincount(h, minlength=D), 0)
+    i32 = lambda t: t.to(torch.int32).contiguous()
+    return {"h": i32(h), "s": s.contiguous(), "rowptr": i32(rowptr), "idx": i32(idx), "sgn": s[idx].contiguous(), "C": C, "D": D}
+
+
+def compact_bilinear_check(x1: Tensor, x2: Tensor, p1: dict, p2: dict):
+    """The kernels' limits, refused on the host before any launch: fp32 contiguous device tensors [B,C,H,W] (or [B,C]: one position)
+    of equal B, H, W, channel counts that are the sketches' and one D in 1 .. 4096.  Returns (B, C1, C2, P, D)."""
+    for t, name in ((x1, "x1"), (x2, "x2")):
+        if not isinstance(t, Tensor) or not t.is_cuda:
+            raise _lib.DeepLipHipError(f"{name}: expected a CUDA (ROCm) tensor; deeplip_amd has no CPU path")
+        if t.dtype != torch.float32 or t.dim() not in (2, 4) or not t.is_contiguous():
+            raise ValueError(f"{name}: expected a contiguous float32 [B,C,H,W] or [B,C] tensor, got {t.dtype} {tuple(t.shape)}")
+    if x1.dim() != x2.dim() or x1.shape[0] != x2.shape[0] or x1.shape[2:] != x2.shape[2:] or x1.numel() == 0 or x2.numel() == 0:
+        raise ValueError(f"compact bilinear pooling: x1 {tuple(x1.shape)} and x2 {tuple(x2.shape)} differ in B, H or W (or are empty)")
+    if x1.shape[1] != p1["C"] or x2.shape[1] != p2["C"]:
+        raise ValueError(f"compact bilinear pooling: {x1.shape[1]} and {x2.shape[1]} channels, the sketches take {p1['C']} and {p2['C']}")
+    D = p1["D"]
+    if D != p2["D"] or not 1 <= D <= CBP_MAX_D:
+        raise ValueError(f"compact bilinear pooling: sketch widths {p1['D']} and {p2['D']} must be one D in 1 .. {CBP_MAX_D}")
+    for p in (p1, p2):
+        if p["h"].device != x1.device:
+            raise ValueError("compact bilinear pooling: the sketch pack lives on another device than the inputs")
+    P = x1[0, 0].numel()
+    return x1.shape[0], x1.shape[1], x2.shape[1], P, D
+
+
+def compact_bilinear(x1: Tensor, x2: Tensor, p1: dict, p2: dict, sum_pool: bool = True, save: bool = False):
+    """cbp [B,D] (sum over positions) or [B,H,W,D] in one launch.  ``save``: also returns psi1, psi2 [B,P,D] for the backward."""
+    B, C1, C2, P, D = compact_bilinear_check(x1, x2, p1, p2)
+    out = _empty((B, D) if sum_pool or x1.dim() == 2 else (B,) + tuple(x1.shape[2:]) + (D,), x1.device)
+    psi1 = _empty((B, P, D), x1.device) if save else None
+    psi2 = _empty((B, P, D), x1.device) if save else None
+    check(lib().dlip_compact_bilinear_f32(ptr(x1), ptr(x2), ptr(p1["rowptr"]), ptr(p1["idx"]), ptr(p1["sgn"]), ptr(p2["rowptr"]),
+                                          ptr(p2["idx"]), ptr(p2["sgn"]), ptr(out), ptr(psi1), ptr(psi2), B, C1, C2, P, D,
+                                          int(bool(sum_pool)), stream_handle()), "dlip_compact_bilinear_f32")
+    return (out, psi1, psi2) if save else out
+
+
+def compact_bilinear_bwd(g: Tensor, psi1: Tensor, psi2: Tensor, p1: dict, p2: dict, shape1, shape2, sum_pool: bool = True,
+                         want1: bool = True, want2: bool = True):
+    """(dx1, dx2) of compact_bilinear in the inputs' own shapes; an output that is not wanted is None, and nothing is launched when
+    neither is."""
+    if not (want1 or want2):
+        return None, None
+    _req(g, "g"); _req(psi1, "psi1"); _req(psi2, "psi2")
+    B, P, D = psi1.shape
+    if g.numel() != (B * D if sum_pool else B * P * D):
+        raise ValueError(f"compact bilinear pooling: g {tuple(g.shape)} does not fit B = {B}, P = {P}, D = {D}, sum_pool = {sum_pool}")
+    dx1 = _empty(tuple(shape1), g.device) if want1 else None
+    dx2 = _empty(tuple(shape2), g.device) if want2 else None
+    check(lib().dlip_compact_bilinear_bwd_f32(ptr(g), ptr(psi1), ptr(psi2), ptr(p1["h"]), ptr(p1["s"]), ptr(p2["h"]), ptr(p2["s"]),
+                                              ptr(dx1), ptr(dx2), B, p1["C"], p2["C"], P, D, int(bool(sum_pool)), stream_handle()),
+          "dlip_compact_bilinear_bwd_f32")
+    return dx1, dx2

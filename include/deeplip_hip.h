@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define DLIP_ABI_VERSION 54
+#define DLIP_ABI_VERSION 55
 #define DLIP_LIFT_WORDS 4098   /* a gradient's power-of-two lift: (2^e, 2^-e), then 2^-e repeated 2048 times (the post_scale vector of
                                   the convolution that consumes the lifted gradient); while it is formed the words behind the pair
                                   hold one maximum per workgroup of the producing pass */
@@ -959,6 +959,29 @@ int dlip_bilinear_pool_bwd_x_f32(const float* p, const float* q, const float* dz
                                  int32_t B, int32_t d1, int32_t d2, int32_t o, int32_t k, dlip_stream_t stream);
 int dlip_bilinear_finish_f32(const float* z, const float* scale, const float* shift, float* out, int32_t B, int32_t o, float eps,
                              dlip_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 55) Compact bilinear pooling, `CompactBilinearPooling(embedding_dim, embedding_dim, 512)`: the fusion head train_fusion.py:31-32,83
+ * of the reference imports and builds, and whose source upstream no longer ships (deeplip_amd.fusion.CompactBilinearPooling).  x1
+ * [B,C1,P], x2 [B,C2,P]: contiguous NCHW with P = H W positions, read with stride P (no permuted copy).  A count sketch is given as
+ * index lists, never as the dense [C,D] matrix: h[i] in [0,D) and s[i] = +-1 per input channel, and the same sorted by bin (CSR):
+ * rowptr [D+1], idx [C] (ascending within a bin) and sgn [C] = s[idx].  1 <= D <= 4096.  Exact fp32 on the vector ALUs under every
+ * arithmetic mode, every sum in a fixed order, no float atomics: a replayed launch repeats the bits.
+ *
+ * dlip_compact_bilinear_f32 (train_fusion.py:31-32,83): psi1[k] = sum_{h1[i] = k} s1[i] x1[i], psi2 likewise, and
+ *   cbp[k] = D sum_m psi1[m] psi2[(k - m) mod D] per (sample, position), which is irfft(rfft(psi1) rfft(psi2)) D.  sum_pool != 0:
+ *   out [B,D] is the sum over positions (ascending); else out [B,P,D].  psi1, psi2 (both NULL, or both [B,P,D]): the sketches are also
+ *   written, for the backward pass.  One launch.
+ * dlip_compact_bilinear_bwd_f32 (train_fusion.py:31-32,83; loss.backward(), :298): dpsi1[m] = D sum_k g[k] psi2[(k - m) mod D],
+ *   dx1[i] = s1[i] dpsi1[h1[i]] written as [B,C1,P]; dx2 likewise with psi1.  g is [B,D] (sum_pool != 0: it serves every position)
+ *   or [B,P,D].  Either output may be NULL; with both NULL nothing is launched.
+ * ------------------------------------------------------------------------------------------ */
+int dlip_compact_bilinear_f32(const float* x1, const float* x2, const int32_t* rowptr1, const int32_t* idx1, const float* sgn1,
+                              const int32_t* rowptr2, const int32_t* idx2, const float* sgn2, float* out, float* psi1, float* psi2,
+                              int32_t B, int32_t C1, int32_t C2, int32_t P, int32_t D, int32_t sum_pool, dlip_stream_t stream);
+int dlip_compact_bilinear_bwd_f32(const float* g, const float* psi1, const float* psi2, const int32_t* h1, const float* s1,
+                                  const int32_t* h2, const float* s2, float* dx1, float* dx2, int32_t B, int32_t C1, int32_t C2, int32_t P,
+                                  int32_t D, int32_t sum_pool, dlip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Step plans.  The reference drives its encoders from a Python loop, one utterance and one torch.nn layer

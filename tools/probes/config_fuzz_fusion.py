@@ -15,7 +15,7 @@ bad = 0
 small = {"data.n_spk": 6, "data.utt_per_spk": 4, "data.video_frames": 9, "data.audio_frames": 80, "train.bs": 12, "train.epoch": 2, "train.steps_per_epoch": 3,
          "data.test_speakers": 4, "data.test_utt_per_spk": 3, "data.trials": 60, "data.trial_targets": 12, "data.test_audio_frames": [60, 100],
          "data.test_video_frames": [5, 14], "test.write_store": False, "test.batch": 8}
-for fus, loss, graph in itertools.product(["linear", "lowfer", "concat", "bilinear"], ["CrossEntropy", "LMCL"], [True, False]):
+for fus, loss, graph in itertools.product(["linear", "lowfer", "concat", "bilinear", "compact_bilinear"], ["CrossEntropy", "LMCL"], [True, False]):
     tag = f"train fusion={fus} loss={loss} graph={graph}"
     try:
         tr = train_fusion.Trainer("train", overrides=dict(small, **{"model.fusion": fus, "train.loss": loss, "train.graph_step": graph}))

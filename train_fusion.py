@@ -137,6 +137,10 @@ class Trainer(object):
             b = self.model_opts.get("bilinear") or {}
             fused_dim = int(b.get("out_dim", 512))
             self.model_fusion = LBP.BNBilinear(self.embedding_dim, self.embedding_dim, fused_dim, k=int(b.get("rank", 30)))
+        elif kind == "compact_bilinear":  # upstream's third named head (train_fusion.py:31-32,83): count-sketch bilinear pooling + L2 norm + BatchNorm
+            c = self.model_opts.get("compact_bilinear") or {}
+            fused_dim = int(c.get("out_dim", 512))
+            self.model_fusion = fusion.BNCompactBilinear(self.embedding_dim, self.embedding_dim, fused_dim)
         elif kind == "concat":
             self.model_fusion = torch.nn.Identity()
             fused_dim = 2 * self.embedding_dim
@@ -166,7 +170,8 @@ class Trainer(object):
         self._init_optim()
 
     def _init_optim(self):
-        param_groups = [{"params": list(self.model_fusion.parameters())}, {"params": self.criterion.parameters()}]
+        # constants kept as parameters (the count sketches of compact_bilinear) stay out of the update, weight decay and gradient buckets
+        param_groups = [{"params": [p for p in self.model_fusion.parameters() if p.requires_grad]}, {"params": self.criterion.parameters()}]
         if self.train_opts["optimizer"] == "sgd":
             o = self.train_opts["sgd"]
             if self.graph_step:     # a recorded step reads its learning rate from a device tensor (MultiStepLR updates it in place)
@@ -234,7 +239,7 @@ class Trainer(object):
         return xv_audio, em_video
 
     def _fuse(self, xv_audio, em_video):
-        if self.fusion_kind in ("lowfer", "bilinear"):      # the two-input heads take the embeddings apart
+        if self.fusion_kind in ("lowfer", "bilinear", "compact_bilinear"):      # the two-input heads take the embeddings apart
             return self.model_fusion(xv_audio, em_video)
         return self.model_fusion(torch.cat([xv_audio, em_video], dim=1).contiguous())
 
