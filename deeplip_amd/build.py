@@ -19,7 +19,7 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "libdeeplip_hip.so")
-SOURCES = ["capi.hip", "plan.hip", "conv_igemm.hip", "conv_igemm_f16x3.hip", "conv_igemm_f16x3_dma.hip", "conv_win_f16x3.hip", "conv_rows_f16x3.hip", "stem3d.hip", "stem3d_f16x3.hip", "pool_ops.hip", "score_ops.hip", "layout_ops.hip", "train_ops.hip", "encoder_train_ops.hip", "video_train_ops.hip", "frontend_ops.hip", "shufflenet_ops.hip", "tcn_dw_ops.hip", "triplet_ops.hip", "bilinear_ops.hip", "compact_bilinear_ops.hip"]
+SOURCES = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))   # every translation unit of the library, by basename
 ARCH = "gfx950"
 
 
@@ -31,10 +31,13 @@ def _hipcc() -> str:
 
 
 def _deps():
-    return [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(CSRC, "dlip_common.h"), os.path.join(CSRC, "conv_common.h"), os.path.join(CSRC, "conv_dma_common.h"),
-                                                       os.path.join(CSRC, "conv_dma_lab.inc"), os.path.join(CSRC, "conv_dma_hooks.h"), os.path.join(CSRC, "conv_dma_hook_consts.inc"),
-                                                       os.path.join(CSRC, "conv_dma_hook_window.inc"), os.path.join(CSRC, "conv_dma_hook_tile256.inc"),
-                                                       os.path.join(CSRC, "conv_dma_lab_menu.inc"), os.path.join(ROOT, "include", "deeplip_hip.h")]
+    """Everything the library is compiled from: every file in csrc/ (sources, headers, .inc) and the public header."""
+    return [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))] + [os.path.join(ROOT, "include", "deeplip_hip.h")]
+
+
+def _compile_cmd(extra=()):
+    return [_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
+            "-Wall", "-Wno-unused-function"] + list(extra)
 
 
 def source_sha() -> str:
@@ -84,8 +87,7 @@ def _build(LIB: str, extra, verbose: bool, tag: str) -> str:
     os.makedirs(LIBDIR, exist_ok=True)
     objs = []
     hipcc = _hipcc()
-    common = [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"),
-              "-I" + CSRC, "-Wall", "-Wno-unused-function"] + list(extra)
+    common = _compile_cmd(extra)
     procs = []
     for s in SOURCES:
         o = os.path.join(LIBDIR, tag + s.replace(".hip", ".o"))
@@ -120,8 +122,7 @@ def prove_compile(source: str = "capi.hip", verbose: bool = True) -> float:
     import tempfile
     import time
     with tempfile.TemporaryDirectory() as td:
-        cmd = [_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
-               "-c", os.path.join(CSRC, source), "-o", os.path.join(td, "probe.o")]
+        cmd = _compile_cmd() + ["-c", os.path.join(CSRC, source), "-o", os.path.join(td, "probe.o")]
         if verbose:
             print(" ".join(cmd), flush=True)
         t0 = time.time()

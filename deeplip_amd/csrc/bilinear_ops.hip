@@ -20,7 +20,8 @@
 // MFMA operand maps (16x16x4 f32): lane l supplies A[row l & 15][k = l >> 4] and B[k = l >> 4][col l & 15]; a lane loads FOUR
 // consecutive floats, and MFMA j of a group takes element j from every lane.  Along the reduction that only permutes the order of
 // the sum (the same for both operands); along the columns of B it makes accumulator `cb` of lane l hold column 4 (l & 15) + cb.
-#include "dlip_common.h"
+#include "dlip_launch.h"
+#include "dlip_reduce.h"
 
 namespace {
 
@@ -303,10 +304,7 @@ __global__ __launch_bounds__(256) void bilinear_finish_kernel(const float* __res
   const float* pz = z + (size_t)b * o;
   double s = 0.0;
   for (int j = threadIdx.x; j < o; j += 256) s += (double)pz[j] * (double)pz[j];
-  s = dlip_wave_sum_f64(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  const float norm = fmaxf((float)sqrt(((red[0] + red[1]) + red[2]) + red[3]), eps);
+  const float norm = fmaxf((float)sqrt(dlip_block_sum4(s, red)), eps);
   for (int j = threadIdx.x; j < o; j += 256) out[(size_t)b * o + j] = pz[j] / norm * scale[j] + shift[j];
 }
 
@@ -317,19 +315,17 @@ bool bilinear_shape_ok(int B, int d1, int d2, int o, int k) {
   return ko < (1ll << 30) && ko * dmax < (1ll << 31) && ko * B < (1ll << 31) && dmax * B < (1ll << 31);
 }
 
-inline bool bl_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 extern "C" int dlip_bilinear_pool_f32(const float* e1, const float* e2, const float* u, const float* v, float* z, float* p, float* q,
                                       int32_t B, int32_t d1, int32_t d2, int32_t o, int32_t k, dlip_stream_t stream) {
   DLIP_CHECK_ARG(e1 && e2 && u && v && z && bilinear_shape_ok(B, d1, d2, o, k));
   DLIP_CHECK_ARG((p == nullptr) == (q == nullptr));
-  DLIP_CHECK_ARG(bl_aligned(e1) && bl_aligned(e2) && bl_aligned(u) && bl_aligned(v));
+  DLIP_CHECK_ARG(dlip_aligned16(e1) && dlip_aligned16(e2) && dlip_aligned16(u) && dlip_aligned16(v));
   const int vec = ((long long)k * o) % 4 == 0;
   // outputs per workgroup: their columns (plus the three an aligned start may add in front) fit one 64-column pass when k allows
   const int opt = k <= 61 ? 61 / k : 1;
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = dlip_hip_stream(stream);
   const dim3 grid((o + opt - 1) / opt);
   if (p)
     hipLaunchKernelGGL(bilinear_fwd_kernel<true>, grid, dim3(256), 0, st, e1, e2, u, v, z, p, q, B, d1, d2, o, k, opt, vec);
@@ -341,9 +337,9 @@ extern "C" int dlip_bilinear_pool_f32(const float* e1, const float* e2, const fl
 extern "C" int dlip_bilinear_pool_bwd_w_f32(const float* e1, const float* e2, const float* p, const float* q, const float* dz, float* du,
                                             float* dv, int32_t B, int32_t d1, int32_t d2, int32_t o, int32_t k, dlip_stream_t stream) {
   DLIP_CHECK_ARG(e1 && e2 && p && q && dz && du && dv && bilinear_shape_ok(B, d1, d2, o, k));
-  DLIP_CHECK_ARG(bl_aligned(du) && bl_aligned(dv));
+  DLIP_CHECK_ARG(dlip_aligned16(du) && dlip_aligned16(dv));
   const int ko = k * o;
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = dlip_hip_stream(stream);
   hipLaunchKernelGGL(bilinear_bwd_w_kernel, dim3((ko + BL_COLS - 1) / BL_COLS), dim3(256), 0, st, e1, e2, p, q, dz, du, dv, B, d1, d2, o, k,
                      (int)(ko % 4 == 0));
   return dlip_launch_status();
@@ -352,10 +348,10 @@ extern "C" int dlip_bilinear_pool_bwd_w_f32(const float* e1, const float* e2, co
 extern "C" int dlip_bilinear_pool_bwd_x_f32(const float* p, const float* q, const float* dz, const float* u, const float* v, float* de1,
                                             float* de2, int32_t B, int32_t d1, int32_t d2, int32_t o, int32_t k, dlip_stream_t stream) {
   DLIP_CHECK_ARG(p && q && dz && u && v && (de1 || de2) && bilinear_shape_ok(B, d1, d2, o, k));
-  DLIP_CHECK_ARG(bl_aligned(p) && bl_aligned(q) && bl_aligned(u) && bl_aligned(v));
+  DLIP_CHECK_ARG(dlip_aligned16(p) && dlip_aligned16(q) && dlip_aligned16(u) && dlip_aligned16(v));
   const int ko = k * o;
   const int dmax = d1 > d2 ? d1 : d2;
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = dlip_hip_stream(stream);
   hipLaunchKernelGGL(bilinear_bwd_x_kernel, dim3((dmax + 15) / 16, (B + 15) / 16, 2), dim3(256), 0, st, p, q, dz, u, v, de1, de2, B, d1, d2, o,
                      k, (int)(ko % 4 == 0));
   return dlip_launch_status();
@@ -364,6 +360,6 @@ extern "C" int dlip_bilinear_pool_bwd_x_f32(const float* p, const float* q, cons
 extern "C" int dlip_bilinear_finish_f32(const float* z, const float* scale, const float* shift, float* out, int32_t B, int32_t o, float eps,
                                         dlip_stream_t stream) {
   DLIP_CHECK_ARG(z && scale && shift && out && B >= 1 && o >= 1 && eps > 0.f);
-  hipLaunchKernelGGL(bilinear_finish_kernel, dim3(B), dim3(256), 0, static_cast<hipStream_t>(stream), z, scale, shift, out, o, eps);
+  hipLaunchKernelGGL(bilinear_finish_kernel, dim3(B), dim3(256), 0, dlip_hip_stream(stream), z, scale, shift, out, o, eps);
   return dlip_launch_status();
 }

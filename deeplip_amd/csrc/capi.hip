@@ -1,5 +1,5 @@
 // ABI bookkeeping entry points of libdeeplip_hip.so (see include/deeplip_hip.h).
-#include "dlip_common.h"
+#include "dlip_launch.h"
 
 extern "C" int dlip_abi_version(void) { return DLIP_ABI_VERSION; }
 
@@ -97,7 +97,7 @@ extern "C" int dlip_range_scope_end(dlip_stream_t stream) {
   const bool over = sc.cur > sc.n;     // more split-producing launches than the scope has slots: the later ones went unguarded
   sc = RangeScope{};
   if (used > 0) {
-    hipLaunchKernelGGL(range_verdict_kernel, dim3((unsigned)used), dim3(64), 0, static_cast<hipStream_t>(stream), slots, used, status_now());
+    hipLaunchKernelGGL(range_verdict_kernel, dim3((unsigned)used), dim3(64), 0, dlip_hip_stream(stream), slots, used, status_now());
     const int e = dlip_launch_status();
     if (e != DLIP_OK) return e;
   }
@@ -159,7 +159,7 @@ extern "C" int dlip_span_scope_end(dlip_stream_t stream, int32_t* used) {
   DLIP_CHECK_ARG(sc.pairs != nullptr);
   if (used) *used = sc.cur;
   if (sc.cur > 0) {
-    hipLaunchKernelGGL(span_collect_kernel, dim3((unsigned)((sc.cur + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), sc.pairs, sc.acc,
+    hipLaunchKernelGGL(span_collect_kernel, dim3((unsigned)((sc.cur + 255) / 256)), dim3(256), 0, dlip_hip_stream(stream), sc.pairs, sc.acc,
                        sc.cur);
     return dlip_launch_status();
   }

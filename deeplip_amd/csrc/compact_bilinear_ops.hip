@@ -22,7 +22,7 @@
 //
 // The index lists come from deeplip_amd.ops.compact_bilinear_pack, which reads them out of the dense sketch and refuses a sketch
 // that is not one +-1 per row; the kernels rely on idx < C, h < D and a monotone rowptr ending at C.
-#include "dlip_common.h"
+#include "dlip_launch.h"
 
 namespace {
 
@@ -226,7 +226,6 @@ bool cbp_shape_ok(int B, int C1, int C2, int P, int D) {
   return rows < (1ll << 31) && rows * D < (1ll << 31) && rows * cmax < (1ll << 31);
 }
 
-inline bool cb_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -236,9 +235,9 @@ extern "C" int dlip_compact_bilinear_f32(const float* x1, const float* x2, const
                                          dlip_stream_t stream) {
   DLIP_CHECK_ARG(x1 && x2 && rowptr1 && idx1 && sgn1 && rowptr2 && idx2 && sgn2 && out && cbp_shape_ok(B, C1, C2, P, D));
   DLIP_CHECK_ARG((psi1 == nullptr) == (psi2 == nullptr));
-  const bool vec = D % 4 == 0 && cb_aligned(out);
+  const bool vec = D % 4 == 0 && dlip_aligned16(out);
   const size_t lds = 3 * (size_t)((D + 3) & ~3) * sizeof(float);      // at most 48 KB
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = dlip_hip_stream(stream);
   const dim3 grid(B), block(cb_threads(D));
   const int pool = sum_pool != 0;
 #define CB_FWD(V, S) \
@@ -258,7 +257,7 @@ extern "C" int dlip_compact_bilinear_bwd_f32(const float* g, const float* psi1, 
   DLIP_CHECK_ARG(g && psi1 && psi2 && h1 && s1 && h2 && s2 && cbp_shape_ok(B, C1, C2, P, D));
   if (!dx1 && !dx2) return DLIP_OK;      // nobody asked for a gradient: nothing launches
   const size_t lds = 4 * (size_t)((D + 3) & ~3) * sizeof(float);      // at most 64 KB
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = dlip_hip_stream(stream);
   const int cmax = C1 > C2 ? C1 : C2;
   const dim3 grid(B * P, (dx1 && dx2) ? 2 : 1), block(cb_threads(D > cmax ? D : cmax));
   const int pool = sum_pool != 0;

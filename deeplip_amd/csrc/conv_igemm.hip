@@ -18,6 +18,8 @@
 //
 // Replaces the torch.nn layers listed against dlip_conv_nhwc_f32 in include/deeplip_hip.h.
 #include "conv_common.h"
+#include "conv_dispatch.h"
+#include "dlip_launch.h"
 
 namespace {
 
@@ -308,15 +310,10 @@ extern "C" int dlip_conv_nhwc_f32(const dlip_conv_desc* d, const float* x, const
   const int rc = dlip_fill_conv_args(d, x, w_krsc, bias, residual, slope, post_scale, post_shift, y, d ? d->C : 0, &a);
   if (rc != DLIP_OK) return rc;
   const long long M = a.M;
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = dlip_hip_stream(stream);
   return launch_cfg(pick_tile(M, d->K), a, st);
 }
 
-extern "C" void dlip_conv_dma_tile(long long M, int K, int nk, int epi, int* bm, int* bn);   // conv_igemm_f16x3_dma.hip
-extern "C" int dlip_conv_dma_enabled(void);                                  // conv_igemm_f16x3.hip
-
-extern "C" int dlip_conv_rows_plan(const dlip_conv_desc* d, int* bm);   // conv_rows_f16x3.hip
-extern "C" int dlip_conv_rows2d_plan(const dlip_conv_desc* d, int c2, int* bm);
 extern "C" int dlip_conv_plan(const dlip_conv_desc* d, int32_t split_f16, int32_t* bm, int32_t* bn) {
   DLIP_CHECK_ARG(d && bm && bn && d->N > 0 && d->Ho > 0 && d->Wo > 0 && d->K > 0);
   if ((split_f16 & 3) == 3 && dlip_conv_dma_enabled()) {   // split-format activations: the LDS-DMA kernel's menu

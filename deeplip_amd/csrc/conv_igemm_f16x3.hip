@@ -16,6 +16,8 @@
 //     k 8-15 of the step) and issues 3 MFMAs per 32x32 tile.
 // Replaces the same reference layers as dlip_conv_nhwc_f32 (include/deeplip_hip.h).
 #include "conv_common.h"
+#include "conv_dispatch.h"
+#include "dlip_launch.h"
 
 namespace {
 
@@ -327,16 +329,6 @@ int launch(const ConvArgs& a, hipStream_t st, int flags) {
 
 }  // namespace
 
-extern "C" int dlip_conv_f16x3_dma_launch(const void* args, void* stream, int epi);   // conv_igemm_f16x3_dma.hip
-extern "C" void dlip_conv_dma_tile(long long M, int K, int nk, int epi, int* bm, int* bn);
-extern "C" int dlip_conv_win_ok(const void* args);                                          // conv_win_f16x3.hip
-extern "C" int dlip_conv_f16x3_win_launch(const void* args, void* stream, int out_split);
-extern "C" int dlip_conv_rows_ok(const void* args);                                         // conv_rows_f16x3.hip
-extern "C" int dlip_conv_f16x3_rows_launch(const void* args, void* stream, int epi);
-extern "C" int dlip_conv_rows_plan(const dlip_conv_desc* d, int* bm);
-extern "C" long long dlip_conv_rows_tiles(const dlip_conv_desc* d);
-extern "C" int dlip_conv_rows_pool_plan(const dlip_conv_desc* d, int* bm);
-
 // Diagnostic switch (dlip_debug_set DLIP_DBG_DMA_ENABLE = 0): keeps split-format launches on the register-staged kernel.
 extern "C" __attribute__((visibility("hidden"))) int dlip_conv_dma_enabled(void) { return dlip_dbg_value[DLIP_DBG_DMA_ENABLE] != 0; }
 
@@ -373,7 +365,7 @@ extern "C" int dlip_conv_nhwc_f16x3(const dlip_conv_desc* d, const float* x, con
   if (big) DLIP_CHECK_ARG((flags & 3) == 1 && residual == nullptr && (long long)d->R * d->S <= 65536);
   const int rc = fill_f16x3(d, x, w_split, w_scale, bias, residual, slope, post_scale, post_shift, y, flags, &a, big ? 65536 : 32);
   if (rc != DLIP_OK) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = dlip_hip_stream(stream);
   // Split-format activations go to the LDS-DMA kernel.  Its epilogue leaves in 16-byte chunks, so an fp32
   // output needs K, ldy in multiples of 4 and a 16-byte aligned y (a split output already has K, ldy % 32 == 0);
   // anything else stays on the register-staged kernel below.

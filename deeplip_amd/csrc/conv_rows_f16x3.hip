@@ -28,14 +28,13 @@
 // same bits here (tests/test_kernels_gpu.py::test_conv_rows_*).
 #include "conv_common.h"
 #include "conv_dma_common.h"
+#include "conv_dispatch.h"
+#include "dlip_launch.h"
 
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
-
-// conv_igemm_f16x3_dma.hip: the per-stream workspace of the balanced split (slabs + ticket words); 0 = none / too small
-extern "C" int dlip_conv_split_workspace(void* stream, size_t slab_floats, float** slabs, int** counters, int* counter_words);
 
 namespace {
 
@@ -954,8 +953,6 @@ int rows_pick_mi(long long M, int K, int nk, int cus, bool tail = true) {   // t
 
 }  // namespace
 
-extern "C" int dlip_conv_dma_enabled(void);   // conv_igemm_f16x3.hip
-
 // Which launches the rows kernel serves: H = 1, one filter row, stride 1, no padding (every tap of every output row exists: a
 // plain row offset), whole 32-channel slices, no residual / second source / pooled epilogue, and enough rows and columns for its
 // 256-column tiles to be the right shape (the fully connected layers on a batch of utterances stay on the ring kernel's split).
@@ -1045,7 +1042,7 @@ extern "C" __attribute__((visibility("hidden"))) int dlip_conv_rows2d_plan(const
 // is too small): the caller then runs the ring kernel
 extern "C" __attribute__((visibility("hidden"))) int dlip_conv_f16x3_rows2d_launch(const void* args, void* stream, int epi) {
   const ConvArgs& a = *static_cast<const ConvArgs*>(args);
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = dlip_hip_stream(stream);
   if (a.x2 != nullptr) return epi ? launch_rows<5, 1, 1, true>(a, st) : launch_rows<5, 0, 1, true>(a, st);
   return epi ? launch_rows<5, 1, 1, false>(a, st) : launch_rows<5, 0, 1, false>(a, st);
 }
@@ -1067,7 +1064,7 @@ extern "C" __attribute__((visibility("hidden"))) int dlip_conv_rows_pool_plan(co
 
 extern "C" __attribute__((visibility("hidden"))) int dlip_conv_f16x3_rows_launch(const void* args, void* stream, int epi) {
   const ConvArgs& a = *static_cast<const ConvArgs*>(args);
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = dlip_hip_stream(stream);
   const int cus = rows_cus();
   int mi = rows_pick_mi(a.M, a.K, a.nk, cus, epi != 2);
   if (const int v = dlip_dbg_value[DLIP_DBG_ROWS]; v >= 3 && v <= 5) mi = v;   // dlip_debug_set: a forced tile height (tests, A/B)

@@ -28,6 +28,8 @@
 // block -- runs with that head in flight (LDS map in the kernel).
 #include "conv_common.h"
 #include "conv_dma_common.h"
+#include "conv_dispatch.h"
+#include "dlip_launch.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -575,17 +577,13 @@ __global__ __launch_bounds__(256) void lds_oob_probe_kernel(int32_t* counts, int
 
 extern "C" int dlip_selftest_lds_oob(int32_t* counts, int32_t blocks, dlip_stream_t stream) {
   DLIP_CHECK_ARG(counts && blocks > 0 && blocks <= 65536);
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = dlip_hip_stream(stream);
   if (hipMemsetAsync(counts, 0, 2 * sizeof(int32_t), st) != hipSuccess) return DLIP_EINVAL;
   hipLaunchKernelGGL(lds_oob_probe_kernel, dim3((unsigned)blocks), dim3(256), 8192, st, counts, 8192);
   return dlip_launch_status();
 }
 
-extern "C" int dlip_conv_dma_enabled(void);   // conv_igemm_f16x3.hip
-
 // Which kernel a split-format launch of `d` goes to (include/deeplip_hip.h): 1 = this one.
-extern "C" int dlip_conv_rows_plan(const dlip_conv_desc* d, int* bm);   // conv_rows_f16x3.hip
-extern "C" int dlip_conv_rows2d_plan(const dlip_conv_desc* d, int c2, int* bm);
 extern "C" int dlip_conv_kernel_kind(const dlip_conv_desc* d) {
   if (!d) return DLIP_EINVAL;
   if (d->C % 32 == 0 && dlip_conv_dma_enabled() &&
@@ -602,7 +600,7 @@ extern "C" __attribute__((visibility("hidden"))) int dlip_conv_f16x3_win_launch(
   // dlip_debug_set(DLIP_DBG_WIN, v) picks a geometry for same-box A/B runs: 3 = 128x64 tile, TWO waves of 64x64 (two workgroups
   // per CU); 4 = 256x64, four waves of 64x64; 5 = (K > 64) 128x128, four waves of 64x64; 6 = (K > 64) 256x128, eight waves of 64x64;
   // 7 = round 5's 2 x 2 waves of 64x32 on the 128x64 tile.
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = dlip_hip_stream(stream);
   const int v = dlip_dbg_value[DLIP_DBG_WIN];
   if (a.K > 64) {
     if (v == 5) return launch_win<128, 128, 2, 2, 1>(a, st, out_split != 0);

@@ -11,6 +11,9 @@
 // to a caller-provided workspace and a second kernel adds them in chunk order: deterministic, no atomics.
 #include "dlip_common.h"
 #include "conv_common.h"   // FastDiv: exact division by launch constants
+#include "conv_dispatch.h"
+#include "dlip_launch.h"
+#include "dlip_reduce.h"
 
 namespace {
 
@@ -373,11 +376,7 @@ __global__ __launch_bounds__(256) void bn_bwd_lift_bound_kernel(const unsigned* 
     if (!(bc == bc)) bc = 3.4e38f;
     b = fmaxf(b, bc);
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) b = fmaxf(b, __shfl_xor(b, off));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = b;
-  __syncthreads();
-  const float bound = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])) * post * (1.f + 0x1p-10f);
+  const float bound = dlip_block_max4(b, red) * post * (1.f + 0x1p-10f);
   float s = 1.f;
   if (bound > 0.f && bound < 3.0e38f) s = exp2f(floorf(log2f(target / bound)));
   if (!(s > 0.f) || s > 1.0e30f) s = 1.0e30f;
@@ -749,8 +748,7 @@ __device__ __forceinline__ void pow2_finalize_parts(const unsigned* parts, int n
   __shared__ unsigned red[4];
   unsigned m = 0u;
   for (int i = threadIdx.x; i < n; i += 256) m = max(m, parts[i]);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off));
+  m = dlip_wave_max(m);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
   __syncthreads();
   const float mx = __uint_as_float(max(max(red[0], red[1]), max(red[2], red[3])));
@@ -813,12 +811,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const f32x4* __restri
   }
   if (amax_acc) {
     __shared__ float amax_red[4];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off));
-    if ((threadIdx.x & 63) == 0) amax_red[threadIdx.x >> 6] = amax;
-    __syncthreads();
+    float m = dlip_block_max4(amax, amax_red);
     if (threadIdx.x == 0) {
-      float m = fmaxf(fmaxf(amax_red[0], amax_red[1]), fmaxf(amax_red[2], amax_red[3]));
       if (!(m == m)) m = 3.4e38f;
       publish(amax_acc + blockIdx.x, __float_as_uint(m));   // one word per workgroup, reduced by pow2_finalize_parts: thousands of
     }                                                       // workgroups meeting in ONE atomic cost 14 us per launch (the hot-line effect)
@@ -838,19 +832,13 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const f32x4* __restri
 // three-launch path; the association of the fp64 column sums differs (fixed here too: deterministic).
 constexpr int BN_SMALL_ROWS = 4096;
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
 // sums over the workgroup of NQ quantities x 4 channels held per lane: butterflies within a wave, then the four waves in wave order
 template <int NQ>
 __device__ __forceinline__ void block_sums(double (&s)[NQ][4], double (*red)[NQ][4]) {
 #pragma unroll
   for (int q = 0; q < NQ; ++q)
 #pragma unroll
-    for (int k = 0; k < 4; ++k) s[q][k] = wave_sum(s[q][k]);
+    for (int k = 0; k < 4; ++k) s[q][k] = dlip_wave_sum_f64(s[q][k]);
   const int wave = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) {
 #pragma unroll
@@ -1007,12 +995,8 @@ __global__ __launch_bounds__(256) void bn_small_bwd_kernel(const float* __restri
   }
   if (amax_acc) {
     __shared__ float amax_red[4];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off));
-    if ((threadIdx.x & 63) == 0) amax_red[threadIdx.x >> 6] = amax;
-    __syncthreads();
+    float m = dlip_block_max4(amax, amax_red);
     if (threadIdx.x == 0) {
-      float m = fmaxf(fmaxf(amax_red[0], amax_red[1]), fmaxf(amax_red[2], amax_red[3]));
       if (!(m == m)) m = 3.4e38f;
       publish(amax_acc + blockIdx.x, __float_as_uint(m));
     }
@@ -1106,12 +1090,8 @@ __global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ x
   }
   if (blockIdx.x == 0)
     for (long long i = (n4 << 2) + threadIdx.x; i < n; i += 256) m = fmaxf(m, fabsf(x[i]));
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-  __syncthreads();
+  m = dlip_block_max4(m, red);
   if (threadIdx.x == 0) {
-    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
     if (!(m == m)) m = 3.4e38f;   // NaN: treated as "huge" (scale 1e-30 path below keeps the product finite)
     atomicMax(acc, __float_as_uint(m));
   }
@@ -1182,11 +1162,7 @@ __global__ __launch_bounds__(256) void split_weights_rows_kernel(const float* __
   const float* row = w + (long long)blockIdx.x * L;
   float m = 0.f;
   for (int i = threadIdx.x; i < L; i += 256) m = fmaxf(m, fabsf(row[i]));
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-  __syncthreads();
-  m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  m = dlip_block_max4(m, red);
   float sc = 1.f;
   if (m > 0.f && m < 3.0e38f) sc = exp2f(floorf(log2f(1023.0f / m)));
   if (threadIdx.x == 0) scale[blockIdx.x] = sc;
@@ -1237,11 +1213,7 @@ __global__ __launch_bounds__(256) void split_weights_perm_kernel(const float* __
   };
   float m = 0.f;
   for (int i = threadIdx.x; i < L; i += 256) m = fmaxf(m, fabsf(src(i)));
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-  __syncthreads();
-  m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  m = dlip_block_max4(m, red);
   float sc = 1.f;
   if (m > 0.f && m < 3.0e38f) sc = exp2f(floorf(log2f(1023.0f / m)));
   if (threadIdx.x == 0) scale[row] = sc;
@@ -1310,11 +1282,7 @@ __global__ __launch_bounds__(256) void split_weights_multi_kernel(const WSplitDe
   } else {
     for (int i = threadIdx.x; i < L; i += 256) m = fmaxf(m, fabsf(src(i)));
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-  __syncthreads();
-  m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  m = dlip_block_max4(m, red);
   float sc = 1.f;
   if (m > 0.f && m < 3.0e38f) sc = exp2f(floorf(log2f(1023.0f / m)));
   if (threadIdx.x == 0) d.scale[row] = sc;
@@ -1344,11 +1312,7 @@ __global__ __launch_bounds__(256) void fill_from_scalar_kernel(const float* __re
   if (i < n) y[i] = src[0];
 }
 
-inline unsigned grid1d(long long n) {
-  long long g = (n + 255) / 256;
-  if (g > 4096) g = 4096;
-  return (unsigned)(g < 1 ? 1 : g);
-}
+constexpr int kGridCap = 4096;
 
 // Grid for an element pass over [M, C4] float4s whose threads want ONE channel group each: a grid whose stride 256 g is a
 // multiple of C4 (g a multiple of C4 / gcd(C4, 256)); 0 when no such grid fits (the kernel then re-reads its parameters).
@@ -1356,7 +1320,7 @@ inline unsigned grid_fixed(long long n4, int C4) {
   int a = C4, b = 256;
   while (b) { const int t = a % b; a = b; b = t; }
   const long long m = C4 / a;
-  long long g = (long long)grid1d(n4) / m * m;
+  long long g = (long long)dlip_grid1d(n4, kGridCap) / m * m;
   if (g == 0 && m <= 4096 && (n4 + 255) / 256 >= 1) g = m <= (n4 + 255) / 256 ? m : 0;
   return (unsigned)g;
 }
@@ -1376,12 +1340,10 @@ extern "C" int32_t dlip_bn_rows_chunks(int32_t M) {
   return (M + rpp - 1) / rpp;
 }
 
-// conv_igemm_f16x3_dma.hip: this stream's self-resetting ticket words (the balanced split's workspace); 0 = none (a capture on a
-// stream that never launched eagerly): the finalize steps then run as launches of their own
-extern "C" int dlip_conv_split_workspace(void* stream, size_t slab_floats, float** slabs, int** counters, int* counter_words);
-
 namespace {
 
+// This stream's self-resetting ticket words (the balanced split's workspace, dlip_conv_split_workspace); NULL = none (a capture on a
+// stream that never launched eagerly): the finalize steps then run as launches of their own
 int* stream_tickets(hipStream_t st, int need) {
   if (dlip_dbg_value[DLIP_DBG_BN_FUSED] == 0) return nullptr;       // dlip_debug_set(8, 0): the round-4 launch sequence (tests, A/B runs)
   float* slabs = nullptr;
@@ -1426,7 +1388,7 @@ int bn_fwd_launch(const float* x, const float* gamma, const float* beta, const f
     hipLaunchKernelGGL(bn_fwd_apply_kernel<true>, dim3(gf), dim3(256), 0, st, reinterpret_cast<const f32x4*>(x), save_mean,
                        save_invstd, gamma, beta, reinterpret_cast<f32x4*>(y), n4, C / 4, slope, act_first, slope_vec);
   else
-    hipLaunchKernelGGL(bn_fwd_apply_kernel<false>, dim3(grid1d(n4)), dim3(256), 0, st, reinterpret_cast<const f32x4*>(x), save_mean,
+    hipLaunchKernelGGL(bn_fwd_apply_kernel<false>, dim3(dlip_grid1d(n4, kGridCap)), dim3(256), 0, st, reinterpret_cast<const f32x4*>(x), save_mean,
                        save_invstd, gamma, beta, reinterpret_cast<f32x4*>(y), n4, C / 4, slope, act_first, slope_vec);
   return dlip_launch_status();
 }
@@ -1465,7 +1427,7 @@ int bn_bwd_launch(const float* dy, const float* x, const float* gamma, const flo
   }
   const long long n4 = (long long)M * (C / 4);
   const unsigned gf = grid_fixed(n4, C / 4);
-  const unsigned grid = gf ? gf : grid1d(n4);
+  const unsigned grid = gf ? gf : dlip_grid1d(n4, kGridCap);
   // (the lift of a LARGE dx stays a launch of its own: a ticket word taking thousands of arrivals, and every workgroup waiting for its
   // stores' acknowledgements in front of it, cost bn_bwd_apply 0.6 ms per lip-clip step -- more than the 20 launches it saved)
   int* lift_ticket = nullptr;
@@ -1493,7 +1455,7 @@ extern "C" int dlip_bn_rows_train_fwd_f32(const float* x, const float* gamma, co
   DLIP_CHECK_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0);
   DLIP_CHECK_ARG(ready_chunks >= 0 && !(ready_chunks > 0 && act_first));
   return bn_fwd_launch(x, gamma, beta, nullptr, y, save_mean, save_invstd, running_mean, running_var, workspace, M, C, momentum, eps,
-                       slope, act_first, ready_chunks, reinterpret_cast<long long*>(num_batches_tracked), static_cast<hipStream_t>(stream));
+                       slope, act_first, ready_chunks, reinterpret_cast<long long*>(num_batches_tracked), dlip_hip_stream(stream));
 }
 
 extern "C" int dlip_bn_rows_train_bwd_f32(const float* dy, const float* x, const float* gamma, const float* beta,
@@ -1504,7 +1466,7 @@ extern "C" int dlip_bn_rows_train_bwd_f32(const float* dy, const float* x, const
   DLIP_CHECK_ARG(M > 0 && C > 0 && (C & 3) == 0);
   DLIP_CHECK_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0);
   return bn_bwd_launch(dy, x, gamma, beta, nullptr, save_mean, save_invstd, dx, dgamma, dbeta, nullptr, workspace, M, C, slope, act_first,
-                       dx_lift2, static_cast<hipStream_t>(stream));
+                       dx_lift2, dlip_hip_stream(stream));
 }
 
 // (ABI 48) dlip_bn_rows_train_bwd_f32 behind a MeanStdPooling whose backward writes nothing: dy is formed per loaded value from the pooled
@@ -1514,7 +1476,7 @@ extern "C" int dlip_meanstd_bwd_coef_f32(const float* y_pool, const float* g_poo
                                          dlip_stream_t stream) {
   DLIP_CHECK_ARG(y_pool && g_pool && coef && B > 0 && C > 0 && T > 1);
   const long long n = (long long)B * C;
-  hipLaunchKernelGGL(ms_coef_kernel, dim3((unsigned)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048)), dim3(256), 0, static_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(ms_coef_kernel, dim3((unsigned)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048)), dim3(256), 0, dlip_hip_stream(stream),
                      y_pool, g_pool, coef, B, C, T);
   return dlip_launch_status();
 }
@@ -1528,7 +1490,7 @@ extern "C" int dlip_bn_rows_train_bwd_ms_f32(const float* ms_coef, int32_t T, co
   MsSrc ms;
   ms.coef = ms_coef; ms.T = T; ms.div_T = dlip_fastdiv((uint32_t)T);
   return bn_bwd_launch(x /* never read as dy */, x, gamma, beta, nullptr, save_mean, save_invstd, dx, dgamma, dbeta, nullptr, workspace, M, C, slope, 0,
-                       dx_lift2, static_cast<hipStream_t>(stream), ms);
+                       dx_lift2, dlip_hip_stream(stream), ms);
 }
 
 // (ABI 47) The first half of dlip_bn_rows_train_bwd_f32 alone: dgamma, dbeta and the lift of a dx that is never written -- the operand
@@ -1543,7 +1505,7 @@ extern "C" int dlip_bn_rows_train_bwd_sums_f32(const float* dy, const float* x, 
   DLIP_CHECK_ARG(M > 0 && C > 0 && (C & 3) == 0);
   DLIP_CHECK_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(ms_coef)) & 15) == 0);
   if (dy == nullptr) dy = x;           // (never read)
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = dlip_hip_stream(stream);
   int* tickets = stream_tickets(st, (C + 63) / 64);
   const int chunks = dlip_bn_rows_chunks(M);
   const int rpp = bn_rows_per_part(M);
@@ -1570,7 +1532,7 @@ extern "C" int dlip_bn_prelu_rows_train_fwd_f32(const float* x, const float* gam
   DLIP_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr));
   DLIP_CHECK_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0);
   return bn_fwd_launch(x, gamma, beta, slope, y, save_mean, save_invstd, running_mean, running_var, workspace, M, C, momentum, eps, 1.f, 0,
-                       0, reinterpret_cast<long long*>(num_batches_tracked), static_cast<hipStream_t>(stream));
+                       0, reinterpret_cast<long long*>(num_batches_tracked), dlip_hip_stream(stream));
 }
 
 extern "C" int dlip_bn_prelu_rows_train_bwd_f32(const float* dy, const float* x, const float* gamma, const float* beta,
@@ -1581,7 +1543,7 @@ extern "C" int dlip_bn_prelu_rows_train_bwd_f32(const float* dy, const float* x,
   DLIP_CHECK_ARG(M > 0 && C > 0 && (C & 3) == 0);
   DLIP_CHECK_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0);
   return bn_bwd_launch(dy, x, gamma, beta, slope, save_mean, save_invstd, dx, dgamma, dbeta, dslope, workspace, M, C, 1.f, 0, dx_lift2,
-                       static_cast<hipStream_t>(stream));
+                       dlip_hip_stream(stream));
 }
 
 extern "C" int dlip_bn_prelu_maxpool_train_fwd_f32(const float* x, const float* gamma, const float* beta, const float* slope, float* y,
@@ -1591,7 +1553,7 @@ extern "C" int dlip_bn_prelu_maxpool_train_fwd_f32(const float* x, const float* 
   DLIP_CHECK_ARG(x && gamma && beta && slope && y && idx && save_mean && save_invstd && workspace && N > 0 && H > 0 && W > 0 && C > 0);
   DLIP_CHECK_ARG((C & 3) == 0 && (running_mean == nullptr) == (running_var == nullptr) && N * H * W < 0x7FFFFFFFll);
   DLIP_CHECK_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0);
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = dlip_hip_stream(stream);
   const int M = (int)(N * H * W);
   const int chunks = dlip_bn_rows_chunks(M);
   long long* nbt = reinterpret_cast<long long*>(num_batches_tracked);
@@ -1603,7 +1565,7 @@ extern "C" int dlip_bn_prelu_maxpool_train_fwd_f32(const float* x, const float* 
                        running_mean, running_var, M, C, chunks, momentum, eps, nbt);
   const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
   const long long n4 = N * Ho * Wo * (C / 4);
-  hipLaunchKernelGGL(bn_prelu_maxpool_fwd_kernel, dim3(grid1d(n4)), dim3(256), 0, st, x, save_mean, save_invstd, gamma, beta, slope,
+  hipLaunchKernelGGL(bn_prelu_maxpool_fwd_kernel, dim3(dlip_grid1d(n4, kGridCap)), dim3(256), 0, st, x, save_mean, save_invstd, gamma, beta, slope,
                      reinterpret_cast<f32x4*>(y), idx, H, W, Ho, Wo, C / 4, n4);
   return dlip_launch_status();
 }
@@ -1617,7 +1579,7 @@ extern "C" int dlip_bn_prelu_maxpool_train_bwd_f32(const float* dy_pooled, const
   DLIP_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && (C & 3) == 0 && N * H * W < 0x7FFFFFFFll);
   DLIP_CHECK_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy_pooled) | reinterpret_cast<uintptr_t>(dy_pooled2) |
                    reinterpret_cast<uintptr_t>(dx)) & 15) == 0);
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = dlip_hip_stream(stream);
   const int M = (int)(N * H * W);
   const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
   const PoolSrc ps = {idx, dy_pooled2, H, W, Ho, Wo, dlip_fastdiv((uint32_t)W), dlip_fastdiv((uint32_t)H), dlip_fastdiv((uint32_t)Wo), dlip_fastdiv((uint32_t)Ho)};
@@ -1632,7 +1594,7 @@ extern "C" int dlip_bn_prelu_maxpool_train_bwd_f32(const float* dy_pooled, const
   unsigned* acc = dx_lift2 ? reinterpret_cast<unsigned*>(dx_lift2) + 2 : nullptr;
   const long long n4 = (long long)M * (C / 4);
   const unsigned gf = grid_fixed(n4, C / 4);
-  const unsigned grid = gf ? gf : grid1d(n4);
+  const unsigned grid = gf ? gf : dlip_grid1d(n4, kGridCap);
   if (gf)
     hipLaunchKernelGGL((bn_bwd_apply_kernel<true, true>), dim3(gf), dim3(256), 0, st, reinterpret_cast<const f32x4*>(dy_pooled),
                        reinterpret_cast<const f32x4*>(x), save_mean, save_invstd, gamma, beta, dgamma, dbeta,
@@ -1653,7 +1615,7 @@ extern "C" int dlip_bn_add_prelu_rows_train_fwd_f32(const float* x, const float*
   DLIP_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr));
   DLIP_CHECK_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(residual) | reinterpret_cast<uintptr_t>(sum) |
                    reinterpret_cast<uintptr_t>(y)) & 15) == 0);
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = dlip_hip_stream(stream);
   const int chunks = dlip_bn_rows_chunks(M);
   long long* nbt = reinterpret_cast<long long*>(num_batches_tracked);
   ColFin fin = {stream_tickets(st, (C + 63) / 64), save_mean, save_invstd, nullptr, running_mean, running_var, nbt, momentum, eps};
@@ -1668,7 +1630,7 @@ extern "C" int dlip_bn_add_prelu_rows_train_fwd_f32(const float* x, const float*
                        reinterpret_cast<const f32x4*>(residual), save_mean, save_invstd, gamma, beta, slope,
                        reinterpret_cast<f32x4*>(sum), reinterpret_cast<f32x4*>(y), n4, C / 4);
   else
-    hipLaunchKernelGGL(bn_add_prelu_fwd_kernel<false>, dim3(grid1d(n4)), dim3(256), 0, st, reinterpret_cast<const f32x4*>(x),
+    hipLaunchKernelGGL(bn_add_prelu_fwd_kernel<false>, dim3(dlip_grid1d(n4, kGridCap)), dim3(256), 0, st, reinterpret_cast<const f32x4*>(x),
                        reinterpret_cast<const f32x4*>(residual), save_mean, save_invstd, gamma, beta, slope,
                        reinterpret_cast<f32x4*>(sum), reinterpret_cast<f32x4*>(y), n4, C / 4);
   return dlip_launch_status();
@@ -1683,7 +1645,7 @@ extern "C" int dlip_bn_add_prelu_rows_train_bwd_f32(const float* dy, const float
   DLIP_CHECK_ARG(M > 0 && C > 0 && (C & 3) == 0);
   DLIP_CHECK_ARG(((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dy2) | reinterpret_cast<uintptr_t>(sum) | reinterpret_cast<uintptr_t>(x) |
                    reinterpret_cast<uintptr_t>(dresidual) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0);
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = dlip_hip_stream(stream);
   const int chunks = dlip_bn_rows_chunks(M);
   ColFin fin = {stream_tickets(st, (C + 63) / 64), dbeta, dgamma, dslope, nullptr, nullptr, nullptr, 0.f, 0.f};
   hipLaunchKernelGGL(add_prelu_bn_partial_kernel, dim3((C + 63) / 64, chunks), dim3(256), 0, st, dy, dy2, sum, x, save_mean, save_invstd,
@@ -1695,7 +1657,7 @@ extern "C" int dlip_bn_add_prelu_rows_train_bwd_f32(const float* dy, const float
   unsigned* acc = dx_lift2 ? reinterpret_cast<unsigned*>(dx_lift2) + 2 : nullptr;
   const long long n4 = (long long)M * (C / 4);
   const unsigned gf = grid_fixed(n4, C / 4);
-  const unsigned grid = gf ? gf : grid1d(n4);
+  const unsigned grid = gf ? gf : dlip_grid1d(n4, kGridCap);
   if (gf)
     hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(gf), dim3(256), 0, st, reinterpret_cast<const f32x4*>(dresidual),
                        reinterpret_cast<const f32x4*>(x), save_mean, save_invstd, gamma, beta, dgamma, dbeta,
@@ -1712,13 +1674,13 @@ extern "C" int dlip_bn_apply_rows_f32(const float* x, const float* mean, const f
                                       const float* slope_vec, float slope, float* y, int32_t M, int32_t C, dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && mean && invstd && gamma && beta && y && M > 0 && C > 0 && (C & 3) == 0);
   DLIP_CHECK_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0);
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = dlip_hip_stream(stream);
   const long long n4 = (long long)M * (C / 4);
   if (const unsigned gf = grid_fixed(n4, C / 4))
     hipLaunchKernelGGL(bn_fwd_apply_kernel<true>, dim3(gf), dim3(256), 0, st, reinterpret_cast<const f32x4*>(x), mean, invstd, gamma, beta,
                        reinterpret_cast<f32x4*>(y), n4, C / 4, slope, 0, slope_vec);
   else
-    hipLaunchKernelGGL(bn_fwd_apply_kernel<false>, dim3(grid1d(n4)), dim3(256), 0, st, reinterpret_cast<const f32x4*>(x), mean, invstd, gamma,
+    hipLaunchKernelGGL(bn_fwd_apply_kernel<false>, dim3(dlip_grid1d(n4, kGridCap)), dim3(256), 0, st, reinterpret_cast<const f32x4*>(x), mean, invstd, gamma,
                        beta, reinterpret_cast<f32x4*>(y), n4, C / 4, slope, 0, slope_vec);
   return dlip_launch_status();
 }
@@ -1726,7 +1688,7 @@ extern "C" int dlip_bn_apply_rows_f32(const float* x, const float* mean, const f
 extern "C" int dlip_colsum_rows_f32(const float* x, float* y, double* workspace, int32_t M, int32_t C,
                                     dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && y && workspace && M > 0 && C > 0 && (C & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0);
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = dlip_hip_stream(stream);
   const int chunks = dlip_bn_rows_chunks(M);
   ColFin fin = {stream_tickets(st, (C + 63) / 64), y, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f};
   hipLaunchKernelGGL(col_partial_kernel<2>, dim3((C + 63) / 64, chunks), dim3(256), 0, st, x, nullptr, nullptr, nullptr,
@@ -1750,7 +1712,7 @@ extern "C" int dlip_meanstd_pool_bwd_f32(const float* x, const float* y, const f
   if (tsplit < 1) tsplit = 1;
   if (tsplit > T) tsplit = T;
   const int tchunk = (T + tsplit - 1) / tsplit;
-  hipLaunchKernelGGL(meanstd_bwd_kernel<false>, dim3(cb, (T + tchunk - 1) / tchunk, B), dim3(bs), 0, static_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(meanstd_bwd_kernel<false>, dim3(cb, (T + tchunk - 1) / tchunk, B), dim3(bs), 0, dlip_hip_stream(stream),
                      reinterpret_cast<const f32x4*>(x), y, dy, reinterpret_cast<f32x4*>(dx), T, C4, tchunk, PoolBnB{});
   return dlip_launch_status();
 }
@@ -1771,7 +1733,7 @@ extern "C" int dlip_meanstd_pool_bwd_bn_f32(const float* z, const float* mean, c
   if (tsplit > T) tsplit = T;
   const int tchunk = (T + tsplit - 1) / tsplit;
   PoolBnB bn; bn.mean = mean; bn.invstd = invstd; bn.gamma = gamma; bn.beta = beta; bn.slope = slope;
-  hipLaunchKernelGGL(meanstd_bwd_kernel<true>, dim3(cb, (T + tchunk - 1) / tchunk, B), dim3(bs), 0, static_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(meanstd_bwd_kernel<true>, dim3(cb, (T + tchunk - 1) / tchunk, B), dim3(bs), 0, dlip_hip_stream(stream),
                      reinterpret_cast<const f32x4*>(z), y, dy, reinterpret_cast<f32x4*>(dx), T, C4, tchunk, bn);
   return dlip_launch_status();
 }
@@ -1780,7 +1742,7 @@ extern "C" int dlip_permute3_f32(const float* x, float* y, int32_t d0, int32_t d
                                  int32_t p2, int32_t flip_axis, dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && y && d0 > 0 && d1 > 0 && d2 > 0 && flip_axis >= -1 && flip_axis <= 2);
   DLIP_CHECK_ARG(p0 >= 0 && p0 < 3 && p1 >= 0 && p1 < 3 && p2 >= 0 && p2 < 3 && p0 != p1 && p0 != p2 && p1 != p2);
-  hipLaunchKernelGGL(permute3_kernel, dim3(grid1d((long long)d0 * d1 * d2)), dim3(256), 0, static_cast<hipStream_t>(stream), x,
+  hipLaunchKernelGGL(permute3_kernel, dim3(dlip_grid1d((long long)d0 * d1 * d2, kGridCap)), dim3(256), 0, dlip_hip_stream(stream), x,
                      y, d0, d1, d2, p0, p1, p2, flip_axis);
   return dlip_launch_status();
 }
@@ -1788,7 +1750,7 @@ extern "C" int dlip_permute3_f32(const float* x, float* y, int32_t d0, int32_t d
 extern "C" int dlip_pow2_scale_f32(const float* x, float* scale2, int64_t n, float target, dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && scale2 && n > 0 && target > 0.f);
   DLIP_CHECK_ARG((reinterpret_cast<uintptr_t>(x) & 15) == 0);
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = dlip_hip_stream(stream);
   if (hipMemsetAsync(scale2, 0, 2 * sizeof(float), st) != hipSuccess) return DLIP_EINVAL;
   const long long blocks = (n / 4 + 255) / 256;
   hipLaunchKernelGGL(absmax_kernel, dim3((unsigned)(blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks))), dim3(256), 0, st, x,
@@ -1799,7 +1761,7 @@ extern "C" int dlip_pow2_scale_f32(const float* x, float* scale2, int64_t n, flo
 
 extern "C" int dlip_pow2_lift_f32(const float* x, float* lift, int64_t n, float target, dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && lift && n > 0 && target > 0.f && (reinterpret_cast<uintptr_t>(x) & 15) == 0);
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = dlip_hip_stream(stream);
   long long blocks = (n / 4 + 255) / 256;
   blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
   if (hipMemsetAsync(lift + 2, 0, sizeof(float), st) != hipSuccess) return DLIP_EINVAL;
@@ -1812,7 +1774,7 @@ extern "C" int dlip_split_pack_scaled_f32(const float* x, float* y, const float*
                                           dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && y && scale && rows > 0 && C > 0 && (C & 31) == 0);
   const long long n4 = rows * (C / 4);
-  hipLaunchKernelGGL(split_pack_scaled_kernel, dim3(grid1d(n4)), dim3(256), 0, static_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(split_pack_scaled_kernel, dim3(dlip_grid1d(n4, kGridCap)), dim3(256), 0, dlip_hip_stream(stream),
                      reinterpret_cast<const f32x4*>(x), y, scale, n4, dlip_range_for(DLIP_ST_PACK));
   return dlip_launch_status();
 }
@@ -1822,14 +1784,14 @@ extern "C" int dlip_split_pack_scaled_pad_f32(const float* x, float* y, const fl
   DLIP_CHECK_ARG(x && y && scale && rows > 0 && C > 0 && (C & 3) == 0 && C_pad >= C && (C_pad & 31) == 0);
   DLIP_CHECK_ARG((reinterpret_cast<uintptr_t>(x) & 15) == 0);
   const long long n4 = rows * (C_pad / 4);
-  hipLaunchKernelGGL(split_pack_scaled_pad_kernel, dim3(grid1d(n4)), dim3(256), 0, static_cast<hipStream_t>(stream), x, y, scale,
+  hipLaunchKernelGGL(split_pack_scaled_pad_kernel, dim3(dlip_grid1d(n4, kGridCap)), dim3(256), 0, dlip_hip_stream(stream), x, y, scale,
                      (long long)rows, C, C_pad, dlip_range_for(DLIP_ST_PACK));
   return dlip_launch_status();
 }
 
 extern "C" int dlip_split_weights_rows_f32(const float* w, float* w_split, float* w_scale, int32_t K, int32_t L, dlip_stream_t stream) {
   DLIP_CHECK_ARG(w && w_split && w_scale && K > 0 && L > 0 && (L & 31) == 0);
-  hipLaunchKernelGGL(split_weights_rows_kernel, dim3((unsigned)K), dim3(256), 0, static_cast<hipStream_t>(stream), w, w_split, w_scale, L);
+  hipLaunchKernelGGL(split_weights_rows_kernel, dim3((unsigned)K), dim3(256), 0, dlip_hip_stream(stream), w, w_split, w_scale, L);
   return dlip_launch_status();
 }
 
@@ -1839,7 +1801,7 @@ extern "C" int dlip_split_weights_perm_f32(const float* w_kct, float* w_split, f
   const int inner = mode == 0 ? C : K;
   if (C_pad <= 0) C_pad = inner;
   DLIP_CHECK_ARG(C_pad >= inner && (C_pad & 31) == 0 && (long long)(mode == 0 ? K : C) * C_pad * T < (1ll << 31));
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = dlip_hip_stream(stream);
   if (mode == 0) hipLaunchKernelGGL(split_weights_perm_kernel<0>, dim3((unsigned)K), dim3(256), 0, st, w_kct, w_split, w_scale, K, C, T, C_pad);
   else hipLaunchKernelGGL(split_weights_perm_kernel<1>, dim3((unsigned)C), dim3(256), 0, st, w_kct, w_split, w_scale, K, C, T, C_pad);
   return dlip_launch_status();
@@ -1852,13 +1814,13 @@ extern "C" int dlip_split_weights_multi_f32(const void* descs, const int32_t* bl
   // the staging buffer: the launch's longest row (T * C_pad floats), at most 32 KB (longer rows are read from memory twice); dynamic
   // LDS, so that a launch of short rows keeps more workgroups on a CU
   int stage_floats = max_row_floats <= 0 || max_row_floats > 8192 ? 8192 : (max_row_floats + 31) / 32 * 32;
-  hipLaunchKernelGGL(split_weights_multi_kernel, dim3((unsigned)n_blocks), dim3(256), (size_t)stage_floats * 4, static_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(split_weights_multi_kernel, dim3((unsigned)n_blocks), dim3(256), (size_t)stage_floats * 4, dlip_hip_stream(stream),
                      static_cast<const WSplitDesc*>(descs), block_desc, stage_floats);
   return dlip_launch_status();
 }
 
 extern "C" int dlip_fill_from_scalar_f32(const float* src, float* y, int32_t n, dlip_stream_t stream) {
   DLIP_CHECK_ARG(src && y && n > 0);
-  hipLaunchKernelGGL(fill_from_scalar_kernel, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), src, y, n);
+  hipLaunchKernelGGL(fill_from_scalar_kernel, dim3((n + 255) / 256), dim3(256), 0, dlip_hip_stream(stream), src, y, n);
   return dlip_launch_status();
 }

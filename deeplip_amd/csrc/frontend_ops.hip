@@ -11,7 +11,8 @@
 //
 // Video: uint8 gray or RGB frames -> centre crop -> /255 -> (x - 0.421)/0.165
 // (models/video_models/dataloaders.py:11-22: Normalize(0,255), CenterCrop(88), Normalize(0.421,0.165)).
-#include "dlip_common.h"
+#include "dlip_launch.h"
+#include "dlip_reduce.h"
 
 namespace {
 
@@ -92,13 +93,8 @@ __global__ __launch_bounds__(256) void powspec_dft64_kernel(const float* __restr
     }
     pw[(long long)r * NBp + k] = p;
   }
-  e = dlip_wave_sum_f64(e);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = e;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const double t = part[0] + part[1] + part[2] + part[3];
-    energy[r] = t == 0.0 ? 2.220446049250313e-16f : (float)t;
-  }
+  const double t = dlip_block_sum4(e, part);
+  if (threadIdx.x == 0) energy[r] = t == 0.0 ? 2.220446049250313e-16f : (float)t;
 }
 
 // Power spectrum STRAIGHT FROM THE WAVEFORM, in the reference's own precision: python_speech_features pre-emphasises, frames and
@@ -252,11 +248,7 @@ __global__ __launch_bounds__(256) void crop_norm_kernel(const uint8_t* __restric
   }
 }
 
-inline unsigned grid_for(long long total) {
-  long long g = (total + 255) / 256;
-  if (g > 2048) g = 2048;
-  return (unsigned)(g < 1 ? 1 : g);
-}
+constexpr int kGridCap = 2048;
 
 }  // namespace
 
@@ -264,7 +256,7 @@ extern "C" int dlip_frame_preemph_f32(const float* x, float* frames, int32_t B, 
                                       int32_t frame_step, int32_t nfft, float preemph, dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && frames && B > 0 && S > 0 && NF > 0 && frame_len > 0 && frame_step > 0 && nfft >= frame_len);
   const long long total = (long long)B * NF * nfft;
-  hipLaunchKernelGGL(frame_preemph_kernel, dim3(grid_for(total)), dim3(256), 0, static_cast<hipStream_t>(stream), x,
+  hipLaunchKernelGGL(frame_preemph_kernel, dim3(dlip_grid1d(total, kGridCap)), dim3(256), 0, dlip_hip_stream(stream), x,
                      frames, S, NF, frame_len, frame_step, nfft, preemph, total);
   return dlip_launch_status();
 }
@@ -272,7 +264,7 @@ extern "C" int dlip_frame_preemph_f32(const float* x, float* frames, int32_t B, 
 extern "C" int dlip_powspec_f32(const float* spec, float* pw, float* energy, int32_t R, int32_t NB, int32_t NBp,
                                 int32_t nfft, dlip_stream_t stream) {
   DLIP_CHECK_ARG(spec && pw && energy && R > 0 && NB > 0 && NBp >= NB && nfft > 0);
-  hipLaunchKernelGGL(powspec_kernel, dim3((R + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), spec, pw, energy,
+  hipLaunchKernelGGL(powspec_kernel, dim3((R + 3) / 4), dim3(256), 0, dlip_hip_stream(stream), spec, pw, energy,
                      R, NB, NBp, 1.0f / (float)nfft);
   return dlip_launch_status();
 }
@@ -282,7 +274,7 @@ extern "C" int dlip_powspec_dft64_f32(const float* frames, float* pw, float* ene
   DLIP_CHECK_ARG(frames && pw && energy && R > 0 && NB > 0 && NBp >= NB && nfft >= 2 && nfft <= 1024 && (nfft & (nfft - 1)) == 0);
   DLIP_CHECK_ARG(NB <= nfft / 2 + 1);
   hipLaunchKernelGGL(powspec_dft64_kernel, dim3(R), dim3(256), (size_t)(3 * nfft + 4) * sizeof(double),
-                     static_cast<hipStream_t>(stream), frames, pw, energy, NB, NBp, nfft);
+                     dlip_hip_stream(stream), frames, pw, energy, NB, NBp, nfft);
   return dlip_launch_status();
 }
 
@@ -295,14 +287,14 @@ extern "C" int dlip_powspec_wave_fft64_f32(const float* x, float* pw, float* ene
   while ((1 << lg) < nfft) ++lg;
   const int threads = nfft / 2;            // 64 .. 512: one butterfly per thread and stage
   const size_t lds = (size_t)(3 * nfft + 8) * sizeof(double);
-  hipLaunchKernelGGL(powspec_wave_fft64_kernel, dim3((unsigned)(B * NF)), dim3((unsigned)threads), lds, static_cast<hipStream_t>(stream), x, pw,
+  hipLaunchKernelGGL(powspec_wave_fft64_kernel, dim3((unsigned)(B * NF)), dim3((unsigned)threads), lds, dlip_hip_stream(stream), x, pw,
                      energy, (long long)S, NF, frame_len, frame_step, nfft, lg, preemph, NB, NBp);
   return dlip_launch_status();
 }
 
 extern "C" int dlip_log_floor_f32(const float* x, float* y, int64_t n, dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && y && n > 0);
-  hipLaunchKernelGGL(log_floor_kernel, dim3(grid_for(n)), dim3(256), 0, static_cast<hipStream_t>(stream), x, y, (long long)n);
+  hipLaunchKernelGGL(log_floor_kernel, dim3(dlip_grid1d(n, kGridCap)), dim3(256), 0, dlip_hip_stream(stream), x, y, (long long)n);
   return dlip_launch_status();
 }
 
@@ -310,7 +302,7 @@ extern "C" int dlip_cmvn_nct_f32(const float* feat, const float* energy, float* 
                                  int32_t ldf, int32_t normalize, dlip_stream_t stream) {
   DLIP_CHECK_ARG(feat && y && B > 0 && NF > 0 && C > 0 && ldf >= C);
   hipLaunchKernelGGL(cmvn_kernel, dim3((unsigned)(((long long)B * C + 255) / 256)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), feat, energy, y, B, NF, C, ldf, normalize);
+                     dlip_hip_stream(stream), feat, energy, y, B, NF, C, ldf, normalize);
   return dlip_launch_status();
 }
 
@@ -318,7 +310,7 @@ extern "C" int dlip_delta_nct_f32(const float* x, float* y, int32_t B, int32_t C
                                   dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && y && B > 0 && C > 0 && NF > 0 && (order == 1 || order == 2));
   const long long rows = (long long)B * C;
-  hipLaunchKernelGGL(delta_kernel, dim3(grid_for(rows * NF)), dim3(256), 0, static_cast<hipStream_t>(stream), x, y, rows, C, NF,
+  hipLaunchKernelGGL(delta_kernel, dim3(dlip_grid1d(rows * NF, kGridCap)), dim3(256), 0, dlip_hip_stream(stream), x, y, rows, C, NF,
                      order);
   return dlip_launch_status();
 }
@@ -327,7 +319,7 @@ extern "C" int dlip_crop_normalize_u8(const uint8_t* x, const int32_t* clip_para
                                       int64_t n_frames, int32_t channels, int32_t H, int32_t W, int32_t crop, dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && y && n_frames > 0 && (channels == 1 || channels == 3) && crop > 0 && H >= crop && W >= crop);
   DLIP_CHECK_ARG(T > 0 && n_frames % T == 0);
-  hipLaunchKernelGGL(crop_norm_kernel, dim3(grid_for(n_frames * crop * crop)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), x, y, (long long)n_frames, channels, H, W, crop, T, clip_params, lengths);
+  hipLaunchKernelGGL(crop_norm_kernel, dim3(dlip_grid1d(n_frames * crop * crop, kGridCap)), dim3(256), 0,
+                     dlip_hip_stream(stream), x, y, (long long)n_frames, channels, H, W, crop, T, clip_params, lengths);
   return dlip_launch_status();
 }

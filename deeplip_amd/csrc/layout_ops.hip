@@ -1,6 +1,6 @@
 // Layout adapters at the drop-in boundary: the reference's modules speak channel-first
 // ([B,F,T] acoustic features, tdnn.py:89), the kernels speak channels-last.
-#include "dlip_common.h"
+#include "dlip_launch.h"
 
 namespace {
 
@@ -75,7 +75,7 @@ extern "C" int dlip_nct_to_ntc_f32(const float* x, float* y, int32_t B, int32_t 
   DLIP_CHECK_ARG(x && y && B > 0 && C > 0 && T > 0 && Cp >= C && B <= 65535);
   // rows = C, cols = T  ->  y [B, T, Cp]
   dim3 grid((T + 31) / 32, (Cp + 31) / 32, B);
-  hipLaunchKernelGGL(transpose_pad_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), x, y, C, T, Cp);
+  hipLaunchKernelGGL(transpose_pad_kernel, grid, dim3(256), 0, dlip_hip_stream(stream), x, y, C, T, Cp);
   return dlip_launch_status();
 }
 
@@ -83,7 +83,7 @@ extern "C" int dlip_nct_to_ntc_split_f32(const float* x, float* y, int32_t B, in
                                          dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && y && B > 0 && C > 0 && T > 0 && Cp >= C && (Cp & 31) == 0 && B <= 65535);
   dim3 grid((T + 31) / 32, Cp / 32, B);
-  hipLaunchKernelGGL(transpose_split_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), x, y, C, T, Cp,
+  hipLaunchKernelGGL(transpose_split_kernel, grid, dim3(256), 0, dlip_hip_stream(stream), x, y, C, T, Cp,
                      dlip_range_for(DLIP_ST_PACK));
   return dlip_launch_status();
 }
@@ -92,7 +92,7 @@ extern "C" int dlip_ntc_to_nct_f32(const float* x, float* y, int32_t B, int32_t 
                                    dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && y && B > 0 && C > 0 && T > 0 && B <= 65535);
   dim3 grid((C + 31) / 32, (T + 31) / 32, B);
-  hipLaunchKernelGGL(transpose_pad_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), x, y, T, C, T);
+  hipLaunchKernelGGL(transpose_pad_kernel, grid, dim3(256), 0, dlip_hip_stream(stream), x, y, T, C, T);
   return dlip_launch_status();
 }
 
@@ -101,7 +101,7 @@ extern "C" int dlip_ingest_rgb_u8(const uint8_t* x, float* y, int64_t n_frames, 
   DLIP_CHECK_ARG(x && y && n_frames > 0 && H > 0 && W > 0);
   long long g = (n_frames * H * W + 255) / 256;
   if (g > 2048) g = 2048;
-  hipLaunchKernelGGL(ingest_rgb_kernel, dim3((unsigned)g), dim3(256), 0, static_cast<hipStream_t>(stream), x, y,
+  hipLaunchKernelGGL(ingest_rgb_kernel, dim3((unsigned)g), dim3(256), 0, dlip_hip_stream(stream), x, y,
                      (long long)n_frames, H * W);
   return dlip_launch_status();
 }
@@ -131,7 +131,7 @@ extern "C" int dlip_affine_act_f32(const float* x, const float* scale, const flo
   DLIP_CHECK_ARG(x && scale && shift && y && M > 0 && C > 0 && (order == 0 || order == 1));
   long long g = (M * C + 255) / 256;
   if (g > 2048) g = 2048;
-  hipLaunchKernelGGL(affine_act_kernel, dim3((unsigned)g), dim3(256), 0, static_cast<hipStream_t>(stream), x, scale,
+  hipLaunchKernelGGL(affine_act_kernel, dim3((unsigned)g), dim3(256), 0, dlip_hip_stream(stream), x, scale,
                      shift, y, (long long)M * C, C, slope, order);
   return dlip_launch_status();
 }
@@ -172,7 +172,7 @@ extern "C" int dlip_split_pack_f32(const float* x, float* y, int64_t rows, int32
   DLIP_CHECK_ARG(x && y && rows > 0 && C > 0 && (C & 31) == 0);
   const long long n4 = rows * (C / 4);
   long long g = (n4 + 255) / 256; if (g > 2048) g = 2048;
-  hipLaunchKernelGGL(split_pack_kernel, dim3((unsigned)g), dim3(256), 0, static_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(split_pack_kernel, dim3((unsigned)g), dim3(256), 0, dlip_hip_stream(stream),
                      reinterpret_cast<const f32x4*>(x), y, n4, dlip_range_for(DLIP_ST_PACK));
   return dlip_launch_status();
 }
@@ -181,7 +181,7 @@ extern "C" int dlip_split_unpack_f32(const float* x, float* y, int64_t rows, int
   DLIP_CHECK_ARG(x && y && rows > 0 && C > 0 && (C & 31) == 0);
   const long long n4 = rows * (C / 4);
   long long g = (n4 + 255) / 256; if (g > 2048) g = 2048;
-  hipLaunchKernelGGL(split_unpack_kernel, dim3((unsigned)g), dim3(256), 0, static_cast<hipStream_t>(stream), x,
+  hipLaunchKernelGGL(split_unpack_kernel, dim3((unsigned)g), dim3(256), 0, dlip_hip_stream(stream), x,
                      reinterpret_cast<f32x4*>(y), n4);
   return dlip_launch_status();
 }
@@ -207,7 +207,7 @@ extern "C" int dlip_mask_frames_f32(const float* x, const int32_t* len, float* y
   DLIP_CHECK_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0);
   const long long n4 = (long long)B * T * (E / 4);
   long long g = (n4 + 255) / 256; if (g > 4096) g = 4096;
-  hipLaunchKernelGGL(mask_frames_kernel, dim3((unsigned)g), dim3(256), 0, static_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(mask_frames_kernel, dim3((unsigned)g), dim3(256), 0, dlip_hip_stream(stream),
                      reinterpret_cast<const f32x4*>(x), reinterpret_cast<f32x4*>(y), len, T, E / 4, n4);
   return dlip_launch_status();
 }

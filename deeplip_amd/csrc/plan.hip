@@ -7,7 +7,7 @@
 // dlip_plan_run -- one host call per step, kernel boundaries back to back on the device.  The library adds
 // nothing to the graph beyond what the caller launched; buffers stay caller-owned (the Python binding keeps
 // every tensor of the recorded step alive in an arena, deeplip_amd/plan.py).
-#include "dlip_common.h"
+#include "dlip_launch.h"
 
 #include <vector>
 
@@ -24,7 +24,7 @@ struct Plan {
 }  // namespace
 
 extern "C" int dlip_plan_begin(dlip_stream_t stream) {
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = dlip_hip_stream(stream);
   DLIP_CHECK_ARG(st != nullptr);   // the null stream cannot be captured
   hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
   hipError_t e = hipStreamIsCapturing(st, &status);
@@ -35,7 +35,7 @@ extern "C" int dlip_plan_begin(dlip_stream_t stream) {
 }
 
 extern "C" int dlip_plan_end(dlip_stream_t stream, dlip_plan_t* plan) {
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = dlip_hip_stream(stream);
   DLIP_CHECK_ARG(st != nullptr && plan != nullptr);
   *plan = nullptr;
   hipGraph_t graph = nullptr;
@@ -69,7 +69,7 @@ extern "C" int dlip_plan_end(dlip_stream_t stream, dlip_plan_t* plan) {
 extern "C" int dlip_plan_run(dlip_plan_t plan, dlip_stream_t stream) {
   DLIP_CHECK_ARG(plan != nullptr);
   Plan* p = static_cast<Plan*>(plan);
-  hipError_t e = hipGraphLaunch(p->exec, static_cast<hipStream_t>(stream));
+  hipError_t e = hipGraphLaunch(p->exec, dlip_hip_stream(stream));
   return e == hipSuccess ? DLIP_OK : (int)e;
 }
 

@@ -2,7 +2,8 @@
 // temporal mean, clip-group mean, mean + unbiased-std statistics pooling.  One thread owns one
 // channel (or a float4 of channels) so every wave access is a contiguous 256 B - 1 KiB segment;
 // statistics accumulate in fp64 (torch's CPU reductions accumulate float inputs in double).
-#include "dlip_common.h"
+#include "dlip_launch.h"
+#include "dlip_reduce.h"
 
 namespace {
 
@@ -173,12 +174,7 @@ __global__ __launch_bounds__(256) void meanstd_kernel(const float* __restrict__ 
   if (SPLIT) dlip_report_range(amax, status);
 }
 
-static inline unsigned grid_for(long long total) {
-  long long g = (total + 255) / 256;
-  if (g > 256 * 8) g = 256 * 8;  // 8 workgroups per CU, grid-stride the rest
-  if (g < 1) g = 1;
-  return (unsigned)g;
-}
+constexpr int kGridCap = 256 * 8;  // 8 workgroups per CU, grid-stride the rest
 
 }  // namespace
 
@@ -188,11 +184,11 @@ extern "C" int dlip_maxpool3x3s2_nhwc_f32(const float* x, float* y, int32_t N, i
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
   const long long total = (long long)N * Ho * Wo * (C / 4);
   if (out_split)
-    hipLaunchKernelGGL(maxpool3x3s2_kernel<true>, dim3(grid_for(total)), dim3(256), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(maxpool3x3s2_kernel<true>, dim3(dlip_grid1d(total, kGridCap)), dim3(256), 0, dlip_hip_stream(stream),
                        reinterpret_cast<const f32x4*>(x), reinterpret_cast<f32x4*>(y), N, H, W, C / 4, Ho, Wo,
                        dlip_range_for(DLIP_ST_PACK));
   else
-    hipLaunchKernelGGL(maxpool3x3s2_kernel<false>, dim3(grid_for(total)), dim3(256), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(maxpool3x3s2_kernel<false>, dim3(dlip_grid1d(total, kGridCap)), dim3(256), 0, dlip_hip_stream(stream),
                        reinterpret_cast<const f32x4*>(x), reinterpret_cast<f32x4*>(y), N, H, W, C / 4, Ho, Wo, DlipRange{});
   return dlip_launch_status();
 }
@@ -200,8 +196,8 @@ extern "C" int dlip_maxpool3x3s2_nhwc_f32(const float* x, float* y, int32_t N, i
 extern "C" int dlip_avgpool_nhwc_f32(const float* x, float* y, int32_t N, int32_t HW, int32_t C,
                                      dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && y && N > 0 && HW > 0 && C > 0);
-  hipLaunchKernelGGL(avgpool_kernel, dim3(grid_for((long long)N * C)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), x, y, N, HW, C);
+  hipLaunchKernelGGL(avgpool_kernel, dim3(dlip_grid1d((long long)N * C, kGridCap)), dim3(256), 0,
+                     dlip_hip_stream(stream), x, y, N, HW, C);
   return dlip_launch_status();
 }
 
@@ -209,16 +205,16 @@ extern "C" int dlip_time_mean_f32(const float* x, const int32_t* len, int32_t le
                                   int32_t ldx, dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && y && B > 0 && T > 0 && C > 0 && ldx >= C);
   DlipLen l; l.len = len; l.mul = 1; l.add = len_add;
-  hipLaunchKernelGGL(time_mean_kernel, dim3(grid_for((long long)B * C)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), x, l, y, B, T, C, ldx);
+  hipLaunchKernelGGL(time_mean_kernel, dim3(dlip_grid1d((long long)B * C, kGridCap)), dim3(256), 0,
+                     dlip_hip_stream(stream), x, l, y, B, T, C, ldx);
   return dlip_launch_status();
 }
 
 extern "C" int dlip_group_mean_f32(const float* x, const int32_t* group_ptr, float* y, int32_t U, int32_t C,
                                    dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && group_ptr && y && U > 0 && C > 0);
-  hipLaunchKernelGGL(group_mean_kernel, dim3(grid_for((long long)U * C)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), x, group_ptr, y, U, C);
+  hipLaunchKernelGGL(group_mean_kernel, dim3(dlip_grid1d((long long)U * C, kGridCap)), dim3(256), 0,
+                     dlip_hip_stream(stream), x, group_ptr, y, U, C);
   return dlip_launch_status();
 }
 
@@ -229,10 +225,10 @@ extern "C" int dlip_meanstd_pool_f32(const float* x, const int32_t* len, int32_t
   const dim3 grid((C + 63) / 64, B);
   DlipLen l; l.len = len; l.mul = 1; l.add = len_add;
   if (out_split)
-    hipLaunchKernelGGL(meanstd_kernel<true>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), x, y, T, C,
+    hipLaunchKernelGGL(meanstd_kernel<true>, grid, dim3(256), 0, dlip_hip_stream(stream), x, y, T, C,
                        (2 * C + 31) / 32 * 32, l, dlip_range_for(DLIP_ST_POOL));
   else
-    hipLaunchKernelGGL(meanstd_kernel<false>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), x, y, T, C, 2 * C, l,
+    hipLaunchKernelGGL(meanstd_kernel<false>, grid, dim3(256), 0, dlip_hip_stream(stream), x, y, T, C, 2 * C, l,
                        DlipRange{});
   return dlip_launch_status();
 }
@@ -243,7 +239,7 @@ extern "C" int dlip_meanstd_pool_bn_f32(const float* z, const float* mean, const
   DLIP_CHECK_ARG((reinterpret_cast<uintptr_t>(z) & 15) == 0);
   DlipLen l; l.len = nullptr; l.mul = 1; l.add = 0;
   PoolBn bn; bn.mean = mean; bn.invstd = invstd; bn.gamma = gamma; bn.beta = beta; bn.slope = slope;
-  hipLaunchKernelGGL((meanstd_kernel<false, true>), dim3((C + 63) / 64, B), dim3(256), 0, static_cast<hipStream_t>(stream), z, y, T, C, 2 * C, l,
+  hipLaunchKernelGGL((meanstd_kernel<false, true>), dim3((C + 63) / 64, B), dim3(256), 0, dlip_hip_stream(stream), z, y, T, C, 2 * C, l,
                      DlipRange{}, bn);
   return dlip_launch_status();
 }
@@ -307,7 +303,7 @@ extern "C" int dlip_attentive_stat_pool_f32(const float* x, const float* hidden,
   DLIP_CHECK_ARG(x && hidden && v && k && y && B > 0 && T > 0 && C > 0 && Hd > 0 && T <= 16000);
   DlipLen l; l.len = len; l.mul = 1; l.add = len_add;
   hipLaunchKernelGGL(attentive_stat_kernel, dim3(B), dim3(256), (size_t)T * sizeof(float),
-                     static_cast<hipStream_t>(stream), x, hidden, v, k, y, alpha_out, T, C, Hd, l);
+                     dlip_hip_stream(stream), x, hidden, v, k, y, alpha_out, T, C, Hd, l);
   return dlip_launch_status();
 }
 
@@ -354,14 +350,9 @@ __global__ __launch_bounds__(256) void attentive_stat_bwd_kernel(const float* __
     if (lane == 0) dal[t] = (float)a;
   }
   __syncthreads();
-  {
-    double part = 0.0;
-    for (int t = threadIdx.x; t < T; t += 256) part += (double)ab[t] * (double)dal[t];
-    part = dlip_wave_sum_f64(part);
-    if (lane == 0) red[wave] = part;
-  }
-  __syncthreads();
-  const double dot = red[0] + red[1] + red[2] + red[3];
+  double dot = 0.0;
+  for (int t = threadIdx.x; t < T; t += 256) dot += (double)ab[t] * (double)dal[t];
+  dot = dlip_block_sum4(dot, red);
   for (int t = threadIdx.x; t < Tpad; t += 256) {
     const float de = t < T ? (float)((double)ab[t] * ((double)dal[t] - dot)) : 0.f;
     dal[t] = de;
@@ -393,7 +384,7 @@ extern "C" int dlip_attentive_stat_pool_bwd_f32(const float* x, const float* hid
   const size_t lds = ((size_t)2 * C + T) * sizeof(float);
   DLIP_CHECK_ARG(lds <= 60 * 1024);
   DlipLen l; l.len = len; l.mul = 1; l.add = len_add;
-  hipLaunchKernelGGL(attentive_stat_bwd_kernel, dim3(B), dim3(256), lds, static_cast<hipStream_t>(stream), x, hidden, v, alpha, y, dy,
+  hipLaunchKernelGGL(attentive_stat_bwd_kernel, dim3(B), dim3(256), lds, dlip_hip_stream(stream), x, hidden, v, alpha, y, dy,
                      dx, dhidden, rde, de, T, C, Hd, l);
   return dlip_launch_status();
 }
@@ -467,8 +458,8 @@ extern "C" int dlip_pool_finish_f32(const double* partials, int64_t M, int32_t K
   const int Kp = (K + 127) / 128 * 128;   // the pooled epilogue exists on the 128-column tiles only
   const long long G = (M + group_rows - 1) / group_rows;
   DLIP_CHECK_ARG(G <= 0x7FFFFFFF);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const unsigned grid = grid_for(G * K);
+  hipStream_t st = dlip_hip_stream(stream);
+  const unsigned grid = dlip_grid1d(G * K, kGridCap);
   const DlipRange status = (mode == 1 && out_split) ? dlip_range_for(DLIP_ST_POOL) : DlipRange{};   // only a split output is a producer
   DlipLen l; l.len = group_len; l.mul = len_mul; l.add = len_add;
   if (mode == 0)

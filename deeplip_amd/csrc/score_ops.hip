@@ -3,7 +3,7 @@
 // first-max argmax, margin softmax cross-entropy value, LowFER concat.
 // All rows are short (<= a few thousand floats): one 64-lane wave owns a row, lanes stride the
 // row with coalesced loads, reductions are wavefront shuffles (no LDS, no atomics) in fp64.
-#include "dlip_common.h"
+#include "dlip_launch.h"
 
 namespace {
 
@@ -244,7 +244,7 @@ extern "C" int dlip_znorm_cat_f32(const float* a, int32_t Da, const float* v, in
   DLIP_CHECK_ARG(y && U > 0 && Da >= 0 && Dv >= 0 && (Da + Dv) > 0);
   DLIP_CHECK_ARG((Da == 0 || a) && (Dv == 0 || v));
   hipLaunchKernelGGL(znorm_cat_kernel, dim3((U + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), a, Da, v, Dv, y, U, biased);
+                     dlip_hip_stream(stream), a, Da, v, Dv, y, U, biased);
   return dlip_launch_status();
 }
 
@@ -255,7 +255,7 @@ extern "C" int dlip_znorm_cat_pooled_f32(const float* a, int32_t Da, const doubl
   DLIP_CHECK_ARG((Da == 0 || a) && (M + group_rows - 1) / group_rows == U);
   DlipLen l; l.len = group_len; l.mul = len_mul; l.add = len_add;
   hipLaunchKernelGGL(znorm_cat_pooled_kernel, dim3((U + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), a, Da, partials, (long long)M, K, (K + 127) / 128 * 128, tile_rows,
+                     dlip_hip_stream(stream), a, Da, partials, (long long)M, K, (K + 127) / 128 * 128, tile_rows,
                      group_rows, l, y, U, biased);
   return dlip_launch_status();
 }
@@ -264,7 +264,7 @@ extern "C" int dlip_l2_normalize_f32(const float* x, float* y, int32_t U, int32_
                                      dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && y && U > 0 && D > 0);
   hipLaunchKernelGGL(l2norm_kernel, dim3((U + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), x, y, U, D, eps);
+                     dlip_hip_stream(stream), x, y, U, D, eps);
   return dlip_launch_status();
 }
 
@@ -273,7 +273,7 @@ extern "C" int dlip_pair_cosine_f32(const float* emb, int32_t N, int32_t D, cons
                                     float weight, int32_t accumulate, dlip_stream_t stream) {
   DLIP_CHECK_ARG(emb && idx_a && idx_b && score && N > 0 && D > 0 && n_trials > 0 && (mode == 0 || mode == 1));
   hipLaunchKernelGGL(pair_cosine_kernel, dim3((n_trials + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), emb, N, D, idx_a, idx_b, score, n_trials, mode, eps, weight,
+                     dlip_hip_stream(stream), emb, N, D, idx_a, idx_b, score, n_trials, mode, eps, weight,
                      accumulate);
   return dlip_launch_status();
 }
@@ -282,7 +282,7 @@ extern "C" int dlip_plda_llr_f32(const float* u, int32_t N, int32_t D, const flo
                                 const int32_t* idx_b, float* score, int32_t n_trials, dlip_stream_t stream) {
   DLIP_CHECK_ARG(u && psi && idx_a && idx_b && score && N > 0 && D > 0 && n_trials > 0);
   hipLaunchKernelGGL(plda_llr_kernel, dim3((n_trials + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), u, N, D, psi, idx_a, idx_b, score, n_trials);
+                     dlip_hip_stream(stream), u, N, D, psi, idx_a, idx_b, score, n_trials);
   return dlip_launch_status();
 }
 
@@ -290,7 +290,7 @@ extern "C" int dlip_logits_argmax_f32(const float* e, const float* W, const floa
                                       int64_t* argmax, int32_t B, int32_t D, int32_t K, int32_t cosine,
                                       dlip_stream_t stream) {
   DLIP_CHECK_ARG(e && W && logits && B > 0 && D > 0 && K > 0 && K <= 1024);
-  hipLaunchKernelGGL(logits_argmax_kernel, dim3(B), dim3(256), 0, static_cast<hipStream_t>(stream), e, W, bias,
+  hipLaunchKernelGGL(logits_argmax_kernel, dim3(B), dim3(256), 0, dlip_hip_stream(stream), e, W, bias,
                      logits, reinterpret_cast<long long*>(argmax), D, K, cosine);
   return dlip_launch_status();
 }
@@ -298,7 +298,7 @@ extern "C" int dlip_logits_argmax_f32(const float* e, const float* W, const floa
 extern "C" int dlip_margin_ce_loss_f32(const float* logits, const int64_t* labels, float* loss, int32_t B,
                                        int32_t K, float scale, float margin, dlip_stream_t stream) {
   DLIP_CHECK_ARG(logits && labels && loss && B > 0 && K > 0);
-  hipLaunchKernelGGL(margin_ce_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), logits,
+  hipLaunchKernelGGL(margin_ce_kernel, dim3(1), dim3(256), 0, dlip_hip_stream(stream), logits,
                      reinterpret_cast<const long long*>(labels), loss, B, K, scale, margin);
   return dlip_launch_status();
 }
@@ -308,7 +308,7 @@ extern "C" int dlip_lowfer_cat_f32(const float* e1, const float* e2, float* y, i
   DLIP_CHECK_ARG(e1 && e2 && y && B > 0 && D > 0);
   long long g = ((long long)B * D + 255) / 256;
   if (g > 2048) g = 2048;
-  hipLaunchKernelGGL(lowfer_cat_kernel, dim3((unsigned)g), dim3(256), 0, static_cast<hipStream_t>(stream), e1, e2,
+  hipLaunchKernelGGL(lowfer_cat_kernel, dim3((unsigned)g), dim3(256), 0, dlip_hip_stream(stream), e1, e2,
                      y, B, D);
   return dlip_launch_status();
 }

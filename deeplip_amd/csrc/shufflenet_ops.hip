@@ -9,7 +9,7 @@
 // Channel layout of a unit's output (deeplip_amd/shufflenet.py): logical channel L of a 2*h-channel output lives at physical
 // channel L (L < h) or hp + L - h (L >= h), hp = h rounded up to 4; the pitch is 2*hp and the padding channels hold zeros.
 // channel_shuffle (shufflenetv2.py:27-40) sends branch channel j to logical 2j (first branch) or 2j + 1 (second branch).
-#include "dlip_common.h"
+#include "dlip_launch.h"
 
 namespace {
 
@@ -282,7 +282,7 @@ extern "C" int dlip_shuffle_stem24_f32(const float* x, const float* w_248x32, co
       (long long)B * T * a.Ho * a.Wo * SK * 4 > DLIP_MAX_BUFFER_BYTES)
     return DLIP_ERANGE;
   const size_t lds = (size_t)(KT * PR * a.pwp) * 4;
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = dlip_hip_stream(stream);
   const int tiles = (ROWS * a.Wo + 15) / 16;     // split between the two pixel halves of the workgroup
   if (tiles <= 12) {
     hipLaunchKernelGGL(shuffle_stem24_f32_kernel<6>, dim3((unsigned)grid), dim3(256), lds, st, a);
@@ -324,7 +324,7 @@ extern "C" int dlip_shuffle_dwpw_f32(const float* x, const float* dw_w, const fl
   // column tile: 64 channels unless K fits a narrower one -- every column block recomputes the depthwise stage of its pixels, so a
   // narrower tile that only trims padding (K = 232: 15 blocks of 16 instead of 4 of 64) measured 2.4x slower per launch
   const int nt = K <= 16 ? 1 : K <= 32 ? 2 : 4;
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = dlip_hip_stream(stream);
   const bool dw = dw_w != nullptr;
   if (nt == 4) launch_dwpw<4>(a, dw, st);
   else if (nt == 2) launch_dwpw<2>(a, dw, st);
@@ -337,7 +337,7 @@ extern "C" int dlip_avgpool3_nhwc_f32(const float* x, float* y, int32_t N, int32
   DLIP_CHECK_ARG(H >= 3 && H <= 5 && W >= 3 && W <= 5);   // AvgPool2d(3) of the map gives exactly one pixel
   const long long total = (long long)N * C;
   if ((long long)N * H * W * C > DLIP_MAX_BUFFER_BYTES / 4) return DLIP_ERANGE;
-  hipLaunchKernelGGL(avgpool3_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), x, y, N,
+  hipLaunchKernelGGL(avgpool3_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, dlip_hip_stream(stream), x, y, N,
                      H, W, C);
   return dlip_launch_status();
 }

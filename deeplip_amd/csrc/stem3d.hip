@@ -11,7 +11,7 @@
 //   * A fragments are gathered straight from the LDS window with ds_read_b32 (tap offset walked in
 //     registers + a per-lane pixel offset; stride-2 pixels x 4 tap quarters = mostly conflict
 //     free), v_mfma_f32_16x16x4_f32 accumulates exact fp32, 11 independent accumulators per wave.
-#include "dlip_common.h"
+#include "dlip_launch.h"
 
 namespace {
 
@@ -144,7 +144,7 @@ extern "C" int dlip_stem3d_bn_act_f32(const float* x, const float* w_248xk, cons
   const long long grid = (long long)B * T * a.row_tiles;
   if (grid > 0x7FFFFFFFll) return DLIP_ERANGE;
   const size_t lds = (size_t)(KT * PR * a.pwp) * 4;
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = dlip_hip_stream(stream);
   const int mt = (ROWS * a.Wo + 15) / 16;
   if (mt <= 11) {
     hipLaunchKernelGGL(stem3d_f32_kernel<11>, dim3((unsigned)grid), dim3(256), lds, st, a);

@@ -22,6 +22,7 @@
 // The fused stem + max-pool kernel (dlip_stem3d_pool_f16x3) is the second kernel of this file: same weights
 // image, window layout and tap gather, different pixel -> lane map (chosen for the pooling) and window transport.
 #include "conv_dma_common.h"
+#include "dlip_launch.h"
 #include <algorithm>
 #include <type_traits>
 #include <cstdio>
@@ -718,7 +719,7 @@ extern "C" int dlip_stem3d_bn_act_f16x3(const float* x, const void* w_split, con
     if (!dbuf) (void)hipMalloc(reinterpret_cast<void**>(&dbuf), 256 * 8 * 8);
     (void)hipMemset(dbuf, 0, 256 * 8 * 8);
     a.stamps = dbuf;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), ldsb, static_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), ldsb, dlip_hip_stream(stream), a);
     (void)hipDeviceSynchronize();
     unsigned long long h[256 * 8];
     (void)hipMemcpy(h, dbuf, sizeof(h), hipMemcpyDeviceToHost);
@@ -731,7 +732,7 @@ extern "C" int dlip_stem3d_bn_act_f16x3(const float* x, const void* w_split, con
     return dlip_launch_status();
   }
 #endif
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), ldsb, static_cast<hipStream_t>(stream), a);
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), ldsb, dlip_hip_stream(stream), a);
   return dlip_launch_status();
 }
 
@@ -771,7 +772,7 @@ static int stem_pool_launch(const void* x, int src_kind, int CH, int Hs, int Ws,
   const DlipRange in_status = dlip_range_for(DLIP_ST_STEM);
   a.status = dlip_range_for(DLIP_ST_STEM);
   a.span = dlip_span_next();
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = dlip_hip_stream(stream);
   {   // pre-pass: the clip as (hi, lo) pairs at the window's row pitch
     const long long chunks = frames * H * (a.pwp / 4);
     const unsigned pgrid = (unsigned)std::min<long long>((chunks + 255) / 256, 256 * 16);

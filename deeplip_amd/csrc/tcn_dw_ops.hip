@@ -9,7 +9,7 @@
 // Layout: channels-last [B, T, C] fp32, C % 4 == 0, weights tap-major [k][C].  Every thread owns one channel quad (float4 loads and
 // stores along C) of one row; a launch serves up to DW_MAX_BR branches that read the same input (the kernel sizes of one dwpw MS-TCN
 // stage), one grid row per branch.
-#include "dlip_common.h"
+#include "dlip_launch.h"
 
 namespace {
 
@@ -191,7 +191,7 @@ extern "C" int dlip_tcn_dw_fwd_f32(const float* x, int32_t n, const float* const
   }
   if ((most + 255) / 256 > 0x7FFFFFFFll) return DLIP_ERANGE;
   hipLaunchKernelGGL(tcn_dw_fwd_kernel, dim3((unsigned)((most + 255) / 256), (unsigned)n), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), a);
+                     dlip_hip_stream(stream), a);
   return dlip_launch_status();
 }
 
@@ -209,7 +209,7 @@ extern "C" int dlip_tcn_dw_dgrad_f32(const float* const* dz, int32_t n, const fl
     a.br[r].w = w[r];
   }
   const long long total = (long long)B * T * (C / 4);
-  hipLaunchKernelGGL(tcn_dw_dgrad_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  hipLaunchKernelGGL(tcn_dw_dgrad_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, dlip_hip_stream(stream), a);
   return dlip_launch_status();
 }
 
@@ -237,7 +237,7 @@ extern "C" int dlip_tcn_dw_wgrad_f32(const float* x, int32_t n, const float* con
   }
   DLIP_CHECK_ARG(off <= workspace_len);
   if (most_chunks > 65535) return DLIP_ERANGE;
-  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipStream_t s = dlip_hip_stream(stream);
   hipLaunchKernelGGL(tcn_dw_wgrad_partial_kernel, dim3((unsigned)((C / 4 + 63) / 64), (unsigned)most_chunks, (unsigned)n), dim3(64), 0,
                      s, a);
   const int e = dlip_launch_status();

@@ -6,7 +6,8 @@
 // deterministic summation order (no atomics).  The gradient GEMMs (57-wide / batch-wide reductions)
 // use the small general GEMM at the end of this file; torch.autograd is only the tape
 // (deeplip_amd/autograd.py).
-#include "dlip_common.h"
+#include "dlip_launch.h"
+#include "dlip_reduce.h"
 
 namespace {
 
@@ -92,11 +93,8 @@ __global__ __launch_bounds__(256) void l1_sum_kernel(const float* __restrict__ w
   __shared__ double red[4];
   double s = 0.0;
   for (long long i = threadIdx.x; i < n; i += 256) s += (double)fabsf(w[i]);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) out[0] = (float)(((red[0] + red[1]) + red[2]) + red[3]);
+  s = dlip_block_sum4(s, red);
+  if (threadIdx.x == 0) out[0] = (float)s;
 }
 
 __global__ __launch_bounds__(256) void l1_sign_kernel(const float* __restrict__ w, const float* __restrict__ gscale, float* __restrict__ dw,
@@ -123,8 +121,7 @@ __global__ __launch_bounds__(256) void margin_ce_bwd_kernel(const float* __restr
   const int lab = (int)labels[b];
   float mx = -__builtin_inff();
   for (int k = lane; k < K; k += 64) mx = fmaxf(mx, scale * (p[k] - (k == lab ? margin : 0.f)) + 1e-8f);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  mx = dlip_wave_max(mx);
   double se = 0.0;
   for (int k = lane; k < K; k += 64) se += exp((double)(scale * (p[k] - (k == lab ? margin : 0.f)) + 1e-8f - mx));
   se = dlip_wave_sum_f64(se);
@@ -197,7 +194,7 @@ extern "C" int dlip_bn1d_train_fwd_f32(const float* x, const float* gamma, const
                                        float slope, dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && gamma && beta && y && save_mean && save_invstd && M > 0 && C > 0);
   DLIP_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr));
-  hipLaunchKernelGGL(bn1d_train_fwd_kernel, dim3((C + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), x,
+  hipLaunchKernelGGL(bn1d_train_fwd_kernel, dim3((C + 255) / 256), dim3(256), 0, dlip_hip_stream(stream), x,
                      gamma, beta, y, save_mean, save_invstd, running_mean, running_var, M, C, momentum, eps, slope);
   return dlip_launch_status();
 }
@@ -206,7 +203,7 @@ extern "C" int dlip_bn1d_train_bwd_f32(const float* dy, const float* x, const fl
                                        const float* save_invstd, const float* gamma, float* dx, float* dgamma,
                                        float* dbeta, int32_t M, int32_t C, dlip_stream_t stream) {
   DLIP_CHECK_ARG(dy && x && save_mean && save_invstd && gamma && dx && dgamma && dbeta && M > 0 && C > 0);
-  hipLaunchKernelGGL(bn1d_train_bwd_kernel, dim3((C + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), dy,
+  hipLaunchKernelGGL(bn1d_train_bwd_kernel, dim3((C + 255) / 256), dim3(256), 0, dlip_hip_stream(stream), dy,
                      x, save_mean, save_invstd, gamma, dx, dgamma, dbeta, M, C);
   return dlip_launch_status();
 }
@@ -216,28 +213,28 @@ extern "C" int dlip_lrelu_bwd_f32(const float* dy, const float* y, float* dx, in
   DLIP_CHECK_ARG(dy && y && dx && n > 0 && slope > 0.f);
   long long g = (n + 255) / 256;
   if (g > 2048) g = 2048;
-  hipLaunchKernelGGL(lrelu_bwd_kernel, dim3((unsigned)g), dim3(256), 0, static_cast<hipStream_t>(stream), dy, y, dx,
+  hipLaunchKernelGGL(lrelu_bwd_kernel, dim3((unsigned)g), dim3(256), 0, dlip_hip_stream(stream), dy, y, dx,
                      (long long)n, slope);
   return dlip_launch_status();
 }
 
 extern "C" int dlip_l1_sum_f32(const float* w, float* out, int64_t n, dlip_stream_t stream) {
   DLIP_CHECK_ARG(w && out && n > 0);
-  hipLaunchKernelGGL(l1_sum_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), w, out, (long long)n);
+  hipLaunchKernelGGL(l1_sum_kernel, dim3(1), dim3(256), 0, dlip_hip_stream(stream), w, out, (long long)n);
   return dlip_launch_status();
 }
 
 extern "C" int dlip_l1_sign_f32(const float* w, const float* grad_scale_dev, float* dw, float coef, int64_t n, dlip_stream_t stream) {
   DLIP_CHECK_ARG(w && dw && n > 0);
   const long long blocks = (n + 255) / 256;
-  hipLaunchKernelGGL(l1_sign_kernel, dim3((unsigned)(blocks > 1024 ? 1024 : blocks)), dim3(256), 0, static_cast<hipStream_t>(stream), w,
+  hipLaunchKernelGGL(l1_sign_kernel, dim3((unsigned)(blocks > 1024 ? 1024 : blocks)), dim3(256), 0, dlip_hip_stream(stream), w,
                      grad_scale_dev, dw, coef, (long long)n);
   return dlip_launch_status();
 }
 
 extern "C" int dlip_colsum_f32(const float* x, float* y, int32_t M, int32_t C, dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && y && M > 0 && C > 0);
-  hipLaunchKernelGGL(colsum_kernel, dim3((C + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), x, y, M, C);
+  hipLaunchKernelGGL(colsum_kernel, dim3((C + 255) / 256), dim3(256), 0, dlip_hip_stream(stream), x, y, M, C);
   return dlip_launch_status();
 }
 
@@ -245,7 +242,7 @@ extern "C" int dlip_margin_ce_bwd_f32(const float* logits, const int64_t* labels
                                       int32_t K, float scale, float margin, float grad_scale,
                                       const float* grad_scale_dev, dlip_stream_t stream) {
   DLIP_CHECK_ARG(logits && labels && dlogits && B > 0 && K > 0);
-  hipLaunchKernelGGL(margin_ce_bwd_kernel, dim3((B + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), logits,
+  hipLaunchKernelGGL(margin_ce_bwd_kernel, dim3((B + 3) / 4), dim3(256), 0, dlip_hip_stream(stream), logits,
                      reinterpret_cast<const long long*>(labels), dlogits, B, K, scale, margin, grad_scale, grad_scale_dev);
   return dlip_launch_status();
 }
@@ -253,7 +250,7 @@ extern "C" int dlip_margin_ce_bwd_f32(const float* logits, const int64_t* labels
 extern "C" int dlip_l2_normalize_bwd_f32(const float* x, const float* dy, float* dx, int32_t U, int32_t D,
                                          float eps, dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && dy && dx && U > 0 && D > 0);
-  hipLaunchKernelGGL(l2norm_bwd_kernel, dim3((U + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), x, dy, dx,
+  hipLaunchKernelGGL(l2norm_bwd_kernel, dim3((U + 3) / 4), dim3(256), 0, dlip_hip_stream(stream), x, dy, dx,
                      U, D, eps);
   return dlip_launch_status();
 }
@@ -299,7 +296,7 @@ extern "C" int dlip_gemm_small_f32(const float* A, const float* B, float* C, int
                                    int32_t trans_a, int32_t trans_b, dlip_stream_t stream) {
   DLIP_CHECK_ARG(A && B && C && M > 0 && N > 0 && K > 0);
   hipLaunchKernelGGL(gemm_small_kernel, dim3((N + 31) / 32, (M + 31) / 32), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), A, B, C, M, N, K, trans_a, trans_b);
+                     dlip_hip_stream(stream), A, B, C, M, N, K, trans_a, trans_b);
   return dlip_launch_status();
 }
 
@@ -310,7 +307,7 @@ extern "C" int dlip_aam_margin_f32(const float* logits, const int64_t* labels, c
   const float th = cosf(3.14159265358979323846f - margin), mm = sinf(3.14159265358979323846f - margin) * margin;
   long long blocks = ((long long)B * K + 255) / 256;
   if (blocks > 1024) blocks = 1024;
-  hipLaunchKernelGGL(aam_margin_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), logits,
+  hipLaunchKernelGGL(aam_margin_kernel, dim3((unsigned)blocks), dim3(256), 0, dlip_hip_stream(stream), logits,
                      reinterpret_cast<const long long*>(labels), g, y, B, K, cm, sm, th, mm, easy_margin, backward);
   return dlip_launch_status();
 }

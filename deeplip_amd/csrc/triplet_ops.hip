@@ -10,7 +10,8 @@
 //           signed integer weights wcount[a,j] = #(active triplets with negative j) - #(active triplets with positive j);
 //           then a fixed-order reduction over the rows.
 //   bwd   : M_ij = (wcount_ij + wcount_ji) g / (N rownorm_i rownorm_j), M_ii = -sum_j M_ij G_ij / rownorm_i^2, dX = M X (MFMA).
-#include "dlip_common.h"
+#include "dlip_launch.h"
+#include "dlip_reduce.h"
 
 namespace {
 
@@ -147,25 +148,6 @@ __global__ __launch_bounds__(256) void triplet_mine_kernel(const float* __restri
   }
 }
 
-__device__ __forceinline__ double triplet_block_sum_f64(double v, double* red) {
-  v = dlip_wave_sum_f64(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const double s = ((red[0] + red[1]) + red[2]) + red[3];
-  __syncthreads();
-  return s;
-}
-
-__device__ __forceinline__ int triplet_block_sum_i32(int v, int* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const int s = red[0] + red[1] + red[2] + red[3];
-  __syncthreads();
-  return s;
-}
-
 // loss.py:28-31 for the triplets anchored at row a: relu(cos(a,n) - cos(a,p) + margin), cos = G_ij / (max(|x_i|, 1e-8) max(|x_j|, 1e-8))
 // (F.cosine_similarity's clamp).  Every triplet counts towards N; the active ones (hinge > 0) enter the sum and the signed
 // weights of row a.  mode all: thread per negative column, loop over the row's positives.
@@ -233,8 +215,10 @@ __global__ __launch_bounds__(256) void triplet_loss_rows_kernel(const float* __r
       }
     }
   }
-  const double s = triplet_block_sum_f64(sum, red);      // (its barriers also close the LDS counts)
-  const int k = triplet_block_sum_i32(cnt, redi);
+  const double s = dlip_block_sum4(sum, red);      // (its barrier also closes the LDS counts)
+  __syncthreads();
+  const int k = dlip_block_sum4(cnt, redi);
+  __syncthreads();
   if (threadIdx.x == 0) {
     rowsum[a] = s;
     rowcnt[a] = k;
@@ -253,8 +237,10 @@ __global__ __launch_bounds__(256) void triplet_loss_finish_kernel(const double* 
     s += rowsum[a];
     k += rowcnt[a];
   }
-  s = triplet_block_sum_f64(s, red);
-  k = triplet_block_sum_i32(k, redi);
+  s = dlip_block_sum4(s, red);
+  __syncthreads();
+  k = dlip_block_sum4(k, redi);
+  __syncthreads();
   if (threadIdx.x == 0) {
     loss[0] = k > 0 ? (float)(s / (double)k) : 0.f;
     n_triplets[0] = k;
@@ -276,7 +262,8 @@ __global__ __launch_bounds__(256) void triplet_bwd_weights_kernel(const float* _
     const int s = wcount[(long long)i * B + j] + wcount[(long long)j * B + i];
     if (s != 0) d += (double)((float)s * scale / (ni * rownorm[j])) * (double)G[(long long)i * B + j];
   }
-  d = triplet_block_sum_f64(d, red);
+  d = dlip_block_sum4(d, red);
+  __syncthreads();
   const float dii = ni > 1e-8f ? (float)(-d / ((double)ni * (double)ni)) : 0.f;
   for (int j = threadIdx.x; j < ldm; j += 256) {
     float m = 0.f;
@@ -300,7 +287,7 @@ extern "C" int dlip_triplet_mine_f32(const float* x, const int32_t* labels, floa
   DLIP_CHECK_ARG(mode == TRIPLET_ALL || neg);
   DLIP_CHECK_ARG((mode != TRIPLET_RANDOM && mode != TRIPLET_SEMIHARD) || u);
   DLIP_CHECK_ARG((reinterpret_cast<uintptr_t>(x) & 15) == 0);
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = dlip_hip_stream(stream);
   hipLaunchKernelGGL(triplet_gemm16_kernel<true>, dim3((B + 63) / 64, (B + 15) / 16), dim3(256), 0, st, x, x, g, rownorm, B, B, E, E, E, B);
   if (mode != TRIPLET_ALL)
     hipLaunchKernelGGL(triplet_mine_kernel, dim3(B), dim3(256), 0, st, g, labels, u, neg, B, margin, mode);
@@ -312,7 +299,7 @@ extern "C" int dlip_triplet_loss_f32(const float* g, const float* rownorm, const
                                      int32_t* n_triplets, int32_t B, dlip_stream_t stream) {
   DLIP_CHECK_ARG(g && rownorm && labels && rowsum && rowcnt && wcount && loss && n_triplets && B >= 1 && B <= TRIPLET_MAX_B);
   DLIP_CHECK_ARG(mode >= TRIPLET_ALL && mode <= TRIPLET_SEMIHARD && (mode == TRIPLET_ALL || neg));
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = dlip_hip_stream(stream);
   hipLaunchKernelGGL(triplet_loss_rows_kernel, dim3(B), dim3(256), 0, st, g, rownorm, labels, neg, rowsum, rowcnt, wcount, B, margin, mode);
   hipLaunchKernelGGL(triplet_loss_finish_kernel, dim3(1), dim3(256), 0, st, rowsum, rowcnt, loss, n_triplets, B);
   return dlip_launch_status();
@@ -324,7 +311,7 @@ extern "C" int dlip_triplet_loss_bwd_f32(const float* x, const float* g, const f
   DLIP_CHECK_ARG(x && g && rownorm && wcount && n_triplets && mw && dx && triplet_shape_ok(B, E));
   DLIP_CHECK_ARG((reinterpret_cast<uintptr_t>(mw) & 15) == 0);
   const int ldm = (B + 15) / 16 * 16;
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = dlip_hip_stream(stream);
   hipLaunchKernelGGL(triplet_bwd_weights_kernel, dim3(B), dim3(256), 0, st, g, rownorm, wcount, n_triplets, gscale, mw, B, ldm);
   hipLaunchKernelGGL(triplet_gemm16_kernel<false>, dim3((E + 63) / 64, (B + 15) / 16), dim3(256), 0, st, mw, x, dx, nullptr, B, E, B, ldm, E, E);
   return dlip_launch_status();

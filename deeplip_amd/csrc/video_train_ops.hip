@@ -14,14 +14,12 @@
 //     (model.py:16-17);
 //   * im2col of the 5x7x7 stride-(1,2,2) stem (C_in = 1) for its weight gradient;
 //   * mask multiply (Dropout forward / backward, tcn.py:80,85).
-#include "dlip_common.h"
+#include "dlip_launch.h"
+#include "dlip_reduce.h"
 
 namespace {
 
-inline unsigned grid_for(long long n, int cap = 1 << 16) {
-  long long g = (n + 255) / 256;
-  return (unsigned)(g < 1 ? 1 : (g > cap ? cap : g));
-}
+constexpr int kGridCap = 1 << 16;
 
 __global__ __launch_bounds__(256) void tap_gather_kernel(const float* __restrict__ x, float* __restrict__ out, int H, int W,
                                                          int ldx, int C4, int Ho, int Wo, int sh, int sw, int oh, int ow,
@@ -720,8 +718,7 @@ __global__ __launch_bounds__(64) void split_stem_weights_kernel(const float* __r
   const float* row = w + (long long)blockIdx.x * 245;
   float m = 0.f;
   for (int i = threadIdx.x; i < 245; i += 64) m = fmaxf(m, fabsf(row[i]));
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+  m = dlip_wave_max(m);
   float sc = 1.f;
   if (m > 0.f && m < 3.0e38f) sc = exp2f(floorf(log2f(1023.0f / m)));
   if (threadIdx.x == 0) scale[blockIdx.x] = sc;
@@ -786,15 +783,13 @@ __global__ __launch_bounds__(256) void chomp_concat_kernel(const ChompCat cc, fl
 
 }  // namespace
 
-#define ST(s) static_cast<hipStream_t>(s)
-
 extern "C" int dlip_tap_gather_f32(const float* x, float* out, int64_t N, int32_t H, int32_t W, int32_t C, int32_t ldx,
                                    int32_t Ho, int32_t Wo, int32_t stride_h, int32_t stride_w, int32_t off_h, int32_t off_w,
                                    int32_t ldo, dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && out && N > 0 && H > 0 && W > 0 && C > 0 && (C & 3) == 0 && (ldx & 3) == 0 && ldx >= C && Ho > 0 && Wo > 0 &&
                  stride_h > 0 && stride_w > 0 && ldo >= C && (ldo & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0);
   const long long n4 = (long long)N * Ho * Wo * (C / 4);
-  hipLaunchKernelGGL(tap_gather_kernel, dim3(grid_for(n4)), dim3(256), 0, ST(stream), x, out, H, W, ldx, C / 4, Ho, Wo, stride_h,
+  hipLaunchKernelGGL(tap_gather_kernel, dim3(dlip_grid1d(n4, kGridCap)), dim3(256), 0, dlip_hip_stream(stream), x, out, H, W, ldx, C / 4, Ho, Wo, stride_h,
                      stride_w, off_h, off_w, ldo, n4);
   return dlip_launch_status();
 }
@@ -808,15 +803,15 @@ extern "C" int dlip_wgrad_operand_f32(const float* x, float* out, int64_t ld_out
   DLIP_CHECK_ARG(J < (1ll << 28) && (long long)N * H < (1ll << 30) && ld_out >= J && (ld_out & 31) == 0 && (C + 31) / 32 <= 65535);
   const bool quads = (ldx & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
   if (quads && C % 128 == 0)
-    hipLaunchKernelGGL(wgrad_operand_wide_kernel<128>, dim3((unsigned)(ld_out / 32), (unsigned)(C / 128)), dim3(256), 0, ST(stream), x, out, H, W,
+    hipLaunchKernelGGL(wgrad_operand_wide_kernel<128>, dim3((unsigned)(ld_out / 32), (unsigned)(C / 128)), dim3(256), 0, dlip_hip_stream(stream), x, out, H, W,
                        ldx, C, Ho, Wo, stride_h, stride_w, R, S, dil_h, dil_w, pad_h, pad_w, (int)J, (long long)ld_out, scale,
                        dlip_range_for(DLIP_ST_PACK));
   else if (quads && C % 64 == 0)
-    hipLaunchKernelGGL(wgrad_operand_wide_kernel<64>, dim3((unsigned)(ld_out / 32), (unsigned)(C / 64)), dim3(256), 0, ST(stream), x, out, H, W,
+    hipLaunchKernelGGL(wgrad_operand_wide_kernel<64>, dim3((unsigned)(ld_out / 32), (unsigned)(C / 64)), dim3(256), 0, dlip_hip_stream(stream), x, out, H, W,
                        ldx, C, Ho, Wo, stride_h, stride_w, R, S, dil_h, dil_w, pad_h, pad_w, (int)J, (long long)ld_out, scale,
                        dlip_range_for(DLIP_ST_PACK));
   else
-    hipLaunchKernelGGL(wgrad_operand_kernel, dim3((unsigned)(ld_out / 32), (unsigned)((C + 31) / 32)), dim3(256), 0, ST(stream), x, out, H, W,
+    hipLaunchKernelGGL(wgrad_operand_kernel, dim3((unsigned)(ld_out / 32), (unsigned)((C + 31) / 32)), dim3(256), 0, dlip_hip_stream(stream), x, out, H, W,
                        ldx, C, Ho, Wo, stride_h, stride_w, R, S, dil_h, dil_w, pad_h, pad_w, (int)J, (long long)ld_out, scale,
                        dlip_range_for(DLIP_ST_PACK));
   return dlip_launch_status();
@@ -829,10 +824,10 @@ extern "C" int dlip_wgrad_operand_split_f32(const float* x, float* out, int64_t 
                  (reinterpret_cast<uintptr_t>(x) & 15) == 0 && C / 64 <= 65535);
   // x as [J, 1, 1, C]: one "image" per position, one tap
   if (C % 128 == 0)
-    hipLaunchKernelGGL(wgrad_operand_wide_kernel<128>, dim3((unsigned)(ld_out / 32), (unsigned)(C / 128)), dim3(256), 0, ST(stream), x, out, 1, 1, C,
+    hipLaunchKernelGGL(wgrad_operand_wide_kernel<128>, dim3((unsigned)(ld_out / 32), (unsigned)(C / 128)), dim3(256), 0, dlip_hip_stream(stream), x, out, 1, 1, C,
                        C, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, (int)J, (long long)ld_out, scale, dlip_range_for(DLIP_ST_PACK), nhwc_split_out);
   else
-    hipLaunchKernelGGL(wgrad_operand_wide_kernel<64>, dim3((unsigned)(ld_out / 32), (unsigned)(C / 64)), dim3(256), 0, ST(stream), x, out, 1, 1, C,
+    hipLaunchKernelGGL(wgrad_operand_wide_kernel<64>, dim3((unsigned)(ld_out / 32), (unsigned)(C / 64)), dim3(256), 0, dlip_hip_stream(stream), x, out, 1, 1, C,
                        C, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, (int)J, (long long)ld_out, scale, dlip_range_for(DLIP_ST_PACK), nhwc_split_out);
   return dlip_launch_status();
 }
@@ -845,13 +840,13 @@ extern "C" int dlip_wgrad_chwn_f32(const float* x, float* out, int64_t N, int32_
   DLIP_CHECK_ARG(nhwc_split_out == nullptr || ((C & 31) == 0 && (reinterpret_cast<uintptr_t>(nhwc_split_out) & 127) == 0));
   const bool quads = (ldx & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
   if (quads && C % 128 == 0)
-    hipLaunchKernelGGL(wgrad_chwn_wide_kernel<128>, dim3((unsigned)(N32 / 32), (unsigned)(C / 128), (unsigned)(H * W)), dim3(256), 0, ST(stream),
+    hipLaunchKernelGGL(wgrad_chwn_wide_kernel<128>, dim3((unsigned)(N32 / 32), (unsigned)(C / 128), (unsigned)(H * W)), dim3(256), 0, dlip_hip_stream(stream),
                        x, out, (int)N, H * W, ldx, C, N32, scale, dlip_range_for(DLIP_ST_PACK), slice_major ? 1 : 0, nhwc_split_out);
   else if (quads && C % 64 == 0)
-    hipLaunchKernelGGL(wgrad_chwn_wide_kernel<64>, dim3((unsigned)(N32 / 32), (unsigned)(C / 64), (unsigned)(H * W)), dim3(256), 0, ST(stream),
+    hipLaunchKernelGGL(wgrad_chwn_wide_kernel<64>, dim3((unsigned)(N32 / 32), (unsigned)(C / 64), (unsigned)(H * W)), dim3(256), 0, dlip_hip_stream(stream),
                        x, out, (int)N, H * W, ldx, C, N32, scale, dlip_range_for(DLIP_ST_PACK), slice_major ? 1 : 0, nhwc_split_out);
   else
-    hipLaunchKernelGGL(wgrad_chwn_kernel, dim3((unsigned)(N32 / 32), (unsigned)((C + 31) / 32), (unsigned)(H * W)), dim3(256), 0, ST(stream), x,
+    hipLaunchKernelGGL(wgrad_chwn_kernel, dim3((unsigned)(N32 / 32), (unsigned)((C + 31) / 32), (unsigned)(H * W)), dim3(256), 0, dlip_hip_stream(stream), x,
                        out, (int)N, H * W, ldx, C, N32, scale, dlip_range_for(DLIP_ST_PACK), 0, 0, slice_major ? 1 : 0, nhwc_split_out);
   return dlip_launch_status();
 }
@@ -866,10 +861,10 @@ extern "C" int dlip_wgrad_operand_split_bn_f32(const float* x, float* out, int64
                  (reinterpret_cast<uintptr_t>(x) & 15) == 0 && C / 64 <= 65535);
   const BnOnLoad bn = {mean, invstd, gamma, beta, slope_vec, slope};
   if (C % 128 == 0)
-    hipLaunchKernelGGL((wgrad_operand_wide_kernel<128, true>), dim3((unsigned)(ld_out / 32), (unsigned)(C / 128)), dim3(256), 0, ST(stream), x, out,
+    hipLaunchKernelGGL((wgrad_operand_wide_kernel<128, true>), dim3((unsigned)(ld_out / 32), (unsigned)(C / 128)), dim3(256), 0, dlip_hip_stream(stream), x, out,
                        1, 1, C, C, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, (int)J, (long long)ld_out, nullptr, dlip_range_for(DLIP_ST_PACK), nhwc_split_out, bn);
   else
-    hipLaunchKernelGGL((wgrad_operand_wide_kernel<64, true>), dim3((unsigned)(ld_out / 32), (unsigned)(C / 64)), dim3(256), 0, ST(stream), x, out,
+    hipLaunchKernelGGL((wgrad_operand_wide_kernel<64, true>), dim3((unsigned)(ld_out / 32), (unsigned)(C / 64)), dim3(256), 0, dlip_hip_stream(stream), x, out,
                        1, 1, C, C, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, (int)J, (long long)ld_out, nullptr, dlip_range_for(DLIP_ST_PACK), nhwc_split_out, bn);
   return dlip_launch_status();
 }
@@ -884,10 +879,10 @@ extern "C" int dlip_wgrad_chwn_bn_f32(const float* x, float* out, int64_t N, int
   const BnOnLoad bn = {mean, invstd, gamma, beta, slope_vec, slope};
   if (C % 128 == 0)
     hipLaunchKernelGGL((wgrad_chwn_wide_kernel<128, true>), dim3((unsigned)(N32 / 32), (unsigned)(C / 128), (unsigned)(H * W)), dim3(256), 0,
-                       ST(stream), x, out, (int)N, H * W, C, C, N32, nullptr, dlip_range_for(DLIP_ST_PACK), 1, nhwc_split_out, bn);
+                       dlip_hip_stream(stream), x, out, (int)N, H * W, C, C, N32, nullptr, dlip_range_for(DLIP_ST_PACK), 1, nhwc_split_out, bn);
   else
     hipLaunchKernelGGL((wgrad_chwn_wide_kernel<64, true>), dim3((unsigned)(N32 / 32), (unsigned)(C / 64), (unsigned)(H * W)), dim3(256), 0,
-                       ST(stream), x, out, (int)N, H * W, C, C, N32, nullptr, dlip_range_for(DLIP_ST_PACK), 1, nhwc_split_out, bn);
+                       dlip_hip_stream(stream), x, out, (int)N, H * W, C, C, N32, nullptr, dlip_range_for(DLIP_ST_PACK), 1, nhwc_split_out, bn);
   return dlip_launch_status();
 }
 
@@ -914,11 +909,11 @@ extern "C" int dlip_wgrad_operand_split_bnbwd_f32(const float* dy, const float* 
   bn.ms_coef = ms_coef; bn.ms_T = ms_T > 0 ? ms_T : 1; bn.C = C;
   const float* src = dy ? dy : z;      // (never read when the gradient is formed on load)
   if (C % 128 == 0 || C > 512)      // (a ragged last block of 128 wastes less than the 64-wide tile costs: 461 -> us on the E-TDNN's 1 500 channels)
-    hipLaunchKernelGGL((wgrad_operand_wide_kernel<128, 2>), dim3((unsigned)(ld_out / 32), (unsigned)((C + 127) / 128)), dim3(256), 0, ST(stream), src, out,
+    hipLaunchKernelGGL((wgrad_operand_wide_kernel<128, 2>), dim3((unsigned)(ld_out / 32), (unsigned)((C + 127) / 128)), dim3(256), 0, dlip_hip_stream(stream), src, out,
                        1, 1, C, C, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, (int)J, (long long)ld_out, lift, dlip_range_for(DLIP_ST_PACK), nhwc_split_out, bn,
                        ld_nhwc);
   else
-    hipLaunchKernelGGL((wgrad_operand_wide_kernel<64, 2>), dim3((unsigned)(ld_out / 32), (unsigned)((C + 63) / 64)), dim3(256), 0, ST(stream), src,
+    hipLaunchKernelGGL((wgrad_operand_wide_kernel<64, 2>), dim3((unsigned)(ld_out / 32), (unsigned)((C + 63) / 64)), dim3(256), 0, dlip_hip_stream(stream), src,
                        out, 1, 1, C, C, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, (int)J, (long long)ld_out, lift, dlip_range_for(DLIP_ST_PACK), nhwc_split_out,
                        bn, ld_nhwc);
   return dlip_launch_status();
@@ -937,10 +932,10 @@ extern "C" int dlip_wgrad_chwn_bnbwd_f32(const float* dy, const float* z, float*
   bn.z = z; bn.dgamma = dgamma; bn.dbeta = dbeta; bn.invM = 1.f / (float)M; bn.act_first = act_first; bn.C = C;
   if (C % 128 == 0)
     hipLaunchKernelGGL((wgrad_chwn_wide_kernel<128, 2>), dim3((unsigned)(N32 / 32), (unsigned)(C / 128), (unsigned)(H * W)), dim3(256), 0,
-                       ST(stream), dy, out, (int)N, H * W, C, C, N32, lift, dlip_range_for(DLIP_ST_PACK), 1, nhwc_split_out, bn);
+                       dlip_hip_stream(stream), dy, out, (int)N, H * W, C, C, N32, lift, dlip_range_for(DLIP_ST_PACK), 1, nhwc_split_out, bn);
   else
     hipLaunchKernelGGL((wgrad_chwn_wide_kernel<64, 2>), dim3((unsigned)(N32 / 32), (unsigned)(C / 64), (unsigned)(H * W)), dim3(256), 0,
-                       ST(stream), dy, out, (int)N, H * W, C, C, N32, lift, dlip_range_for(DLIP_ST_PACK), 1, nhwc_split_out, bn);
+                       dlip_hip_stream(stream), dy, out, (int)N, H * W, C, C, N32, lift, dlip_range_for(DLIP_ST_PACK), 1, nhwc_split_out, bn);
   return dlip_launch_status();
 }
 
@@ -950,7 +945,7 @@ extern "C" int dlip_stem_wgrad_chwn_f32(const float* x, float* out, int32_t B, i
                  (reinterpret_cast<uintptr_t>(out) & 127) == 0 && (H * W + 31) / 32 <= 65535);
   // the clip as [frames][1 pixel][H W "channels"]: out[dt][p][n] = x[n + dt - 2][p] inside the clip of frame n
   for (int dt = 0; dt < 5; ++dt)
-    hipLaunchKernelGGL(wgrad_chwn_kernel, dim3((unsigned)(N32 / 32), (unsigned)((H * W + 31) / 32), 1u), dim3(256), 0, ST(stream), x,
+    hipLaunchKernelGGL(wgrad_chwn_kernel, dim3((unsigned)(N32 / 32), (unsigned)((H * W + 31) / 32), 1u), dim3(256), 0, dlip_hip_stream(stream), x,
                        out + (long long)dt * H * W * N32, B * T, 1, H * W, H * W, N32, nullptr, dlip_range_for(DLIP_ST_PACK), T, dt - 2,
                        slice_major ? 2 : 0);
   return dlip_launch_status();
@@ -965,7 +960,7 @@ extern "C" int dlip_upsample_zero_f32(const float* dz, float* out, int64_t N, in
   const unsigned gx = (unsigned)((rowlen + 255) / 256 > 16 ? 16 : (rowlen + 255) / 256);
   long long gy = 4096 / gx;                              // ~4 096 workgroups, each walking rows / gy output rows
   if (gy > rows) gy = rows;
-  hipLaunchKernelGGL(upsample_zero_kernel, dim3(gx, (unsigned)gy), dim3(256), 0, ST(stream), reinterpret_cast<const f32x4*>(dz),
+  hipLaunchKernelGGL(upsample_zero_kernel, dim3(gx, (unsigned)gy), dim3(256), 0, dlip_hip_stream(stream), reinterpret_cast<const f32x4*>(dz),
                      reinterpret_cast<f32x4*>(out), Ho, Wo, Hu, Wu, C / 4, stride_h, stride_w, (int)rows);
   return dlip_launch_status();
 }
@@ -980,7 +975,7 @@ extern "C" int dlip_upsample_zero_split_f32(const float* dz, float* out_split, c
   const unsigned gx = (unsigned)((rowlen + 255) / 256 > 16 ? 16 : (rowlen + 255) / 256);
   long long gy = 4096 / gx;
   if (gy > rows) gy = rows;
-  hipLaunchKernelGGL(upsample_zero_split_kernel, dim3(gx, (unsigned)gy), dim3(256), 0, ST(stream), reinterpret_cast<const f32x4*>(dz), out_split,
+  hipLaunchKernelGGL(upsample_zero_split_kernel, dim3(gx, (unsigned)gy), dim3(256), 0, dlip_hip_stream(stream), reinterpret_cast<const f32x4*>(dz), out_split,
                      scale, Ho, Wo, Hu, Wu, C / 4, stride_h, stride_w, (int)rows, dlip_range_for(DLIP_ST_PACK));
   return dlip_launch_status();
 }
@@ -988,7 +983,7 @@ extern "C" int dlip_upsample_zero_split_f32(const float* dz, float* out_split, c
 extern "C" int dlip_prelu_rows_fwd_f32(const float* x, const float* slope, float* y, int64_t M, int32_t C, dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && slope && y && M > 0 && C > 0 && (C & 3) == 0);
   const long long n4 = (long long)M * (C / 4);
-  hipLaunchKernelGGL(prelu_fwd_kernel, dim3(grid_for(n4)), dim3(256), 0, ST(stream), reinterpret_cast<const f32x4*>(x), slope,
+  hipLaunchKernelGGL(prelu_fwd_kernel, dim3(dlip_grid1d(n4, kGridCap)), dim3(256), 0, dlip_hip_stream(stream), reinterpret_cast<const f32x4*>(x), slope,
                      reinterpret_cast<f32x4*>(y), C / 4, n4);
   return dlip_launch_status();
 }
@@ -997,7 +992,7 @@ extern "C" int dlip_prelu_rows_bwd_f32(const float* dy, const float* x, const fl
                                        int64_t M, int32_t C, dlip_stream_t stream) {
   DLIP_CHECK_ARG(dy && x && slope && dx && dslope_terms && M > 0 && C > 0 && (C & 3) == 0);
   const long long n4 = (long long)M * (C / 4);
-  hipLaunchKernelGGL(prelu_bwd_kernel, dim3(grid_for(n4)), dim3(256), 0, ST(stream), reinterpret_cast<const f32x4*>(dy),
+  hipLaunchKernelGGL(prelu_bwd_kernel, dim3(dlip_grid1d(n4, kGridCap)), dim3(256), 0, dlip_hip_stream(stream), reinterpret_cast<const f32x4*>(dy),
                      reinterpret_cast<const f32x4*>(x), slope, reinterpret_cast<f32x4*>(dx), reinterpret_cast<f32x4*>(dslope_terms),
                      C / 4, n4);
   return dlip_launch_status();
@@ -1007,7 +1002,7 @@ extern "C" int dlip_add_prelu_rows_fwd_f32(const float* a, const float* b, const
                                            dlip_stream_t stream) {
   DLIP_CHECK_ARG(a && b && slope && sum && y && M > 0 && C > 0 && (C & 3) == 0);
   const long long n4 = (long long)M * (C / 4);
-  hipLaunchKernelGGL(add_prelu_fwd_kernel, dim3(grid_for(n4)), dim3(256), 0, ST(stream), reinterpret_cast<const f32x4*>(a),
+  hipLaunchKernelGGL(add_prelu_fwd_kernel, dim3(dlip_grid1d(n4, kGridCap)), dim3(256), 0, dlip_hip_stream(stream), reinterpret_cast<const f32x4*>(a),
                      reinterpret_cast<const f32x4*>(b), slope, reinterpret_cast<f32x4*>(sum), reinterpret_cast<f32x4*>(y), C / 4, n4);
   return dlip_launch_status();
 }
@@ -1017,7 +1012,7 @@ extern "C" int dlip_maxpool3x3s2_bwd_f32(const float* x, const float* dy, float*
   DLIP_CHECK_ARG(x && dy && dx && N > 0 && H > 0 && W > 0 && C > 0 && (C & 3) == 0);
   const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
   const long long n4 = (long long)N * H * W * (C / 4);
-  hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(grid_for(n4)), dim3(256), 0, ST(stream), x, dy, reinterpret_cast<f32x4*>(dx), H, W, Ho,
+  hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(dlip_grid1d(n4, kGridCap)), dim3(256), 0, dlip_hip_stream(stream), x, dy, reinterpret_cast<f32x4*>(dx), H, W, Ho,
                      Wo, C / 4, n4);
   return dlip_launch_status();
 }
@@ -1027,7 +1022,7 @@ extern "C" int dlip_maxpool3x3s2_idx_f32(const float* x, float* y, uint32_t* idx
   DLIP_CHECK_ARG(x && y && idx && N > 0 && H > 0 && W > 0 && C > 0 && (C & 3) == 0);
   const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
   const long long n4 = (long long)N * Ho * Wo * (C / 4);
-  hipLaunchKernelGGL(maxpool_idx_fwd_kernel, dim3(grid_for(n4)), dim3(256), 0, ST(stream), x, reinterpret_cast<f32x4*>(y), idx, H, W, Ho,
+  hipLaunchKernelGGL(maxpool_idx_fwd_kernel, dim3(dlip_grid1d(n4, kGridCap)), dim3(256), 0, dlip_hip_stream(stream), x, reinterpret_cast<f32x4*>(y), idx, H, W, Ho,
                      Wo, C / 4, n4);
   return dlip_launch_status();
 }
@@ -1037,7 +1032,7 @@ extern "C" int dlip_maxpool3x3s2_bwd_idx_f32(const uint32_t* idx, const float* d
   DLIP_CHECK_ARG(idx && dy && dx && N > 0 && H > 0 && W > 0 && C > 0 && (C & 3) == 0);
   const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
   const long long n4 = (long long)N * H * W * (C / 4);
-  hipLaunchKernelGGL(maxpool_idx_bwd_kernel, dim3(grid_for(n4)), dim3(256), 0, ST(stream), idx, reinterpret_cast<const f32x4*>(dy),
+  hipLaunchKernelGGL(maxpool_idx_bwd_kernel, dim3(dlip_grid1d(n4, kGridCap)), dim3(256), 0, dlip_hip_stream(stream), idx, reinterpret_cast<const f32x4*>(dy),
                      reinterpret_cast<f32x4*>(dx), H, W, Ho, Wo, C / 4, n4);
   return dlip_launch_status();
 }
@@ -1046,7 +1041,7 @@ extern "C" int dlip_row_broadcast_f32(const float* dy, const int32_t* lengths, f
                                       float scale, dlip_stream_t stream) {
   DLIP_CHECK_ARG(dy && dx && N > 0 && P > 0 && C > 0 && (C & 3) == 0);
   const long long n4 = (long long)N * P * (C / 4);
-  hipLaunchKernelGGL(row_broadcast_kernel, dim3(grid_for(n4)), dim3(256), 0, ST(stream), reinterpret_cast<const f32x4*>(dy), lengths,
+  hipLaunchKernelGGL(row_broadcast_kernel, dim3(dlip_grid1d(n4, kGridCap)), dim3(256), 0, dlip_hip_stream(stream), reinterpret_cast<const f32x4*>(dy), lengths,
                      reinterpret_cast<f32x4*>(dx), P, C / 4, scale, n4);
   return dlip_launch_status();
 }
@@ -1054,7 +1049,7 @@ extern "C" int dlip_row_broadcast_f32(const float* dy, const int32_t* lengths, f
 extern "C" int dlip_stem_im2col_f32(const float* x, float* col, int32_t B, int32_t T, int32_t H, int32_t W, dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && col && B > 0 && T > 0 && H > 1 && W > 1 && (H & 1) == 0 && (W & 1) == 0);
   const long long n = (long long)B * T * (H / 2) * (W / 2) * 248;
-  hipLaunchKernelGGL(stem_im2col_kernel, dim3(grid_for(n)), dim3(256), 0, ST(stream), x, col, T, H, W, H / 2, W / 2, n);
+  hipLaunchKernelGGL(stem_im2col_kernel, dim3(dlip_grid1d(n, kGridCap)), dim3(256), 0, dlip_hip_stream(stream), x, col, T, H, W, H / 2, W / 2, n);
   return dlip_launch_status();
 }
 
@@ -1064,20 +1059,20 @@ extern "C" int dlip_stem_wgrad_operand_f32(const float* x, float* out, int64_t l
                  (reinterpret_cast<uintptr_t>(out) & 127) == 0);
   const long long J = (long long)B * T * (H / 2) * (W / 2);
   DLIP_CHECK_ARG(ld_out >= J && (ld_out & 31) == 0 && (long long)B * T * H * W < (1ll << 31) && ld_out / 32 < (1ll << 31));
-  hipLaunchKernelGGL(stem_wgrad_operand_kernel, dim3((unsigned)(ld_out / 32)), dim3(256), 0, ST(stream), x, out, T, H, W, H / 2, W / 2, J,
+  hipLaunchKernelGGL(stem_wgrad_operand_kernel, dim3((unsigned)(ld_out / 32)), dim3(256), 0, dlip_hip_stream(stream), x, out, T, H, W, H / 2, W / 2, J,
                      (long long)ld_out, dlip_range_for(DLIP_ST_PACK));
   return dlip_launch_status();
 }
 
 extern "C" int dlip_split_stem_weights_f32(const float* w, float* w_img, float* w_scale, int32_t K, dlip_stream_t stream) {
   DLIP_CHECK_ARG(w && w_img && w_scale && K > 0);
-  hipLaunchKernelGGL(split_stem_weights_kernel, dim3((unsigned)K), dim3(64), 0, ST(stream), w, w_img, w_scale);
+  hipLaunchKernelGGL(split_stem_weights_kernel, dim3((unsigned)K), dim3(64), 0, dlip_hip_stream(stream), w, w_img, w_scale);
   return dlip_launch_status();
 }
 
 extern "C" int dlip_dropout_keep_f32(const float* x, const float* u, float* y, int64_t n, float p, float scale, dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && u && y && n > 0 && p >= 0.f && p < 1.f);
-  hipLaunchKernelGGL(dropout_keep_kernel, dim3(grid_for(n)), dim3(256), 0, ST(stream), x, u, y, p, scale, (long long)n);
+  hipLaunchKernelGGL(dropout_keep_kernel, dim3(dlip_grid1d(n, kGridCap)), dim3(256), 0, dlip_hip_stream(stream), x, u, y, p, scale, (long long)n);
   return dlip_launch_status();
 }
 
@@ -1101,13 +1096,13 @@ extern "C" int dlip_chomp_concat_f32(const float* const* branches, const int32_t
   }
   cc.Ct4 = off / 4;
   DLIP_CHECK_ARG((reinterpret_cast<uintptr_t>(cat) & 15) == 0);
-  if (backward) hipLaunchKernelGGL(chomp_concat_kernel<true>, dim3(grid_for(cc.start[n_branches])), dim3(256), 0, ST(stream), cc, cat);
-  else hipLaunchKernelGGL(chomp_concat_kernel<false>, dim3(grid_for(cc.start[n_branches])), dim3(256), 0, ST(stream), cc, cat);
+  if (backward) hipLaunchKernelGGL(chomp_concat_kernel<true>, dim3(dlip_grid1d(cc.start[n_branches], kGridCap)), dim3(256), 0, dlip_hip_stream(stream), cc, cat);
+  else hipLaunchKernelGGL(chomp_concat_kernel<false>, dim3(dlip_grid1d(cc.start[n_branches], kGridCap)), dim3(256), 0, dlip_hip_stream(stream), cc, cat);
   return dlip_launch_status();
 }
 
 extern "C" int dlip_mul_mask_f32(const float* x, const float* mask, float* y, int64_t n, float scale, dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && mask && y && n > 0);
-  hipLaunchKernelGGL(mul_mask_kernel, dim3(grid_for(n)), dim3(256), 0, ST(stream), x, mask, y, scale, (long long)n);
+  hipLaunchKernelGGL(mul_mask_kernel, dim3(dlip_grid1d(n, kGridCap)), dim3(256), 0, dlip_hip_stream(stream), x, mask, y, scale, (long long)n);
   return dlip_launch_status();
 }
