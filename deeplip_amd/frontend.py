@@ -13,6 +13,7 @@ zero-pad collate of models/video_models/dataset.py:123-139.
 """
 from __future__ import annotations
 
+import decimal
 import math
 from typing import List, Optional, Sequence, Tuple
 
@@ -46,6 +47,12 @@ def mel_filterbank(nfilt: int, nfft: int, rate: int, lowfreq: float = 0.0, highf
     return fb
 
 
+def round_half_up(x: float) -> int:
+    """sigproc.round_half_up: ties go up (220.5 -> 221, 1102.5 -> 1103), where Python's round() takes them to the even
+    neighbour.  Decided on the exact value of the double, as the package does."""
+    return int(decimal.Decimal(x).quantize(decimal.Decimal("1"), rounding=decimal.ROUND_HALF_UP))
+
+
 def num_frames(n_samples: int, frame_len: int, frame_step: int) -> int:
     """sigproc.framesig: 1 + ceil((slen - frame_len) / frame_step) for slen > frame_len, else 1."""
     return 1 if n_samples <= frame_len else 1 + int(math.ceil((1.0 * n_samples - frame_len) / frame_step))
@@ -59,8 +66,16 @@ class AudioFrontend:
         if feat_type not in ("mfcc", "fbank", "logfbank"):
             raise NotImplementedError("Other features are not implemented!")   # datasets.py:75-76
         self.feat_type, self.rate, self.nfft = feat_type, rate, nfft
-        self.frame_len = int(round(win_len * rate))      # sigproc uses round_half_up; 400 / 160 are exact
-        self.frame_step = int(round(win_shift * rate))
+        # sigproc.framesig rounds half UP: 22.05 kHz steps by 220.5 -> 221 samples and 44.1 kHz frames 1102.5 -> 1103, where
+        # round() (half to even) gave 220 and 1102 -- another number of frames than the reference's loader produces
+        self.frame_len = round_half_up(win_len * rate)
+        self.frame_step = round_half_up(win_shift * rate)
+        if self.frame_len < 1 or self.frame_step < 1:
+            raise ValueError(f"AudioFrontend: win_len * rate and win_shift * rate must round to at least one sample, got "
+                             f"{self.frame_len} and {self.frame_step}")
+        if nfft < self.frame_len:
+            raise ValueError(f"AudioFrontend: nfft must be >= the frame length ({self.frame_len} samples = win_len {win_len} s at "
+                             f"{rate} Hz), got nfft={nfft}")
         self.num_bin, self.num_cep, self.preemph, self.normalize, self.energy = num_bin, num_cep, preemph, normalize, energy
         self.delta = delta            # datasets.py:81-82: [feat | delta(N=1) | delta(N=2)] after the normalisation
         # How the power spectrum is formed (``dft``):
@@ -76,6 +91,10 @@ class AudioFrontend:
             raise ValueError(f"AudioFrontend: dft must be 'fft64', 'gemm32' or 'direct64', got {dft!r}")
         if dft == "fft64" and (nfft < 128 or nfft > 1024 or nfft & (nfft - 1)):
             dft = "gemm32"            # (the FFT kernel takes powers of two 128 .. 1024; any other nfft keeps the GEMM route)
+        if dft == "direct64" and (nfft < 2 or nfft > 1024 or nfft & (nfft - 1)):
+            raise ValueError(f"AudioFrontend: dft='direct64' needs nfft to be a power of two <= 1024, got nfft={nfft}")
+        if dft == "gemm32" and nfft % 4:
+            raise ValueError(f"AudioFrontend: dft='gemm32' needs nfft to be a multiple of 4 (the GEMM's reduction length), got nfft={nfft}")
         self.dft = dft
         self.dft64 = dft == "direct64"
         self.device = torch.device(device)

@@ -547,10 +547,20 @@ def psf_get_filterbanks(nfilt=26, nfft=512, samplerate=16000, lowfreq=0.0, highf
     return np.nan_to_num(up + down)
 
 
+def psf_frame_geometry(rate=16000, winlen=0.025, winstep=0.01):
+    """(frame_len, frame_step) in samples as sigproc.framesig takes them from base.fbank's winlen * samplerate and
+    winstep * samplerate: the package's round_half_up, Decimal(x).quantize(Decimal('1'), ROUND_HALF_UP) -- NOT Python's
+    round(), which is half-to-even and differs at 22.05 kHz (220.5 -> 221, not 220) and 44.1 kHz (1102.5 -> 1103, not 1102)."""
+    from decimal import ROUND_HALF_UP, Decimal
+    return tuple(int(Decimal(winlen_or_step * rate).quantize(Decimal("1"), rounding=ROUND_HALF_UP))
+                 for winlen_or_step in (winlen, winstep))
+
+
 def psf_fbank(signal, rate=16000, winlen=0.025, winstep=0.01, nfilt=26, nfft=512, preemph=0.97):
     """base.fbank -> (feat [NF, nfilt], energy [NF])."""
     mel_filterbank = psf_get_filterbanks
-    frames = _psf_frames(np.asarray(signal, dtype=np.float64), int(round(winlen * rate)), int(round(winstep * rate)), preemph)
+    frame_len, frame_step = psf_frame_geometry(rate, winlen, winstep)
+    frames = _psf_frames(np.asarray(signal, dtype=np.float64), frame_len, frame_step, preemph)
     pspec = 1.0 / nfft * np.square(np.absolute(np.fft.rfft(frames, nfft)))    # sigproc.powspec
     energy = np.sum(pspec, 1)
     energy = np.where(energy == 0, np.finfo(float).eps, energy)

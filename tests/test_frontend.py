@@ -21,6 +21,23 @@ def test_filterbank_and_oracle_self_consistency():
     assert np.abs(f.mean(1)).max() < 1e-5 and np.abs(f.std(1) - 1).max() < 1e-4    # CMVN
 
 
+def test_frame_geometry_rounds_half_up_like_sigproc():
+    """python_speech_features.sigproc.framesig takes frame length and step through round_half_up; Python's round() is half-to-even
+    and gave 220 (not 221) samples of step at 22.05 kHz and 1102 (not 1103) of frame at 44.1 kHz.  Known answers, for the product
+    and -- stated on its own -- the oracle; then the number of frames around the frame length."""
+    from deeplip_amd.frontend import AudioFrontend, num_frames, round_half_up
+    assert [round_half_up(v) for v in (220.5, 1102.5, 275.625, 110.25, 0.5, 1.5, 2.5, 2.4999)] == [221, 1103, 276, 110, 1, 2, 3, 2]
+    for rate, want in ((22050, (551, 221)), (44100, (1103, 441)), (11025, (276, 110)), (8000, (200, 80)), (16000, (400, 160))):
+        fe = AudioFrontend(rate=rate, nfft=2048, device="cpu")
+        assert (fe.frame_len, fe.frame_step) == want, rate
+        assert O.psf_frame_geometry(rate) == want, rate
+        L, step = want
+        for S, nf in ((1, 1), (L - 1, 1), (L, 1), (L + 1, 2), (L + step, 2), (L + step + 1, 3)):
+            assert num_frames(S, L, step) == nf, (rate, S)
+            feat, energy = O.psf_fbank(np.ones(S), rate=rate, nfft=2048)
+            assert feat.shape == (nf, 26) and energy.shape == (nf,), (rate, S)
+
+
 @pytest.mark.gpu
 # 80 bands at nfft=512: 19 one-bin filters sit next to DC where pre-emphasis leaves ~1e-9 of the spectrum, i.e.
 # at the fp32 noise floor of a 512-point DFT (the reference's numpy FFT runs in fp64): banks denser than the shipped
