@@ -3,7 +3,14 @@
     f16x3   every product of fp32 values as hi*hi + hi*lo + lo*hi on the f16 matrix core, fp32 accumulate (fp32-grade: 5e-7 against
             the CPU reference where the bar is 1e-4; three times the exact mode's speed).  A value the split format cannot hold
             (|v| >= 65520, or a whole tensor below 2^-2) RAISES DeepLipRangeError at the next check.
-    f32     exact fp32 MFMA: the reference's arithmetic (models/video_models/model.py:82-85 computes in fp32 end to end).
+    f32     exact fp32 MFMA: the reference's arithmetic (models/video_models/model.py:82-85 computes in fp32 end to end).  Eval path:
+            every contraction.  Training: forward and data gradient of every convolution; the WEIGHT gradient is a split-fp16 GEMM in
+            this mode too, with BOTH operands (layer input and output gradient) lifted by a power of two of their own to a largest
+            magnitude of ~1024 -- so a finite operand whose largest magnitude is ~1e-27 or more is silent (never DeepLipRangeError)
+            and fp32-grade: an element is stored to 2^-22 of its own magnitude or 3e-11 of its operand's largest, whichever is
+            larger (tests/test_train_f32_gpu.py: inputs x 2^-20 .. 2^+20, gradients x 1 and x 1e-6, against fp64).  The limits: the
+            lift is capped at 1e30 (no power of two: below ~1e-27 dividing it out is no longer exact), and an Inf / NaN in an operand
+            leaves the lift at 1 and is REPORTED by the operand producer (DeepLipRangeError), in this mode too.
     auto    f16x3, and what leaves its range is computed again -- the same batch, the same process, the same model object -- on
             the exact f32 pack, logged and counted (``STATS``).  The default: the measured configuration IS the product's.
 

@@ -82,7 +82,10 @@ def wgrad_gemm(dz_rows, tap_rows, n_taps):
     return out
 
 
-# Arithmetic of the convolutions of a TRAINING step (forward and data gradient; the weight gradient has always been split-fp16):
+# Arithmetic of the convolutions of a TRAINING step (forward and data gradient).  The weight gradient is a split-fp16 product in BOTH
+# modes: under "f16x3" of the operand images the forward formed (x unlifted -- the mode's range contract covers it -- dy lifted), under
+# "f32" of wgrad_conv_fused's / the stem's GEMM operands with x AND dy each lifted by a power of two of their own (any fp32 magnitude of
+# the layer input is silent and fp32-grade: tests/test_train_f32_gpu.py).
 # "f16x3" = the split-fp16 kernels of the extraction path -- activations split once per convolution (dlip_split_pack_f32; a
 # gradient after its power-of-two lift), the CURRENT weights split on the device (dlip_split_weights_rows_f32), fp32 out: 2.6x the
 # rate of the exact-fp32 MFMA kernel at fp32-grade accuracy -- or "f32", the exact kernel (what the training path used before).
@@ -109,6 +112,14 @@ def lift_inv(scale2, K):
     inv = torch.empty((K,), device=scale2.device, dtype=torch.float32)
     check(lib().dlip_fill_from_scalar_f32(scale2[1:].data_ptr(), ptr(inv), K, stream_handle()), "dlip_fill_from_scalar_f32")
     return inv
+
+
+def lift_fwd(scale2, K):
+    """[K] copies of 2^e: what a convolution's accumulator is DIVIDED by when its activation operand carries the lift (the ``w_scale``
+    vector of ops.conv_nhwc, whose epilogue forms acc / w_scale -- a power of two: exact)."""
+    fwd = torch.empty((K,), device=scale2.device, dtype=torch.float32)
+    check(lib().dlip_fill_from_scalar_f32(scale2.data_ptr(), ptr(fwd), K, stream_handle()), "dlip_fill_from_scalar_f32")
+    return fwd
 
 
 # ---- the step's weight images in ONE launch (round 4) ----------------------------------------------------------------------------
@@ -253,6 +264,15 @@ def prepare_weights(owner=None):
         WEIGHT_PREP.prepare()
 
 
+def _conv_exact(x, w_krsc, bias, stride, pad, dil):
+    """The exact fp32 kernel with the bias added BEHIND the accumulation (the epilogue's post_shift), as torch does.  As ``bias`` it
+    would initialise the accumulators, and every product would then be rounded at the bias's magnitude: with an input of 1e-3 under a
+    bias of 0.1 the output of a TDNN block's BatchNorm sat 2.8e-5 from fp64 where torch's own fp32 is at 5e-6 (tests/test_train_f32_gpu.py)."""
+    if bias is None:
+        return ops.conv_nhwc(x, w_krsc, None, stride=stride, pad=pad, dil=dil)
+    return ops.conv_nhwc(x, w_krsc, None, stride=stride, pad=pad, dil=dil, post_scale=const_vec(bias.numel(), 1.0, x.device), post_shift=bias)
+
+
 def conv_train(x, w_krsc, bias, stride=(1, 1), pad=(0, 0), dil=(1, 1), lift=False, scale2=None, w_ref=None, transposed=False,
                xs_ready=None, stats=None):
     """One convolution of a training step on NHWC fp32 ``x`` with CURRENT weights -> fp32 NHWC.  Weights: ``w_krsc`` [K,R,S,C]
@@ -292,7 +312,7 @@ def conv_train(x, w_krsc, bias, stride=(1, 1), pad=(0, 0), dil=(1, 1), lift=Fals
         if TRAIN_CONV != "f16x3" or Cx % 32 or K % 4 or Cw != Cx:
             w3 = w_ref.contiguous().view(Ko, Ci, R_ * S_)
             w_krsc = (_permute3(w3, (1, 2, 0), flip_axis=2).view(Ci, R_, S_, Ko) if transposed else _permute3(w3, (0, 2, 1)).view(Ko, R_, S_, Ci))
-            return ops.conv_nhwc(x, w_krsc, bias, stride=stride, pad=pad, dil=dil)
+            return _conv_exact(x, w_krsc, bias, stride, pad, dil)
         dev = x.device
         key = (w_ref.data_ptr(), tuple(w_ref.shape), bool(transposed), Cw)
         hit = WEIGHT_PREP.lookup(key, w_ref) if w_ref.is_contiguous() else None
@@ -308,7 +328,7 @@ def conv_train(x, w_krsc, bias, stride=(1, 1), pad=(0, 0), dil=(1, 1), lift=Fals
     else:
         K = w_krsc.shape[0]
         if TRAIN_CONV != "f16x3" or Cx % 32 or K % 4 or w_krsc.shape[3] != Cx:
-            return ops.conv_nhwc(x, w_krsc, bias, stride=stride, pad=pad, dil=dil)
+            return _conv_exact(x, w_krsc, bias, stride, pad, dil)
         dev = x.device
         L = w_krsc.numel() // K
         ws = torch.empty_like(w_krsc)
@@ -358,11 +378,18 @@ def wgrad_conv_fused(x, dy, R, S, stride, pad, dil, scale2=None):
     dzT_s = torch.empty((K, J32), device=dev, dtype=torch.float32)
     check(lib().dlip_wgrad_operand_f32(ptr(dy), ptr(dzT_s), J32, N, Ho, Wo, K, K, Ho, Wo, 1, 1, 1, 1, 1, 1, 0, 0, ptr(scale2), stream_handle()),
           "dlip_wgrad_operand_f32")
+    # "f32": the layer input may have ANY fp32 magnitude (the forward and the data gradient never split it), so it gets a power-of-two
+    # lift of its own, like dy -- one more absmax pass -- and the GEMM's epilogue divides by both powers (exact).  "f16x3" leaves x as
+    # it is: there the forward has split the same tensor unlifted already, and the mode's range contract covers both.
+    x_lift = None
+    if TRAIN_CONV == "f32":
+        x = x.contiguous()
+        x_lift = pow2_lift(x)
     xT_s = torch.empty((taps * Cx, J32), device=dev, dtype=torch.float32)
     check(lib().dlip_wgrad_operand_f32(ptr(x), ptr(xT_s), J32, N, H, W, Cx, _pixel_pitch(x), Ho, Wo, stride[0], stride[1], R, S, dil[0], dil[1],
-                                       pad[0], pad[1], None, stream_handle()), "dlip_wgrad_operand_f32")
+                                       pad[0], pad[1], ptr(x_lift), stream_handle()), "dlip_wgrad_operand_f32")
     inv = lift_inv(scale2, K)
-    ones = const_vec(K, 1.0, dev)
+    ones = const_vec(K, 1.0, dev) if x_lift is None else lift_fwd(x_lift, K)
     zeros = const_vec(K, 0.0, dev)
     out = torch.empty((taps * Cx, K), device=dev, dtype=torch.float32)
     ops.conv_nhwc(xT_s.view(1, 1, taps * Cx, J32), dzT_s.view(K, 1, 1, J32), None, w_scale=ones, x_split=True, post_scale=inv,
@@ -658,11 +685,19 @@ class StemConvTrainFn(Function):
         dzT_s = torch.empty((K, J32), device=dev, dtype=torch.float32)
         check(lib().dlip_wgrad_operand_f32(ptr(dy), ptr(dzT_s), J32, B * T, Ho, Wo, K, K, Ho, Wo, 1, 1, 1, 1, 1, 1, 0, 0, ptr(scale2), stream_handle()),
               "dlip_wgrad_operand_f32")
+        # "f32": a clip of any fp32 magnitude -- the operand is written from a copy of the clip lifted by its own power of two, and
+        # the GEMM's epilogue divides by it (see wgrad_conv_fused)
+        w_scale = const_vec(K, 1.0, dev)
+        if TRAIN_CONV == "f32":
+            x_lift = pow2_lift(x)
+            # (a scalar multiply spelled with the kernel there is: channel_scale takes the LAST axis, the W pixels of a row, as channels)
+            x = ops.channel_scale(x, lift_fwd(x_lift, W), const_vec(W, 0.0, dev))
+            w_scale = lift_fwd(x_lift, K)
         xT_s = torch.empty((248, J32), device=dev, dtype=torch.float32)
         check(lib().dlip_stem_wgrad_operand_f32(ptr(x), ptr(xT_s), J32, B, T, H, W, stream_handle()), "dlip_stem_wgrad_operand_f32")
         inv = lift_inv(scale2, K)
         out = torch.empty((248, K), device=dev, dtype=torch.float32)
-        ops.conv_nhwc(xT_s.view(1, 1, 248, J32), dzT_s.view(K, 1, 1, J32), None, w_scale=const_vec(K, 1.0, dev), x_split=True,
+        ops.conv_nhwc(xT_s.view(1, 1, 248, J32), dzT_s.view(K, 1, 1, J32), None, w_scale=w_scale, x_split=True,
                       post_scale=inv, post_shift=const_vec(K, 0.0, dev), out=out.view(1, 1, 248, K))
         dweight = _permute3(out[:245].contiguous().view(1, 245, K), (0, 2, 1)).view(K, 1, 5, 7, 7)
         return None, dweight

@@ -1,6 +1,8 @@
 """Range guard of the split-fp16 ("f16x3") arithmetic.  The reference is fp32 end to end (model.py:82-85); the split
 activation format stores hi + lo fp16, so |v| >= 65520 cannot be represented.  Every producer of split values reports
-such a value to a status block the Python layer turns into DeepLipRangeError; the recourse is the exact "f32" mode."""
+such a value to a status block the Python layer turns into DeepLipRangeError; the recourse is the exact "f32" mode (eval path:
+no split tensor at all; training: exact forward and data gradient, and a split weight-gradient GEMM whose two operands are each
+lifted by their own power of two, silent and fp32-grade at any input magnitude -- tests/test_train_f32_gpu.py)."""
 import numpy as np
 import pytest
 import torch

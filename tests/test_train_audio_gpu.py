@@ -149,9 +149,13 @@ def load(module, prefix):
 
 
 def test_speaker_encoder_two_sgd_steps_vs_reference_golden(golden):
+    speaker_encoder_two_sgd_steps_vs_reference_golden(golden["audio_train"])
+
+
+def speaker_encoder_two_sgd_steps_vs_reference_golden(g):
+    """(the body of the test above, in whichever arithmetic is configured: test_train_f32_gpu.py runs it again under arith "f32")"""
     from models.audio_models.loss import LMCL
     from models.audio_models.tdnn import SpeakerEmbNet
-    g = golden["audio_train"]
     opts = {"arch": "tdnn", "tdnn": {"input_dim": 24, "hidden_dim": [512] * 4 + [1500],
                                      "context": [[-2, -1, 0, 1, 2], [-2, 0, 2], [-3, 0, 3], [0], [0]], "tdnn_layers": 5,
                                      "embedding_dim": 512, "pooling": "statistic", "attention_hidden_size": 64, "bn_first": True}}
@@ -239,9 +243,13 @@ def test_attentive_speaker_encoder_two_sgd_steps_vs_reference_golden(golden):
     """`pooling: attentive_statistic` trains: two SGD steps of SpeakerEmbNet + LMCL against values captured from the reference's own
     classes (tests/golden/capture_golden.py: audio_attn_train; lr 1e-4 -- at the config's 0.01 the reference's second forward is NaN
     on these inputs, see the capture script)."""
+    attentive_speaker_encoder_two_sgd_steps_vs_reference_golden(golden["audio_attn_train"])
+
+
+def attentive_speaker_encoder_two_sgd_steps_vs_reference_golden(g):
+    """(the body of the test above, in whichever arithmetic is configured: test_train_f32_gpu.py runs it again under arith "f32")"""
     from models.audio_models.loss import LMCL
     from models.audio_models.tdnn import SpeakerEmbNet
-    g = golden["audio_attn_train"]
     opts = {"arch": "tdnn", "tdnn": {"input_dim": 24, "hidden_dim": [512] * 4 + [1500],
                                      "context": [[-2, -1, 0, 1, 2], [-2, 0, 2], [-3, 0, 3], [0], [0]], "tdnn_layers": 5,
                                      "embedding_dim": 512, "pooling": "attentive_statistic", "attention_hidden_size": 64, "bn_first": True}}

@@ -414,6 +414,11 @@ def _build(dropout):
 def test_lipreading_train_step_matches_reference_golden():
     """loss, logits, argmax, gradients (every parameter: norm and sum; selected tensors element-wise), BatchNorm
     running statistics after the step and the loss of the next forward vs the reference class on CPU."""
+    lipreading_train_step_vs_reference_golden()
+
+
+def lipreading_train_step_vs_reference_golden():
+    """(the body of the test above, in whichever arithmetic is configured: test_train_f32_gpu.py runs it again under arith "f32")"""
     g = np.load(GOLD)
     net = _build(0.0)
     net.train()
@@ -543,6 +548,11 @@ def test_recorded_training_step_is_bit_identical_to_eager(B, T):
     generator's offsets under capture are torch's business).  Two DIFFERENT Adam variants diverge by 5e-4 after two steps on this
     model -- the biases in front of a BatchNorm have pure-rounding-noise gradients, which Adam turns into +-lr steps
     (tools/probes/adam_variants.py) -- so only like is compared with like."""
+    recorded_training_step_vs_eager(B, T)
+
+
+def recorded_training_step_vs_eager(B, T):
+    """(the body of the test above, in whichever arithmetic is configured: test_train_f32_gpu.py runs it again under arith "f32")"""
     from deeplip_amd import autograd as ag
     from deeplip_amd.train_plan import TrainStepGraph
     from models.video_models.model import Lipreading
