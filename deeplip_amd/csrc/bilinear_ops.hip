@@ -321,7 +321,7 @@ extern "C" int dlip_bilinear_pool_f32(const float* e1, const float* e2, const fl
                                       int32_t B, int32_t d1, int32_t d2, int32_t o, int32_t k, dlip_stream_t stream) {
   DLIP_CHECK_ARG(e1 && e2 && u && v && z && bilinear_shape_ok(B, d1, d2, o, k));
   DLIP_CHECK_ARG((p == nullptr) == (q == nullptr));
-  DLIP_CHECK_ARG(dlip_aligned16(e1) && dlip_aligned16(e2) && dlip_aligned16(u) && dlip_aligned16(v));
+  DLIP_CHECK_ARG(dlip_aligned16(e1, e2, u, v));
   const int vec = ((long long)k * o) % 4 == 0;
   // outputs per workgroup: their columns (plus the three an aligned start may add in front) fit one 64-column pass when k allows
   const int opt = k <= 61 ? 61 / k : 1;
@@ -337,7 +337,7 @@ extern "C" int dlip_bilinear_pool_f32(const float* e1, const float* e2, const fl
 extern "C" int dlip_bilinear_pool_bwd_w_f32(const float* e1, const float* e2, const float* p, const float* q, const float* dz, float* du,
                                             float* dv, int32_t B, int32_t d1, int32_t d2, int32_t o, int32_t k, dlip_stream_t stream) {
   DLIP_CHECK_ARG(e1 && e2 && p && q && dz && du && dv && bilinear_shape_ok(B, d1, d2, o, k));
-  DLIP_CHECK_ARG(dlip_aligned16(du) && dlip_aligned16(dv));
+  DLIP_CHECK_ARG(dlip_aligned16(du, dv));
   const int ko = k * o;
   hipStream_t st = dlip_hip_stream(stream);
   hipLaunchKernelGGL(bilinear_bwd_w_kernel, dim3((ko + BL_COLS - 1) / BL_COLS), dim3(256), 0, st, e1, e2, p, q, dz, du, dv, B, d1, d2, o, k,
@@ -348,7 +348,7 @@ extern "C" int dlip_bilinear_pool_bwd_w_f32(const float* e1, const float* e2, co
 extern "C" int dlip_bilinear_pool_bwd_x_f32(const float* p, const float* q, const float* dz, const float* u, const float* v, float* de1,
                                             float* de2, int32_t B, int32_t d1, int32_t d2, int32_t o, int32_t k, dlip_stream_t stream) {
   DLIP_CHECK_ARG(p && q && dz && u && v && (de1 || de2) && bilinear_shape_ok(B, d1, d2, o, k));
-  DLIP_CHECK_ARG(dlip_aligned16(p) && dlip_aligned16(q) && dlip_aligned16(u) && dlip_aligned16(v));
+  DLIP_CHECK_ARG(dlip_aligned16(p, q, u, v));
   const int ko = k * o;
   const int dmax = d1 > d2 ? d1 : d2;
   hipStream_t st = dlip_hip_stream(stream);

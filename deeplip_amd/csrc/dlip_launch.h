@@ -9,7 +9,17 @@ inline unsigned dlip_grid1d(long long n, long long cap) {
   return (unsigned)(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
-// float4 / 128-bit access needs this
-inline bool dlip_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// Every one of the pointers is a multiple of BYTES (a power of two).  A null pointer is aligned: whether it may be null is the caller's
+// own condition.
+template <unsigned BYTES, class... P>
+inline bool dlip_aligned(const P*... p) {
+  static_assert(BYTES > 0 && (BYTES & (BYTES - 1)) == 0, "a power of two");
+  return ((reinterpret_cast<uintptr_t>(p) | ... | uintptr_t(0)) & (BYTES - 1)) == 0;
+}
+// float4 / 128-bit access needs the first; the split-format images (whole 128-byte blocks of 32 hi | 32 lo halves) the second
+template <class... P>
+inline bool dlip_aligned16(const P*... p) { return dlip_aligned<16>(p...); }
+template <class... P>
+inline bool dlip_aligned128(const P*... p) { return dlip_aligned<128>(p...); }
 
 inline hipStream_t dlip_hip_stream(dlip_stream_t stream) { return static_cast<hipStream_t>(stream); }

@@ -9,6 +9,8 @@
 // Column reductions over M = B*T' ~ 2e4 rows: rows are cut into fixed chunks of 512, a workgroup
 // reduces one (chunk, 64-column block) in fp64 (16 row groups x 16 lanes x float4, LDS tree), partials go
 // to a caller-provided workspace and a second kernel adds them in chunk order: deterministic, no atomics.
+#include <type_traits>
+
 #include "dlip_common.h"
 #include "conv_common.h"   // FastDiv: exact division by launch constants
 #include "conv_dispatch.h"
@@ -1355,59 +1357,110 @@ int* stream_tickets(hipStream_t st, int need) {
 
 bool bn_small(int M) { return M <= BN_SMALL_ROWS && dlip_dbg_value[DLIP_DBG_BN_FUSED] != 0; }
 
+// Rows per lane of the small-row kernels (M <= BN_SMALL_ROWS): launch(R) with R = 4 / 8 / 16 as a compile-time constant
+template <class F>
+void bn_small_rows(int M, F&& launch) {
+  if (M <= 1024) launch(std::integral_constant<int, 4>{});
+  else if (M <= 2048) launch(std::integral_constant<int, 8>{});
+  else launch(std::integral_constant<int, 16>{});
+}
+
+// The fallback of the three-sum passes (dbeta, dgamma, dslope: fin.out0 .. out2) on a stream without ticket words; the second sum's partial
+// rows lie behind the first's
+void col_finalize3_launch(double* workspace, int chunks, int C, const ColFin& fin, hipStream_t st) {
+  if (fin.ticket) return;
+  hipLaunchKernelGGL(col_finalize3_kernel, dim3((C + 15) / 16), dim3(256), 0, st, workspace, workspace + (long long)chunks * C * 2,
+                     fin.out0, fin.out1, fin.out2, C, chunks);
+}
+
+// The BatchNorm backward's apply pass over M rows (POOL: g read through a max-pooling's argmax, `ps`), and the power-of-two lift of the dx
+// it wrote when dx_lift2 is given: the per-workgroup maxima go behind the pair, a one-workgroup launch folds them.
+// (the lift of a LARGE dx stays a launch of its own: a ticket word taking thousands of arrivals, and every workgroup waiting for its
+// stores' acknowledgements in front of it, cost bn_bwd_apply 0.6 ms per lip-clip step -- more than the 20 launches it saved.  So the
+// kernel's lift ticket is always NULL here.)
+template <bool POOL>
+void bn_bwd_apply_launch(const float* g, const float* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                         const float* dgamma, const float* dbeta, float* dx, int M, int C, float slope, int act_first,
+                         const float* slope_vec, float* dx_lift2, hipStream_t st, const PoolSrc ps = PoolSrc{}, const MsSrc ms = MsSrc{}) {
+  unsigned* acc = dx_lift2 ? reinterpret_cast<unsigned*>(dx_lift2) + 2 : nullptr;   // per-workgroup maxima behind the pair
+  const long long n4 = (long long)M * (C / 4);
+  const unsigned gf = grid_fixed(n4, C / 4);
+  const unsigned grid = gf ? gf : dlip_grid1d(n4, kGridCap);
+  if (gf)
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<true, POOL>), dim3(grid), dim3(256), 0, st, reinterpret_cast<const f32x4*>(g),
+                       reinterpret_cast<const f32x4*>(x), mean, invstd, gamma, beta, dgamma, dbeta, reinterpret_cast<f32x4*>(dx), n4, C / 4, M,
+                       slope, act_first, slope_vec, acc, nullptr, ps, ms);
+  else
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<false, POOL>), dim3(grid), dim3(256), 0, st, reinterpret_cast<const f32x4*>(g),
+                       reinterpret_cast<const f32x4*>(x), mean, invstd, gamma, beta, dgamma, dbeta, reinterpret_cast<f32x4*>(dx), n4, C / 4, M,
+                       slope, act_first, slope_vec, acc, nullptr, ps, ms);
+  if (acc) hipLaunchKernelGGL(pow2_finalize_parts_kernel, dim3(1), dim3(256), 0, st, acc, (int)grid, dx_lift2, 1024.0f);
+}
+
+// The two steps of the shared forward, defined behind it (the template kernels of this file are emitted in the order of their first use;
+// declared ahead, these two leave that order, and with it the code object, as it was)
+void bn_stats_launch(const float* x, double* workspace, int M, int C, float slope, int act_first, int ready_chunks, const ColFin& fin,
+                     hipStream_t st);
+void bn_fwd_apply_launch(const float* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                         const float* slope_vec, float slope, int act_first, float* y, int M, int C, hipStream_t st);
+
 // Shared forward: statistics (a pass over x, or `ready_chunks` partial rows from the producing convolution), finalize, apply.
 int bn_fwd_launch(const float* x, const float* gamma, const float* beta, const float* slope_vec, float* y, float* save_mean,
                   float* save_invstd, float* running_mean, float* running_var, double* workspace, int M, int C, float momentum,
                   float eps, float slope, int act_first, int ready_chunks, long long* nbt, hipStream_t st) {
   if (ready_chunks == 0 && bn_small(M) && y != nullptr) {
-    const dim3 grid(C / 4), block(256);
-    if (M <= 1024) hipLaunchKernelGGL(bn_small_fwd_kernel<4>, grid, block, 0, st, x, gamma, beta, slope_vec, y, save_mean, save_invstd,
-                                      running_mean, running_var, nbt, M, C, momentum, eps, slope, act_first);
-    else if (M <= 2048) hipLaunchKernelGGL(bn_small_fwd_kernel<8>, grid, block, 0, st, x, gamma, beta, slope_vec, y, save_mean, save_invstd,
-                                           running_mean, running_var, nbt, M, C, momentum, eps, slope, act_first);
-    else hipLaunchKernelGGL(bn_small_fwd_kernel<16>, grid, block, 0, st, x, gamma, beta, slope_vec, y, save_mean, save_invstd,
-                            running_mean, running_var, nbt, M, C, momentum, eps, slope, act_first);
+    bn_small_rows(M, [&](auto R) {
+      hipLaunchKernelGGL(bn_small_fwd_kernel<decltype(R)::value>, dim3(C / 4), dim3(256), 0, st, x, gamma, beta, slope_vec, y, save_mean,
+                         save_invstd, running_mean, running_var, nbt, M, C, momentum, eps, slope, act_first);
+    });
     return dlip_launch_status();
   }
-  // ready_chunks > 0: `workspace` already holds that many partial rows {sum x, sum x^2} [chunk][C][2] -- written by the convolution
-  // that produced x (dlip_conv_nhwc_stats_f16x3) -- and the statistics pass over x is not launched
+  const ColFin fin = {ready_chunks == 0 ? stream_tickets(st, (C + 63) / 64) : nullptr, save_mean, save_invstd, nullptr, running_mean,
+                      running_var, nbt, momentum, eps};
+  bn_stats_launch(x, workspace, M, C, slope, act_first, ready_chunks, fin, st);
+  if (y == nullptr) return dlip_launch_status();   // statistics only: the consumer applies the BatchNorm on load (dlip_wgrad_*_bn_f32)
+  bn_fwd_apply_launch(x, save_mean, save_invstd, gamma, beta, slope_vec, slope, act_first, y, M, C, st);
+  return dlip_launch_status();
+}
+
+// Statistics pass: the partial rows {sum x, sum x^2} of x, then mean / invstd / running statistics out of them -- by the pass's own
+// last workgroups where the stream has ticket words (fin.ticket), else by a launch of its own.
+// ready_chunks > 0: `workspace` already holds that many partial rows [chunk][C][2] -- written by the convolution that produced x
+// (dlip_conv_nhwc_stats_f16x3) -- and the pass over x is not launched (fin.ticket is NULL)
+void bn_stats_launch(const float* x, double* workspace, int M, int C, float slope, int act_first, int ready_chunks, const ColFin& fin,
+                     hipStream_t st) {
   const int chunks = ready_chunks > 0 ? ready_chunks : dlip_bn_rows_chunks(M);
-  bool finalized = false;
-  if (ready_chunks == 0) {
-    ColFin fin = {stream_tickets(st, (C + 63) / 64), save_mean, save_invstd, nullptr, running_mean, running_var, nbt, momentum, eps};
-    finalized = fin.ticket != nullptr;
+  if (ready_chunks == 0)
     hipLaunchKernelGGL(col_partial_kernel<0>, dim3((C + 63) / 64, chunks), dim3(256), 0, st, x, nullptr, nullptr, nullptr,
                        nullptr, nullptr, workspace, M, C, slope, act_first, nullptr, bn_rows_per_part(M), fin);
-  }
-  if (!finalized)
-    hipLaunchKernelGGL(bn_fwd_finalize_kernel, dim3((C + 15) / 16), dim3(256), 0, st, workspace, save_mean, save_invstd,
-                       running_mean, running_var, M, C, chunks, momentum, eps, nbt);
-  if (y == nullptr) return dlip_launch_status();   // statistics only: the consumer applies the BatchNorm on load (dlip_wgrad_*_bn_f32)
+  if (!fin.ticket)
+    hipLaunchKernelGGL(bn_fwd_finalize_kernel, dim3((C + 15) / 16), dim3(256), 0, st, workspace, fin.out0, fin.out1,
+                       fin.running_mean, fin.running_var, M, C, chunks, fin.momentum, fin.eps, fin.nbt);
+}
+
+void bn_fwd_apply_launch(const float* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                         const float* slope_vec, float slope, int act_first, float* y, int M, int C, hipStream_t st) {
   const long long n4 = (long long)M * (C / 4);
   if (const unsigned gf = grid_fixed(n4, C / 4))
-    hipLaunchKernelGGL(bn_fwd_apply_kernel<true>, dim3(gf), dim3(256), 0, st, reinterpret_cast<const f32x4*>(x), save_mean,
-                       save_invstd, gamma, beta, reinterpret_cast<f32x4*>(y), n4, C / 4, slope, act_first, slope_vec);
+    hipLaunchKernelGGL(bn_fwd_apply_kernel<true>, dim3(gf), dim3(256), 0, st, reinterpret_cast<const f32x4*>(x), mean, invstd, gamma, beta,
+                       reinterpret_cast<f32x4*>(y), n4, C / 4, slope, act_first, slope_vec);
   else
-    hipLaunchKernelGGL(bn_fwd_apply_kernel<false>, dim3(dlip_grid1d(n4, kGridCap)), dim3(256), 0, st, reinterpret_cast<const f32x4*>(x), save_mean,
-                       save_invstd, gamma, beta, reinterpret_cast<f32x4*>(y), n4, C / 4, slope, act_first, slope_vec);
-  return dlip_launch_status();
+    hipLaunchKernelGGL(bn_fwd_apply_kernel<false>, dim3(dlip_grid1d(n4, kGridCap)), dim3(256), 0, st, reinterpret_cast<const f32x4*>(x), mean, invstd,
+                       gamma, beta, reinterpret_cast<f32x4*>(y), n4, C / 4, slope, act_first, slope_vec);
 }
 
 // Shared backward: slope_vec != NULL = the PReLU form (dslope written; act_first = 0), else the LeakyReLU forms.
 int bn_bwd_launch(const float* dy, const float* x, const float* gamma, const float* beta, const float* slope_vec,
                   const float* save_mean, const float* save_invstd, float* dx, float* dgamma, float* dbeta, float* dslope,
                   double* workspace, int M, int C, float slope, int act_first, float* dx_lift2, hipStream_t st, const MsSrc ms = MsSrc{}) {
-  unsigned* acc = dx_lift2 ? reinterpret_cast<unsigned*>(dx_lift2) + 2 : nullptr;   // per-workgroup maxima behind the pair
   int* tickets = stream_tickets(st, (C + 63) / 64);
   if (bn_small(M) && C / 4 <= 4096) {
-    const unsigned grid = (unsigned)(C / 4);
-    if (M <= 1024) hipLaunchKernelGGL(bn_small_bwd_kernel<4>, dim3(grid), dim3(256), 0, st, dy, x, save_mean, save_invstd, gamma, beta, slope_vec,
-                                      dx, dgamma, dbeta, dslope, M, C, slope, act_first, acc, tickets);
-    else if (M <= 2048) hipLaunchKernelGGL(bn_small_bwd_kernel<8>, dim3(grid), dim3(256), 0, st, dy, x, save_mean, save_invstd, gamma, beta,
-                                           slope_vec, dx, dgamma, dbeta, dslope, M, C, slope, act_first, acc, tickets);
-    else hipLaunchKernelGGL(bn_small_bwd_kernel<16>, dim3(grid), dim3(256), 0, st, dy, x, save_mean, save_invstd, gamma, beta, slope_vec, dx,
-                            dgamma, dbeta, dslope, M, C, slope, act_first, acc, tickets);
-    if (acc && !tickets) hipLaunchKernelGGL(pow2_finalize_parts_kernel, dim3(1), dim3(256), 0, st, acc, (int)grid, dx_lift2, 1024.0f);
+    unsigned* acc = dx_lift2 ? reinterpret_cast<unsigned*>(dx_lift2) + 2 : nullptr;
+    bn_small_rows(M, [&](auto R) {
+      hipLaunchKernelGGL(bn_small_bwd_kernel<decltype(R)::value>, dim3(C / 4), dim3(256), 0, st, dy, x, save_mean, save_invstd, gamma, beta,
+                         slope_vec, dx, dgamma, dbeta, dslope, M, C, slope, act_first, acc, tickets);
+    });
+    if (acc && !tickets) hipLaunchKernelGGL(pow2_finalize_parts_kernel, dim3(1), dim3(256), 0, st, acc, C / 4, dx_lift2, 1024.0f);
     return dlip_launch_status();
   }
   const int chunks = dlip_bn_rows_chunks(M);
@@ -1416,31 +1469,39 @@ int bn_bwd_launch(const float* dy, const float* x, const float* gamma, const flo
   if (slope_vec) {
     hipLaunchKernelGGL(col_partial_kernel<3>, dim3((C + 63) / 64, chunks), dim3(256), 0, st, x, dy, save_mean, save_invstd,
                        gamma, beta, workspace, M, C, 1.f, 0, slope_vec, rpp, fin);
-    if (!tickets)
-      hipLaunchKernelGGL(col_finalize3_kernel, dim3((C + 15) / 16), dim3(256), 0, st, workspace, workspace + (long long)chunks * C * 2,
-                         dbeta, dgamma, dslope, C, chunks);
+    col_finalize3_launch(workspace, chunks, C, fin, st);
   } else {
     fin.ms = ms;
     hipLaunchKernelGGL(col_partial_kernel<1>, dim3((C + 63) / 64, chunks), dim3(256), 0, st, x, dy, save_mean, save_invstd,
                        gamma, beta, workspace, M, C, slope, act_first, nullptr, rpp, fin);
     if (!tickets) hipLaunchKernelGGL(col_finalize_kernel, dim3((C + 15) / 16), dim3(256), 0, st, workspace, dbeta, dgamma, C, chunks);
   }
-  const long long n4 = (long long)M * (C / 4);
-  const unsigned gf = grid_fixed(n4, C / 4);
-  const unsigned grid = gf ? gf : dlip_grid1d(n4, kGridCap);
-  // (the lift of a LARGE dx stays a launch of its own: a ticket word taking thousands of arrivals, and every workgroup waiting for its
-  // stores' acknowledgements in front of it, cost bn_bwd_apply 0.6 ms per lip-clip step -- more than the 20 launches it saved)
-  int* lift_ticket = nullptr;
-  if (gf)
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(gf), dim3(256), 0, st, reinterpret_cast<const f32x4*>(dy),
-                       reinterpret_cast<const f32x4*>(x), save_mean, save_invstd, gamma, beta, dgamma, dbeta,
-                       reinterpret_cast<f32x4*>(dx), n4, C / 4, M, slope, act_first, slope_vec, acc, lift_ticket, PoolSrc{}, ms);
-  else
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, dim3(grid), dim3(256), 0, st, reinterpret_cast<const f32x4*>(dy),
-                       reinterpret_cast<const f32x4*>(x), save_mean, save_invstd, gamma, beta, dgamma, dbeta,
-                       reinterpret_cast<f32x4*>(dx), n4, C / 4, M, slope, act_first, slope_vec, acc, lift_ticket, PoolSrc{}, ms);
-  if (acc && !lift_ticket) hipLaunchKernelGGL(pow2_finalize_parts_kernel, dim3(1), dim3(256), 0, st, acc, (int)grid, dx_lift2, 1024.0f);
+  bn_bwd_apply_launch<false>(dy, x, save_mean, save_invstd, gamma, beta, dgamma, dbeta, dx, M, C, slope, act_first, slope_vec, dx_lift2, st,
+                             PoolSrc{}, ms);
   return dlip_launch_status();
+}
+
+// Launch geometry of meanstd_bwd_kernel: enough workgroups to fill the chip -- ceil(C4 / bs) column blocks x frame chunks x utterances
+struct MeanstdBwdGrid {
+  dim3 grid;
+  int bs, tchunk;
+};
+MeanstdBwdGrid meanstd_bwd_grid(int B, int T, int C4) {
+  int bs = 256;
+  for (int cand : {128, 64})
+    if ((C4 + cand - 1) / cand * cand < (C4 + bs - 1) / bs * bs) bs = cand;   // C4 = 375 (E-TDNN's 1 500 channels): 3 x 128, not 2 x 256
+  const int cb = (C4 + bs - 1) / bs;
+  int tsplit = (int)((4096 + (long long)cb * B - 1) / ((long long)cb * B));
+  if (tsplit < 1) tsplit = 1;
+  if (tsplit > T) tsplit = T;
+  const int tchunk = (T + tsplit - 1) / tsplit;
+  return {dim3(cb, (T + tchunk - 1) / tchunk, B), bs, tchunk};
+}
+
+// Workgroups of absmax_kernel over n floats read as quads
+unsigned absmax_blocks(long long n) {
+  const long long blocks = (n / 4 + 255) / 256;
+  return (unsigned)(blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks));
 }
 
 }  // namespace
@@ -1452,7 +1513,7 @@ extern "C" int dlip_bn_rows_train_fwd_f32(const float* x, const float* gamma, co
                                           int64_t* num_batches_tracked, dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && gamma && beta && save_mean && save_invstd && workspace && M > 0 && C > 0 && (C & 3) == 0);   // (y NULL: statistics only)
   DLIP_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr));
-  DLIP_CHECK_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0);
+  DLIP_CHECK_ARG(dlip_aligned16(x, y));
   DLIP_CHECK_ARG(ready_chunks >= 0 && !(ready_chunks > 0 && act_first));
   return bn_fwd_launch(x, gamma, beta, nullptr, y, save_mean, save_invstd, running_mean, running_var, workspace, M, C, momentum, eps,
                        slope, act_first, ready_chunks, reinterpret_cast<long long*>(num_batches_tracked), dlip_hip_stream(stream));
@@ -1464,7 +1525,7 @@ extern "C" int dlip_bn_rows_train_bwd_f32(const float* dy, const float* x, const
                                           int32_t act_first, float* dx_lift2, dlip_stream_t stream) {
   DLIP_CHECK_ARG(dy && x && gamma && beta && save_mean && save_invstd && dx && dgamma && dbeta && workspace);
   DLIP_CHECK_ARG(M > 0 && C > 0 && (C & 3) == 0);
-  DLIP_CHECK_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0);
+  DLIP_CHECK_ARG(dlip_aligned16(x, dy, dx));
   return bn_bwd_launch(dy, x, gamma, beta, nullptr, save_mean, save_invstd, dx, dgamma, dbeta, nullptr, workspace, M, C, slope, act_first,
                        dx_lift2, dlip_hip_stream(stream));
 }
@@ -1486,7 +1547,7 @@ extern "C" int dlip_bn_rows_train_bwd_ms_f32(const float* ms_coef, int32_t T, co
                                              double* workspace, int32_t M, int32_t C, float slope, float* dx_lift2, dlip_stream_t stream) {
   DLIP_CHECK_ARG(ms_coef && x && gamma && beta && save_mean && save_invstd && dx && dgamma && dbeta && workspace);
   DLIP_CHECK_ARG(M > 0 && C > 0 && (C & 3) == 0 && T > 1 && M % T == 0 && !bn_small(M));
-  DLIP_CHECK_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(ms_coef)) & 15) == 0);
+  DLIP_CHECK_ARG(dlip_aligned16(x, dx, ms_coef));
   MsSrc ms;
   ms.coef = ms_coef; ms.T = T; ms.div_T = dlip_fastdiv((uint32_t)T);
   return bn_bwd_launch(x /* never read as dy */, x, gamma, beta, nullptr, save_mean, save_invstd, dx, dgamma, dbeta, nullptr, workspace, M, C, slope, 0,
@@ -1503,7 +1564,7 @@ extern "C" int dlip_bn_rows_train_bwd_sums_f32(const float* dy, const float* x, 
   DLIP_CHECK_ARG(x && gamma && beta && save_mean && save_invstd && dgamma && dbeta && workspace && amax_parts && dx_lift2);
   DLIP_CHECK_ARG((dy != nullptr || ms_coef != nullptr) && (ms_coef == nullptr || (ms_T > 1 && !act_first && M % ms_T == 0)));
   DLIP_CHECK_ARG(M > 0 && C > 0 && (C & 3) == 0);
-  DLIP_CHECK_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(ms_coef)) & 15) == 0);
+  DLIP_CHECK_ARG(dlip_aligned16(x, dy, ms_coef));
   if (dy == nullptr) dy = x;           // (never read)
   hipStream_t st = dlip_hip_stream(stream);
   int* tickets = stream_tickets(st, (C + 63) / 64);
@@ -1530,7 +1591,7 @@ extern "C" int dlip_bn_prelu_rows_train_fwd_f32(const float* x, const float* gam
                                                 int64_t* num_batches_tracked, dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && gamma && beta && slope && save_mean && save_invstd && workspace && M > 0 && C > 0 && (C & 3) == 0);   // (y NULL: statistics only)
   DLIP_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr));
-  DLIP_CHECK_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0);
+  DLIP_CHECK_ARG(dlip_aligned16(x, y));
   return bn_fwd_launch(x, gamma, beta, slope, y, save_mean, save_invstd, running_mean, running_var, workspace, M, C, momentum, eps, 1.f, 0,
                        0, reinterpret_cast<long long*>(num_batches_tracked), dlip_hip_stream(stream));
 }
@@ -1541,7 +1602,7 @@ extern "C" int dlip_bn_prelu_rows_train_bwd_f32(const float* dy, const float* x,
                                                 float* dx_lift2, dlip_stream_t stream) {
   DLIP_CHECK_ARG(dy && x && gamma && beta && slope && save_mean && save_invstd && dx && dgamma && dbeta && dslope && workspace);
   DLIP_CHECK_ARG(M > 0 && C > 0 && (C & 3) == 0);
-  DLIP_CHECK_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0);
+  DLIP_CHECK_ARG(dlip_aligned16(x, dy, dx));
   return bn_bwd_launch(dy, x, gamma, beta, slope, save_mean, save_invstd, dx, dgamma, dbeta, dslope, workspace, M, C, 1.f, 0, dx_lift2,
                        dlip_hip_stream(stream));
 }
@@ -1552,17 +1613,12 @@ extern "C" int dlip_bn_prelu_maxpool_train_fwd_f32(const float* x, const float* 
                                                   float momentum, float eps, int64_t* num_batches_tracked, dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && gamma && beta && slope && y && idx && save_mean && save_invstd && workspace && N > 0 && H > 0 && W > 0 && C > 0);
   DLIP_CHECK_ARG((C & 3) == 0 && (running_mean == nullptr) == (running_var == nullptr) && N * H * W < 0x7FFFFFFFll);
-  DLIP_CHECK_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0);
+  DLIP_CHECK_ARG(dlip_aligned16(x, y));
   hipStream_t st = dlip_hip_stream(stream);
   const int M = (int)(N * H * W);
-  const int chunks = dlip_bn_rows_chunks(M);
-  long long* nbt = reinterpret_cast<long long*>(num_batches_tracked);
-  ColFin fin = {stream_tickets(st, (C + 63) / 64), save_mean, save_invstd, nullptr, running_mean, running_var, nbt, momentum, eps};
-  hipLaunchKernelGGL(col_partial_kernel<0>, dim3((C + 63) / 64, chunks), dim3(256), 0, st, x, nullptr, nullptr, nullptr,
-                     nullptr, nullptr, workspace, M, C, 1.f, 0, nullptr, bn_rows_per_part(M), fin);
-  if (!fin.ticket)
-    hipLaunchKernelGGL(bn_fwd_finalize_kernel, dim3((C + 15) / 16), dim3(256), 0, st, workspace, save_mean, save_invstd,
-                       running_mean, running_var, M, C, chunks, momentum, eps, nbt);
+  const ColFin fin = {stream_tickets(st, (C + 63) / 64), save_mean, save_invstd, nullptr, running_mean, running_var,
+                      reinterpret_cast<long long*>(num_batches_tracked), momentum, eps};
+  bn_stats_launch(x, workspace, M, C, 1.f, 0, 0, fin, st);
   const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
   const long long n4 = N * Ho * Wo * (C / 4);
   hipLaunchKernelGGL(bn_prelu_maxpool_fwd_kernel, dim3(dlip_grid1d(n4, kGridCap)), dim3(256), 0, st, x, save_mean, save_invstd, gamma, beta, slope,
@@ -1577,33 +1633,18 @@ extern "C" int dlip_bn_prelu_maxpool_train_bwd_f32(const float* dy_pooled, const
                                                   dlip_stream_t stream) {
   DLIP_CHECK_ARG(dy_pooled && idx && x && gamma && beta && slope && save_mean && save_invstd && dx && dgamma && dbeta && dslope && workspace);
   DLIP_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && (C & 3) == 0 && N * H * W < 0x7FFFFFFFll);
-  DLIP_CHECK_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy_pooled) | reinterpret_cast<uintptr_t>(dy_pooled2) |
-                   reinterpret_cast<uintptr_t>(dx)) & 15) == 0);
+  DLIP_CHECK_ARG(dlip_aligned16(x, dy_pooled, dy_pooled2, dx));
   hipStream_t st = dlip_hip_stream(stream);
   const int M = (int)(N * H * W);
   const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
   const PoolSrc ps = {idx, dy_pooled2, H, W, Ho, Wo, dlip_fastdiv((uint32_t)W), dlip_fastdiv((uint32_t)H), dlip_fastdiv((uint32_t)Wo), dlip_fastdiv((uint32_t)Ho)};
   const int Mp = (int)(N * Ho * Wo);
   const int chunks = dlip_bn_rows_chunks(Mp);           // (the sums run over the POOLED rows; workspace sized for M >= Mp)
-  ColFin fin = {stream_tickets(st, (C + 63) / 64), dbeta, dgamma, dslope, nullptr, nullptr, nullptr, 0.f, 0.f};
+  const ColFin fin = {stream_tickets(st, (C + 63) / 64), dbeta, dgamma, dslope, nullptr, nullptr, nullptr, 0.f, 0.f};
   hipLaunchKernelGGL(pool_bn_partial_kernel, dim3((C + 63) / 64, chunks), dim3(256), 0, st, x, dy_pooled, ps, save_mean, save_invstd,
                      gamma, beta, slope, workspace, Mp, M, C, bn_rows_per_part(Mp), fin);
-  if (!fin.ticket)
-    hipLaunchKernelGGL(col_finalize3_kernel, dim3((C + 15) / 16), dim3(256), 0, st, workspace, workspace + (long long)chunks * C * 2,
-                       dbeta, dgamma, dslope, C, chunks);
-  unsigned* acc = dx_lift2 ? reinterpret_cast<unsigned*>(dx_lift2) + 2 : nullptr;
-  const long long n4 = (long long)M * (C / 4);
-  const unsigned gf = grid_fixed(n4, C / 4);
-  const unsigned grid = gf ? gf : dlip_grid1d(n4, kGridCap);
-  if (gf)
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<true, true>), dim3(gf), dim3(256), 0, st, reinterpret_cast<const f32x4*>(dy_pooled),
-                       reinterpret_cast<const f32x4*>(x), save_mean, save_invstd, gamma, beta, dgamma, dbeta,
-                       reinterpret_cast<f32x4*>(dx), n4, C / 4, M, 1.f, 0, slope, acc, nullptr, ps);
-  else
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<false, true>), dim3(grid), dim3(256), 0, st, reinterpret_cast<const f32x4*>(dy_pooled),
-                       reinterpret_cast<const f32x4*>(x), save_mean, save_invstd, gamma, beta, dgamma, dbeta,
-                       reinterpret_cast<f32x4*>(dx), n4, C / 4, M, 1.f, 0, slope, acc, nullptr, ps);
-  if (acc) hipLaunchKernelGGL(pow2_finalize_parts_kernel, dim3(1), dim3(256), 0, st, acc, (int)grid, dx_lift2, 1024.0f);
+  col_finalize3_launch(workspace, chunks, C, fin, st);
+  bn_bwd_apply_launch<true>(dy_pooled, x, save_mean, save_invstd, gamma, beta, dgamma, dbeta, dx, M, C, 1.f, 0, slope, dx_lift2, st, ps);
   return dlip_launch_status();
 }
 
@@ -1613,17 +1654,11 @@ extern "C" int dlip_bn_add_prelu_rows_train_fwd_f32(const float* x, const float*
                                                    float momentum, float eps, int64_t* num_batches_tracked, dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && residual && gamma && beta && slope && sum && y && save_mean && save_invstd && workspace && M > 0 && C > 0 && (C & 3) == 0);
   DLIP_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr));
-  DLIP_CHECK_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(residual) | reinterpret_cast<uintptr_t>(sum) |
-                   reinterpret_cast<uintptr_t>(y)) & 15) == 0);
+  DLIP_CHECK_ARG(dlip_aligned16(x, residual, sum, y));
   hipStream_t st = dlip_hip_stream(stream);
-  const int chunks = dlip_bn_rows_chunks(M);
-  long long* nbt = reinterpret_cast<long long*>(num_batches_tracked);
-  ColFin fin = {stream_tickets(st, (C + 63) / 64), save_mean, save_invstd, nullptr, running_mean, running_var, nbt, momentum, eps};
-  hipLaunchKernelGGL(col_partial_kernel<0>, dim3((C + 63) / 64, chunks), dim3(256), 0, st, x, nullptr, nullptr, nullptr,
-                     nullptr, nullptr, workspace, M, C, 1.f, 0, nullptr, bn_rows_per_part(M), fin);
-  if (!fin.ticket)
-    hipLaunchKernelGGL(bn_fwd_finalize_kernel, dim3((C + 15) / 16), dim3(256), 0, st, workspace, save_mean, save_invstd,
-                       running_mean, running_var, M, C, chunks, momentum, eps, nbt);
+  const ColFin fin = {stream_tickets(st, (C + 63) / 64), save_mean, save_invstd, nullptr, running_mean, running_var,
+                      reinterpret_cast<long long*>(num_batches_tracked), momentum, eps};
+  bn_stats_launch(x, workspace, M, C, 1.f, 0, 0, fin, st);
   const long long n4 = (long long)M * (C / 4);
   if (const unsigned gf = grid_fixed(n4, C / 4))
     hipLaunchKernelGGL(bn_add_prelu_fwd_kernel<true>, dim3(gf), dim3(256), 0, st, reinterpret_cast<const f32x4*>(x),
@@ -1643,51 +1678,29 @@ extern "C" int dlip_bn_add_prelu_rows_train_bwd_f32(const float* dy, const float
                                                    dlip_stream_t stream) {
   DLIP_CHECK_ARG(dy && sum && x && gamma && beta && slope && save_mean && save_invstd && dresidual && dx && dgamma && dbeta && dslope && workspace);
   DLIP_CHECK_ARG(M > 0 && C > 0 && (C & 3) == 0);
-  DLIP_CHECK_ARG(((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dy2) | reinterpret_cast<uintptr_t>(sum) | reinterpret_cast<uintptr_t>(x) |
-                   reinterpret_cast<uintptr_t>(dresidual) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0);
+  DLIP_CHECK_ARG(dlip_aligned16(dy, dy2, sum, x, dresidual, dx));
   hipStream_t st = dlip_hip_stream(stream);
   const int chunks = dlip_bn_rows_chunks(M);
-  ColFin fin = {stream_tickets(st, (C + 63) / 64), dbeta, dgamma, dslope, nullptr, nullptr, nullptr, 0.f, 0.f};
+  const ColFin fin = {stream_tickets(st, (C + 63) / 64), dbeta, dgamma, dslope, nullptr, nullptr, nullptr, 0.f, 0.f};
   hipLaunchKernelGGL(add_prelu_bn_partial_kernel, dim3((C + 63) / 64, chunks), dim3(256), 0, st, dy, dy2, sum, x, save_mean, save_invstd,
                      slope, dresidual, workspace, M, C, bn_rows_per_part(M), fin);
-  if (!fin.ticket)
-    hipLaunchKernelGGL(col_finalize3_kernel, dim3((C + 15) / 16), dim3(256), 0, st, workspace, workspace + (long long)chunks * C * 2,
-                       dbeta, dgamma, dslope, C, chunks);
+  col_finalize3_launch(workspace, chunks, C, fin, st);
   // second pass: bn2's input gradient from g (= dresidual) and x -- the BatchNorm backward's apply pass at slope 1
-  unsigned* acc = dx_lift2 ? reinterpret_cast<unsigned*>(dx_lift2) + 2 : nullptr;
-  const long long n4 = (long long)M * (C / 4);
-  const unsigned gf = grid_fixed(n4, C / 4);
-  const unsigned grid = gf ? gf : dlip_grid1d(n4, kGridCap);
-  if (gf)
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(gf), dim3(256), 0, st, reinterpret_cast<const f32x4*>(dresidual),
-                       reinterpret_cast<const f32x4*>(x), save_mean, save_invstd, gamma, beta, dgamma, dbeta,
-                       reinterpret_cast<f32x4*>(dx), n4, C / 4, M, 1.f, 0, nullptr, acc, nullptr);
-  else
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, dim3(grid), dim3(256), 0, st, reinterpret_cast<const f32x4*>(dresidual),
-                       reinterpret_cast<const f32x4*>(x), save_mean, save_invstd, gamma, beta, dgamma, dbeta,
-                       reinterpret_cast<f32x4*>(dx), n4, C / 4, M, 1.f, 0, nullptr, acc, nullptr);
-  if (acc) hipLaunchKernelGGL(pow2_finalize_parts_kernel, dim3(1), dim3(256), 0, st, acc, (int)grid, dx_lift2, 1024.0f);
+  bn_bwd_apply_launch<false>(dresidual, x, save_mean, save_invstd, gamma, beta, dgamma, dbeta, dx, M, C, 1.f, 0, nullptr, dx_lift2, st);
   return dlip_launch_status();
 }
 
 extern "C" int dlip_bn_apply_rows_f32(const float* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
                                       const float* slope_vec, float slope, float* y, int32_t M, int32_t C, dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && mean && invstd && gamma && beta && y && M > 0 && C > 0 && (C & 3) == 0);
-  DLIP_CHECK_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0);
-  hipStream_t st = dlip_hip_stream(stream);
-  const long long n4 = (long long)M * (C / 4);
-  if (const unsigned gf = grid_fixed(n4, C / 4))
-    hipLaunchKernelGGL(bn_fwd_apply_kernel<true>, dim3(gf), dim3(256), 0, st, reinterpret_cast<const f32x4*>(x), mean, invstd, gamma, beta,
-                       reinterpret_cast<f32x4*>(y), n4, C / 4, slope, 0, slope_vec);
-  else
-    hipLaunchKernelGGL(bn_fwd_apply_kernel<false>, dim3(dlip_grid1d(n4, kGridCap)), dim3(256), 0, st, reinterpret_cast<const f32x4*>(x), mean, invstd, gamma,
-                       beta, reinterpret_cast<f32x4*>(y), n4, C / 4, slope, 0, slope_vec);
+  DLIP_CHECK_ARG(dlip_aligned16(x, y));
+  bn_fwd_apply_launch(x, mean, invstd, gamma, beta, slope_vec, slope, 0, y, M, C, dlip_hip_stream(stream));
   return dlip_launch_status();
 }
 
 extern "C" int dlip_colsum_rows_f32(const float* x, float* y, double* workspace, int32_t M, int32_t C,
                                     dlip_stream_t stream) {
-  DLIP_CHECK_ARG(x && y && workspace && M > 0 && C > 0 && (C & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0);
+  DLIP_CHECK_ARG(x && y && workspace && M > 0 && C > 0 && (C & 3) == 0 && dlip_aligned16(x));
   hipStream_t st = dlip_hip_stream(stream);
   const int chunks = dlip_bn_rows_chunks(M);
   ColFin fin = {stream_tickets(st, (C + 63) / 64), y, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f};
@@ -1700,20 +1713,11 @@ extern "C" int dlip_colsum_rows_f32(const float* x, float* y, double* workspace,
 extern "C" int dlip_meanstd_pool_bwd_f32(const float* x, const float* y, const float* dy, float* dx, int32_t B, int32_t T,
                                          int32_t C, dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && y && dy && dx && B > 0 && T > 1 && C > 0 && (C & 3) == 0);
-  DLIP_CHECK_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0);
+  DLIP_CHECK_ARG(dlip_aligned16(x, dx));
   DLIP_CHECK_ARG(B <= 65535);
-  const int C4 = C / 4;
-  // enough workgroups to fill the chip: ceil(C4 / 256) column blocks x frame chunks x utterances
-  int bs = 256;
-  for (int cand : {128, 64})
-    if ((C4 + cand - 1) / cand * cand < (C4 + bs - 1) / bs * bs) bs = cand;   // C4 = 375 (E-TDNN's 1 500 channels): 3 x 128, not 2 x 256
-  const int cb = (C4 + bs - 1) / bs;
-  int tsplit = (int)((4096 + (long long)cb * B - 1) / ((long long)cb * B));
-  if (tsplit < 1) tsplit = 1;
-  if (tsplit > T) tsplit = T;
-  const int tchunk = (T + tsplit - 1) / tsplit;
-  hipLaunchKernelGGL(meanstd_bwd_kernel<false>, dim3(cb, (T + tchunk - 1) / tchunk, B), dim3(bs), 0, dlip_hip_stream(stream),
-                     reinterpret_cast<const f32x4*>(x), y, dy, reinterpret_cast<f32x4*>(dx), T, C4, tchunk, PoolBnB{});
+  const MeanstdBwdGrid g = meanstd_bwd_grid(B, T, C / 4);
+  hipLaunchKernelGGL(meanstd_bwd_kernel<false>, g.grid, dim3(g.bs), 0, dlip_hip_stream(stream), reinterpret_cast<const f32x4*>(x), y, dy,
+                     reinterpret_cast<f32x4*>(dx), T, C / 4, g.tchunk, PoolBnB{});
   return dlip_launch_status();
 }
 
@@ -1721,20 +1725,12 @@ extern "C" int dlip_meanstd_pool_bwd_bn_f32(const float* z, const float* mean, c
                                             float slope, const float* y, const float* dy, float* dx, int32_t B, int32_t T, int32_t C,
                                             dlip_stream_t stream) {
   DLIP_CHECK_ARG(z && mean && invstd && gamma && beta && y && dy && dx && B > 0 && T > 1 && C > 0 && (C & 3) == 0);
-  DLIP_CHECK_ARG(((reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0);
+  DLIP_CHECK_ARG(dlip_aligned16(z, dx));
   DLIP_CHECK_ARG(B <= 65535);
-  const int C4 = C / 4;
-  int bs = 256;
-  for (int cand : {128, 64})
-    if ((C4 + cand - 1) / cand * cand < (C4 + bs - 1) / bs * bs) bs = cand;
-  const int cb = (C4 + bs - 1) / bs;
-  int tsplit = (int)((4096 + (long long)cb * B - 1) / ((long long)cb * B));
-  if (tsplit < 1) tsplit = 1;
-  if (tsplit > T) tsplit = T;
-  const int tchunk = (T + tsplit - 1) / tsplit;
+  const MeanstdBwdGrid g = meanstd_bwd_grid(B, T, C / 4);
   PoolBnB bn; bn.mean = mean; bn.invstd = invstd; bn.gamma = gamma; bn.beta = beta; bn.slope = slope;
-  hipLaunchKernelGGL(meanstd_bwd_kernel<true>, dim3(cb, (T + tchunk - 1) / tchunk, B), dim3(bs), 0, dlip_hip_stream(stream),
-                     reinterpret_cast<const f32x4*>(z), y, dy, reinterpret_cast<f32x4*>(dx), T, C4, tchunk, bn);
+  hipLaunchKernelGGL(meanstd_bwd_kernel<true>, g.grid, dim3(g.bs), 0, dlip_hip_stream(stream), reinterpret_cast<const f32x4*>(z), y, dy,
+                     reinterpret_cast<f32x4*>(dx), T, C / 4, g.tchunk, bn);
   return dlip_launch_status();
 }
 
@@ -1749,23 +1745,19 @@ extern "C" int dlip_permute3_f32(const float* x, float* y, int32_t d0, int32_t d
 
 extern "C" int dlip_pow2_scale_f32(const float* x, float* scale2, int64_t n, float target, dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && scale2 && n > 0 && target > 0.f);
-  DLIP_CHECK_ARG((reinterpret_cast<uintptr_t>(x) & 15) == 0);
+  DLIP_CHECK_ARG(dlip_aligned16(x));
   hipStream_t st = dlip_hip_stream(stream);
   if (hipMemsetAsync(scale2, 0, 2 * sizeof(float), st) != hipSuccess) return DLIP_EINVAL;
-  const long long blocks = (n / 4 + 255) / 256;
-  hipLaunchKernelGGL(absmax_kernel, dim3((unsigned)(blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks))), dim3(256), 0, st, x,
-                     reinterpret_cast<unsigned*>(scale2), (long long)n);
+  hipLaunchKernelGGL(absmax_kernel, dim3(absmax_blocks(n)), dim3(256), 0, st, x, reinterpret_cast<unsigned*>(scale2), (long long)n);
   hipLaunchKernelGGL(pow2_finalize_kernel, dim3(1), dim3(1), 0, st, scale2, target);
   return dlip_launch_status();
 }
 
 extern "C" int dlip_pow2_lift_f32(const float* x, float* lift, int64_t n, float target, dlip_stream_t stream) {
-  DLIP_CHECK_ARG(x && lift && n > 0 && target > 0.f && (reinterpret_cast<uintptr_t>(x) & 15) == 0);
+  DLIP_CHECK_ARG(x && lift && n > 0 && target > 0.f && dlip_aligned16(x));
   hipStream_t st = dlip_hip_stream(stream);
-  long long blocks = (n / 4 + 255) / 256;
-  blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
   if (hipMemsetAsync(lift + 2, 0, sizeof(float), st) != hipSuccess) return DLIP_EINVAL;
-  hipLaunchKernelGGL(absmax_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x, reinterpret_cast<unsigned*>(lift) + 2, (long long)n);
+  hipLaunchKernelGGL(absmax_kernel, dim3(absmax_blocks(n)), dim3(256), 0, st, x, reinterpret_cast<unsigned*>(lift) + 2, (long long)n);
   hipLaunchKernelGGL(pow2_finalize_parts_kernel, dim3(1), dim3(256), 0, st, reinterpret_cast<const unsigned*>(lift) + 2, 1, lift, target);
   return dlip_launch_status();
 }
@@ -1782,7 +1774,7 @@ extern "C" int dlip_split_pack_scaled_f32(const float* x, float* y, const float*
 extern "C" int dlip_split_pack_scaled_pad_f32(const float* x, float* y, const float* scale, int64_t rows, int32_t C, int32_t C_pad,
                                               dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && y && scale && rows > 0 && C > 0 && (C & 3) == 0 && C_pad >= C && (C_pad & 31) == 0);
-  DLIP_CHECK_ARG((reinterpret_cast<uintptr_t>(x) & 15) == 0);
+  DLIP_CHECK_ARG(dlip_aligned16(x));
   const long long n4 = rows * (C_pad / 4);
   hipLaunchKernelGGL(split_pack_scaled_pad_kernel, dim3(dlip_grid1d(n4, kGridCap)), dim3(256), 0, dlip_hip_stream(stream), x, y, scale,
                      (long long)rows, C, C_pad, dlip_range_for(DLIP_ST_PACK));
@@ -1810,7 +1802,7 @@ extern "C" int dlip_split_weights_perm_f32(const float* w_kct, float* w_split, f
 static_assert(sizeof(WSplitDesc) == 48, "include/deeplip_hip.h: struct dlip_wsplit_desc");
 extern "C" int dlip_split_weights_multi_f32(const void* descs, const int32_t* block_desc, int32_t n_blocks, int32_t max_row_floats,
                                             dlip_stream_t stream) {
-  DLIP_CHECK_ARG(descs && block_desc && n_blocks > 0 && (reinterpret_cast<uintptr_t>(descs) & 7) == 0 && max_row_floats >= 0);
+  DLIP_CHECK_ARG(descs && block_desc && n_blocks > 0 && dlip_aligned<8>(descs) && max_row_floats >= 0);
   // the staging buffer: the launch's longest row (T * C_pad floats), at most 32 KB (longer rows are read from memory twice); dynamic
   // LDS, so that a launch of short rows keeps more workgroups on a CU
   int stage_floats = max_row_floats <= 0 || max_row_floats > 8192 ? 8192 : (max_row_floats + 31) / 32 * 32;

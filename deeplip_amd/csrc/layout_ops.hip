@@ -204,7 +204,7 @@ __global__ __launch_bounds__(256) void mask_frames_kernel(const f32x4* __restric
 
 extern "C" int dlip_mask_frames_f32(const float* x, const int32_t* len, float* y, int32_t B, int32_t T, int32_t E, dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && len && y && B > 0 && T > 0 && E > 0 && (E & 3) == 0);
-  DLIP_CHECK_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0);
+  DLIP_CHECK_ARG(dlip_aligned16(x, y));
   const long long n4 = (long long)B * T * (E / 4);
   long long g = (n4 + 255) / 256; if (g > 4096) g = 4096;
   hipLaunchKernelGGL(mask_frames_kernel, dim3((unsigned)g), dim3(256), 0, dlip_hip_stream(stream),

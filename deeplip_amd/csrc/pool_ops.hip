@@ -221,7 +221,7 @@ extern "C" int dlip_group_mean_f32(const float* x, const int32_t* group_ptr, flo
 extern "C" int dlip_meanstd_pool_f32(const float* x, const int32_t* len, int32_t len_add, float* y, int32_t B, int32_t T, int32_t C,
                                      int32_t out_split, dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && y && B > 0 && B <= 65535 && T > 0 && C > 0 && (C & 3) == 0);
-  DLIP_CHECK_ARG((reinterpret_cast<uintptr_t>(x) & 15) == 0);
+  DLIP_CHECK_ARG(dlip_aligned16(x));
   const dim3 grid((C + 63) / 64, B);
   DlipLen l; l.len = len; l.mul = 1; l.add = len_add;
   if (out_split)
@@ -236,7 +236,7 @@ extern "C" int dlip_meanstd_pool_f32(const float* x, const int32_t* len, int32_t
 extern "C" int dlip_meanstd_pool_bn_f32(const float* z, const float* mean, const float* invstd, const float* gamma, const float* beta,
                                         float slope, float* y, int32_t B, int32_t T, int32_t C, dlip_stream_t stream) {
   DLIP_CHECK_ARG(z && mean && invstd && gamma && beta && y && B > 0 && B <= 65535 && T > 0 && C > 0 && (C & 3) == 0);
-  DLIP_CHECK_ARG((reinterpret_cast<uintptr_t>(z) & 15) == 0);
+  DLIP_CHECK_ARG(dlip_aligned16(z));
   DlipLen l; l.len = nullptr; l.mul = 1; l.add = 0;
   PoolBn bn; bn.mean = mean; bn.invstd = invstd; bn.gamma = gamma; bn.beta = beta; bn.slope = slope;
   hipLaunchKernelGGL((meanstd_kernel<false, true>), dim3((C + 63) / 64, B), dim3(256), 0, dlip_hip_stream(stream), z, y, T, C, 2 * C, l,

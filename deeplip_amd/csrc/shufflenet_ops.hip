@@ -302,8 +302,8 @@ extern "C" int dlip_shuffle_dwpw_f32(const float* x, const float* dw_w, const fl
   DLIP_CHECK_ARG((dw_w == nullptr) == (dw_b == nullptr));
   DLIP_CHECK_ARG(stride == 1 || (stride == 2 && dw_w));
   DLIP_CHECK_ARG((Cin & 3) == 0 && (ldx & 3) == 0 && ldx >= Cin);
-  DLIP_CHECK_ARG((reinterpret_cast<uintptr_t>(x) & 15) == 0);
-  DLIP_CHECK_ARG(dw_w == nullptr || ((reinterpret_cast<uintptr_t>(dw_w) & 15) == 0 && (reinterpret_cast<uintptr_t>(dw_b) & 15) == 0));
+  DLIP_CHECK_ARG(dlip_aligned16(x));
+  DLIP_CHECK_ARG(dw_w == nullptr || dlip_aligned16(dw_w, dw_b));
   DLIP_CHECK_ARG(Kp >= K && (Kp & 63) == 0);
   DLIP_CHECK_ARG(hp == 0 || (hp >= K && (par == 0 || par == 1) && ldy >= 2 * hp));   // the padding reaches channel 2hp - 1
   DLIP_CHECK_ARG(hp != 0 || ldy >= K);

@@ -148,7 +148,6 @@ __global__ __launch_bounds__(256) void tcn_dw_wgrad_reduce_kernel(const DwArgs a
   *reinterpret_cast<f32x4*>(br.y + (size_t)j * C + c4 * 4) = v;
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // Checks shared by the three entry points; fills the branch table's geometry.
 int dw_setup(DwArgs& a, int32_t n, const int32_t* k, const int32_t* pad, const int32_t* t_out, int32_t B, int32_t T, int32_t C,
@@ -173,18 +172,18 @@ int dw_setup(DwArgs& a, int32_t n, const int32_t* k, const int32_t* pad, const i
 extern "C" int dlip_tcn_dw_fwd_f32(const float* x, int32_t n, const float* const* w, const float* const* bias,
                                    const float* const* slope, float* const* y, const int32_t* k, const int32_t* pad,
                                    const int32_t* t_out, int32_t B, int32_t T, int32_t C, int32_t d, dlip_stream_t stream) {
-  DLIP_CHECK_ARG(x && w && y && aligned16(x));
+  DLIP_CHECK_ARG(x && w && y && dlip_aligned16(x));
   DwArgs a;
   a.x = x; a.dx = nullptr;
   const int st = dw_setup(a, n, k, pad, t_out, B, T, C, d);
   if (st != DLIP_OK) return st;
   long long most = 0;
   for (int r = 0; r < n; ++r) {
-    DLIP_CHECK_ARG(w[r] && y[r] && aligned16(w[r]) && aligned16(y[r]));
+    DLIP_CHECK_ARG(w[r] && y[r] && dlip_aligned16(w[r], y[r]));
     a.br[r].w = w[r];
     a.br[r].bias = bias ? bias[r] : nullptr;
     a.br[r].slope = slope ? slope[r] : nullptr;
-    DLIP_CHECK_ARG(aligned16(a.br[r].bias) && aligned16(a.br[r].slope));
+    DLIP_CHECK_ARG(dlip_aligned16(a.br[r].bias, a.br[r].slope));
     a.br[r].y = y[r];
     const long long tot = (long long)B * t_out[r] * (C / 4);
     most = tot > most ? tot : most;
@@ -198,13 +197,13 @@ extern "C" int dlip_tcn_dw_fwd_f32(const float* x, int32_t n, const float* const
 extern "C" int dlip_tcn_dw_dgrad_f32(const float* const* dz, int32_t n, const float* const* w, const int32_t* k, const int32_t* pad,
                                      const int32_t* t_out, float* dx, int32_t B, int32_t T, int32_t C, int32_t d,
                                      dlip_stream_t stream) {
-  DLIP_CHECK_ARG(dz && w && dx && aligned16(dx));
+  DLIP_CHECK_ARG(dz && w && dx && dlip_aligned16(dx));
   DwArgs a;
   a.x = nullptr; a.dx = dx;
   const int st = dw_setup(a, n, k, pad, t_out, B, T, C, d);
   if (st != DLIP_OK) return st;
   for (int r = 0; r < n; ++r) {
-    DLIP_CHECK_ARG(dz[r] && w[r] && aligned16(dz[r]) && aligned16(w[r]));
+    DLIP_CHECK_ARG(dz[r] && w[r] && dlip_aligned16(dz[r], w[r]));
     a.br[r].dz = dz[r];
     a.br[r].w = w[r];
   }
@@ -218,7 +217,7 @@ extern "C" int dlip_tcn_dw_wgrad_chunks(int32_t rows) { return rows > 0 ? (rows 
 extern "C" int dlip_tcn_dw_wgrad_f32(const float* x, int32_t n, const float* const* dz, float* const* dw, const int32_t* k,
                                      const int32_t* pad, const int32_t* t_out, int32_t B, int32_t T, int32_t C, int32_t d,
                                      double* workspace, int64_t workspace_len, dlip_stream_t stream) {
-  DLIP_CHECK_ARG(x && dz && dw && workspace && aligned16(x));
+  DLIP_CHECK_ARG(x && dz && dw && workspace && dlip_aligned16(x));
   DwArgs a;
   a.x = x; a.dx = nullptr;
   const int st = dw_setup(a, n, k, pad, t_out, B, T, C, d);
@@ -226,7 +225,7 @@ extern "C" int dlip_tcn_dw_wgrad_f32(const float* x, int32_t n, const float* con
   long long off = 0;
   int most_chunks = 0, most_k = 0;
   for (int r = 0; r < n; ++r) {
-    DLIP_CHECK_ARG(dz[r] && dw[r] && aligned16(dz[r]) && aligned16(dw[r]));
+    DLIP_CHECK_ARG(dz[r] && dw[r] && dlip_aligned16(dz[r], dw[r]));
     a.br[r].dz = dz[r];
     a.br[r].y = dw[r];
     a.br[r].chunks = dlip_tcn_dw_wgrad_chunks(B * t_out[r]);

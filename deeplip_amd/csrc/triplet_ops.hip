@@ -286,7 +286,7 @@ extern "C" int dlip_triplet_mine_f32(const float* x, const int32_t* labels, floa
   DLIP_CHECK_ARG(x && labels && g && rownorm && triplet_shape_ok(B, E) && mode >= TRIPLET_ALL && mode <= TRIPLET_SEMIHARD);
   DLIP_CHECK_ARG(mode == TRIPLET_ALL || neg);
   DLIP_CHECK_ARG((mode != TRIPLET_RANDOM && mode != TRIPLET_SEMIHARD) || u);
-  DLIP_CHECK_ARG((reinterpret_cast<uintptr_t>(x) & 15) == 0);
+  DLIP_CHECK_ARG(dlip_aligned16(x));
   hipStream_t st = dlip_hip_stream(stream);
   hipLaunchKernelGGL(triplet_gemm16_kernel<true>, dim3((B + 63) / 64, (B + 15) / 16), dim3(256), 0, st, x, x, g, rownorm, B, B, E, E, E, B);
   if (mode != TRIPLET_ALL)
@@ -309,7 +309,7 @@ extern "C" int dlip_triplet_loss_bwd_f32(const float* x, const float* g, const f
                                          const int32_t* n_triplets, const float* gscale, float* mw, float* dx, int32_t B, int32_t E,
                                          dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && g && rownorm && wcount && n_triplets && mw && dx && triplet_shape_ok(B, E));
-  DLIP_CHECK_ARG((reinterpret_cast<uintptr_t>(mw) & 15) == 0);
+  DLIP_CHECK_ARG(dlip_aligned16(mw));
   const int ldm = (B + 15) / 16 * 16;
   hipStream_t st = dlip_hip_stream(stream);
   hipLaunchKernelGGL(triplet_bwd_weights_kernel, dim3(B), dim3(256), 0, st, g, rownorm, wcount, n_triplets, gscale, mw, B, ldm);

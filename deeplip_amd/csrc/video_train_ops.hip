@@ -781,13 +781,55 @@ __global__ __launch_bounds__(256) void chomp_concat_kernel(const ChompCat cc, fl
   }
 }
 
+// One launcher per operand family.  `tile` is the caller's choice (its rule differs per entry point and stays there): 128 | 64 = the wide
+// kernels' channels per workgroup (16-byte aligned x, ldx % 4 == 0; C % tile == 0 unless AFF == 2), 0 = the generic 32 x 32 kernel (AFF == 0).
+template <int AFF>
+void wgrad_operand_launch(int tile, const float* x, float* out, int H, int W, int ldx, int C, int Ho, int Wo, int sh, int sw, int R, int S,
+                          int dh, int dw, int ph, int pw, int J, long long ldo, const float* scale, float* nhwc_out, const BnOnLoad& bn,
+                          int ld_nhwc, hipStream_t st) {
+  const int ct = tile ? tile : 32;      // channels per workgroup (AFF == 2: the last block may be ragged)
+  const dim3 grid((unsigned)(ldo / 32), (unsigned)((C + ct - 1) / ct));
+  if (tile == 128)
+    hipLaunchKernelGGL((wgrad_operand_wide_kernel<128, AFF>), grid, dim3(256), 0, st, x, out, H, W, ldx, C, Ho, Wo, sh, sw, R, S, dh, dw, ph, pw, J,
+                       ldo, scale, dlip_range_for(DLIP_ST_PACK), nhwc_out, bn, ld_nhwc);
+  else if (tile == 64)
+    hipLaunchKernelGGL((wgrad_operand_wide_kernel<64, AFF>), grid, dim3(256), 0, st, x, out, H, W, ldx, C, Ho, Wo, sh, sw, R, S, dh, dw, ph, pw, J,
+                       ldo, scale, dlip_range_for(DLIP_ST_PACK), nhwc_out, bn, ld_nhwc);
+  else if constexpr (AFF == 0)
+    hipLaunchKernelGGL(wgrad_operand_kernel, grid, dim3(256), 0, st, x, out, H, W, ldx, C, Ho, Wo, sh, sw, R, S, dh, dw, ph, pw, J, ldo, scale,
+                       dlip_range_for(DLIP_ST_PACK));
+}
+
+template <int AFF>
+void wgrad_chwn_launch(int tile, const float* x, float* out, int N, int HW, int ldx, int C, int N32, const float* scale, int layout,
+                       float* nhwc_out, const BnOnLoad& bn, hipStream_t st) {
+  const int ct = tile ? tile : 32;
+  const dim3 grid((unsigned)(N32 / 32), (unsigned)((C + ct - 1) / ct), (unsigned)HW);
+  if (tile == 128)
+    hipLaunchKernelGGL((wgrad_chwn_wide_kernel<128, AFF>), grid, dim3(256), 0, st, x, out, N, HW, ldx, C, N32, scale, dlip_range_for(DLIP_ST_PACK),
+                       layout, nhwc_out, bn);
+  else if (tile == 64)
+    hipLaunchKernelGGL((wgrad_chwn_wide_kernel<64, AFF>), grid, dim3(256), 0, st, x, out, N, HW, ldx, C, N32, scale, dlip_range_for(DLIP_ST_PACK),
+                       layout, nhwc_out, bn);
+  else if constexpr (AFF == 0)
+    hipLaunchKernelGGL(wgrad_chwn_kernel, grid, dim3(256), 0, st, x, out, N, HW, ldx, C, N32, scale, dlip_range_for(DLIP_ST_PACK), 0, 0, layout,
+                       nhwc_out);
+}
+
+// x as [J, 1, 1, C]: one "image" per position, one tap (the dlip_wgrad_operand_split*_f32 entries)
+template <int AFF>
+void wgrad_operand_split_launch(int tile, const float* x, float* out, long long J, long long ld_out, int C, const float* scale,
+                                float* nhwc_out, const BnOnLoad& bn, int ld_nhwc, hipStream_t st) {
+  wgrad_operand_launch<AFF>(tile, x, out, 1, 1, C, C, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, (int)J, ld_out, scale, nhwc_out, bn, ld_nhwc, st);
+}
+
 }  // namespace
 
 extern "C" int dlip_tap_gather_f32(const float* x, float* out, int64_t N, int32_t H, int32_t W, int32_t C, int32_t ldx,
                                    int32_t Ho, int32_t Wo, int32_t stride_h, int32_t stride_w, int32_t off_h, int32_t off_w,
                                    int32_t ldo, dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && out && N > 0 && H > 0 && W > 0 && C > 0 && (C & 3) == 0 && (ldx & 3) == 0 && ldx >= C && Ho > 0 && Wo > 0 &&
-                 stride_h > 0 && stride_w > 0 && ldo >= C && (ldo & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0);
+                 stride_h > 0 && stride_w > 0 && ldo >= C && (ldo & 3) == 0 && dlip_aligned16(out));
   const long long n4 = (long long)N * Ho * Wo * (C / 4);
   hipLaunchKernelGGL(tap_gather_kernel, dim3(dlip_grid1d(n4, kGridCap)), dim3(256), 0, dlip_hip_stream(stream), x, out, H, W, ldx, C / 4, Ho, Wo, stride_h,
                      stride_w, off_h, off_w, ldo, n4);
@@ -798,56 +840,32 @@ extern "C" int dlip_wgrad_operand_f32(const float* x, float* out, int64_t ld_out
                                       int32_t Ho, int32_t Wo, int32_t stride_h, int32_t stride_w, int32_t R, int32_t S, int32_t dil_h,
                                       int32_t dil_w, int32_t pad_h, int32_t pad_w, const float* scale, dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && out && N > 0 && H > 0 && W > 0 && C > 0 && ldx >= C && Ho > 0 && Wo > 0 && stride_h > 0 &&
-                 stride_w > 0 && R > 0 && S > 0 && (reinterpret_cast<uintptr_t>(out) & 127) == 0);
+                 stride_w > 0 && R > 0 && S > 0 && dlip_aligned128(out));
   const long long J = (long long)N * Ho * Wo;
   DLIP_CHECK_ARG(J < (1ll << 28) && (long long)N * H < (1ll << 30) && ld_out >= J && (ld_out & 31) == 0 && (C + 31) / 32 <= 65535);
-  const bool quads = (ldx & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
-  if (quads && C % 128 == 0)
-    hipLaunchKernelGGL(wgrad_operand_wide_kernel<128>, dim3((unsigned)(ld_out / 32), (unsigned)(C / 128)), dim3(256), 0, dlip_hip_stream(stream), x, out, H, W,
-                       ldx, C, Ho, Wo, stride_h, stride_w, R, S, dil_h, dil_w, pad_h, pad_w, (int)J, (long long)ld_out, scale,
-                       dlip_range_for(DLIP_ST_PACK));
-  else if (quads && C % 64 == 0)
-    hipLaunchKernelGGL(wgrad_operand_wide_kernel<64>, dim3((unsigned)(ld_out / 32), (unsigned)(C / 64)), dim3(256), 0, dlip_hip_stream(stream), x, out, H, W,
-                       ldx, C, Ho, Wo, stride_h, stride_w, R, S, dil_h, dil_w, pad_h, pad_w, (int)J, (long long)ld_out, scale,
-                       dlip_range_for(DLIP_ST_PACK));
-  else
-    hipLaunchKernelGGL(wgrad_operand_kernel, dim3((unsigned)(ld_out / 32), (unsigned)((C + 31) / 32)), dim3(256), 0, dlip_hip_stream(stream), x, out, H, W,
-                       ldx, C, Ho, Wo, stride_h, stride_w, R, S, dil_h, dil_w, pad_h, pad_w, (int)J, (long long)ld_out, scale,
-                       dlip_range_for(DLIP_ST_PACK));
+  const bool quads = (ldx & 3) == 0 && dlip_aligned16(x);
+  const int tile = quads && C % 128 == 0 ? 128 : quads && C % 64 == 0 ? 64 : 0;
+  wgrad_operand_launch<0>(tile, x, out, H, W, ldx, C, Ho, Wo, stride_h, stride_w, R, S, dil_h, dil_w, pad_h, pad_w, (int)J, ld_out, scale,
+                          nullptr, BnOnLoad{}, 0, dlip_hip_stream(stream));
   return dlip_launch_status();
 }
 
 extern "C" int dlip_wgrad_operand_split_f32(const float* x, float* out, int64_t ld_out, int64_t J, int32_t C, const float* scale,
                                             float* nhwc_split_out, dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && out && nhwc_split_out && J > 0 && J < (1ll << 28) && C > 0 && (C & 63) == 0 && ld_out >= J && (ld_out & 31) == 0);
-  DLIP_CHECK_ARG(((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(nhwc_split_out)) & 127) == 0 &&
-                 (reinterpret_cast<uintptr_t>(x) & 15) == 0 && C / 64 <= 65535);
-  // x as [J, 1, 1, C]: one "image" per position, one tap
-  if (C % 128 == 0)
-    hipLaunchKernelGGL(wgrad_operand_wide_kernel<128>, dim3((unsigned)(ld_out / 32), (unsigned)(C / 128)), dim3(256), 0, dlip_hip_stream(stream), x, out, 1, 1, C,
-                       C, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, (int)J, (long long)ld_out, scale, dlip_range_for(DLIP_ST_PACK), nhwc_split_out);
-  else
-    hipLaunchKernelGGL(wgrad_operand_wide_kernel<64>, dim3((unsigned)(ld_out / 32), (unsigned)(C / 64)), dim3(256), 0, dlip_hip_stream(stream), x, out, 1, 1, C,
-                       C, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, (int)J, (long long)ld_out, scale, dlip_range_for(DLIP_ST_PACK), nhwc_split_out);
+  DLIP_CHECK_ARG(dlip_aligned128(out, nhwc_split_out) && dlip_aligned16(x) && C / 64 <= 65535);
+  wgrad_operand_split_launch<0>(C % 128 == 0 ? 128 : 64, x, out, J, ld_out, C, scale, nhwc_split_out, BnOnLoad{}, 0, dlip_hip_stream(stream));
   return dlip_launch_status();
 }
 
 extern "C" int dlip_wgrad_chwn_f32(const float* x, float* out, int64_t N, int32_t H, int32_t W, int32_t C, int32_t ldx, int32_t N32,
                                    const float* scale, int32_t slice_major, float* nhwc_split_out, dlip_stream_t stream) {
-  DLIP_CHECK_ARG(x && out && N > 0 && H > 0 && W > 0 && C > 0 && ldx >= C && N32 >= N && (N32 & 31) == 0 &&
-                 (reinterpret_cast<uintptr_t>(out) & 127) == 0);
+  DLIP_CHECK_ARG(x && out && N > 0 && H > 0 && W > 0 && C > 0 && ldx >= C && N32 >= N && (N32 & 31) == 0 && dlip_aligned128(out));
   DLIP_CHECK_ARG((long long)H * W <= 65535 && (C + 31) / 32 <= 65535 && N < (1ll << 31));
-  DLIP_CHECK_ARG(nhwc_split_out == nullptr || ((C & 31) == 0 && (reinterpret_cast<uintptr_t>(nhwc_split_out) & 127) == 0));
-  const bool quads = (ldx & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
-  if (quads && C % 128 == 0)
-    hipLaunchKernelGGL(wgrad_chwn_wide_kernel<128>, dim3((unsigned)(N32 / 32), (unsigned)(C / 128), (unsigned)(H * W)), dim3(256), 0, dlip_hip_stream(stream),
-                       x, out, (int)N, H * W, ldx, C, N32, scale, dlip_range_for(DLIP_ST_PACK), slice_major ? 1 : 0, nhwc_split_out);
-  else if (quads && C % 64 == 0)
-    hipLaunchKernelGGL(wgrad_chwn_wide_kernel<64>, dim3((unsigned)(N32 / 32), (unsigned)(C / 64), (unsigned)(H * W)), dim3(256), 0, dlip_hip_stream(stream),
-                       x, out, (int)N, H * W, ldx, C, N32, scale, dlip_range_for(DLIP_ST_PACK), slice_major ? 1 : 0, nhwc_split_out);
-  else
-    hipLaunchKernelGGL(wgrad_chwn_kernel, dim3((unsigned)(N32 / 32), (unsigned)((C + 31) / 32), (unsigned)(H * W)), dim3(256), 0, dlip_hip_stream(stream), x,
-                       out, (int)N, H * W, ldx, C, N32, scale, dlip_range_for(DLIP_ST_PACK), 0, 0, slice_major ? 1 : 0, nhwc_split_out);
+  DLIP_CHECK_ARG(nhwc_split_out == nullptr || ((C & 31) == 0 && dlip_aligned128(nhwc_split_out)));
+  const bool quads = (ldx & 3) == 0 && dlip_aligned16(x);
+  const int tile = quads && C % 128 == 0 ? 128 : quads && C % 64 == 0 ? 64 : 0;
+  wgrad_chwn_launch<0>(tile, x, out, (int)N, H * W, ldx, C, N32, scale, slice_major ? 1 : 0, nhwc_split_out, BnOnLoad{}, dlip_hip_stream(stream));
   return dlip_launch_status();
 }
 
@@ -857,15 +875,9 @@ extern "C" int dlip_wgrad_operand_split_bn_f32(const float* x, float* out, int64
                                                float slope, float* nhwc_split_out, dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && out && nhwc_split_out && mean && invstd && gamma && beta && J > 0 && J < (1ll << 28) && C > 0 && (C & 63) == 0 &&
                  ld_out >= J && (ld_out & 31) == 0);
-  DLIP_CHECK_ARG(((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(nhwc_split_out)) & 127) == 0 &&
-                 (reinterpret_cast<uintptr_t>(x) & 15) == 0 && C / 64 <= 65535);
+  DLIP_CHECK_ARG(dlip_aligned128(out, nhwc_split_out) && dlip_aligned16(x) && C / 64 <= 65535);
   const BnOnLoad bn = {mean, invstd, gamma, beta, slope_vec, slope};
-  if (C % 128 == 0)
-    hipLaunchKernelGGL((wgrad_operand_wide_kernel<128, true>), dim3((unsigned)(ld_out / 32), (unsigned)(C / 128)), dim3(256), 0, dlip_hip_stream(stream), x, out,
-                       1, 1, C, C, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, (int)J, (long long)ld_out, nullptr, dlip_range_for(DLIP_ST_PACK), nhwc_split_out, bn);
-  else
-    hipLaunchKernelGGL((wgrad_operand_wide_kernel<64, true>), dim3((unsigned)(ld_out / 32), (unsigned)(C / 64)), dim3(256), 0, dlip_hip_stream(stream), x, out,
-                       1, 1, C, C, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, (int)J, (long long)ld_out, nullptr, dlip_range_for(DLIP_ST_PACK), nhwc_split_out, bn);
+  wgrad_operand_split_launch<1>(C % 128 == 0 ? 128 : 64, x, out, J, ld_out, C, nullptr, nhwc_split_out, bn, 0, dlip_hip_stream(stream));
   return dlip_launch_status();
 }
 
@@ -874,15 +886,9 @@ extern "C" int dlip_wgrad_chwn_bn_f32(const float* x, float* out, int64_t N, int
                                       const float* slope_vec, float slope, float* nhwc_split_out, dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && out && nhwc_split_out && mean && invstd && gamma && beta && N > 0 && H > 0 && W > 0 && C > 0 && (C & 63) == 0 &&
                  N32 >= N && (N32 & 31) == 0);
-  DLIP_CHECK_ARG(((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(nhwc_split_out)) & 127) == 0 &&
-                 (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (long long)H * W <= 65535 && C / 64 <= 65535 && N < (1ll << 31));
+  DLIP_CHECK_ARG(dlip_aligned128(out, nhwc_split_out) && dlip_aligned16(x) && (long long)H * W <= 65535 && C / 64 <= 65535 && N < (1ll << 31));
   const BnOnLoad bn = {mean, invstd, gamma, beta, slope_vec, slope};
-  if (C % 128 == 0)
-    hipLaunchKernelGGL((wgrad_chwn_wide_kernel<128, true>), dim3((unsigned)(N32 / 32), (unsigned)(C / 128), (unsigned)(H * W)), dim3(256), 0,
-                       dlip_hip_stream(stream), x, out, (int)N, H * W, C, C, N32, nullptr, dlip_range_for(DLIP_ST_PACK), 1, nhwc_split_out, bn);
-  else
-    hipLaunchKernelGGL((wgrad_chwn_wide_kernel<64, true>), dim3((unsigned)(N32 / 32), (unsigned)(C / 64), (unsigned)(H * W)), dim3(256), 0,
-                       dlip_hip_stream(stream), x, out, (int)N, H * W, C, C, N32, nullptr, dlip_range_for(DLIP_ST_PACK), 1, nhwc_split_out, bn);
+  wgrad_chwn_launch<1>(C % 128 == 0 ? 128 : 64, x, out, (int)N, H * W, C, C, N32, nullptr, 1, nhwc_split_out, bn, dlip_hip_stream(stream));
   return dlip_launch_status();
 }
 
@@ -901,21 +907,14 @@ extern "C" int dlip_wgrad_operand_split_bnbwd_f32(const float* dy, const float* 
                  (C & 3) == 0 && ld_out >= J && (ld_out & 31) == 0);
   DLIP_CHECK_ARG((dy != nullptr || ms_coef != nullptr) && (ms_coef == nullptr || (ms_T > 1 && !act_first && J % ms_T == 0)));
   DLIP_CHECK_ARG(ld_nhwc == 0 ? (C & 31) == 0 || nhwc_split_out == nullptr : (ld_nhwc >= C && (ld_nhwc & 31) == 0));
-  DLIP_CHECK_ARG(((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(nhwc_split_out)) & 127) == 0 &&
-                 ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(ms_coef)) & 15) == 0 &&
-                 (C + 63) / 64 <= 65535);
+  DLIP_CHECK_ARG(dlip_aligned128(out, nhwc_split_out) && dlip_aligned16(dy, z, ms_coef) && (C + 63) / 64 <= 65535);
   BnOnLoad bn = {mean, invstd, gamma, beta, nullptr, slope};
   bn.z = z; bn.dgamma = dgamma; bn.dbeta = dbeta; bn.invM = 1.f / (float)M; bn.act_first = act_first;
   bn.ms_coef = ms_coef; bn.ms_T = ms_T > 0 ? ms_T : 1; bn.C = C;
   const float* src = dy ? dy : z;      // (never read when the gradient is formed on load)
-  if (C % 128 == 0 || C > 512)      // (a ragged last block of 128 wastes less than the 64-wide tile costs: 461 -> us on the E-TDNN's 1 500 channels)
-    hipLaunchKernelGGL((wgrad_operand_wide_kernel<128, 2>), dim3((unsigned)(ld_out / 32), (unsigned)((C + 127) / 128)), dim3(256), 0, dlip_hip_stream(stream), src, out,
-                       1, 1, C, C, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, (int)J, (long long)ld_out, lift, dlip_range_for(DLIP_ST_PACK), nhwc_split_out, bn,
-                       ld_nhwc);
-  else
-    hipLaunchKernelGGL((wgrad_operand_wide_kernel<64, 2>), dim3((unsigned)(ld_out / 32), (unsigned)((C + 63) / 64)), dim3(256), 0, dlip_hip_stream(stream), src,
-                       out, 1, 1, C, C, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, (int)J, (long long)ld_out, lift, dlip_range_for(DLIP_ST_PACK), nhwc_split_out,
-                       bn, ld_nhwc);
+  // (a ragged last block of 128 wastes less than the 64-wide tile costs: 461 -> us on the E-TDNN's 1 500 channels)
+  const int tile = C % 128 == 0 || C > 512 ? 128 : 64;
+  wgrad_operand_split_launch<2>(tile, src, out, J, ld_out, C, lift, nhwc_split_out, bn, ld_nhwc, dlip_hip_stream(stream));
   return dlip_launch_status();
 }
 
@@ -925,24 +924,18 @@ extern "C" int dlip_wgrad_chwn_bnbwd_f32(const float* dy, const float* z, float*
                                          float* nhwc_split_out, dlip_stream_t stream) {
   DLIP_CHECK_ARG(dy && z && out && mean && invstd && gamma && beta && dgamma && dbeta && lift && N > 0 && H > 0 && W > 0 && M > 0 && C > 0 &&
                  (C & 63) == 0 && N32 >= N && (N32 & 31) == 0);
-  DLIP_CHECK_ARG(((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(nhwc_split_out)) & 127) == 0 &&
-                 ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(z)) & 15) == 0 && (long long)H * W <= 65535 && C / 64 <= 65535 &&
+  DLIP_CHECK_ARG(dlip_aligned128(out, nhwc_split_out) && dlip_aligned16(dy, z) && (long long)H * W <= 65535 && C / 64 <= 65535 &&
                  N < (1ll << 31));
   BnOnLoad bn = {mean, invstd, gamma, beta, nullptr, slope};
   bn.z = z; bn.dgamma = dgamma; bn.dbeta = dbeta; bn.invM = 1.f / (float)M; bn.act_first = act_first; bn.C = C;
-  if (C % 128 == 0)
-    hipLaunchKernelGGL((wgrad_chwn_wide_kernel<128, 2>), dim3((unsigned)(N32 / 32), (unsigned)(C / 128), (unsigned)(H * W)), dim3(256), 0,
-                       dlip_hip_stream(stream), dy, out, (int)N, H * W, C, C, N32, lift, dlip_range_for(DLIP_ST_PACK), 1, nhwc_split_out, bn);
-  else
-    hipLaunchKernelGGL((wgrad_chwn_wide_kernel<64, 2>), dim3((unsigned)(N32 / 32), (unsigned)(C / 64), (unsigned)(H * W)), dim3(256), 0,
-                       dlip_hip_stream(stream), dy, out, (int)N, H * W, C, C, N32, lift, dlip_range_for(DLIP_ST_PACK), 1, nhwc_split_out, bn);
+  wgrad_chwn_launch<2>(C % 128 == 0 ? 128 : 64, dy, out, (int)N, H * W, C, C, N32, lift, 1, nhwc_split_out, bn, dlip_hip_stream(stream));
   return dlip_launch_status();
 }
 
 extern "C" int dlip_stem_wgrad_chwn_f32(const float* x, float* out, int32_t B, int32_t T, int32_t H, int32_t W, int32_t N32,
                                         int32_t slice_major, dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && out && B > 0 && T > 0 && H > 0 && W > 0 && N32 >= (long long)B * T && (N32 & 31) == 0 &&
-                 (reinterpret_cast<uintptr_t>(out) & 127) == 0 && (H * W + 31) / 32 <= 65535);
+                 dlip_aligned128(out) && (H * W + 31) / 32 <= 65535);
   // the clip as [frames][1 pixel][H W "channels"]: out[dt][p][n] = x[n + dt - 2][p] inside the clip of frame n
   for (int dt = 0; dt < 5; ++dt)
     hipLaunchKernelGGL(wgrad_chwn_kernel, dim3((unsigned)(N32 / 32), (unsigned)((H * W + 31) / 32), 1u), dim3(256), 0, dlip_hip_stream(stream), x,
@@ -968,7 +961,7 @@ extern "C" int dlip_upsample_zero_f32(const float* dz, float* out, int64_t N, in
 extern "C" int dlip_upsample_zero_split_f32(const float* dz, float* out_split, const float* scale, int64_t N, int32_t Ho, int32_t Wo,
                                             int32_t Hu, int32_t Wu, int32_t C, int32_t stride_h, int32_t stride_w, dlip_stream_t stream) {
   DLIP_CHECK_ARG(dz && out_split && scale && N > 0 && Ho > 0 && Wo > 0 && Hu > 0 && Wu > 0 && C > 0 && (C & 31) == 0 && stride_h > 0 && stride_w > 0);
-  DLIP_CHECK_ARG(((reinterpret_cast<uintptr_t>(dz) & 15) | (reinterpret_cast<uintptr_t>(out_split) & 127)) == 0);
+  DLIP_CHECK_ARG(dlip_aligned16(dz) && dlip_aligned128(out_split));
   const long long rows = (long long)N * Hu;
   DLIP_CHECK_ARG(rows < (1ll << 31) && (long long)Wu * (C / 4) < (1ll << 30));
   const int rowlen = Wu * (C / 4);
@@ -1055,8 +1048,7 @@ extern "C" int dlip_stem_im2col_f32(const float* x, float* col, int32_t B, int32
 
 extern "C" int dlip_stem_wgrad_operand_f32(const float* x, float* out, int64_t ld_out, int32_t B, int32_t T, int32_t H, int32_t W,
                                            dlip_stream_t stream) {
-  DLIP_CHECK_ARG(x && out && B > 0 && T > 0 && H > 1 && W > 1 && (H & 1) == 0 && (W & 1) == 0 &&
-                 (reinterpret_cast<uintptr_t>(out) & 127) == 0);
+  DLIP_CHECK_ARG(x && out && B > 0 && T > 0 && H > 1 && W > 1 && (H & 1) == 0 && (W & 1) == 0 && dlip_aligned128(out));
   const long long J = (long long)B * T * (H / 2) * (W / 2);
   DLIP_CHECK_ARG(ld_out >= J && (ld_out & 31) == 0 && (long long)B * T * H * W < (1ll << 31) && ld_out / 32 < (1ll << 31));
   hipLaunchKernelGGL(stem_wgrad_operand_kernel, dim3((unsigned)(ld_out / 32)), dim3(256), 0, dlip_hip_stream(stream), x, out, T, H, W, H / 2, W / 2, J,
@@ -1086,7 +1078,7 @@ extern "C" int dlip_chomp_concat_f32(const float* const* branches, const int32_t
   for (int j = 0; j < 4; ++j) {
     if (j < n_branches) {
       DLIP_CHECK_ARG(branches[j] && widths[j] > 0 && (widths[j] & 3) == 0 && lengths[j] >= T && ((lengths[j] - T) & 1) == 0 &&
-                     (reinterpret_cast<uintptr_t>(branches[j]) & 15) == 0);
+                     dlip_aligned16(branches[j]));
       cc.z[j] = const_cast<float*>(branches[j]); cc.L[j] = lengths[j]; cc.C4[j] = widths[j] / 4; cc.off4[j] = off / 4;
       off += widths[j];
       cc.start[j + 1] = cc.start[j] + (long long)B * (backward ? lengths[j] : T) * cc.C4[j];
@@ -1095,7 +1087,7 @@ extern "C" int dlip_chomp_concat_f32(const float* const* branches, const int32_t
     }
   }
   cc.Ct4 = off / 4;
-  DLIP_CHECK_ARG((reinterpret_cast<uintptr_t>(cat) & 15) == 0);
+  DLIP_CHECK_ARG(dlip_aligned16(cat));
   if (backward) hipLaunchKernelGGL(chomp_concat_kernel<true>, dim3(dlip_grid1d(cc.start[n_branches], kGridCap)), dim3(256), 0, dlip_hip_stream(stream), cc, cat);
   else hipLaunchKernelGGL(chomp_concat_kernel<false>, dim3(dlip_grid1d(cc.start[n_branches], kGridCap)), dim3(256), 0, dlip_hip_stream(stream), cc, cat);
   return dlip_launch_status();

@@ -104,7 +104,8 @@ def test_tdnn_block_train_fn_gradients(B, T, C, K, S, dil, act_first):
         assert float(bg.grad.abs().max()) < 1e-4 * float(dy.abs().sum() / K) + 1e-5
 
 
-@pytest.mark.parametrize("B,T,C,K1,K2,S2,dil2", [(9, 60, 64, 128, 64, 1, 1), (7, 70, 64, 512, 128, 3, 2), (5, 44, 32, 64, 96, 3, 1), (6, 50, 64, 100, 64, 1, 1)])
+@pytest.mark.parametrize("B,T,C,K1,K2,S2,dil2", [(9, 60, 64, 128, 64, 1, 1), (7, 70, 64, 512, 128, 3, 2), (5, 44, 32, 64, 96, 3, 1), (6, 50, 64, 100, 64, 1, 1),
+                                                 (6, 50, 64, 64, 64, 1, 1)])      # (k = 1 behind 64 channels: the producer's 64-channel tile)
 def test_tdnn_blocks_with_the_activation_applied_on_load(B, T, C, K1, K2, S2, dil2):
     """Round 5: a TDNN block's activated output is not stored when the next block can take it on load -- the next block's operand
     producers read the raw convolution output and apply BatchNorm + LeakyReLU per loaded value (dlip_wgrad_*_bn_f32).  Two blocks in a
@@ -346,7 +347,8 @@ def test_full_size_training_step_vs_fp64_oracle():
 @pytest.mark.parametrize("B,T,C,K,S,dil,act_first", [(40, 120, 64, 128, 1, 1, False), (40, 120, 64, 128, 3, 2, False), (24, 200, 128, 64, 5, 1, False),
                                                      (40, 120, 64, 128, 1, 1, True), (36, 130, 64, 192, 3, 1, False),
                                                      # (ABI 49) a k = 1 layer whose width is no multiple of 64 / of 32: the ragged last channel block
-                                                     (40, 120, 64, 100, 1, 1, False), (20, 250, 128, 1500, 1, 1, False)])
+                                                     (40, 120, 64, 100, 1, 1, False), (20, 250, 128, 1500, 1, 1, False),
+                                                     (35, 118, 64, 64, 1, 1, False)])       # (the k = 1 producer's 64-channel tile, not ragged)
 def test_tdnn_block_backward_with_the_batchnorm_gradient_formed_on_load(B, T, C, K, S, dil, act_first, monkeypatch):
     """ABI 47: conv -> BatchNorm -> LeakyReLU under backward() at more than 4 096 rows -- the BatchNorm's input gradient dz is formed per loaded
     value by the operand producers of the convolution in front (dlip_wgrad_*_bnbwd_f32) behind a sums pass that also bounds its lift

@@ -149,13 +149,14 @@ def test_fused_batchnorm_prelu_vs_torch_autograd(M, C):
     assert rel_err(rm.cpu().numpy(), bn.running_mean.numpy()) < 1e-5 and rel_err(rv.cpu().numpy(), bn.running_var.numpy()) < 1e-5
 
 
-@pytest.mark.parametrize("M,C", [(70, 768), (1300, 256), (4096, 12), (5000, 64), (300000, 8)])
+@pytest.mark.parametrize("M,C", [(70, 768), (1300, 256), (4096, 12), (5000, 64), (300000, 8), (70, 12)])
 def test_batchnorm_launch_sequences_agree(M, C):
     """ABI 44: the finalize steps of the train-mode BatchNorm / column-sum entry points run in the LAST workgroup of the pass before
     them (ticket words of the stream's workspace) and tensors of <= 4096 rows take one launch per direction; dlip_debug_set(8, 0)
     restores ABI 43's separate launches.  Both sequences: same results (the fp64 column sums are associated differently: 2e-6), the
     same power-of-two lift of dx, num_batches_tracked incremented once per forward, and repeatable bits.  300 000 rows: parts longer
-    than 512 rows (at most 512 parts per launch)."""
+    than 512 rows (at most 512 parts per launch).  70 x 12: too few quads for a grid that is a multiple of the C / 4 = 3 channel quads,
+    so the separate launches' apply passes take their per-element channel index (the FIXED = false kernels)."""
     from deeplip_amd import _lib, autograd as ag, autograd_video as av
     x = (rnd(M, C, seed=31) * 1.7 + 0.3).to(DEV)
     ga = (1.0 + 0.3 * rnd(C, seed=32)).to(DEV)
@@ -205,12 +206,13 @@ def test_batchnorm_launch_sequences_agree(M, C):
     assert torch.equal(a["lift"][0], b["lift"][0])
 
 
-@pytest.mark.parametrize("N,H,W,C", [(6, 44, 44, 64), (3, 9, 11, 8), (2, 5, 7, 64), (700, 8, 8, 12)])
+@pytest.mark.parametrize("N,H,W,C", [(6, 44, 44, 64), (3, 9, 11, 8), (2, 5, 7, 64), (700, 8, 8, 12), (1, 5, 7, 12)])
 def test_stem_batchnorm_prelu_maxpool_as_one_function(N, H, W, C):
     """Round 5: maxpool(prelu(bn_train(x))) of the stem (model.py:83-85) without the full-resolution tensors between the three --
     (1) against torch autograd (fp64) of BatchNorm + PReLU + max_pool2d: output, dx, dgamma, dbeta, dslope, running statistics;
     (2) against the three-Function path (BNPReLUFn + MaxPoolFn): the SAME pooled output bit for bit (hence the same argmax codes)
-    and gradients to 2e-6; (3) the lift of dx; repeatable bits."""
+    and gradients to 2e-6; (3) the lift of dx; repeatable bits.  (1 x 5 x 7 x 12: the backward's apply pass without a fixed channel per
+    thread, as in test_batchnorm_launch_sequences_agree.)"""
     from deeplip_amd import autograd_video as av
     x = (rnd(N, H, W, C, seed=41) * 1.7 + 0.3)
     ga = (1.0 + 0.3 * rnd(C, seed=42)); be = 0.2 * rnd(C, seed=43)
@@ -268,11 +270,12 @@ def test_stem_batchnorm_prelu_maxpool_as_one_function(N, H, W, C):
     assert e * inv == 1.0 and 512.0 <= amax * e <= 1024.0 and bool((lift[2:8] == inv).all())
 
 
-@pytest.mark.parametrize("M,C", [(2 * 22 * 22, 64), (9000, 128), (70, 512), (300000, 8)])
+@pytest.mark.parametrize("M,C", [(2 * 22 * 22, 64), (9000, 128), (70, 512), (300000, 8), (70, 12)])
 def test_block_tail_batchnorm_add_prelu_as_one_function(M, C):
     """Round 5: prelu(bn2(x) + residual) -- the end of a BasicBlock (resnet.py:62-69) under model.train() -- as one Function:
     (1) against torch autograd (fp64); (2) the SAME output bits as BNRowsActFn + AddPReLUFn and gradients to 2e-6; (3) the forked
-    output: two gradients arriving separately == their sum arriving once; (4) repeatable bits, num_batches_tracked, the lift."""
+    output: two gradients arriving separately == their sum arriving once; (4) repeatable bits, num_batches_tracked, the lift.
+    (70 x 12: both apply passes without a fixed channel per thread, as in test_batchnorm_launch_sequences_agree.)"""
     from deeplip_amd import autograd as ag, autograd_video as av
     x = (rnd(M, C, seed=51) * 1.7 + 0.3)
     res = rnd(M, C, seed=52)
