@@ -266,7 +266,7 @@ def ensure_conv_workspace() -> None:
 
 
 # ---- diagnostic overrides (tests, tools): dlip_debug_set ----
-DBG_CONV_TILE, DBG_DMA_TILE, DBG_DMA_ENABLE, DBG_STREAMK, DBG_WIN, DBG_NINNER, DBG_ROWS, DBG_ROWS2D, DBG_BN_FUSED, DBG_ROWS_TAIL = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
+DBG_CONV_TILE, DBG_DMA_TILE, DBG_DMA_ENABLE, DBG_STREAMK, DBG_WIN, DBG_NINNER, DBG_ROWS, DBG_ROWS2D, DBG_BN_FUSED, DBG_ROWS_TAIL, DBG_GROUPED = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 
 
 DEBUG = {}          # what this process set through debug_set (key -> value; -1 / absent = the built-in choice)

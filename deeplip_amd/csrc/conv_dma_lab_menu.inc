@@ -2,8 +2,8 @@
 #ifdef DLIP_LAB
 // Lab build only (DLIP_STAMP_PRINT set): launch with the s_memtime stamps buffer, wait, print the median cycles
 // between the stamps of each workgroup's first segment (tools/probes/stamps.sh).
-template <typename K>
-int dlip_lab_stamped_launch(K kern, unsigned G, int threads, size_t lds, hipStream_t st, const ConvArgs& b, StreamK sk, int BM, int BN) {
+template <typename K, typename SK>
+int dlip_lab_stamped_launch(K kern, unsigned G, int threads, size_t lds, hipStream_t st, const ConvArgs& b, SK sk, int BM, int BN) {
   static unsigned long long* dbuf = nullptr;
   static size_t cap = 0;
   if (cap < (size_t)G * 30) { if (dbuf) (void)hipFree(dbuf); (void)hipMalloc(reinterpret_cast<void**>(&dbuf), (size_t)G * 30 * 8); cap = (size_t)G * 30; }

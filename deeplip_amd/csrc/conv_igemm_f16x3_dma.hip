@@ -72,6 +72,33 @@ struct StreamK {
   DLIP_LAB_STREAMK_FIELDS   // (conv_dma_hooks.h: nothing in the product build)
 };
 
+// BORDER GROUPS (the GROUPED twin of the 256 x 128 instances).  A pad > 0 convolution is a union of at most 3 x 3 PADDING-FREE
+// convolutions: per output row index ho the filter rows that stay inside the image are a contiguous range [r_lo, r_hi), the same
+// per wo; consecutive indices with the same range form a class (first rows, interior, last rows), and every (row class x column
+// class) pair is a group: an output sub-rectangle all of whose rows use exactly the sub-filter [r_lo, r_hi) x [s_lo, s_hi), no tap
+// out of range.  On small maps the taps that fall into the padding are a large share of the slices (3 x 3 map, stride 1: 32 of 81;
+// 6 x 6: 68 of 324) and each went through the ring and all three MFMAs as a row of zeros.  ONE launch runs all groups: per column
+// block the groups' (row tile, slice) spaces are concatenated, and the balanced split cuts that compacted space.  Within a tile
+// nothing changes: the per-row tap mask is all-valid, and walk, ring, ping-pong halves and MFMA blocks are the ungrouped kernel's.
+// Tile order of the twin: column block OUTER, then group, then the group's row tiles -- the only order it implements (launch_one
+// keeps a launch whose order is FORCED inner / paired, dlip_debug_set(5, 1 | 2), on the ungrouped kernel).
+// The table travels by value in the kernel arguments (no device table, no copy: legal inside a stream capture).
+constexpr int kMaxGroups = 9;
+struct ConvGroup {
+  int it0, tile0;        // first slice / first tile of the group in ONE column block's enumeration (unused entries: INT_MAX)
+  int nk, ntaps, S;      // slices of a tile (ntaps * cchunks + the second source's nk2); taps and width of the sub-filter
+  int M, HoWo, Wo;       // rows = N * HoWo; positions and width of the output sub-rectangle
+  int ho0, wo0;          // its origin in the output grid
+  int x0;                // pixels: window origin of the sub-rectangle's first position + the sub-filter's origin, (..) * W + (..)
+  int w0;                // bytes: the sub-filter's first tap within a packed filter row, (r_lo * S + s_lo) * Cw * 4
+  FastDiv div_howo, div_wo;
+};
+struct ConvGroups {
+  int n, slices, tiles;  // groups; slices and tiles of one column block (sums over the groups)
+  int useful;            // sum over the groups of taps x positions (of R S Ho Wo): what is left of the reduction
+  ConvGroup g[kMaxGroups];
+};
+
 // EPI: what the epilogue does with act(acc / wscale + bias + residual) * post_scale + post_shift
 //   0  fp32 rows of y;  1  split-format rows of y (reports |v| >= 65520 to the range-status word);
 //   2  no y: per tile and row-group segment, the column sums of v and v^2 in fp64 (a.pool)
@@ -82,9 +109,23 @@ struct StreamK {
 // lost -- a static priority for the second half of the waves, that half issuing half a slice late, the halves taking turns as a
 // slice's issuer, the pieces spread one by one behind MFMA quarter-groups -- are in DESIGN.md section 4 with their numbers and in
 // the history of this file, no longer in its text.
-template <int BM, int BN, int WAVES_M, int WAVES_N, int EPI, int NSTAGE, int OCC, bool DUAL, int VAR = 0>
-__global__ __launch_bounds__(64 * WAVES_M* WAVES_N, OCC) void conv_igemm_f16x3_dma_kernel(const ConvArgs a, const StreamK sk) {
+struct StreamKG : StreamK {
+  ConvGroups grp;
+};
+__device__ __forceinline__ const ConvGroup& sk_group(const StreamKG& sk, int i) { return sk.grp.g[i]; }
+__device__ __forceinline__ int sk_group_slices(const StreamKG& sk) { return sk.grp.slices; }
+__device__ __forceinline__ int sk_group_tiles(const StreamKG& sk) { return sk.grp.tiles; }
+// (the ungrouped instances never read these: one dummy entry keeps their text free of the distinction)
+__device__ __forceinline__ ConvGroup sk_group(const StreamK&, int) { return ConvGroup{}; }
+__device__ __forceinline__ int sk_group_slices(const StreamK&) { return 0; }
+__device__ __forceinline__ int sk_group_tiles(const StreamK&) { return 0; }
+template <bool GROUPED> struct StreamKOf { typedef StreamK type; };
+template <> struct StreamKOf<true> { typedef StreamKG type; };
+
+template <int BM, int BN, int WAVES_M, int WAVES_N, int EPI, int NSTAGE, int OCC, bool DUAL, int VAR = 0, bool GROUPED = false>
+__global__ __launch_bounds__(64 * WAVES_M* WAVES_N, OCC) void conv_igemm_f16x3_dma_kernel(const ConvArgs a, const typename StreamKOf<GROUPED>::type sk) {
   constexpr bool OSPLIT = EPI == 1;
+  static_assert(!GROUPED || (BM == 256 && BN == 128 && NSTAGE == 3 && VAR == 0 && EPI != 2), "border groups: the 256 x 128 product tile, fp32 / split rows");
   constexpr int NW = WAVES_M * WAVES_N, NT = 64 * NW;
   constexpr int RPP = NT / 8;   // rows one pass of the workgroup covers (8 lanes x 16 B per row)
   static_assert(BM % RPP == 0 && BN % RPP == 0, "tile rows must be whole passes");
@@ -154,8 +195,22 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N, OCC) void conv_igemm_f16x3_d
   // gv / Gv / itv = workgroup index, grid and slice space of ONE lane (== g, sk.G, sk.iters when P == 1).  They are formed where
   // they are needed -- here, at a segment's tile decode and in the (rare) hand-off -- from an opaque copy of g, so that none of them
   // lives across the main loop: carried through it (the first version) they cost every 256 x 128 launch 4 - 10 % in scalar spills.
-  long long it_begin, it_end;
-  {
+  long long it_begin = 0, it_end = 0;
+  bool ranged = true;
+  if constexpr (GROUPED) {
+    // a PLAIN grouped launch (no workspace: one workgroup per tile): the tiles differ in length, so workgroup g takes tile g of the
+    // launch-wide numbering (column block, group, row tile) instead of an equal share of the slices
+    if (sk.counters == nullptr) {
+      const int tn = g / sk.grp.tiles, tr = g - tn * sk.grp.tiles;
+      int gi = 0;
+#pragma unroll
+      for (int i = 1; i < kMaxGroups; ++i) gi += tr >= sk.grp.g[i].tile0 ? 1 : 0;
+      it_begin = (long long)tn * sk.grp.slices + sk.grp.g[gi].it0 + (tr - sk.grp.g[gi].tile0) * sk.grp.g[gi].nk;
+      it_end = it_begin + sk.grp.g[gi].nk;
+      ranged = false;
+    }
+  }
+  if (ranged) {
     const int P = a.n_inner == 2 ? a.tiles_n : 1;
     const int gv = P > 1 ? g / P : g, Gv = P > 1 ? sk.G / P : sk.G;
     const long long itv = P > 1 ? sk.iters / P : sk.iters;
@@ -167,15 +222,35 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N, OCC) void conv_igemm_f16x3_d
   dlip_span_enter(sk.span, g);
   DLIP_LAB_WG_STAMP(8, true);
   for (long long it = it_begin; it < it_end;) {
-    const int tile = (int)(it / a.nk);
-    const int k0 = (int)(it - (long long)tile * a.nk);
-    const int kn = (int)((it_end - it) < (long long)(a.nk - k0) ? (it_end - it) : (long long)(a.nk - k0));
+    // (GROUPED) the segment's group: at most 8 compares on the groups' first slices, then the division by that group's nk.  Of what
+    // the entry holds only the sub-filter's width and tap count stay live in the main loop (the walk needs them); everything the
+    // hand-off and the epilogue use is read again behind the loop through an opaque copy of the group's index (cf. the paired lanes).
+    int grp_i = 0, seg_nk = a.nk, seg_tile, seg_k0;
+    if constexpr (GROUPED) {
+      const int tn = (int)(it / sk.grp.slices);
+      const int rem = (int)(it - (long long)tn * sk.grp.slices);
+#pragma unroll
+      for (int i = 1; i < kMaxGroups; ++i) grp_i += rem >= sk.grp.g[i].it0 ? 1 : 0;
+      seg_nk = sk.grp.g[grp_i].nk;
+      const int loc = rem - sk.grp.g[grp_i].it0;
+      seg_tile = loc / seg_nk;          // row tile within the group
+      seg_k0 = loc - seg_tile * seg_nk;
+    } else {
+      seg_tile = (int)(it / a.nk);
+      seg_k0 = (int)(it - (long long)seg_tile * a.nk);
+    }
+    const int tile = seg_tile, k0 = seg_k0;
+    const int kn = (int)((it_end - it) < (long long)(seg_nk - k0) ? (it_end - it) : (long long)(seg_nk - k0));
     // Tile order (chosen per launch, launch_one): output-channel block OUTER -- a workgroup's range, and (through the
     // XCD remap of g) an XCD's eighth of the launch, stays on one 128-channel weight block while the activation rows
     // stream through once per block -- or INNER (a.n_inner) when the whole filter bank fits the XCD's L2.
     const int tiles_m = (a.M + BM - 1) / BM;
     int tile_n = tile / tiles_m;
     int tile_m = tile - tile_n * tiles_m;
+    if constexpr (GROUPED) {
+      tile_m = tile;
+      tile_n = (int)(it / sk.grp.slices);
+    } else
     if (a.n_inner == 2) {   // paired lanes: `tile` counts the row tiles of this workgroup's column block g % P
       int g_o = g;
       asm volatile("" : "+s"(g_o));   // (opaque: the division below is redone per segment instead of living across the loop)
@@ -205,6 +280,23 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N, OCC) void conv_igemm_f16x3_d
     {
       int hi0[AQ], wi0[AQ];
       uint32_t colbits[AQ];
+      if constexpr (GROUPED) {
+        // row m of the group = (n, ho', wo') of its output sub-rectangle; every tap of the sub-filter is inside the image
+        const ConvGroup& gr = sk.grp.g[grp_i];
+#pragma unroll
+        for (int j = 0; j < AQ; ++j) {
+          const int m = tile_m * BM + row_of(j);
+          const int mc = m < gr.M ? m : gr.M - 1;
+          const int n = dlip_div(mc, gr.div_howo);
+          const int rem = mc - n * gr.HoWo;
+          const int ho = dlip_div(rem, gr.div_wo);
+          const int wo = rem - ho * gr.Wo;
+          a_off[j] = (((n * a.H + ho * a.sh) * a.W + wo * a.sw + gr.x0) * a.ldx + csrc) * 4;
+          if constexpr (DUAL)
+            a2_off[j] = m < gr.M ? (uint32_t)((((n * a.H2 + (gr.ho0 + ho) * a.s2h) * a.W2 + (gr.wo0 + wo) * a.s2w) * a.ldx2 + csrc) * 4) : DLIP_OOB_OFFSET;
+          a_mask[j] = m < gr.M ? 0u : ~0u;
+        }
+      } else {
 #pragma unroll
       for (int j = 0; j < AQ; ++j) {
         const int m = tile_m * BM + row_of(j);
@@ -238,6 +330,7 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N, OCC) void conv_igemm_f16x3_d
         for (int j = 0; j < AQ; ++j)
           a_mask[j] = tile_m * BM + row_of(j) >= a.M ? ~0u : ~a_mask[j];
       }
+      }
     }
     // (a weight row past K carries the out-of-range offset itself: 2^31 plus any tap offset stays out of range -- one add per piece)
     uint32_t b_off[BQ];
@@ -245,35 +338,48 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N, OCC) void conv_igemm_f16x3_d
     for (int j = 0; j < BQ; ++j) {
       const int n = tile_n * BN + rbase + RPP * j;
       b_off[j] = n < a.K ? (uint32_t)((n * a.rsc + csrc) * 4) : DLIP_OOB_OFFSET;
+      if constexpr (GROUPED) b_off[j] += (uint32_t)sk.grp.g[grp_i].w0;   // the sub-filter's first tap (weights stay as packed)
     }
 
     // Reduction walk: 32-channel slice OUTER, filter tap INNER (conv_igemm_f16x3.hip), entered at slice k0.
     // DUAL: c0 runs on past the a.Cw channels of the first source -- slice nk1 + i is channels 32 i .. of x2,
     // whose weights sit behind the R S Cw tap weights of each output channel's row.
-    int c0 = (k0 / ntaps) * BK, tap = k0 % ntaps;
-    if constexpr (DUAL) {
-      if (k0 >= nk1) { c0 = a.Cw + (k0 - nk1) * BK; tap = 0; }
+    // (GROUPED) the walk runs over the group's sub-filter: tap (r', s') of it is tap (r_lo + r') S + (s_lo + s') of the packed row, so
+    // the weight offset follows the FULL filter's row pitch (w_row) behind the group's first tap (folded into b_off)
+    int seg_nt = ntaps, seg_S = a.S, seg_nk1 = nk1, w_dr = 0, w_sub0 = 0;
+    if constexpr (GROUPED) {
+      seg_nt = sk.grp.g[grp_i].ntaps;
+      seg_S = sk.grp.g[grp_i].S;
+      seg_nk1 = seg_nk - (DUAL ? a.nk2 : 0);
+      w_dr = a.S * a.Cw * 4;
+      if constexpr (DUAL) w_sub0 = sk.grp.g[grp_i].w0;
     }
-    int s_pos = tap % a.S, x_row = (tap / a.S) * x_dr;
-    int tap_dh = (tap / a.S) * a.dh, tap_dw = s_pos * a.dw;   // (BIGTAPS) the tap's row / column offset in pixels
-    int x_tap = x_row + s_pos * x_ds + c0 * 4, w_tap = (tap * a.Cw + c0) * 4;
-    if constexpr (BIGTAPS) { x_tap = x_row + s_pos * x_ds + (c0 / BK) * a.cs_x; w_tap = tap * a.wt + (c0 / BK) * a.cs_w; }
+    int c0 = (k0 / seg_nt) * BK, tap = k0 % seg_nt;
     if constexpr (DUAL) {
-      if (c0 >= a.Cw) { x_tap = (c0 - a.Cw) * 4; w_tap = (ntaps * a.Cw + c0 - a.Cw) * 4; }
+      if (k0 >= seg_nk1) { c0 = a.Cw + (k0 - seg_nk1) * BK; tap = 0; }
+    }
+    int s_pos = tap % seg_S, x_row = (tap / seg_S) * x_dr;
+    int w_row = GROUPED ? (tap / seg_S) * w_dr : 0;
+    int tap_dh = (tap / a.S) * a.dh, tap_dw = s_pos * a.dw;   // (BIGTAPS) the tap's row / column offset in pixels
+    int x_tap = x_row + s_pos * x_ds + c0 * 4, w_tap = GROUPED ? w_row + (s_pos * a.Cw + c0) * 4 : (tap * a.Cw + c0) * 4;
+    if constexpr (BIGTAPS) { x_tap = x_row + s_pos * x_ds + (c0 / BK) * a.cs_x; w_tap = tap * a.wt + (c0 / BK) * a.cs_w; }
+    if constexpr (DUAL) {   // (the second source's weights sit behind the FULL R S Cw taps)
+      if (c0 >= a.Cw) { x_tap = (c0 - a.Cw) * 4; w_tap = (ntaps * a.Cw + c0 - a.Cw) * 4 - w_sub0; }
     }
     auto advance = [&]() {
       if (DUAL && c0 >= a.Cw) {          // second source: one slice per 32 channels
         c0 += BK;
       } else {
         ++tap;
-        if (++s_pos == a.S) { s_pos = 0; x_row += x_dr; if constexpr (BIGTAPS) tap_dh += a.dh; }
-        if (tap == ntaps) { tap = 0; s_pos = 0; x_row = 0; c0 += BK; if constexpr (BIGTAPS) tap_dh = 0; }
+        if (++s_pos == seg_S) { s_pos = 0; x_row += x_dr; if constexpr (BIGTAPS) tap_dh += a.dh; if constexpr (GROUPED) w_row += w_dr; }
+        if (tap == seg_nt) { tap = 0; s_pos = 0; x_row = 0; c0 += BK; if constexpr (BIGTAPS) tap_dh = 0; if constexpr (GROUPED) w_row = 0; }
         if constexpr (BIGTAPS) tap_dw = s_pos * a.dw;
       }
       x_tap = x_row + s_pos * x_ds + c0 * 4;
-      w_tap = (tap * a.Cw + c0) * 4;
+      if constexpr (GROUPED) w_tap = w_row + (s_pos * a.Cw + c0) * 4;
+      else w_tap = (tap * a.Cw + c0) * 4;
       if constexpr (BIGTAPS) { x_tap = x_row + s_pos * x_ds + (c0 / BK) * a.cs_x; w_tap = tap * a.wt + (c0 / BK) * a.cs_w; }
-      if (DUAL && c0 >= a.Cw) { x_tap = (c0 - a.Cw) * 4; w_tap = (ntaps * a.Cw + c0 - a.Cw) * 4; }
+      if (DUAL && c0 >= a.Cw) { x_tap = (c0 - a.Cw) * 4; w_tap = (ntaps * a.Cw + c0 - a.Cw) * 4 - w_sub0; }
     };
     auto tap_ok = [&](int j) -> bool {
       if constexpr (BIGTAPS) return (unsigned)(a_h0[j] + tap_dh) < (unsigned)a.H && (unsigned)(a_w0[j] + tap_dw) < (unsigned)a.W;
@@ -562,18 +668,29 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N, OCC) void conv_igemm_f16x3_d
     asm volatile("" : "+v"(tid_e));
     const int lane_e = tid_e & 63, lrow_e = tid_e & (FR - 1), half_e = (tid_e & 63) / FR;   // pixel in block; channel quad (k group)
 
+    // (GROUPED) the group's entry, read AGAIN through an opaque copy of its index: what the hand-off and the epilogue need of it
+    // (rows, sub-rectangle, fast-divs, first slice / tile) is formed here instead of living across the main loop
+    int grp_e = grp_i;
+    if constexpr (GROUPED) {
+      grp_e = __builtin_amdgcn_readfirstlane(grp_e);   // (workgroup-uniform by construction; this pins it to an SGPR)
+      asm volatile("" : "+s"(grp_e));
+    }
+    const ConvGroup& ge = sk_group(sk, grp_e);
+    const int tile_nk = GROUPED ? ge.nk : a.nk;
+
     bool finish = true;
-    if (kn != a.nk) {   // split tile (workgroup-uniform branch)
+    if (kn != tile_nk) {   // split tile (workgroup-uniform branch)
       constexpr int SLAB = BM * BN;   // floats
       volatile int* bcast = reinterpret_cast<volatile int*>(smem);
-      const long long t0 = (long long)tile * a.nk;
+      // (GROUPED) the tile's ABSOLUTE first slice and its launch-wide number (the ticket word): column block, group, row tile
+      const long long t0 = GROUPED ? (long long)tile_n * sk_group_slices(sk) + ge.it0 + (long long)tile * ge.nk : (long long)tile * a.nk;
       // (paired lanes) this lane's workgroup index / grid / slice space, and the tile's ticket word = its number in tile_m-major order
-      const int P = a.n_inner == 2 ? a.tiles_n : 1, lane_n = P > 1 ? tile_n : 0;
+      const int P = (!GROUPED && a.n_inner == 2) ? a.tiles_n : 1, lane_n = P > 1 ? tile_n : 0;
       const int gv = P > 1 ? g / P : g, Gv = P > 1 ? sk.G / P : sk.G;
       const long long itv = P > 1 ? sk.iters / P : sk.iters;
-      const int tile_id = P > 1 ? tile * P + lane_n : tile;
+      const int tile_id = GROUPED ? tile_n * sk_group_tiles(sk) + ge.tile0 + tile : P > 1 ? tile * P + lane_n : tile;
       const int gf = (int)(((t0 + 1) * Gv - 1) / itv);                   // owner of the tile's first slice (index within the lane)
-      const int gl = (int)(((t0 + a.nk) * Gv - 1) / itv);                // owner of its last slice
+      const int gl = (int)(((t0 + tile_nk) * Gv - 1) / itv);             // owner of its last slice
       const int others = gl - gf;                                        // parts besides this one
       // (experiment, round 4, off in the product: VERDICT item "slab traffic") parts on one XCD -- neighbours in work order are,
       // except across the 8 XCD boundaries -- share an L2: plain stores (they stop in L2) and sc0 loads (past this CU's L1) would do
@@ -687,6 +804,20 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N, OCC) void conv_igemm_f16x3_d
       char* img = reinterpret_cast<char*>(smem);
       const f32x4* tab = reinterpret_cast<const f32x4*>(smem + RING / 4);
       const bool post = a.pscale != nullptr;
+      // row m of the tile's row space -> its row of y / the residual.  (GROUPED) row m of the group is (n, ho', wo') of its
+      // sub-rectangle: pixel (n, ho0 + ho', wo0 + wo') of the full output grid
+      const int rows_e = GROUPED ? ge.M : a.M;       // rows of the tile's row space (its `m < rows_e` tests)
+      auto out_row = [&](int m) -> int {
+        if constexpr (GROUPED) {
+          const int mc = m < ge.M ? m : ge.M - 1;
+          const int n = dlip_div(mc, ge.div_howo);
+          const int rem = mc - n * ge.HoWo;
+          const int ho = dlip_div(rem, ge.div_wo);
+          return n * a.HoWo + (ge.ho0 + ho) * a.Wo + ge.wo0 + (rem - ho * ge.Wo);
+        } else {
+          return m;
+        }
+      };
       float amax = 0.f;                              // largest |v| this lane converts to fp16 (EPI 1)
       __syncthreads();                               // every wave is done with the ring (and the table is written)
 #pragma unroll
@@ -700,8 +831,8 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N, OCC) void conv_igemm_f16x3_d
             const int pp = lane_e % CPR;
             const int c = (pp & ~15) | ((pp ^ r) & 15);
             const int m = tile_m * BM + band0 + r;
-            const bool ok = m < a.M && (kcol0 + (c >> 3) * 32) < a.K;
-            dma_piece(rrw, ok ? (uint32_t)((m * a.ldr + kcol0) * 4 + c * 16) : DLIP_OOB_OFFSET, lds0 + piece * 1024);
+            const bool ok = m < rows_e && (kcol0 + (c >> 3) * 32) < a.K;
+            dma_piece(rrw, ok ? (uint32_t)((out_row(m) * a.ldr + kcol0) * 4 + c * 16) : DLIP_OOB_OFFSET, lds0 + piece * 1024);
           }
           wait_vmcnt<0>();
           __syncthreads();
@@ -841,7 +972,7 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N, OCC) void conv_igemm_f16x3_d
                 continue;
               }
             }
-            const uint32_t off = (m < a.M && kfirst < a.K) ? (uint32_t)((m * a.ldy + kcol0) * 4 + c * 16) : DLIP_OOB_OFFSET;
+            const uint32_t off = (m < rows_e && kfirst < a.K) ? (uint32_t)((out_row(m) * a.ldy + kcol0) * 4 + c * 16) : DLIP_OOB_OFFSET;
             __builtin_amdgcn_raw_buffer_store_b128(v, yr, (int)off, 0, 0);
           }
         }
@@ -983,12 +1114,108 @@ int kernel_slots(KernelSlots& ks, int dev, K kern, int threads, size_t lds) {
   return ks.slots[dev];
 }
 
-template <int BM, int BN, int WAVES_M, int WAVES_N, int NSTAGE, int OCC, int EPI, bool DUAL, int VAR = 0>
-int launch_one(const ConvArgs& a, hipStream_t st) {
+// Border groups of a launch (kernel comment at ConvGroup).  The classes of one dimension: runs of output indices o whose valid
+// filter taps { t : 0 <= o stride - pad + t dil < In } -- a contiguous range for any stride and dilation -- are the same.
+// Returns the number of classes, or -1 if there are more than three or an index has no valid tap at all.
+struct DimClass { int o0, o1, t_lo, t_hi; };
+int dim_classes(int In, int Out, int T, int stride, int pad, int dil, DimClass* c) {
+  int n = 0;
+  for (int o = 0; o < Out; ++o) {
+    const int base = o * stride - pad;
+    int lo = 0, hi = T;
+    while (lo < T && base + lo * dil < 0) ++lo;
+    while (hi > lo && base + (hi - 1) * dil >= In) --hi;
+    if (hi <= lo) return -1;
+    if (n > 0 && c[n - 1].t_lo == lo && c[n - 1].t_hi == hi) { c[n - 1].o1 = o + 1; continue; }
+    if (n == 3) return -1;
+    c[n++] = DimClass{o, o + 1, lo, hi};
+  }
+  return n;
+}
+
+// The group table of `a` for row tiles of BM rows; false where the construction does not apply: no padding, a weight gradient's
+// layouts, more than three classes in a dimension, a reduction the "few tiles" modes of the split serve (nk >= 256).
+bool conv_groups(const ConvArgs& a, int BM, ConvGroups* out) {
+  if ((a.ph <= 0 && a.pw <= 0) || a.R * a.S > 32 || a.wg_R != 0 || a.nk >= 256 || a.HoWo <= 0 || a.M % a.HoWo != 0) return false;
+  const int Ho = a.HoWo / a.Wo, N = a.M / a.HoWo;
+  DimClass rc[3], cc[3];
+  const int nr = dim_classes(a.H, Ho, a.R, a.sh, a.ph, a.dh, rc), nc = dim_classes(a.W, a.Wo, a.S, a.sw, a.pw, a.dw, cc);
+  if (nr <= 0 || nc <= 0) return false;
+  ConvGroups& t = *out;
+  t.n = 0;
+  t.useful = 0;
+  long long slices = 0, tiles = 0;
+  for (int i = 0; i < nr; ++i)
+    for (int j = 0; j < nc; ++j) {
+      ConvGroup& g = t.g[t.n++];
+      const int gr = rc[i].t_hi - rc[i].t_lo, gs = cc[j].t_hi - cc[j].t_lo;
+      g.S = gs;
+      g.ntaps = gr * gs;
+      g.nk = g.ntaps * a.cchunks + a.nk2;
+      g.Wo = cc[j].o1 - cc[j].o0;
+      g.HoWo = (rc[i].o1 - rc[i].o0) * g.Wo;
+      const long long M = (long long)N * g.HoWo;
+      g.M = (int)M;
+      g.ho0 = rc[i].o0;
+      g.wo0 = cc[j].o0;
+      g.x0 = (g.ho0 * a.sh - a.ph + rc[i].t_lo * a.dh) * a.W + (g.wo0 * a.sw - a.pw + cc[j].t_lo * a.dw);
+      g.w0 = (rc[i].t_lo * a.S + cc[j].t_lo) * a.Cw * 4;
+      g.div_howo = dlip_fastdiv((uint32_t)g.HoWo);
+      g.div_wo = dlip_fastdiv((uint32_t)g.Wo);
+      g.it0 = (int)slices;
+      g.tile0 = (int)tiles;
+      const long long gt = (M + BM - 1) / BM;
+      tiles += gt;
+      slices += gt * g.nk;
+      t.useful += g.ntaps * g.HoWo;
+      if (slices > 0x3FFFFFFFll) return false;
+    }
+  for (int i = t.n; i < kMaxGroups; ++i) {
+    t.g[i] = ConvGroup{};
+    t.g[i].it0 = t.g[i].tile0 = 0x7FFFFFFF;
+    t.g[i].nk = t.g[i].ntaps = t.g[i].S = t.g[i].M = t.g[i].HoWo = t.g[i].Wo = 1;
+  }
+  t.slices = (int)slices;
+  t.tiles = (int)tiles;
+  return true;
+}
+
+// Which launches take the grouped twin by themselves (dlip_debug_set(10, 1 | 0): whenever legal | never): at least this share of the
+// slices in the padding AND a first-source reduction of at least kGroupedMinSlices slices.  Measured per layer at B = 64, grouped
+// against ungrouped alternating in one process (tools/bench_grouped.py, profiles/r7/grouped_layers_ab.txt; medians):
+//   share 39.5 %, 144 slices  (4.0.conv2, 4.1.conv1)   -20 %, -18 %   (42 and 35 us; spread of the ungrouped rounds 18 and 7 us)
+//   share 21 %,    72 slices  (3.0.conv2, 3.1.x, 4.0.conv1)   -12 %, -4.5 %, -5 %   (28, 10, 6 us; spread 5, 7, 18 us)
+//   share 21 %,    36 slices  (3.0.conv1, 11 -> 6)     -3 % and +1 % in two runs (4 us, spread 4 us)   -- out
+//   share 12 % / 6 %, 36 / 18 slices  (2.0.conv2, 2.0.conv1)   +1 %, +2 %   -- out
+// A group costs what a launch's tile costs outside the slice loop (row set-up, prologue, epilogue) once more per row tile and adds
+// partial tiles (layer 4: 72 tiles for 66); over a short reduction that is as much as the slices it saves.  The share alone cannot
+// tell 3.0.conv1 from 4.0.conv1 (both 64/81), the reduction's length does.
+constexpr double kGroupedMinZeroShare = 0.15;
+constexpr int kGroupedMinSlices = 64;
+inline bool grouped_by_rule(const ConvArgs& a, const ConvGroups& gt) {
+  return (double)gt.useful <= (1.0 - kGroupedMinZeroShare) * a.R * a.S * a.HoWo && a.nk - a.nk2 >= kGroupedMinSlices;
+}
+long long g_grouped_launches = 0;   // (dlip_conv_grouped_query: lets a test see which route a launch took)
+
+template <int BM, int BN, int WAVES_M, int WAVES_N, int NSTAGE, int OCC, int EPI, bool DUAL, int VAR = 0, bool GROUPED = false>
+int launch_one(const ConvArgs& a, hipStream_t st, const ConvGroups* groups = nullptr) {
+  if constexpr (!GROUPED && BM == 256 && BN == 128 && NSTAGE == 3 && VAR == 0 && EPI != 2) {
+    // Border groups: the 256 x 128 product tile, padding, <= 32 taps and pixel-major operands (this dispatch branch), no weight-
+    // gradient layout, not the pooled epilogue (its segments are clips; a one-position group has none of BM rows), at most three
+    // classes per dimension (conv_groups), the tile order not forced to one the twin does not implement.
+    const int mode = dlip_dbg_value[DLIP_DBG_GROUPED];
+    if (mode != 0 && dlip_dbg_value[DLIP_DBG_NINNER] <= 0) {
+      ConvGroups gt;
+      if (conv_groups(a, BM, &gt) && (mode > 0 || grouped_by_rule(a, gt)))
+        return launch_one<BM, BN, WAVES_M, WAVES_N, NSTAGE, OCC, EPI, DUAL, VAR, true>(a, st, &gt);
+    }
+  }
   ConvArgs b = a;
   const int tiles_m = (a.M + BM - 1) / BM;
   b.tiles_n = (a.K + BN - 1) / BN;
-  const long long tiles = (long long)tiles_m * b.tiles_n;
+  const long long tiles = GROUPED ? (long long)groups->tiles * b.tiles_n : (long long)tiles_m * b.tiles_n;
+  // (GROUPED: the tiles differ in length; the cost model below takes their mean)
+  const double nk_mean = GROUPED ? (double)groups->slices / groups->tiles : (double)a.nk;
   if (tiles <= 0 || tiles > 0x7FFFFFFFll) return DLIP_EINVAL;
   if (EPI == 2 && a.pool_group < BM) return DLIP_EINVAL;   // a tile may contain at most one row-group boundary
   constexpr bool WIN = (VAR & 128) != 0;   // window mode: two window slots + NSTAGE weight stages (kernel comment)
@@ -997,15 +1224,16 @@ int launch_one(const ConvArgs& a, hipStream_t st) {
   constexpr size_t lds = (WIN ? win_ring : (size_t)NSTAGE * (BM + BN) * ROWB) + 5 * BN * sizeof(float);   // ring + epilogue parameter table
   constexpr int threads = 64 * WAVES_M * WAVES_N;
   static_assert(lds <= 160 * 1024, "LDS ring exceeds a CU");
-  auto kern = conv_igemm_f16x3_dma_kernel<BM, BN, WAVES_M, WAVES_N, EPI, NSTAGE, OCC, DUAL, VAR>;
+  auto kern = conv_igemm_f16x3_dma_kernel<BM, BN, WAVES_M, WAVES_N, EPI, NSTAGE, OCC, DUAL, VAR, GROUPED>;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return DLIP_EINVAL;
   static KernelSlots ks;   // one per instantiation
   const int sl = kernel_slots(ks, dev, kern, threads, lds);
   if (sl <= 0) return DLIP_EINVAL;
 
-  StreamK sk;
-  sk.iters = tiles * a.nk;
+  typename StreamKOf<GROUPED>::type sk;
+  sk.iters = GROUPED ? (long long)groups->slices * b.tiles_n : tiles * a.nk;
+  if constexpr (GROUPED) sk.grp = *groups;
   sk.slabs = nullptr;
   sk.counters = nullptr;
   long long G = tiles;                                  // plain launch: one tile per workgroup
@@ -1013,7 +1241,7 @@ int launch_one(const ConvArgs& a, hipStream_t st) {
   if (balanced && tiles <= kMaxSplitTiles) {
     // Plain: ceil(tiles / slots) rounds of one tile-time.  Balanced: tiles / slots tile-times plus the
     // slab hand-off (one slab written and read per workgroup, all the reads at the very end).
-    const double tile_us = 2.0 * BM * BN * 32.0 * a.nk / (kSlotFlops * (WAVES_M * WAVES_N / 4.0) * 1e-6);   // an 8-wave workgroup owns its CU
+    const double tile_us = 2.0 * BM * BN * 32.0 * nk_mean / (kSlotFlops * (WAVES_M * WAVES_N / 4.0) * 1e-6);   // an 8-wave workgroup owns its CU
     const double plain_us = (double)((tiles + sl - 1) / sl) * tile_us;
     long long Gb = sl;
     // small problems: at least 16 slices per workgroup (every extra part costs the finisher a serial slab read)
@@ -1026,15 +1254,15 @@ int launch_one(const ConvArgs& a, hipStream_t st) {
     const long long max_parts = a.nk >= 16384 ? 4 * kMaxPartsPerTile : a.nk >= 4096 ? 2 * kMaxPartsPerTile : kMaxPartsPerTile;
     // (no such bound where the parts go to the parallel reduce launch below: a 1 x 1 shortcut's weight gradient -- ONE 64 x 128
     // tile of 3 509 slices -- used 64 of the chip's 512 slots)
-    const bool reduce_ok = EPI == 0 && !DUAL && a.res == nullptr && a.nk >= 256 && tiles <= 64 && dlip_dbg_value[DLIP_DBG_STREAMK] != 4;
+    const bool reduce_ok = !GROUPED && EPI == 0 && !DUAL && a.res == nullptr && a.nk >= 256 && tiles <= 64 && dlip_dbg_value[DLIP_DBG_STREAMK] != 4;
     if (Gb > tiles * max_parts && !reduce_ok) Gb = tiles * max_parts;   // (same-box A/B of this rule alone: no change on either training step)
-    const double bal_us = (double)sk.iters / Gb / a.nk * tile_us + kHandoffUs * (BM * BN / 16384.0);
+    const double bal_us = (double)sk.iters / Gb / nk_mean * tile_us + kHandoffUs * (BM * BN / 16384.0);
     // Short reductions on a full chip (nk <= 16 slices, at least one tile per slot: the k = 1 TDNN layers) run
     // plain: a tile's slab hand-off costs as much as a third of such a tile, and the under-filled last round of a
     // plain launch runs faster than the model's whole tile-time (measured: 53.9 vs 57.6 us on tdnn.k1, 113.9 vs
     // 115.3 on tdnn.9; the deep 3x3 / dilated layers gain 12 % from the split and keep it).
     const bool short_full = a.nk <= 16 && tiles >= sl;
-    if ((balanced == 2 || (bal_us < plain_us && !short_full)) && Gb * a.nk != sk.iters) G = Gb;
+    if ((balanced == 2 || (bal_us < plain_us && !short_full)) && (GROUPED ? Gb != tiles : Gb * a.nk != sk.iters)) G = Gb;
   }
   if (G != tiles) {
     Workspace* w = workspace_for(dev, st, (size_t)2 * G * BM * BN);
@@ -1047,7 +1275,7 @@ int launch_one(const ConvArgs& a, hipStream_t st) {
   }
   sk.il_tiles = 0;
   sk.l2_local = dlip_dbg_value[DLIP_DBG_STREAMK] == 3 ? 1 : 0;
-  if (G != tiles && a.nk >= 256 && tiles >= 1 && tiles <= 64 && G / tiles >= 2) {
+  if (!GROUPED && G != tiles && a.nk >= 256 && tiles >= 1 && tiles <= 64 && G / tiles >= 2) {
     G = G / tiles * tiles;          // whole parts: every workgroup stays inside one tile
     sk.il_tiles = (int)tiles;
   }
@@ -1070,6 +1298,10 @@ int launch_one(const ConvArgs& a, hipStream_t st) {
   // to split -- layer 3 (K = 256): the two blocks of a row range run side by side on one XCD instead of back to back on one CU
   // (the dominant kernel's FETCH_SIZE per launch 372 -> see profiles/r5/pmc_summary.json; dlip_debug_set(5, 2 | 1 | 0) forces a mode)
   if (b.n_inner == 1 && b.tiles_n == 2 && BM == 256 && sk.il_tiles == 0 && !sk.reduce_later && (G & 1) == 0 && tiles > 64) b.n_inner = 2;
+  if constexpr (GROUPED) {
+    b.n_inner = 0;   // (the twin's own order: kernel comment at ConvGroup)
+    ++g_grouped_launches;
+  } else
   if (dlip_dbg_value[DLIP_DBG_NINNER] >= 0) {
     const int v = dlip_dbg_value[DLIP_DBG_NINNER];
     if (v == 2) b.n_inner = (b.tiles_n > 1 && sk.il_tiles == 0 && !sk.reduce_later && G % b.tiles_n == 0) ? 2 : (b.tiles_n > 1 ? 1 : 0);
@@ -1221,6 +1453,34 @@ extern "C" __attribute__((visibility("hidden"))) int dlip_conv_f16x3_dma_launch(
     default:
       return launch_dma<256, 128, 4, 2, 3, 1, 0>(a, st, epi);
   }
+}
+
+// Tests and tools (not part of the public header): the border-group table launch_one would build for a 256 x 128 launch of this
+// geometry -- the same conv_groups() -- and how many grouped launches this process has made.  No device call.
+//   geom = {N, H, W, C, R, S, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, nk2}
+//   out  = {legal, taken by the built-in rule, groups, slices per column block, tiles per column block, sum of taps x positions,
+//           R S Ho Wo, grouped launches so far}
+extern "C" int dlip_conv_grouped_query(const int32_t* geom, int64_t* out) {
+  DLIP_CHECK_ARG(geom != nullptr && out != nullptr);
+  for (int i = 0; i < 12; ++i) DLIP_CHECK_ARG(geom[i] > 0 || ((i == 8 || i == 9) && geom[i] == 0));
+  ConvArgs a = {};
+  const int N = geom[0];
+  a.H = geom[1]; a.W = geom[2]; a.C = geom[3]; a.R = geom[4]; a.S = geom[5];
+  a.sh = geom[6]; a.sw = geom[7]; a.ph = geom[8]; a.pw = geom[9]; a.dh = geom[10]; a.dw = geom[11];
+  a.nk2 = geom[12];
+  const int Ho = (a.H + 2 * a.ph - a.dh * (a.R - 1) - 1) / a.sh + 1, Wo = (a.W + 2 * a.pw - a.dw * (a.S - 1) - 1) / a.sw + 1;
+  DLIP_CHECK_ARG(Ho > 0 && Wo > 0 && a.nk2 >= 0);
+  a.Wo = Wo; a.HoWo = Ho * Wo; a.M = N * a.HoWo;
+  a.cchunks = (a.C + BK - 1) / BK; a.Cw = a.cchunks * BK;
+  a.nk = a.R * a.S * a.cchunks + a.nk2;
+  ConvGroups gt = {};
+  const bool legal = a.R * a.S <= 32 && conv_groups(a, 256, &gt);
+  out[0] = legal ? 1 : 0;
+  out[1] = legal && grouped_by_rule(a, gt) ? 1 : 0;
+  out[2] = gt.n; out[3] = gt.slices; out[4] = gt.tiles; out[5] = gt.useful;
+  out[6] = (int64_t)a.R * a.S * a.HoWo;
+  out[7] = g_grouped_launches;
+  return DLIP_OK;
 }
 
 // ---- caller-owned workspace (include/deeplip_hip.h) ----

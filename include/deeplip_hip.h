@@ -847,6 +847,8 @@ int dlip_range_scope_end(dlip_stream_t stream);
  * 8 the train-mode BatchNorm / column-sum entry points' launch sequence (0 = ABI 43's: statistics, finalize, apply [, lift] as separate
  * launches; otherwise the finalize steps run in the last workgroup of the pass before them and few-row tensors take one launch);
  * 9 the rows kernel's short last round (0 = off: every tile the full height);
+ * 10 the LDS-DMA kernel's border groups (a padded convolution on the 256 x 128 tile run as its padding-free sub-convolutions in one
+ * launch: 0 = never, 1 = whenever the construction applies; built in where a launch's share of padding taps is large enough);
  * value -1 restores the built-in choice. */
 int dlip_debug_set(int32_t key, int32_t value);
 
