@@ -13,7 +13,7 @@ import torch  # must be imported first: the library binds to the HIP runtime tor
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DLIP_LIB_PATH") or os.path.join(_PKG, "lib", "libdeeplip_hip.so")  # env override: A/B builds
-ABI_VERSION = 55
+ABI_VERSION = 56
 LIFT_WORDS = 4098
 LIFT_BCAST = 2048
 
@@ -183,6 +183,8 @@ SIGNATURES = {
     "dlip_bilinear_finish_f32": [c_f, c_f, c_f, c_f, c_i32, c_i32, C.c_float, c_stream],
     "dlip_compact_bilinear_f32": [c_f] * 11 + [c_i32] * 6 + [c_stream],
     "dlip_compact_bilinear_bwd_f32": [c_f] * 9 + [c_i32] * 6 + [c_stream],
+    "dlip_time_tail_zero_f32": [c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_i32, c_stream],
+    "dlip_avgpool_time_ragged_f32": [c_f, c_f, c_i32, c_f, c_i32, c_i32, c_i32, c_i32, c_stream],
 }
 
 

@@ -97,27 +97,45 @@ class SpeakerEmbNet(nn.Module):
             h = _basic_block_train(b, h)
         return ag.linear(av.avgpool(h), self.fc.weight, self.fc.bias)
 
+    def frames_consumed(self) -> int:
+        """Frames the convolutions take off an utterance: none (every convolution is zero-padded; the TDNN encoders' valid convolutions
+        take 22).  The shortest utterance the encoder embeds is one frame."""
+        return 0
+
     @arith.guarded_eval
     def extract_embedding(self, x: Tensor, lengths=None) -> Tuple[Tensor, Tensor]:
         """[B,1,F,T] (or [B,F,T]) -> (embedding [B,E], the same tensor): the TDNN encoder's (xv, x_a) interface with
-        a single fully connected layer."""
-        if lengths is not None:
-            raise NotImplementedError("the resnet speech encoder's padded convolutions read across an utterance's end: ragged "
-                                      "batches (lengths) exist for the TDNN / E-TDNN encoders only")
+        a single fully connected layer.  ``lengths`` (eval mode; B values in [1, T], or an int32 device tensor, which is not read on
+        the host): a ragged batch padded to T -- whatever the padding holds, row b equals extract_embedding(x[b:b+1, :, :, :lengths[b]]).
+        Every layer's input is kept zero at frames t >= L_b, where a zero-padded convolution over the batch reads what it reads at the
+        end of the utterance run alone; after k stride-2 stages L_b has become ((L_b - 1) >> k) + 1, so the one length vector and a
+        shift count serve every layer (ops.time_tail_zero behind each convolution, ops.avgpool_time_ragged for the pooling)."""
         if self.training:
+            if lengths is not None:
+                raise NotImplementedError("the resnet speech encoder takes a ragged batch (lengths) in eval mode only: a training batch "
+                                          "is cropped to one length (datasets.py:112-115)")
             e = self._embed_train(x)
             return e, e
         p = _cached_pack(self, x.device, self._pack)
         split = p["stem"].wscale is not None
         h = self._input_nhwc(x, p["cp"])
+        lens = ops.lengths_i32(lengths, x.device, n=h.shape[0], lo=1, hi=h.shape[2])
+        if lens is not None:
+            ops.time_tail_zero(h, lens, 0)     # the caller's padding need not be zero
         if split:
             h = ops.split_pack(h)
         h = ops.conv_nhwc(h, p["stem"].w, p["stem"].b, pad=(1, 1), slope=p["stem"].slope, w_scale=p["stem"].wscale,
                           x_split=split, out_split=split)
+        if lens is not None:
+            ops.time_tail_zero(h, lens, 0)
         blocks = self._blocks()
+        shift = 0
         for i, (b, bp) in enumerate(zip(blocks, p["blocks"])):
-            h = b.run(h, bp, split=split, out_split=split and i + 1 < len(blocks))   # the pooling kernel reads fp32
-        e = ops.linear(ops.avgpool(h), p["fc"].w, p["fc"].b, w_scale=p["fc"].wscale)
+            shift += int(b.stride == 2)
+            h = b.run(h, bp, split=split, out_split=split and i + 1 < len(blocks),   # the pooling kernel reads fp32
+                      time_lengths=None if lens is None else (lens, shift))
+        pooled = ops.avgpool(h) if lens is None else ops.avgpool_time_ragged(h, lens, shift)
+        e = ops.linear(pooled, p["fc"].w, p["fc"].b, w_scale=p["fc"].wscale)
         return e, e
 
     def forward(self, x: Tensor) -> Tensor:

@@ -23,3 +23,12 @@ template <class... P>
 inline bool dlip_aligned128(const P*... p) { return dlip_aligned<128>(p...); }
 
 inline hipStream_t dlip_hip_stream(dlip_stream_t stream) { return static_cast<hipStream_t>(stream); }
+
+// Ragged batches through stride-2 stages (the ResNet speech encoder): utterance frames valid on a W-frame time axis that `shift`
+// stride-2 convolutions (kernel 3, padding 1: L -> (L - 1) / 2 + 1) stand in front of, from the INPUT length `len` -- clamped to
+// [1, W << shift], so the result lies in [1, W] whatever the vector holds.  Device code of layout_ops / pool_ops.
+__host__ __device__ __forceinline__ int dlip_time_valid(int len, int shift, int W) {
+  const long long cap = (long long)W << shift;
+  const long long l = len < 1 ? 1 : (len > cap ? cap : (long long)len);
+  return (int)((l - 1) >> shift) + 1;
+}

@@ -211,3 +211,30 @@ extern "C" int dlip_mask_frames_f32(const float* x, const int32_t* len, float* y
                      reinterpret_cast<const f32x4*>(x), reinterpret_cast<f32x4*>(y), len, T, E / 4, n4);
   return dlip_launch_status();
 }
+
+namespace {
+// x[n, h, w >= Lk, :] = 0 in place for x [N,H,W,C] (H frequency, W time), Lk = ((clamp(len[n], 1, W << shift) - 1) >> shift) + 1:
+// the frames past utterance n's end after `shift` stride-2 stages.  Store-only: one workgroup per (n, h) row writes that row's own
+// contiguous tail of (W - Lk) C floats as 16-byte zeros and never reads x, so the pass costs the padding share of the tensor; the grid
+// does not depend on the lengths (a recorded plan replays with new ones).  All-zero bits are the zero of the fp32 container AND of the
+// split activation format (split_pack_kernel: hi = (half)0 = +0, lo = (half)(0 - 0) = +0), so one kernel serves both.
+__global__ __launch_bounds__(256) void time_tail_zero_kernel(f32x4* __restrict__ x, const int32_t* __restrict__ len, int shift, int H,
+                                                             int W, int C4) {
+  const int n = blockIdx.x / H;
+  const int Lk = dlip_time_valid(len[n], shift, W);
+  f32x4* tail = x + ((long long)blockIdx.x * W + Lk) * C4;
+  const int n4 = (W - Lk) * C4;
+  const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+  for (int i = threadIdx.x; i < n4; i += 256) tail[i] = z;
+}
+}  // namespace
+
+extern "C" int dlip_time_tail_zero_f32(float* x, const int32_t* lengths, int32_t shift, int32_t N, int32_t H, int32_t W, int32_t C,
+                                       dlip_stream_t stream) {
+  DLIP_CHECK_ARG(x && lengths && N > 0 && H > 0 && W > 0 && C > 0 && (C & 3) == 0 && shift >= 0 && shift <= 16);
+  DLIP_CHECK_ARG((long long)N * H <= 0x7fffffffLL && (long long)W * (C / 4) <= 0x7fffffffLL && W <= (0x7fffffff >> shift));
+  DLIP_CHECK_ARG(dlip_aligned16(x));
+  hipLaunchKernelGGL(time_tail_zero_kernel, dim3((unsigned)(N * H)), dim3(256), 0, dlip_hip_stream(stream),
+                     reinterpret_cast<f32x4*>(x), lengths, shift, H, W, C / 4);
+  return dlip_launch_status();
+}

@@ -174,6 +174,39 @@ __global__ __launch_bounds__(256) void meanstd_kernel(const float* __restrict__ 
   if (SPLIT) dlip_report_range(amax, status);
 }
 
+// y[n, c] = mean over h < H, w < Lk of x[n, h, w, c], Lk = dlip_time_valid(len[n], shift, W): AdaptiveAvgPool2d(1) of utterance n
+// alone, taken from its row of a zero-padded batch (divisor H Lk, not H W).  One workgroup per (utterance, 64-channel block) as
+// meanstd_kernel: 16 lanes x float4 span the block, 16 position groups split the H Lk valid positions (ascending), fp64 sums, the
+// 16 partial rows meet in LDS in a fixed order -- no atomics, the same bits on every run.
+__global__ __launch_bounds__(256) void avgpool_time_ragged_kernel(const float* __restrict__ x, const int32_t* __restrict__ len,
+                                                                  int shift, float* __restrict__ y, int H, int W, int C) {
+  __shared__ double part[16][64];
+  const int n = blockIdx.y, c0 = blockIdx.x * 64;
+  const int Lk = dlip_time_valid(len[n], shift, W);
+  const int lx = threadIdx.x & 15, g = threadIdx.x >> 4;
+  const int c = c0 + lx * 4;
+  double s[4] = {0, 0, 0, 0};
+  if (c < C) {   // C % 4 == 0: a float4 is all inside or all outside
+    const float* p = x + (long long)n * H * W * C + c;
+    const int P = H * Lk;
+    for (int i = g; i < P; i += 16) {
+      const int h = i / Lk, w = i - h * Lk;
+      const f32x4 v = *reinterpret_cast<const f32x4*>(p + ((long long)h * W + w) * C);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) s[k] += (double)v[k];
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) part[g][lx * 4 + k] = s[k];
+  __syncthreads();
+  if (threadIdx.x < 64 && c0 + (int)threadIdx.x < C) {
+    double ss = 0.0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) ss += part[i][threadIdx.x];
+    y[(long long)n * C + c0 + threadIdx.x] = (float)(ss / ((double)H * (double)Lk));
+  }
+}
+
 constexpr int kGridCap = 256 * 8;  // 8 workgroups per CU, grid-stride the rest
 
 }  // namespace
@@ -207,6 +240,16 @@ extern "C" int dlip_time_mean_f32(const float* x, const int32_t* len, int32_t le
   DlipLen l; l.len = len; l.mul = 1; l.add = len_add;
   hipLaunchKernelGGL(time_mean_kernel, dim3(dlip_grid1d((long long)B * C, kGridCap)), dim3(256), 0,
                      dlip_hip_stream(stream), x, l, y, B, T, C, ldx);
+  return dlip_launch_status();
+}
+
+extern "C" int dlip_avgpool_time_ragged_f32(const float* x, const int32_t* lengths, int32_t shift, float* y, int32_t N, int32_t H,
+                                            int32_t W, int32_t C, dlip_stream_t stream) {
+  DLIP_CHECK_ARG(x && lengths && y && N > 0 && N <= 65535 && H > 0 && W > 0 && C > 0 && (C & 3) == 0 && shift >= 0 && shift <= 16);
+  DLIP_CHECK_ARG((long long)H * W <= 0x7fffffffLL && W <= (0x7fffffff >> shift));
+  DLIP_CHECK_ARG(dlip_aligned16(x));
+  hipLaunchKernelGGL(avgpool_time_ragged_kernel, dim3((C + 63) / 64, N), dim3(256), 0, dlip_hip_stream(stream), x, lengths, shift, y,
+                     H, W, C);
   return dlip_launch_status();
 }
 

@@ -687,6 +687,33 @@ def mask_frames(x: Tensor, lengths: Tensor) -> Tensor:
     return y
 
 
+def _time_ragged_args(x: Tensor, lengths: Tensor, shift: int, name: str):
+    _req(x, "x")
+    _req(lengths, "lengths", torch.int32)
+    if lengths is None or x.dim() != 4 or lengths.numel() != x.shape[0] or x.shape[3] % 4 or not 0 <= int(shift) <= 16:
+        raise ValueError(f"{name}: x [N,H,W,C] with C % 4 == 0, one int32 length per image, 0 <= shift <= 16")
+    return x.shape
+
+
+def time_tail_zero(x: Tensor, lengths: Tensor, shift: int = 0) -> Tensor:
+    """x [N,H,W,C] (W = time; fp32 or the split activation format), IN PLACE: frames w >= ((clamp(lengths[n], 1, W << shift) - 1) >> shift)
+    + 1 of image n become zeros -- the padding of a ragged batch behind ``shift`` stride-2 stages (dlip_time_tail_zero_f32: store-only,
+    the lengths stay on the device).  Returns x."""
+    N, H, W, Cc = _time_ragged_args(x, lengths, shift, "time_tail_zero")
+    check(lib().dlip_time_tail_zero_f32(ptr(x), ptr(lengths), int(shift), N, H, W, Cc, stream_handle()), "dlip_time_tail_zero_f32")
+    return x
+
+
+def avgpool_time_ragged(x: Tensor, lengths: Tensor, shift: int = 0) -> Tensor:
+    """x [N,H,W,C] fp32 -> [N,C]: the mean over every h and the valid frames w < Lk of image n (Lk as time_tail_zero): AdaptiveAvgPool2d(1)
+    of each utterance at its own length (dlip_avgpool_time_ragged_f32)."""
+    N, H, W, Cc = _time_ragged_args(x, lengths, shift, "avgpool_time_ragged")
+    y = _empty((N, Cc), x.device)
+    check(lib().dlip_avgpool_time_ragged_f32(ptr(x), ptr(lengths), int(shift), ptr(y), N, H, W, Cc, stream_handle()),
+          "dlip_avgpool_time_ragged_f32")
+    return y
+
+
 def l1_sum(w: Tensor) -> Tensor:
     """sum |w| as a 0-d device tensor (dlip_l1_sum_f32: fp64 accumulation, fixed order)."""
     _req(w, "w")

@@ -16,7 +16,7 @@ from __future__ import annotations
 import contextlib
 
 import math
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
@@ -109,19 +109,28 @@ class BasicBlock(nn.Module):
         return p
 
     def run(self, x: Tensor, p: Dict[str, packing.Packed], split: bool = False, out_split: bool = False,
-            pool_group: Optional[int] = None, pool_lengths: Optional[Tensor] = None, pool_len_mul: int = 1, calib=None):
+            pool_group: Optional[int] = None, pool_lengths: Optional[Tensor] = None, pool_len_mul: int = 1, calib=None,
+            time_lengths: Optional[Tuple[Tensor, int]] = None):
         """x NHWC.  conv1+bn1+relu1 | (1x1 s2 conv + bn) | conv2+bn2 + residual + relu2.
         ``split``: x is in the split activation format (f16x3 packing only) and so are the block's
         internal tensors; ``out_split`` keeps the result in it for the next block; ``pool_group`` (split only):
-        return ops.Pooled column sums over groups of that many output pixels instead of the output."""
+        return ops.Pooled column sums over groups of that many output pixels instead of the output.
+        ``time_lengths`` = (int32 device input lengths [N], stride-2 stages in front of this block's OUTPUT): a ragged batch along W
+        whose x is zero past every image's end -- the tails of conv1's output and of the block's output (BN shift, neighbour spill,
+        residual) are zeroed too, so each image's valid frames equal those of the image run alone (ops.time_tail_zero)."""
+        if time_lengths is not None and pool_group is not None:
+            raise ValueError("BasicBlock.run: time_lengths (a ragged time axis) has no pooled-output form (pool_group)")
         s = (self.stride, self.stride)
         h = ops.conv_nhwc(x, p["conv1"].w, p["conv1"].b, stride=s, pad=(1, 1), slope=p["conv1"].slope,
                           w_scale=p["conv1"].wscale, x_split=split, out_split=split)
+        if time_lengths is not None:
+            ops.time_tail_zero(h, *time_lengths)
         if calib is not None and not split:      # a calibrating exact pass: (owner model, block index) -> note |h|, |out|
             packing.calib_note(calib[0], f"h{calib[1]}", h)
         if split and FUSE_SHORTCUT and "conv2+down" in p and pool_group is None:
             q = p["conv2+down"]   # conv2 + bn2 + (1x1 s2 conv + bn)(x) + relu2 in one reduction (resnet.py:62-68)
-            return ops.conv2_nhwc(h, x, q.w, q.b, q.wscale, pad=(1, 1), stride2=s, slope=q.slope, out_split=out_split)
+            out = ops.conv2_nhwc(h, x, q.w, q.b, q.wscale, pad=(1, 1), stride2=s, slope=q.slope, out_split=out_split)
+            return out if time_lengths is None else ops.time_tail_zero(out, *time_lengths)
         res = ops.conv_nhwc(x, p["down"].w, p["down"].b, stride=s, w_scale=p["down"].wscale,
                             x_split=split, out_split=split) if "down" in p else x
         if pool_group is not None:   # the block's output leaves as pooled partial sums only
@@ -131,7 +140,7 @@ class BasicBlock(nn.Module):
                             w_scale=p["conv2"].wscale, x_split=split, out_split=out_split)
         if calib is not None and not split:
             packing.calib_note(calib[0], f"o{calib[1]}", out)
-        return out
+        return out if time_lengths is None else ops.time_tail_zero(out, *time_lengths)
 
 
 def _basic_block_train(b: "BasicBlock", x, fork: bool = False):

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define DLIP_ABI_VERSION 55
+#define DLIP_ABI_VERSION 56
 #define DLIP_LIFT_WORDS 4098   /* a gradient's power-of-two lift: (2^e, 2^-e), then 2^-e repeated 2048 times (the post_scale vector of
                                   the convolution that consumes the lifted gradient); while it is formed the words behind the pair
                                   hold one maximum per workgroup of the producing pass */
@@ -984,6 +984,27 @@ int dlip_compact_bilinear_f32(const float* x1, const float* x2, const int32_t* r
 int dlip_compact_bilinear_bwd_f32(const float* g, const float* psi1, const float* psi2, const int32_t* h1, const float* s1,
                                   const int32_t* h2, const float* s2, float* dx1, float* dx2, int32_t B, int32_t C1, int32_t C2, int32_t P,
                                   int32_t D, int32_t sum_pool, dlip_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 56) Ragged batches through the ResNet speech encoder (`arch: resnet`, deeplip_amd/audio_resnet.py): a zero-padded batch of
+ * utterances of differing length, every row computed as if run alone -- what replaces the one-utterance loop of train_audio.py:343-373
+ * (batch 1, one launch sequence per utterance) for that encoder.  x is NHWC [N,H,W,C] with H = frequency and W = time; `lengths`
+ * (device int32 [N]) holds the INPUT lengths in frames and `shift` the number of stride-2 stages in front of x, so utterance n is
+ * valid for its first Lk = ((clamp(lengths[n], 1, W << shift) - 1) >> shift) + 1 frames of W (a stride-2 3x3 convolution with padding 1
+ * maps L frames to (L - 1) / 2 + 1).  0 <= shift <= 16, C % 4 == 0, x 16-byte aligned.
+ *
+ * dlip_time_tail_zero_f32 (train_audio.py:343-373, arch resnet): in place, x[n, h, w >= Lk, :] = +0 -- the frames past an utterance's
+ *   end, which a convolution's epilogue fills with its BatchNorm shift, neighbour spill and the residual, made the zeros the next
+ *   zero-padded convolution reads when the utterance is run alone.  Store-only (x is never read: the traffic is the padding share of
+ *   the tensor); all-zero bits, the zero of the fp32 container and of the split activation format alike.  The grid is N H whatever
+ *   the lengths hold: a recorded plan replays with a new vector.
+ * dlip_avgpool_time_ragged_f32 (train_audio.py:343-373, arch resnet: AdaptiveAvgPool2d(1) of each utterance at its own length):
+ *   y[n, c] = sum_{h < H, w < Lk} x[n,h,w,c] / (H Lk), fp64 sums in a fixed order, no atomics.  x fp32 (not split), y [N,C]; N <= 65535.
+ * ------------------------------------------------------------------------------------------ */
+int dlip_time_tail_zero_f32(float* x, const int32_t* lengths, int32_t shift, int32_t N, int32_t H, int32_t W, int32_t C,
+                            dlip_stream_t stream);
+int dlip_avgpool_time_ragged_f32(const float* x, const int32_t* lengths, int32_t shift, float* y, int32_t N, int32_t H, int32_t W,
+                                 int32_t C, dlip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Step plans.  The reference drives its encoders from a Python loop, one utterance and one torch.nn layer

@@ -98,8 +98,8 @@ class Trainer(object):
         F_ = self.model_opts[arch]["input_dim"] if arch != "resnet" else int(d.get("feat_dim", 40))
         self.trainset = SyntheticAVSet(d["n_spk"], d["utt_per_spk"], 0, 1, F_, d["audio_frames"], key="atrain")
         # test lists hold utterances of differing duration, as the reference's do (data.test_ragged; train_audio.py:343-373 feeds them
-        # one at a time at their own lengths); the resnet's padded convolutions have no ragged batch
-        rag = dict(ragged=bool(d.get("test_ragged", False)) and arch != "resnet", audio_range=tuple(d.get("test_audio_frames", (137, 412))))
+        # one at a time at their own lengths); every encoder takes them as length-bucketed ragged batches
+        rag = dict(ragged=bool(d.get("test_ragged", False)), audio_range=tuple(d.get("test_audio_frames", (137, 412))))
         self.voxtestset = SyntheticAVSet(d["test_speakers"], d["test_utt_per_spk"], 0, 1, F_, d["audio_frames"], key="atest", **rag)
         # the reference's three A+V evaluation lists (train_audio.py:119-139: lomgriddevloader / lomgridtestloader / gridtestloader)
         self.lomgriddevset = SyntheticAVSet(d["test_speakers"], d["test_utt_per_spk"], 0, 1, F_, d["audio_frames"], key="alomdev", **rag)
@@ -361,9 +361,14 @@ class Trainer(object):
             self._extractor = None
         if self._extractor is None:
             ex = RaggedExtractor(lambda a, l: torch.cat(self.model.extract_embedding(a, lengths=l), dim=1), None, self.device, batch=batch,
-                                 audio_min_frames=self.model.frames_consumed() + 2)
+                                 audio_min_frames=self._min_frames())
             self._extractor = (key, ex)
         return self._extractor[1]
+
+    def _min_frames(self) -> int:
+        """The shortest utterance the encoder embeds: one frame for the ResNet (zero-padded convolutions, average pooling); for the
+        TDNNs the frames their valid convolutions consume + the two pooled frames the unbiased std needs (pooling.py:24-26)."""
+        return 1 if self.model_opts["arch"] == "resnet" else self.model.frames_consumed() + 2
 
     def close(self):
         """Release the recorded extraction plans (their arenas) and the recorded training steps."""
