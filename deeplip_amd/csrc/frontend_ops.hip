@@ -16,10 +16,30 @@
 
 namespace {
 
+// RAGGED WAVEFORM BATCHES.  The kernels below that carry a `kRagged` switch serve two entry points each: <false> is the rectangular
+// kernel (no length is read, every row is whole), <true> reads one length per row of a zero-padded batch and computes each row as if
+// it had been run alone -- the reference's loop extracts one utterance at a time (train_fusion.py:334-349, train_audio.py:343-373).
+// sigproc.framesig's frame count of an s-sample signal: 1 + ceil((s - L) / step) above one frame length, else 1.
+__device__ __forceinline__ int wave_frames(long long s, int L, int step) {
+  return s <= L ? 1 : 1 + (int)((s - L + step - 1) / step);
+}
+__device__ __forceinline__ long long clamp_len(int v, long long hi) { return v < 1 ? 1 : (v > hi ? hi : v); }
+
+// sample lengths [B] -> frame lengths [B] on the device: a recorded plan follows whatever lengths its buffer holds at replay time
+__global__ __launch_bounds__(256) void wave_frame_lengths_kernel(const int32_t* __restrict__ slen, int32_t* __restrict__ flen, int B,
+                                                                 long long S, int L, int step) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b < B) flen[b] = wave_frames(clamp_len(slen[b], S), L, step);
+}
+
 // frames[b*NF + f][j] = (j < L ? pre(b, f*step + j) : 0), pre(n) = x[n] - coef*x[n-1] (x[-1] -> x[0] alone,
 // samples beyond the signal are zero padding as python_speech_features.sigproc.framesig does).
-__global__ __launch_bounds__(256) void frame_preemph_kernel(const float* __restrict__ x, float* __restrict__ y,
-                                                            int S, int NF, int L, int step, int nfft, float coef,
+// kRagged: row b ends at S_b = clamp(slen[b], 1, S).  The reference pre-emphasises the S_b-sample signal and framesig zero-pads
+// AFTERWARDS, so position S_b holds 0 and not -coef * x[S_b - 1]; samples >= S_b are never read (the caller's padding may hold
+// anything) and frames f >= NF_b are all zero.
+template <bool kRagged>
+__global__ __launch_bounds__(256) void frame_preemph_kernel(const float* __restrict__ x, const int32_t* __restrict__ slen,
+                                                            float* __restrict__ y, int S, int NF, int L, int step, int nfft, float coef,
                                                             long long total) {
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int j = (int)(i % nfft);
@@ -28,7 +48,13 @@ __global__ __launch_bounds__(256) void frame_preemph_kernel(const float* __restr
     const long long b = r / NF;
     float v = 0.f;
     const int n = f * step + j;
-    if (j < L && n < S) {
+    int Sb = S;
+    bool live = true;
+    if (kRagged) {
+      Sb = (int)clamp_len(slen[b], S);
+      live = f < wave_frames(Sb, L, step);
+    }
+    if (live && j < L && n < Sb) {
       const float* xb = x + b * S;
       v = n == 0 ? xb[0] : xb[n] - coef * xb[n - 1];
     }
@@ -104,7 +130,12 @@ __global__ __launch_bounds__(256) void powspec_dft64_kernel(const float* __restr
 // pre-emphasised in fp64 (coefficient a double: 0.97, not 0.97f) into LDS in bit-reversed order, a radix-2 decimation-in-time FFT of
 // nfft points runs there (log2(nfft) stages of nfft / 2 butterflies, one per thread and stage; twiddles from an LDS table of
 // sincospi), and the first NB bins leave as |.|^2 / nfft in fp32 together with the frame's energy (summed in fp64).
-__global__ __launch_bounds__(512) void powspec_wave_fft64_kernel(const float* __restrict__ x, float* __restrict__ pw, float* __restrict__ energy,
+// kRagged: as frame_preemph_kernel -- the row ends at S_b = clamp(slen[b], 1, S); a frame f >= NF_b runs no FFT and leaves a zero
+// power-spectrum row and a zero energy (the dense mel / log / DCT products behind see finite values; the ragged CMVN does not read
+// them).  That exit depends on blockIdx alone, so the whole workgroup takes it, and it sits in front of the first barrier.
+template <bool kRagged>
+__global__ __launch_bounds__(512) void powspec_wave_fft64_kernel(const float* __restrict__ x, const int32_t* __restrict__ slen,
+                                                                 float* __restrict__ pw, float* __restrict__ energy,
                                                                  long long S, int NF, int L, int step, int nfft, int lg, double coef, int NB,
                                                                  int NBp) {
   extern __shared__ double sh[];          // [nfft] re | [nfft] im | [nfft / 2] cos | [nfft / 2] sin | [8] wave sums
@@ -116,6 +147,14 @@ __global__ __launch_bounds__(512) void powspec_wave_fft64_kernel(const float* __
   const long long r = blockIdx.x;
   const int f = (int)(r % NF);
   const float* xb = x + (r / NF) * S;
+  if (kRagged) {
+    S = clamp_len(slen[r / NF], S);
+    if (f >= wave_frames(S, L, step)) {
+      for (int k = threadIdx.x; k < NBp; k += blockDim.x) pw[r * NBp + k] = 0.f;
+      if (threadIdx.x == 0) energy[r] = 0.f;
+      return;
+    }
+  }
   const int half = nfft >> 1;
   for (int j = threadIdx.x; j < nfft; j += blockDim.x) {
     const long long n = (long long)f * step + j;
@@ -175,34 +214,44 @@ __global__ __launch_bounds__(256) void log_floor_kernel(const float* __restrict_
 // feat [B, NF, C] (c0 optionally replaced by log(energy)) -> CMVN over the NF frames of each utterance:
 // (x - mean)/(std_biased + 2e-12) (datasets.py:52-53), written channel-first [B, C, NF] like the
 // reference loaders (datasets.py:135).  One thread per (b, c), fp64 statistics.
+// kRagged: the statistics run over the row's own n = clamp(flen[b], 1, NF) frames, summed front to back by one thread -- an order
+// that n alone decides, so a row depends neither on its neighbours nor on the padded width NF -- and columns t >= n leave as exact
+// zeros.  n = 1: std 0, (x - x) / 2e-12 = 0, as numpy gives.
+template <bool kRagged>
 __global__ __launch_bounds__(256) void cmvn_kernel(const float* __restrict__ feat, const float* __restrict__ energy,
-                                                   float* __restrict__ y, int B, int NF, int C, int ldf, int normalize) {
+                                                   const int32_t* __restrict__ flen, float* __restrict__ y, int B, int NF, int C, int ldf,
+                                                   int normalize) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= (long long)B * C) return;
   const int c = (int)(i % C);
   const long long b = i / C;
+  const int n = kRagged ? (int)clamp_len(flen[b], NF) : NF;
   const float* p = feat + b * NF * ldf + c;
   const float* en = (energy && c == 0) ? energy + b * NF : nullptr;
   double s = 0.0;
-  for (int f = 0; f < NF; ++f) s += (double)(en ? logf(en[f]) : p[(long long)f * ldf]);
-  const double mean = s / NF;
+  for (int f = 0; f < n; ++f) s += (double)(en ? logf(en[f]) : p[(long long)f * ldf]);
+  const double mean = s / n;
   double q = 0.0;
-  for (int f = 0; f < NF; ++f) {
+  for (int f = 0; f < n; ++f) {
     const double d = (double)(en ? logf(en[f]) : p[(long long)f * ldf]) - mean;
     q += d * d;
   }
   const float mu = normalize ? (float)mean : 0.f;
-  const float den = normalize ? (float)sqrt(q / NF) + 2e-12f : 1.f;
+  const float den = normalize ? (float)sqrt(q / n) + 2e-12f : 1.f;
   float* o = y + (b * C + c) * NF;
-  for (int f = 0; f < NF; ++f) o[f] = ((en ? logf(en[f]) : p[(long long)f * ldf]) - mu) / den;
+  for (int f = 0; f < n; ++f) o[f] = ((en ? logf(en[f]) : p[(long long)f * ldf]) - mu) / den;
+  for (int f = n; f < NF; ++f) o[f] = 0.f;
 }
 
 // python_speech_features.delta as SpkTrainDataset._delta applies it (datasets.py:55-63): x [B, C, NF] (channel first, as
 // the loaders hold features) -> y [B, (1 + order) C, NF] = [x | delta(x, N=1) | delta(x, N=2)] -- BOTH differences are
 // taken of the base features (the reference does not difference the deltas again):
 //   delta(x, N)[t] = sum_{n=-N..N} n x[clamp(t + n)] / (2 sum_{n=1..N} n^2)        (edge padding)
-__global__ __launch_bounds__(256) void delta_kernel(const float* __restrict__ x, float* __restrict__ y, long long rows, int C,
-                                                    int NF, int order) {
+// kRagged: the edge padding repeats the row's own last frame n - 1 (n = clamp(flen[b], 1, NF)), not column NF - 1, and columns
+// t >= n are zeros in all 1 + order blocks.
+template <bool kRagged>
+__global__ __launch_bounds__(256) void delta_kernel(const float* __restrict__ x, const int32_t* __restrict__ flen, float* __restrict__ y,
+                                                    long long rows, int C, int NF, int order) {
   const long long total = rows * NF;                 // rows = B * C
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int t = (int)(i % NF);
@@ -210,8 +259,13 @@ __global__ __launch_bounds__(256) void delta_kernel(const float* __restrict__ x,
     const long long b = r / C;
     const int c = (int)(r - b * C);
     const float* p = x + r * NF;
-    auto at = [&](int u) { return p[u < 0 ? 0 : (u >= NF ? NF - 1 : u)]; };
+    const int n = kRagged ? (int)clamp_len(flen[b], NF) : NF;
     float* o = y + (b * (1 + order) * C + c) * NF + t;
+    if (kRagged && t >= n) {
+      for (int k = 0; k <= order; ++k) o[(long long)k * C * NF] = 0.f;
+      continue;
+    }
+    auto at = [&](int u) { return p[u < 0 ? 0 : (u >= n ? n - 1 : u)]; };
     o[0] = p[t];
     if (order >= 1) o[(long long)C * NF] = (at(t + 1) - at(t - 1)) / 2.0f;
     if (order >= 2) o[(long long)2 * C * NF] = (2.0f * at(t + 2) + at(t + 1) - at(t - 1) - 2.0f * at(t - 2)) / 10.0f;
@@ -252,12 +306,32 @@ constexpr int kGridCap = 2048;
 
 }  // namespace
 
-extern "C" int dlip_frame_preemph_f32(const float* x, float* frames, int32_t B, int32_t S, int32_t NF, int32_t frame_len,
-                                      int32_t frame_step, int32_t nfft, float preemph, dlip_stream_t stream) {
+// Each pair of entry points (rectangular | ragged) shares one launch: lengths == NULL picks the kernel that reads none.
+static int frame_preemph(const float* x, const int32_t* slen, float* frames, int32_t B, int32_t S, int32_t NF, int32_t frame_len,
+                         int32_t frame_step, int32_t nfft, float preemph, dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && frames && B > 0 && S > 0 && NF > 0 && frame_len > 0 && frame_step > 0 && nfft >= frame_len);
   const long long total = (long long)B * NF * nfft;
-  hipLaunchKernelGGL(frame_preemph_kernel, dim3(dlip_grid1d(total, kGridCap)), dim3(256), 0, dlip_hip_stream(stream), x,
-                     frames, S, NF, frame_len, frame_step, nfft, preemph, total);
+  hipLaunchKernelGGL(slen ? frame_preemph_kernel<true> : frame_preemph_kernel<false>, dim3(dlip_grid1d(total, kGridCap)), dim3(256), 0,
+                     dlip_hip_stream(stream), x, slen, frames, S, NF, frame_len, frame_step, nfft, preemph, total);
+  return dlip_launch_status();
+}
+
+extern "C" int dlip_frame_preemph_f32(const float* x, float* frames, int32_t B, int32_t S, int32_t NF, int32_t frame_len,
+                                      int32_t frame_step, int32_t nfft, float preemph, dlip_stream_t stream) {
+  return frame_preemph(x, nullptr, frames, B, S, NF, frame_len, frame_step, nfft, preemph, stream);
+}
+
+extern "C" int dlip_frame_preemph_ragged_f32(const float* x, const int32_t* sample_len, float* frames, int32_t B, int32_t S, int32_t NF,
+                                             int32_t frame_len, int32_t frame_step, int32_t nfft, float preemph, dlip_stream_t stream) {
+  DLIP_CHECK_ARG(sample_len);
+  return frame_preemph(x, sample_len, frames, B, S, NF, frame_len, frame_step, nfft, preemph, stream);
+}
+
+extern "C" int dlip_wave_frame_lengths_i32(const int32_t* sample_len, int32_t* frame_lengths, int32_t B, int64_t S, int32_t frame_len,
+                                           int32_t frame_step, dlip_stream_t stream) {
+  DLIP_CHECK_ARG(sample_len && frame_lengths && B > 0 && S > 0 && frame_len > 0 && frame_step > 0);
+  hipLaunchKernelGGL(wave_frame_lengths_kernel, dim3((B + 255) / 256), dim3(256), 0, dlip_hip_stream(stream), sample_len, frame_lengths,
+                     B, (long long)S, frame_len, frame_step);
   return dlip_launch_status();
 }
 
@@ -278,8 +352,9 @@ extern "C" int dlip_powspec_dft64_f32(const float* frames, float* pw, float* ene
   return dlip_launch_status();
 }
 
-extern "C" int dlip_powspec_wave_fft64_f32(const float* x, float* pw, float* energy, int64_t B, int64_t S, int32_t NF, int32_t frame_len,
-                                           int32_t frame_step, int32_t nfft, double preemph, int32_t NB, int32_t NBp, dlip_stream_t stream) {
+static int powspec_wave_fft64(const float* x, const int32_t* slen, float* pw, float* energy, int64_t B, int64_t S, int32_t NF,
+                              int32_t frame_len, int32_t frame_step, int32_t nfft, double preemph, int32_t NB, int32_t NBp,
+                              dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && pw && energy && B > 0 && S > 0 && NF > 0 && frame_len > 0 && frame_step > 0 && nfft >= frame_len);
   DLIP_CHECK_ARG(nfft >= 128 && nfft <= 1024 && (nfft & (nfft - 1)) == 0 && NB > 0 && NB <= nfft / 2 + 1 && NBp >= NB);
   DLIP_CHECK_ARG(B * (long long)NF < (1ll << 31));
@@ -287,9 +362,22 @@ extern "C" int dlip_powspec_wave_fft64_f32(const float* x, float* pw, float* ene
   while ((1 << lg) < nfft) ++lg;
   const int threads = nfft / 2;            // 64 .. 512: one butterfly per thread and stage
   const size_t lds = (size_t)(3 * nfft + 8) * sizeof(double);
-  hipLaunchKernelGGL(powspec_wave_fft64_kernel, dim3((unsigned)(B * NF)), dim3((unsigned)threads), lds, dlip_hip_stream(stream), x, pw,
-                     energy, (long long)S, NF, frame_len, frame_step, nfft, lg, preemph, NB, NBp);
+  hipLaunchKernelGGL(slen ? powspec_wave_fft64_kernel<true> : powspec_wave_fft64_kernel<false>, dim3((unsigned)(B * NF)),
+                     dim3((unsigned)threads), lds, dlip_hip_stream(stream), x, slen, pw, energy, (long long)S, NF, frame_len, frame_step,
+                     nfft, lg, preemph, NB, NBp);
   return dlip_launch_status();
+}
+
+extern "C" int dlip_powspec_wave_fft64_f32(const float* x, float* pw, float* energy, int64_t B, int64_t S, int32_t NF, int32_t frame_len,
+                                           int32_t frame_step, int32_t nfft, double preemph, int32_t NB, int32_t NBp, dlip_stream_t stream) {
+  return powspec_wave_fft64(x, nullptr, pw, energy, B, S, NF, frame_len, frame_step, nfft, preemph, NB, NBp, stream);
+}
+
+extern "C" int dlip_powspec_wave_fft64_ragged_f32(const float* x, const int32_t* sample_len, float* pw, float* energy, int64_t B, int64_t S,
+                                                  int32_t NF, int32_t frame_len, int32_t frame_step, int32_t nfft, double preemph, int32_t NB,
+                                                  int32_t NBp, dlip_stream_t stream) {
+  DLIP_CHECK_ARG(sample_len);
+  return powspec_wave_fft64(x, sample_len, pw, energy, B, S, NF, frame_len, frame_step, nfft, preemph, NB, NBp, stream);
 }
 
 extern "C" int dlip_log_floor_f32(const float* x, float* y, int64_t n, dlip_stream_t stream) {
@@ -298,21 +386,42 @@ extern "C" int dlip_log_floor_f32(const float* x, float* y, int64_t n, dlip_stre
   return dlip_launch_status();
 }
 
+static int cmvn_nct(const float* feat, const float* energy, const int32_t* flen, float* y, int32_t B, int32_t NF, int32_t C, int32_t ldf,
+                    int32_t normalize, dlip_stream_t stream) {
+  DLIP_CHECK_ARG(feat && y && B > 0 && NF > 0 && C > 0 && ldf >= C);
+  hipLaunchKernelGGL(flen ? cmvn_kernel<true> : cmvn_kernel<false>, dim3((unsigned)(((long long)B * C + 255) / 256)), dim3(256), 0,
+                     dlip_hip_stream(stream), feat, energy, flen, y, B, NF, C, ldf, normalize);
+  return dlip_launch_status();
+}
+
 extern "C" int dlip_cmvn_nct_f32(const float* feat, const float* energy, float* y, int32_t B, int32_t NF, int32_t C,
                                  int32_t ldf, int32_t normalize, dlip_stream_t stream) {
-  DLIP_CHECK_ARG(feat && y && B > 0 && NF > 0 && C > 0 && ldf >= C);
-  hipLaunchKernelGGL(cmvn_kernel, dim3((unsigned)(((long long)B * C + 255) / 256)), dim3(256), 0,
-                     dlip_hip_stream(stream), feat, energy, y, B, NF, C, ldf, normalize);
+  return cmvn_nct(feat, energy, nullptr, y, B, NF, C, ldf, normalize, stream);
+}
+
+extern "C" int dlip_cmvn_nct_ragged_f32(const float* feat, const float* energy, const int32_t* frame_lengths, float* y, int32_t B, int32_t NF,
+                                        int32_t C, int32_t ldf, int32_t normalize, dlip_stream_t stream) {
+  DLIP_CHECK_ARG(frame_lengths);
+  return cmvn_nct(feat, energy, frame_lengths, y, B, NF, C, ldf, normalize, stream);
+}
+
+static int delta_nct(const float* x, const int32_t* flen, float* y, int32_t B, int32_t C, int32_t NF, int32_t order, dlip_stream_t stream) {
+  DLIP_CHECK_ARG(x && y && B > 0 && C > 0 && NF > 0 && (order == 1 || order == 2));
+  const long long rows = (long long)B * C;
+  hipLaunchKernelGGL(flen ? delta_kernel<true> : delta_kernel<false>, dim3(dlip_grid1d(rows * NF, kGridCap)), dim3(256), 0,
+                     dlip_hip_stream(stream), x, flen, y, rows, C, NF, order);
   return dlip_launch_status();
 }
 
 extern "C" int dlip_delta_nct_f32(const float* x, float* y, int32_t B, int32_t C, int32_t NF, int32_t order,
                                   dlip_stream_t stream) {
-  DLIP_CHECK_ARG(x && y && B > 0 && C > 0 && NF > 0 && (order == 1 || order == 2));
-  const long long rows = (long long)B * C;
-  hipLaunchKernelGGL(delta_kernel, dim3(dlip_grid1d(rows * NF, kGridCap)), dim3(256), 0, dlip_hip_stream(stream), x, y, rows, C, NF,
-                     order);
-  return dlip_launch_status();
+  return delta_nct(x, nullptr, y, B, C, NF, order, stream);
+}
+
+extern "C" int dlip_delta_nct_ragged_f32(const float* x, const int32_t* frame_lengths, float* y, int32_t B, int32_t C, int32_t NF,
+                                         int32_t order, dlip_stream_t stream) {
+  DLIP_CHECK_ARG(frame_lengths);
+  return delta_nct(x, frame_lengths, y, B, C, NF, order, stream);
 }
 
 extern "C" int dlip_crop_normalize_u8(const uint8_t* x, const int32_t* clip_params, const int32_t* lengths, int32_t T, float* y,

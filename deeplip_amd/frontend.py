@@ -1,6 +1,7 @@
 """GPU-side preprocessing in front of the encoders.
 
-``AudioFrontend`` turns waveforms [B, S] into the [B, F, T] feature tensors the reference's loaders
+``AudioFrontend`` turns waveforms [B, S] (with ``lengths``: a zero-padded batch of utterances of differing duration, each row
+computed as if run alone -- DESIGN.md section 4c) into the [B, F, T] feature tensors the reference's loaders
 produce with python_speech_features (models/audio_models/datasets.py:65-83: ``mfcc`` / ``fbank`` /
 ``logfbank`` with winlen 0.025, winstep 0.01; conf/fusion_config.yaml:8-40), followed by the
 per-utterance mean/variance normalisation of datasets.py:52-53.  The 512-point real DFT, the mel
@@ -118,21 +119,39 @@ class AudioFrontend:
     def feat_dim(self) -> int:
         return (3 if self.delta else 1) * (self.num_cep if self.feat_type == "mfcc" else self.num_bin)
 
-    def __call__(self, wave: torch.Tensor) -> torch.Tensor:
-        """wave [B, S] float32 (cuda) -> features [B, F, NF] float32."""
+    def __call__(self, wave: torch.Tensor, lengths=None):
+        """wave [B, S] float32 (cuda) -> features [B, F, NF] float32.
+
+        ``lengths`` (B sample counts in [1, S] as a sequence / numpy array, or an int32 device tensor [B]): a RAGGED batch -- wave is
+        padded to S samples and row b holds lengths[b] of them.  Returns ``(features [B, F, NF], frame_lengths int32 device [B])`` with
+        NF = num_frames(S): row b's columns [0, frame_lengths[b]) equal ``self(wave[b:b+1, :lengths[b]])``, the reference's
+        one-utterance-at-a-time loop (train_fusion.py:334-349, train_audio.py:343-373), whatever the padding holds (it is never read:
+        the reference pre-emphasises the utterance's own samples and zero-pads afterwards); columns past them are zeros.  Host lengths
+        are validated here; a device vector is clamped by the kernels and never read on the host, and nothing below synchronises, so
+        the call records into a step plan (deeplip_amd/plan.py) and ``frame_lengths`` is the encoders' ``lengths``."""
         wave = wave.contiguous().float()
         B, S = wave.shape
+        lens = ops.lengths_i32(lengths, wave.device, n=B, lo=1, hi=S)           # None: the rectangular batch, no length is read
         NF = num_frames(S, self.frame_len, self.frame_step)
         R = B * NF
         pw = ops._empty((R, self.nbp), wave.device)
         energy = ops._empty((R,), wave.device)
+        geom = (self.frame_len, self.frame_step, self.nfft)
         if self.dft == "fft64":
-            check(lib().dlip_powspec_wave_fft64_f32(ptr(wave), ptr(pw), ptr(energy), B, S, NF, self.frame_len, self.frame_step, self.nfft,
-                                                    float(self.preemph), self.nb, self.nbp, stream_handle()), "dlip_powspec_wave_fft64_f32")
+            if lens is None:
+                check(lib().dlip_powspec_wave_fft64_f32(ptr(wave), ptr(pw), ptr(energy), B, S, NF, *geom, float(self.preemph), self.nb,
+                                                        self.nbp, stream_handle()), "dlip_powspec_wave_fft64_f32")
+            else:
+                check(lib().dlip_powspec_wave_fft64_ragged_f32(ptr(wave), ptr(lens), ptr(pw), ptr(energy), B, S, NF, *geom, float(self.preemph),
+                                                               self.nb, self.nbp, stream_handle()), "dlip_powspec_wave_fft64_ragged_f32")
         else:
             frames = ops._empty((R, self.nfft), wave.device)
-            check(lib().dlip_frame_preemph_f32(ptr(wave), ptr(frames), B, S, NF, self.frame_len, self.frame_step, self.nfft,
-                                               self.preemph, stream_handle()), "dlip_frame_preemph_f32")
+            if lens is None:
+                check(lib().dlip_frame_preemph_f32(ptr(wave), ptr(frames), B, S, NF, *geom, self.preemph, stream_handle()),
+                      "dlip_frame_preemph_f32")
+            else:
+                check(lib().dlip_frame_preemph_ragged_f32(ptr(wave), ptr(lens), ptr(frames), B, S, NF, *geom, self.preemph, stream_handle()),
+                      "dlip_frame_preemph_ragged_f32")
             if self.dft == "direct64":
                 check(lib().dlip_powspec_dft64_f32(ptr(frames), ptr(pw), ptr(energy), R, self.nb, self.nbp, self.nfft, stream_handle()),
                       "dlip_powspec_dft64_f32")
@@ -140,7 +159,10 @@ class AudioFrontend:
                 spec = ops.linear(frames, self.w_dft)                          # [R, 2*nb]  (DFT as GEMM)
                 check(lib().dlip_powspec_f32(ptr(spec), ptr(pw), ptr(energy), R, self.nb, self.nbp, self.nfft, stream_handle()),
                       "dlip_powspec_f32")
-        mel = torch.zeros((R, self.nfp), device=wave.device, dtype=torch.float32)
+        if lens is None:
+            mel = torch.zeros((R, self.nfp), device=wave.device, dtype=torch.float32)
+        else:                   # (a buffer of the plan's arena when a step is being recorded: nothing is allocated under capture)
+            mel = ops._empty((R, self.nfp), wave.device).zero_()
         ops.conv_nhwc(pw.view(1, 1, R, self.nbp), self.w_mel.view(self.num_bin, 1, 1, self.nbp),
                       out=mel.view(1, 1, R, self.nfp))                         # [R, num_bin] (+ zero pad)
         feat, C_, en = mel, self.num_bin, None
@@ -153,13 +175,25 @@ class AudioFrontend:
             C_ = self.num_cep
             en = energy if self.energy else None                               # appendEnergy: c0 = log(energy)
         out = ops._empty((B, C_, NF), wave.device)
-        check(lib().dlip_cmvn_nct_f32(ptr(feat), ptr(en), ptr(out), B, NF, C_, feat.shape[1], int(self.normalize),
-                                      stream_handle()), "dlip_cmvn_nct_f32")
+        nf = None
+        if lens is None:
+            check(lib().dlip_cmvn_nct_f32(ptr(feat), ptr(en), ptr(out), B, NF, C_, feat.shape[1], int(self.normalize),
+                                          stream_handle()), "dlip_cmvn_nct_f32")
+        else:
+            nf = ops._empty((B,), wave.device, torch.int32)
+            check(lib().dlip_wave_frame_lengths_i32(ptr(lens), ptr(nf), B, S, self.frame_len, self.frame_step, stream_handle()),
+                  "dlip_wave_frame_lengths_i32")
+            check(lib().dlip_cmvn_nct_ragged_f32(ptr(feat), ptr(en), ptr(nf), ptr(out), B, NF, C_, feat.shape[1], int(self.normalize),
+                                                 stream_handle()), "dlip_cmvn_nct_ragged_f32")
         if self.delta:
             out3 = ops._empty((B, 3 * C_, NF), wave.device)
-            check(lib().dlip_delta_nct_f32(ptr(out), ptr(out3), B, C_, NF, 2, stream_handle()), "dlip_delta_nct_f32")
-            return out3
-        return out
+            if lens is None:
+                check(lib().dlip_delta_nct_f32(ptr(out), ptr(out3), B, C_, NF, 2, stream_handle()), "dlip_delta_nct_f32")
+            else:
+                check(lib().dlip_delta_nct_ragged_f32(ptr(out), ptr(nf), ptr(out3), B, C_, NF, 2, stream_handle()),
+                      "dlip_delta_nct_ragged_f32")
+            out = out3
+        return out if lens is None else (out, nf)
 
 
 class VideoFrontend:

@@ -25,7 +25,8 @@ class SyntheticAVSet:
     of audio frames in ``audio_range`` and 1 .. ``clips_per_utt`` clips, each with its own length in ``video_range``, all drawn
     from a generator keyed by (key, seed).  ``audio_len`` [N], ``clip_len`` [Nc], ``clip_ptr`` [N+1] (CSR: the clips of
     utterance u are clip_ptr[u] .. clip_ptr[u+1]) describe the set; ``audio_item`` / ``clip_item`` yield single items at their own
-    length (the reference's loop), ``audio_padded`` / ``clips_padded`` the zero-padded batches of pad_packed_collate."""
+    length (the reference's loop), ``audio_padded`` / ``clips_padded`` the zero-padded batches of pad_packed_collate.  ``wave_len`` /
+    ``wave_item`` / ``waves_padded``: the same utterances as waveforms, for pipelines that start in front of the feature extraction."""
 
     def __init__(self, n_spk: int, utt_per_spk: int, clips_per_utt: int = 1, video_frames: int = 29,
                  audio_dim: int = 24, audio_frames: int = 300, key: str = "synth", seed: int = wg.DEFAULT_SEED,
@@ -88,6 +89,36 @@ class SyntheticAVSet:
         items = [self.clip_item(c)[None] for c in clip_idx]                      # [1,T_c,88,88]
         L = np.array([it.shape[1] for it in items], dtype=np.int32)
         return pad_stack(items, int(T or L.max()), axis=1, rows=rows), L
+
+    # ---- waveforms: what the GPU front-end starts from (deeplip_amd/frontend.py; the reference's loaders read .wav files and compute
+    #      the features per utterance on the host, models/audio_models/datasets.py:65-83).  A generator key of their own
+    #      (key + ".wave"): the feature tensors above keep their values.
+    def wave_len(self, frame_len: int = 400, frame_step: int = 160) -> np.ndarray:
+        """Sample counts [N] int64: utterance u has a duration that frames into exactly ``audio_len[u]`` frames of ``frame_len`` /
+        ``frame_step`` samples (sigproc.framesig) and, the single-frame ones apart, does not end on the frame grid -- its last frame
+        is partly zero padding, as a real recording's is."""
+        r = np.random.Generator(np.random.PCG64([int(self.seed) & 0xFFFFFFFF, zlib.crc32((self.key + ".wave").encode())]))
+        cut = r.integers(0, frame_step, size=len(self.utts)).astype(np.int64)             # samples short of the frame grid
+        full = frame_len + (self.audio_len - 1) * frame_step
+        return np.where(self.audio_len > 1, full - cut, np.maximum(frame_len - cut, 1)).astype(np.int64)
+
+    def wave_item(self, i: int, frame_len: int = 400, frame_step: int = 160) -> np.ndarray:
+        """[wave_len[i]] float32: three partials whose frequencies and weights belong to the speaker, phases and noise to the utterance."""
+        n = int(self.wave_len(frame_len, frame_step)[i])
+        gen = lambda tag: np.random.Generator(np.random.PCG64([int(self.seed) & 0xFFFFFFFF, zlib.crc32(f"{self.key}.wave.{tag}".encode())]))
+        spk, utt = gen(f"spk{self.utts[i][0]}"), gen(f"utt{i}")
+        w = 2.0 * np.pi * spk.uniform(0.005, 0.2, size=3)                                # radians per sample
+        amp = spk.uniform(0.2, 1.0, size=3)
+        t = np.arange(n, dtype=np.float64)
+        x = (amp[:, None] * np.sin(w[:, None] * t[None, :] + utt.uniform(0.0, 2.0 * np.pi, size=3)[:, None])).sum(0)
+        return (x + 0.1 * self.session * utt.standard_normal(n)).astype(np.float32)
+
+    def waves_padded(self, idx, S: int = None, rows: int = None, frame_len: int = 400, frame_step: int = 160) -> Tuple[np.ndarray, np.ndarray]:
+        """-> (wave [n, S] float32 zero-padded, sample_lengths int32 [n])"""
+        from .ragged import pad_stack
+        items = [self.wave_item(i, frame_len, frame_step) for i in idx]
+        L = np.array([it.shape[0] for it in items], dtype=np.int32)
+        return pad_stack(items, int(S or L.max()), axis=0, rows=rows), L
 
     # ---- rectangular batches (every item the same length)
     def audio(self, idx) -> np.ndarray:

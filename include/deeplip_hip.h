@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define DLIP_ABI_VERSION 56
+#define DLIP_ABI_VERSION 57
 #define DLIP_LIFT_WORDS 4098   /* a gradient's power-of-two lift: (2^e, 2^-e), then 2^-e repeated 2048 times (the post_scale vector of
                                   the convolution that consumes the lifted gradient); while it is formed the words behind the pair
                                   hold one maximum per workgroup of the producing pass */
@@ -142,7 +142,9 @@ int dlip_conv2_nhwc_f16x3(const dlip_conv_desc* d, const float* x, const float* 
  * clips: frames * Ho*Wo of the last convolution; utterances: input frames - the frames the valid convolutions consume),
  * so one length vector in HBM serves the whole step and a recorded plan replays with new lengths.  The valid rows'
  * values equal the unpadded run's (a valid convolution / a per-frame trunk never reads past them; the stem's pre-pass
- * zeroes the padding frames, dlip_stem3d_pool_f16x3). */
+ * zeroes the padding frames, dlip_stem3d_pool_f16x3).  The speech side starts one stage earlier since ABI 57: a zero-padded batch of
+ * waveforms + sample counts goes through the front-end's ragged entry points (dlip_wave_frame_lengths_i32 and the *_ragged_f32
+ * kernels further down), which hand the frame counts on as this very length vector. */
 int64_t dlip_conv_pool_partial_bytes(const dlip_conv_desc* d, int32_t* tile_rows);
 int dlip_conv_pool_f16x3(const dlip_conv_desc* d, const float* x, const void* w_split, const float* w_scale,
                          const float* bias, const float* residual, const float* slope, const float* post_scale,
@@ -1005,6 +1007,39 @@ int dlip_time_tail_zero_f32(float* x, const int32_t* lengths, int32_t shift, int
                             dlip_stream_t stream);
 int dlip_avgpool_time_ragged_f32(const float* x, const int32_t* lengths, int32_t shift, float* y, int32_t N, int32_t H, int32_t W,
                                  int32_t C, dlip_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 57) RAGGED BATCHES through the audio front-end: a zero-padded batch of WAVEFORMS x [B,S] + one sample count per row, every row
+ * computed as if it had been run alone -- what replaces calling the front-end once per utterance at batch 1 (the reference's loop,
+ * train_fusion.py:334-349, train_audio.py:343-373) in front of the ragged encoders above.  sample_len (device int32 [B]) is clamped
+ * to [1, S] by every kernel that reads it and never read on the host: a recorded plan replays with a new vector.  With
+ * S_b = clamp(sample_len[b], 1, S) and NF_b = 1 if S_b <= frame_len else 1 + ceil((S_b - frame_len) / frame_step) (sigproc.framesig):
+ *
+ * dlip_wave_frame_lengths_i32: frame_lengths[b] = NF_b, on the device -- the length vector the ragged CMVN / delta kernels below and
+ *   the encoders (dlip_conv_pool_f16x3's group_len, dlip_time_tail_zero_f32) read.
+ * dlip_frame_preemph_ragged_f32 / dlip_powspec_wave_fft64_ragged_f32: the rectangular entry points with the row ending at S_b.  Frame
+ *   f < NF_b is computed from samples < S_b exactly as the rectangular kernel computes it for an S_b-sample signal; samples >= S_b
+ *   read as zero AFTER the pre-emphasis (sigproc.preemphasis runs on the S_b-sample signal, framesig zero-pads its result: position
+ *   S_b holds 0, not -preemph * x[S_b - 1]) and are never loaded, so the caller's padding may hold anything.  Frames f >= NF_b: all
+ *   zero (frames), resp. no FFT, a zero power-spectrum row and energy 0 -- finite input for the dense mel / log / DCT products.
+ * dlip_cmvn_nct_ragged_f32: mean and population standard deviation over the row's own NF_b frames (summed in frame order by one
+ *   thread in fp64: the order depends on NF_b alone, not on the neighbours or on NF; no atomics), (x - mean) / (std + 2e-12)
+ *   (datasets.py:52-53); NF_b = 1 gives zeros as numpy does; columns t >= NF_b are written as exact zeros.
+ * dlip_delta_nct_ragged_f32: python_speech_features.delta's edge padding repeats the row's own last valid frame NF_b - 1; columns
+ *   t >= NF_b are zeros in all 1 + order blocks.
+ * frame_lengths (device int32 [B]) is clamped to [1, NF].  Full lengths give the rectangular entry points' results bit for bit.
+ * ------------------------------------------------------------------------------------------ */
+int dlip_wave_frame_lengths_i32(const int32_t* sample_len, int32_t* frame_lengths, int32_t B, int64_t S, int32_t frame_len,
+                                int32_t frame_step, dlip_stream_t stream);
+int dlip_frame_preemph_ragged_f32(const float* x, const int32_t* sample_len, float* frames, int32_t B, int32_t S, int32_t NF,
+                                  int32_t frame_len, int32_t frame_step, int32_t nfft, float preemph, dlip_stream_t stream);
+int dlip_powspec_wave_fft64_ragged_f32(const float* x, const int32_t* sample_len, float* pw, float* energy, int64_t B, int64_t S,
+                                       int32_t NF, int32_t frame_len, int32_t frame_step, int32_t nfft, double preemph, int32_t NB,
+                                       int32_t NBp, dlip_stream_t stream);
+int dlip_cmvn_nct_ragged_f32(const float* feat, const float* energy, const int32_t* frame_lengths, float* y, int32_t B, int32_t NF,
+                             int32_t C, int32_t ldf, int32_t normalize, dlip_stream_t stream);
+int dlip_delta_nct_ragged_f32(const float* x, const int32_t* frame_lengths, float* y, int32_t B, int32_t C, int32_t NF, int32_t order,
+                              dlip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Step plans.  The reference drives its encoders from a Python loop, one utterance and one torch.nn layer

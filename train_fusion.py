@@ -60,7 +60,7 @@ class Trainer(object):
             d = opts
             *path, leaf = k.split(".")
             for p in path:
-                d = d[p]
+                d = d.setdefault(p, {}) if p == "python_data_config" else d[p]      # (an optional section: older configs lack it)
             d[leaf] = v
         self.train_opts, self.model_opts = opts["train"], opts["model"]
         self.data_opts, self.test_opts = opts["data"], opts["test"]
@@ -94,7 +94,14 @@ class Trainer(object):
 
         d = self.data_opts
         acfg = self.model_opts["audio_config"]
-        feat_dim = acfg[acfg["arch"]]["input_dim"]
+        # the features' section of the reference's config (conf/fusion_config.yaml:8-40 upstream).  test_from_waves (build-owned, off by
+        # default): the test lists' speech side starts from waveforms -- GPU front-end + encoder per length-bucketed batch
+        # (deeplip_amd/extract.py, waves=True) where the reference computes each utterance's features on the host (train_fusion.py:334-338)
+        self.feat_opts = dict(d.get("python_data_config") or {})
+        self.test_from_waves = bool(self.feat_opts.get("test_from_waves", False))
+        # the resnet takes [B,1,F,T] with F = the feature dimension of the data section (its input_dim counts channels)
+        feat_dim = acfg[acfg["arch"]]["input_dim"] if acfg["arch"] != "resnet" else int(self.feat_opts.get("feat_dim", 40))
+        self.feat_dim = feat_dim
         self.trainset = SyntheticAVSet(d["n_spk"], d["utt_per_spk"], d["clips_per_utt"], d["video_frames"], feat_dim,
                                        d["audio_frames"], key="train")
         # test lists: utterances and clips of differing duration, as the reference's are (data.test_ragged; its loop takes each
@@ -112,6 +119,9 @@ class Trainer(object):
 
         if acfg["arch"] in ("tdnn", "etdnn"):
             self.model_audio = tdnn.SpeakerEmbNet(acfg)
+        elif acfg["arch"] == "resnet":                                       # train_audio.py:64-66 (`import models.resnet`)
+            import models.resnet as resnet
+            self.model_audio = resnet.SpeakerEmbNet(acfg)
         else:
             raise NotImplementedError("Other models are not implemented!")
         vcfg = self.model_opts["video_config"]
@@ -455,12 +465,32 @@ class Trainer(object):
             self._extractor[1].close()
             self._extractor = None
         if self._extractor is None:
-            ex = RaggedExtractor(lambda a, l: self.model_audio.extract_embedding(a, lengths=l)[0],          # train_fusion.py:338
+            arch = self.model_opts["audio_config"]["arch"]
+            audio_fn = lambda a, l: self.model_audio.extract_embedding(a, lengths=l)[0]                    # train_fusion.py:338
+            geom = {}
+            if self.test_from_waves:
+                fe = self._test_frontend(arch)
+
+                def audio_fn(wave, sample_len):  # front-end and encoder in one recorded step; the frame lengths stay on the device
+                    feats, n_frames = fe(wave, sample_len)
+                    return self.model_audio.extract_embedding(feats, lengths=n_frames)[0]
+                geom = {"wave_geometry": (fe.frame_len, fe.frame_step)}
+            ex = RaggedExtractor(audio_fn,
                                  lambda v, l: self.model_video.embed(v, lengths=l),                        # :346-348 (mean over T)
-                                 self.device, batch=batch, audio_min_frames=self.model_audio.frames_consumed() + 2,
-                                 max_arena_bytes=int(self.test_opts.get("max_arena_gb", 64)) << 30)
+                                 self.device, batch=batch, audio_min_frames=1 if arch == "resnet" else self.model_audio.frames_consumed() + 2,
+                                 max_arena_bytes=int(self.test_opts.get("max_arena_gb", 64)) << 30, **geom)
             self._extractor = (key, ex)
         return self._extractor[1]
+
+    def _test_frontend(self, arch):
+        """The loaders' feature extraction (data.python_data_config; models/audio_models/datasets.py:65-83) as the GPU front-end, with as
+        many coefficients / bands as the speech encoder takes."""
+        from deeplip_amd.frontend import AudioFrontend
+        o = self.feat_opts
+        feat = o.get("feat_type", "mfcc" if arch != "resnet" else "fbank")
+        return AudioFrontend(feat, rate=int(o.get("rate", 16000)), win_len=float(o.get("win_len", 0.025)), win_shift=float(o.get("win_shift", 0.01)),
+                             nfft=int(o.get("nfft", 512)), num_cep=self.feat_dim, device=self.device,
+                             **({} if feat == "mfcc" else {"num_bin": self.feat_dim}))
 
     def close(self):
         """Release the recorded plans (extraction arenas, the training pipeline) this trainer holds."""
@@ -488,6 +518,8 @@ class Trainer(object):
         n_loc = hi - lo
         xa = torch.empty((n_loc, D), device=self.device)
         xv = torch.empty((n_loc, D), device=self.device)
+        if self.test_from_waves and not dataset.ragged:
+            raise ValueError("data.python_data_config.test_from_waves needs data.test_ragged: true (the rectangular lists are fed features)")
         if n_loc and dataset.ragged:
             # utterances / clips of differing length: length-bucketed batches, one recorded plan per padded shape, every row
             # equal to the reference's one-at-a-time result (deeplip_amd/extract.py, tests/test_ragged_gpu.py)
@@ -495,7 +527,7 @@ class Trainer(object):
             hc = None
             if self._host_cache is not None:           # test.cache_host_batches: a second pass over a list re-uses its pinned batches
                 hc = self._host_cache.setdefault(id(dataset), {})
-            xa, xv = ex.run(dataset, lo, hi, D, u8=u8, host_cache=hc)                                      # :349 inside (clip-group mean)
+            xa, xv = ex.run(dataset, lo, hi, D, u8=u8, host_cache=hc, waves=self.test_from_waves)          # :349 inside (clip-group mean)
             self.extract_stats = dict(ex.stats)
         elif n_loc:
             cpu = dataset.clips                        # clips per utterance (constant over a synthetic set)
@@ -637,6 +669,9 @@ def main():
     ap.add_argument("--eager-step", action="store_true",
                     help="--mode train: issue every launch of every step from Python instead of replaying the recorded encoder plan + "
                          "the recorded head step (train.graph_step: false)")
+    ap.add_argument("--from-waves", action="store_true",
+                    help="av_test / av_fusion: feed the speech encoder from the test lists' waveforms through the GPU front-end "
+                         "(data.python_data_config.test_from_waves: true; needs data.test_ragged)")
     arith.add_argument(ap)
     args = ap.parse_args()
     ov = {}
@@ -645,6 +680,8 @@ def main():
         ov[k] = yaml.safe_load(v)
     if args.eager_step:
         ov["train.graph_step"] = False
+    if args.from_waves:
+        ov["data.python_data_config.test_from_waves"] = True
     rc = _self_launch(args.gpus, args.config, ov, "train.gpus_id")
     if rc is not None:
         sys.exit(rc)
