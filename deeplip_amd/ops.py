@@ -832,6 +832,100 @@ def pair_cosine(emb: Tensor, idx_a: Tensor, idx_b: Tensor, mode: int = 0, eps: f
     return out
 
 
+# ---- cohort score normalisation (csrc/score_norm_ops.hip, ABI 58) ----
+TOPK_MAX_N = 32768                      # a row of the score matrix lives in LDS (dlip_topk_stats_f32)
+SCORE_NORM_MODES = {"z": 0, "t": 1, "s": 2}
+_COHORT_SCRATCH_BYTES = 256 << 20       # cohort_stats: the score-matrix chunk stays at or below this
+
+
+def topk_stats(s: Tensor, k: int, n: Optional[int] = None) -> Tuple[Tensor, Tensor]:
+    """s [R, ld] -> (mean [R], sd [R]): mean and population deviation (divisor k) of the k largest of each row's first ``n``
+    values (default: all ld of them; columns [n, ld) are never read).  Exact selection, ties at the k-th value counted exactly,
+    fp64 statistics rounded to fp32 once.  1 <= k <= n <= 32768."""
+    if s.dim() != 2:
+        raise ValueError("topk_stats: s must be [R, ld]")
+    R, ld = s.shape
+    n = ld if n is None else int(n)
+    if not 1 <= n <= ld:
+        raise ValueError(f"topk_stats: n={n} outside [1, {ld}]")
+    if n > TOPK_MAX_N:
+        raise ValueError(f"topk_stats: rows of {n} values exceed the kernel's {TOPK_MAX_N}")
+    if not 1 <= int(k) <= n:
+        raise ValueError(f"topk_stats: k={k} outside [1, {n}]")
+    if R < 1:
+        raise ValueError("topk_stats: no rows")
+    _req(s, "s")                          # behind the shape checks: those are refused the same way on a box without a GPU
+    mean, sd = _empty((R,), s.device), _empty((R,), s.device)
+    check(lib().dlip_topk_stats_f32(ptr(s), R, n, ld, int(k), ptr(mean), ptr(sd), stream_handle()), "dlip_topk_stats_f32")
+    return mean, sd
+
+
+def score_norm(scores: Tensor, idx_a: Tensor, idx_b: Tensor, mu: Tensor, sd: Tensor, mode: str = "s", eps: float = 1e-6,
+               weight: float = 1.0, out: Optional[Tensor] = None) -> Tensor:
+    """weight * z(scores[i]) with za = (s - mu[idx_a[i]]) / max(sd[idx_a[i]], eps), zb likewise through idx_b; mode "z" -> za,
+    "t" -> zb, "s" -> (za + zb) / 2.  With ``out`` the result is ADDED to it (pair_cosine's convention: the halves of a score
+    fusion are normalised separately and summed)."""
+    _req(scores, "scores"); _req(idx_a, "idx_a", torch.int32); _req(idx_b, "idx_b", torch.int32); _req(mu, "mu"); _req(sd, "sd")
+    if mode not in SCORE_NORM_MODES:
+        raise ValueError(f"score_norm: mode {mode!r} is none of {sorted(SCORE_NORM_MODES)}")
+    n = scores.numel()
+    if idx_a.numel() != n or idx_b.numel() != n:
+        raise ValueError(f"score_norm: {n} scores, {idx_a.numel()} / {idx_b.numel()} indices")
+    if mu.numel() != sd.numel() or mu.numel() < 1 or n < 1:
+        raise ValueError(f"score_norm: mu has {mu.numel()} entries, sd {sd.numel()}, {n} scores")
+    acc = out is not None
+    if out is None:
+        out = _empty((n,), scores.device)
+    _req(out, "out")
+    if out.numel() != n:
+        raise ValueError(f"score_norm: out has {out.numel()} entries for {n} scores")
+    check(lib().dlip_score_norm_f32(ptr(scores), ptr(idx_a), ptr(idx_b), n, ptr(mu), ptr(sd), mu.numel(), SCORE_NORM_MODES[mode],
+                                    eps, weight, int(acc), ptr(out), stream_handle()), "dlip_score_norm_f32")
+    return out
+
+
+def cohort_chunk_rows(n_rows: int, n_cohort: int, chunk_rows: Optional[int] = None) -> int:
+    """Rows of the embedding table per chunk of cohort_stats: the caller's, else as many as keep the fp32 score-matrix chunk
+    [rows, n_cohort] at or below 256 MiB."""
+    if chunk_rows is None:
+        chunk_rows = max(1, _COHORT_SCRATCH_BYTES // (4 * n_cohort))
+    if int(chunk_rows) < 1:
+        raise ValueError(f"cohort_stats: chunk_rows={chunk_rows}")
+    return min(int(chunk_rows), n_rows)
+
+
+def cohort_stats(emb: Tensor, cohort: Tensor, top_k: Optional[int] = None, chunk_rows: Optional[int] = None) -> Tuple[Tensor, Tensor]:
+    """emb [U, D], cohort [Nc, D] -> (mu [U], sd [U]): per row of ``emb`` the mean and population deviation of its ``top_k``
+    largest cosine scores against the cohort (None: all Nc).  Both tables are L2-normalised (eps 1e-12, as all_pairs_cosine does);
+    ``emb`` is then walked in row chunks, each one exact-fp32 GEMM into a scratch block followed by one topk_stats launch.  The
+    scratch comes from ``_empty`` (a StepPlan's arena while one records) and nothing here synchronises or reads the device."""
+    if emb.dim() != 2 or cohort.dim() != 2:
+        raise ValueError("cohort_stats: emb must be [U, D] and cohort [Nc, D]")
+    (U, D), (Nc, Dc) = emb.shape, cohort.shape
+    if D != Dc:
+        raise ValueError(f"cohort_stats: embeddings have D={D}, the cohort D={Dc}")
+    if D % 4:
+        raise ValueError("cohort_stats: embedding dimension must be a multiple of 4")
+    if U < 1 or Nc < 1:
+        raise ValueError(f"cohort_stats: {U} embeddings, {Nc} cohort rows")
+    if Nc > TOPK_MAX_N:
+        raise ValueError(f"cohort_stats: a cohort of {Nc} exceeds the selection kernel's {TOPK_MAX_N} (DESIGN.md 3f)")
+    k = Nc if top_k is None else int(top_k)
+    if not 1 <= k <= Nc:
+        raise ValueError(f"cohort_stats: top_k={top_k} outside [1, {Nc}]")
+    rows = cohort_chunk_rows(U, Nc, chunk_rows)
+    _req(emb, "emb"); _req(cohort, "cohort")      # behind the shape checks (as topk_stats)
+    e, c = l2_normalize(emb), l2_normalize(cohort)
+    mu, sd = _empty((U,), emb.device), _empty((U,), emb.device)
+    scratch = _empty((rows, Nc), emb.device)
+    for r0 in range(0, U, rows):
+        r = min(rows, U - r0)
+        linear(e[r0:r0 + r], c, out=scratch[:r].view(1, 1, r, Nc))
+        check(lib().dlip_topk_stats_f32(ptr(scratch), r, Nc, Nc, k, mu.data_ptr() + 4 * r0, sd.data_ptr() + 4 * r0, stream_handle()),
+              "dlip_topk_stats_f32")
+    return mu, sd
+
+
 def logits_argmax(e: Tensor, W: Tensor, bias: Optional[Tensor] = None, cosine: bool = False) -> Tuple[Tensor, Tensor]:
     _req(e, "e"); _req(W, "W"); _req(bias, "bias")
     B, D = e.shape

@@ -115,6 +115,164 @@ def feature_fusion_scores(audio_emb, video_emb, idx_a, idx_b) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------------------
+# Cohort score normalisation (build-owned: the reference scores raw cosines only)
+#   C [Nc, D] cohort, E [U, D] table; S[u, j] = <l2n(E[u]), l2n(C[j])>; top(u) = the K largest of S[u, :]; mu[u] / sd[u] = mean and
+#   POPULATION deviation (divisor K) of top(u); z_a = (s - mu[a]) / max(sd[a], eps), z_b likewise, for the UNCHANGED trial score s.
+# ------------------------------------------------------------------------------------------
+# kind -> (mode of ops.score_norm, whether the cohort is cut to the top_k nearest)
+SCORE_NORM_KINDS = {"znorm": ("z", False), "tnorm": ("t", False), "snorm": ("s", False), "asnorm": ("s", True)}
+DEFAULT_TOP_K = 300
+
+
+def score_norm_kind(kind) -> Optional[str]:
+    """``None`` / "none" / "" -> None (no normalisation), else the lower-cased name; an unknown name is a ValueError."""
+    if kind is None or str(kind).lower() in ("none", ""):
+        return None
+    k = str(kind).lower()
+    if k not in SCORE_NORM_KINDS:
+        raise ValueError(f"score normalisation {kind!r} is none of {sorted(SCORE_NORM_KINDS)} (or 'none')")
+    return k
+
+
+def cohort_top_k(kind: str, top_k, n_cohort: int) -> Optional[int]:
+    """The K of a normalisation over a cohort of ``n_cohort``: None (all of it) for znorm / tnorm / snorm; for asnorm ``top_k``
+    (None: 300) clipped to the cohort's size.  top_k < 1 is a ValueError."""
+    if not SCORE_NORM_KINDS[kind][1]:
+        return None
+    k = DEFAULT_TOP_K if top_k is None else int(top_k)
+    if k < 1:
+        raise ValueError(f"{kind}: top_k={top_k} must be at least 1")
+    return min(k, int(n_cohort))
+
+
+class TrialRows:
+    """Which rows of an [n_rows, D] table a trial list uses: ``rows`` (int64 device vector, ascending; None when every row is
+    used) and the trial indices renumbered into that compacted table."""
+
+    def __init__(self, rows: Optional[torch.Tensor], idx_a: torch.Tensor, idx_b: torch.Tensor, n_rows: int):
+        self.rows, self.idx_a, self.idx_b, self.n_rows = rows, idx_a, idx_b, n_rows
+        self.n_used = n_rows if rows is None else int(rows.numel())
+
+
+def _used_rows_host(ia: np.ndarray, ib: np.ndarray, n_rows: int):
+    """Host half of trial_rows: (ascending used rows or None when all are, renumbered ia, renumbered ib); indices outside
+    [0, n_rows) are a ValueError."""
+    ia, ib = np.asarray(ia, dtype=np.int64).ravel(), np.asarray(ib, dtype=np.int64).ravel()
+    if ia.size != ib.size or ia.size == 0:
+        raise ValueError(f"trial indices: {ia.size} and {ib.size} entries")
+    lo, hi = min(ia.min(), ib.min()), max(ia.max(), ib.max())
+    if lo < 0 or hi >= n_rows:
+        raise ValueError(f"trial indices span [{lo}, {hi}], the table has rows [0, {n_rows})")
+    used = np.unique(np.concatenate([ia, ib]))
+    if used.size == n_rows:
+        return None, ia.astype(np.int32), ib.astype(np.int32)
+    remap = np.full(n_rows, -1, dtype=np.int64)
+    remap[used] = np.arange(used.size)
+    return used, remap[ia].astype(np.int32), remap[ib].astype(np.int32)
+
+
+def trial_rows(idx_a: torch.Tensor, idx_b: torch.Tensor, n_rows: int) -> TrialRows:
+    """The rows a trial list uses, worked out ON THE HOST (the indices are read back once: not inside a StepPlan -- build it
+    before and pass it as ``rows=``).  Validates the indices against the table."""
+    used, ra, rb = _used_rows_host(idx_a.cpu().numpy(), idx_b.cpu().numpy(), n_rows)
+    if used is None:
+        return TrialRows(None, idx_a, idx_b, n_rows)
+    dev = idx_a.device
+    return TrialRows(torch.from_numpy(used).to(dev), torch.from_numpy(ra).to(dev), torch.from_numpy(rb).to(dev), n_rows)
+
+
+def _check_tables(what: str, emb: torch.Tensor, cohort: torch.Tensor) -> None:
+    """Shape refusals shared by the normalised scorings, before anything is launched."""
+    if emb.dim() != 2 or cohort.dim() != 2:
+        raise ValueError(f"{what}: the table must be [U, D] and the cohort [Nc, D]")
+    if emb.shape[1] != cohort.shape[1]:
+        raise ValueError(f"{what}: embeddings have D={emb.shape[1]}, the cohort D={cohort.shape[1]}")
+    if emb.shape[1] % 4:
+        raise ValueError(f"{what}: embedding dimension must be a multiple of 4")
+    if not 1 <= cohort.shape[0] <= ops.TOPK_MAX_N:
+        raise ValueError(f"{what}: a cohort of {cohort.shape[0]} rows is outside [1, {ops.TOPK_MAX_N}]")
+
+
+def normalised_scores(emb: torch.Tensor, idx_a: torch.Tensor, idx_b: torch.Tensor, cohort: torch.Tensor, kind: str = "asnorm",
+                      top_k: Optional[int] = DEFAULT_TOP_K, eps: float = 1e-6, scores: Optional[torch.Tensor] = None,
+                      rows: Optional[TrialRows] = None, weight: float = 1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Trial scores normalised against a cohort [Nc, D]: ``kind`` "znorm" (z_a), "tnorm" (z_b), "snorm" ((z_a + z_b) / 2, whole
+    cohort) or "asnorm" (the same over each utterance's ``top_k`` nearest cohort rows; default 300, clipped to Nc).  ``scores``
+    are the raw trial scores (default: ``cosine_scores(emb, idx_a, idx_b)``) and stay what they are; the cohort statistics are
+    computed only for the table rows the trials use (``rows`` = ``trial_rows(idx_a, idx_b, U)``; None: worked out here, which
+    reads the indices back to the host once).  ``weight`` / ``out``: as ops.score_norm (added into ``out``)."""
+    kind = score_norm_kind(kind)
+    if kind is None:
+        raise ValueError("normalised_scores: kind is 'none'; call cosine_scores for raw scores")
+    _check_tables("normalised_scores", emb, cohort)
+    k = cohort_top_k(kind, top_k, cohort.shape[0])
+    for t, n in ((emb, "emb"), (cohort, "cohort"), (idx_a, "idx_a"), (idx_b, "idx_b")):
+        if not t.is_cuda:
+            raise DeepLipHipError(f"normalised_scores: {n} must be a CUDA (ROCm) tensor; there is no CPU path")
+    if rows is None:
+        rows = trial_rows(idx_a, idx_b, emb.shape[0])
+    elif rows.n_rows != emb.shape[0]:
+        raise ValueError(f"normalised_scores: rows= was built for a table of {rows.n_rows} rows, this one has {emb.shape[0]}")
+    if scores is None:
+        scores = cosine_scores(emb, idx_a, idx_b)
+    used = emb
+    if rows.rows is not None:       # a gather of rows (a copy, no arithmetic) into a block of the arena
+        used = torch.index_select(emb, 0, rows.rows, out=ops._empty((rows.n_used, emb.shape[1]), emb.device))
+    mu, sd = ops.cohort_stats(used, cohort, top_k=k)
+    return ops.score_norm(scores, rows.idx_a, rows.idx_b, mu, sd, mode=SCORE_NORM_KINDS[kind][0], eps=eps, weight=weight, out=out)
+
+
+def score_fusion_normalised(audio_emb, video_emb, idx_a, idx_b, audio_cohort, video_cohort, kind: str = "asnorm",
+                            top_k: Optional[int] = DEFAULT_TOP_K, eps: float = 1e-6, video_idx=None) -> torch.Tensor:
+    """score_fusion with each modality's cosine normalised against THAT modality's cohort, then 0.5 / 0.5: the raw halves are
+    exactly score_fusion's (sklearn cosine of the speech rows, F.cosine_similarity(eps=1e-8) of the lip rows).  ``video_idx`` =
+    (idx_a, idx_b) into the lip table when it is indexed apart from the speech table."""
+    va, vb = (idx_a, idx_b) if video_idx is None else video_idx
+    sa = ops.pair_cosine(audio_emb, idx_a, idx_b, mode=0)
+    sv = ops.pair_cosine(video_emb, va, vb, mode=1, eps=1e-8)
+    s = normalised_scores(audio_emb, idx_a, idx_b, audio_cohort, kind, top_k, eps, scores=sa, weight=0.5)
+    return normalised_scores(video_emb, va, vb, video_cohort, kind, top_k, eps, scores=sv, weight=0.5, out=s)
+
+
+def feature_fusion_scores_normalised(audio_emb, video_emb, idx_a, idx_b, audio_cohort, video_cohort, kind: str = "asnorm",
+                                     top_k: Optional[int] = DEFAULT_TOP_K, eps: float = 1e-6) -> torch.Tensor:
+    """feature_fusion_scores normalised once, on the fused scores: the cohort's two halves (row j of both = cohort member j) are
+    fused by the same znorm_cat as the table."""
+    if audio_cohort.shape[0] != video_cohort.shape[0]:
+        raise ValueError(f"feature fusion: {audio_cohort.shape[0]} speech and {video_cohort.shape[0]} lip cohort rows (row j of both "
+                         "is one cohort member)")
+    fused = ops.znorm_cat(video_emb.contiguous(), audio_emb.contiguous(), biased=True)
+    cohort = ops.znorm_cat(video_cohort.contiguous(), audio_cohort.contiguous(), biased=True)
+    return normalised_scores(fused, idx_a, idx_b, cohort, kind, top_k, eps)
+
+
+def speaker_groups(speakers: Sequence) -> Tuple[np.ndarray, np.ndarray, list]:
+    """Host half of speaker_mean_cohort: (order, group_ptr, labels) -- ``order`` sorts the rows by label (stable: rows of one
+    speaker keep their order), ``group_ptr`` [n_spk + 1] int32 bounds each speaker's run in that order, ``labels`` are the
+    distinct labels in sorted order."""
+    lab = np.asarray(list(speakers))
+    if lab.ndim != 1 or lab.size == 0:
+        raise ValueError("speaker_mean_cohort: one speaker label per row")
+    order = np.argsort(lab, kind="stable")
+    s = lab[order]
+    starts = np.r_[0, np.flatnonzero(s[1:] != s[:-1]) + 1]
+    return order.astype(np.int64), np.r_[starts, s.size].astype(np.int32), s[starts].tolist()
+
+
+def speaker_mean_cohort(table_or_emb, speakers: Sequence) -> torch.Tensor:
+    """[N, D] rows + one speaker label per row -> [n_spk, D] speaker means, speakers in sorted label order: rows are sorted by
+    label on the host, gathered, and reduced on the device by the group-mean kernel."""
+    emb = table_or_emb.emb if isinstance(table_or_emb, EmbeddingTable) else table_or_emb
+    order, gptr, _ = speaker_groups(speakers)
+    if emb.dim() != 2 or emb.shape[0] != order.size:
+        raise ValueError(f"speaker_mean_cohort: {order.size} labels for a table of shape {tuple(emb.shape)}")
+    if not emb.is_cuda:
+        raise DeepLipHipError("speaker_mean_cohort: the means run on the GPU (group-mean kernel); pass a CUDA (ROCm) table")
+    rows = torch.index_select(emb.contiguous(), 0, torch.from_numpy(order).to(emb.device))
+    return ops.group_mean(rows, torch.from_numpy(gptr).to(emb.device))
+
+
+# ------------------------------------------------------------------------------------------
 # EER on the host (20 000 scalars; the reference does this with sklearn + scipy on the CPU too)
 # ------------------------------------------------------------------------------------------
 def roc_curve(y_true: np.ndarray, y_score: np.ndarray, pos_label: int = 1):

@@ -17,6 +17,15 @@ bodies -- and each can be overridden per call by keyword (``trial_path=``, ``emb
 (``DLIP_TRIAL_LIST``, ``DLIP_EMB_DIR``, ``DLIP_VIDEO_EMBEDDING_DIR``, ``DLIP_VIDEO_TRIAL_LIST``, ``DLIP_PLDA_MODEL``).
 The positional signature stays the reference's: ONE argument.
 
+Score normalisation (build-owned).  The cosine and fusion entry points take ``score_norm=`` ("znorm", "tnorm",
+"snorm", "asnorm"; None / "none": the reference's raw scores, bit for bit, and no cohort is read), ``top_k=`` (asnorm's cohort
+cut, default 300), ``cohort_dir=`` (a tree of ``.npy`` files, one embedding each, as ``save_npy_tree`` writes: the cohort of the
+speech / fused store the function reads) and, the fusion variants, ``cohort_video_dir=`` (the same for the lip embeddings; for
+feature fusion file j of both trees, in sorted order, is cohort member j).  They resolve like the paths -- keyword, ``set_paths``,
+environment (``DLIP_SCORE_NORM``, ``DLIP_SCORE_NORM_TOP_K``, ``DLIP_COHORT_DIR``, ``DLIP_COHORT_VIDEO_DIR``) -- which is how a
+trainer that calls ``fn(log_time)`` reaches them.  The PLDA entry points take the keywords and refuse a normalisation (cohort
+LLRs are not built).
+
 There is no CPU path: the tables live on the current ROCm device and the scores come from ``dlip_*`` launches.
 """
 from __future__ import annotations
@@ -56,13 +65,16 @@ AUDIO_DEFAULTS["eer_cos_lomgrid"] = dict(trial="data/trial/A_lomgrid_trial_2w", 
 AUDIO_DEFAULTS["eer_cos_grid"] = dict(trial="data/trial/A_grid_trial_2w", sub="test_xv_grid")
 
 _ENV = {"trial": "DLIP_TRIAL_LIST", "emb_dir": "DLIP_EMB_DIR", "video_dir": "DLIP_VIDEO_EMBEDDING_DIR",
-        "video_trial": "DLIP_VIDEO_TRIAL_LIST", "plda": "DLIP_PLDA_MODEL"}
+        "video_trial": "DLIP_VIDEO_TRIAL_LIST", "plda": "DLIP_PLDA_MODEL",
+        "score_norm": "DLIP_SCORE_NORM", "top_k": "DLIP_SCORE_NORM_TOP_K", "cohort_dir": "DLIP_COHORT_DIR",
+        "cohort_video_dir": "DLIP_COHORT_VIDEO_DIR"}
 _process_paths: Dict[str, Dict[str, str]] = {}
 
 
 def set_paths(name: Optional[str] = None, **paths) -> None:
     """Process-wide override of a function's default files (``name=None``: of every function), e.g.
-    ``set_paths("eer_cos_lomgrid", trial="exp/run/trials.txt")``.  Keys: trial, emb_dir, video_dir, video_trial, plda.
+    ``set_paths("eer_cos_lomgrid", trial="exp/run/trials.txt")``.  Keys: trial, emb_dir, video_dir, video_trial, plda, and the
+    score normalisation's score_norm, top_k, cohort_dir, cohort_video_dir.
     ``set_paths(name)`` without keywords clears the override."""
     key = name or "*"
     if not paths:
@@ -98,6 +110,38 @@ def _resolve(name: str, defaults: Dict[str, str], exp_dir: str, kw: Dict[str, Op
                 d = alt
         out["emb_dir"] = d
     return out
+
+
+def _norm_request(what: str, p: Dict[str, str], video: bool = False):
+    """The resolved score normalisation of a call: None (raw scores; nothing else is looked at) or (kind, top_k or None) with the
+    cohort directories it needs checked -- a missing one is a ValueError that names the path, before any device work."""
+    kind = scoring.score_norm_kind(p.get("score_norm"))
+    if kind is None:
+        return None
+    top_k = p.get("top_k")
+    top_k = None if top_k is None or str(top_k).lower() in ("none", "") else int(top_k)
+    if top_k is not None and top_k < 1:
+        raise ValueError(f"{what}: top_k={top_k} must be at least 1")
+    for key, kw, env in (("cohort_dir", "cohort_dir=", "DLIP_COHORT_DIR"),) + \
+            ((("cohort_video_dir", "cohort_video_dir=", "DLIP_COHORT_VIDEO_DIR"),) if video else ()):
+        d = p.get(key)
+        if d is None:
+            raise ValueError(f"{what}: score_norm={kind!r} needs a cohort: pass {kw}, call scoring_entry.set_paths({key}=...) or set {env}")
+        if not os.path.isdir(d):
+            raise ValueError(f"{what}: score_norm={kind!r}: the cohort directory {d!r} ({kw[:-1]}) does not exist")
+    return kind, top_k
+
+
+def load_cohort(root: str, dev) -> scoring.EmbeddingTable:
+    """A cohort directory -- a tree of ``.npy`` files, one embedding each (what ``save_npy_tree`` writes) -- read once, over a
+    sorted walk, into one device-resident table."""
+    files = []
+    for d, subdirs, names in os.walk(root):
+        subdirs.sort()
+        files += [os.path.relpath(os.path.join(d, n), root) for n in sorted(names) if n.endswith(".npy")]
+    if not files:
+        raise ValueError(f"the cohort directory {root!r} holds no .npy file")
+    return scoring.EmbeddingTable.load_npy_tree(root, files, device=dev)
 
 
 def _device(device) -> torch.device:
@@ -183,17 +227,28 @@ def make_entry_points(defaults: Dict[str, Dict[str, str]]) -> Dict[str, Callable
     """The ten functions of one ``utils`` module, bound to that module's default paths."""
 
     def _cos(name):
-        def f(exp_dir, *, trial_path=None, emb_dir=None, device=None, return_scores=False):
-            p = _resolve(name, defaults[name], exp_dir, dict(trial=trial_path, emb_dir=emb_dir))
+        def f(exp_dir, *, trial_path=None, emb_dir=None, device=None, return_scores=False, score_norm=None, top_k=None,
+              cohort_dir=None):
+            p = _resolve(name, defaults[name], exp_dir, dict(trial=trial_path, emb_dir=emb_dir, score_norm=score_norm, top_k=top_k,
+                                                             cohort_dir=cohort_dir))
+            norm = _norm_request(name, p)
             dev = _device(device)
             y, pairs = _read_trials(p["trial"])
             table, ia, ib = _audio_table(p, pairs, dev)
-            return _finish(y, scoring.cosine_scores(table.emb, ia, ib), return_scores)      # utils.py:262
+            s = scoring.cosine_scores(table.emb, ia, ib)                                    # utils.py:262
+            if norm is not None:
+                s = scoring.normalised_scores(table.emb, ia, ib, load_cohort(p["cohort_dir"], dev).emb, norm[0], norm[1], scores=s)
+            return _finish(y, s, return_scores)
         return f
 
     def _plda(name):
-        def f(exp_dir, *, trial_path=None, emb_dir=None, plda_path=None, device=None, return_scores=False):
-            p = _resolve(name, defaults[name], exp_dir, dict(trial=trial_path, emb_dir=emb_dir, plda=plda_path))
+        def f(exp_dir, *, trial_path=None, emb_dir=None, plda_path=None, device=None, return_scores=False, score_norm=None,
+              top_k=None, cohort_dir=None):
+            p = _resolve(name, defaults[name], exp_dir, dict(trial=trial_path, emb_dir=emb_dir, plda=plda_path, score_norm=score_norm,
+                                                             top_k=top_k, cohort_dir=cohort_dir))
+            if scoring.score_norm_kind(p.get("score_norm")) is not None:
+                raise ValueError(f"{name}: score_norm={p['score_norm']!r} was requested, but cohort normalisation of PLDA "
+                                 "log-likelihood ratios is not built (cosine and fusion entry points only)")
             dev = _device(device)
             model = load_plda(p["plda"])                                                    # utils.py:286
             y, pairs = _read_trials(p["trial"])
@@ -202,9 +257,12 @@ def make_entry_points(defaults: Dict[str, Dict[str, str]]) -> Dict[str, Callable
         return f
 
     def _scorefusion(name):
-        def f(exp_dir, *, trial_path=None, emb_dir=None, video_dir=None, video_trial_path=None, device=None, return_scores=False):
+        def f(exp_dir, *, trial_path=None, emb_dir=None, video_dir=None, video_trial_path=None, device=None, return_scores=False,
+              score_norm=None, top_k=None, cohort_dir=None, cohort_video_dir=None):
             p = _resolve(name, defaults[name], exp_dir, dict(trial=trial_path, emb_dir=emb_dir, video_dir=video_dir,
-                                                             video_trial=video_trial_path))
+                                                             video_trial=video_trial_path, score_norm=score_norm, top_k=top_k,
+                                                             cohort_dir=cohort_dir, cohort_video_dir=cohort_video_dir))
+            norm = _norm_request(name, p, video=True)
             dev = _device(device)
             y, pairs = _read_trials(p["trial"])
             table, ia, ib = _audio_table(p, pairs, dev)
@@ -215,18 +273,30 @@ def make_entry_points(defaults: Dict[str, Dict[str, str]]) -> Dict[str, Callable
                                  "the two score lists element by element)")
             vt = _video_table(p["video_dir"], _unique([u for ab in vpairs for u in ab]), dev)
             va, vb = vt.trial_indices(vpairs)
+            if norm is not None:     # each half against its own modality's cohort, then 0.5 / 0.5
+                s = scoring.score_fusion_normalised(table.emb, vt.emb, ia, ib, load_cohort(p["cohort_dir"], dev).emb,
+                                                    load_cohort(p["cohort_video_dir"], dev).emb, norm[0], norm[1], video_idx=(va, vb))
+                return _finish(y, s, return_scores)
             s = ops.pair_cosine(table.emb, ia, ib, mode=0, weight=0.5)                      # 0.5 * sklearn cosine (:341-345)
             s = ops.pair_cosine(vt.emb, va, vb, mode=1, eps=1e-8, weight=0.5, out=s)        # + 0.5 * F.cosine_similarity (:372-378)
             return _finish(y, s, return_scores)
         return f
 
     def _featurefusion(name):
-        def f(exp_dir, *, trial_path=None, emb_dir=None, video_dir=None, device=None, return_scores=False):
-            p = _resolve(name, defaults[name], exp_dir, dict(trial=trial_path, emb_dir=emb_dir, video_dir=video_dir))
+        def f(exp_dir, *, trial_path=None, emb_dir=None, video_dir=None, device=None, return_scores=False, score_norm=None,
+              top_k=None, cohort_dir=None, cohort_video_dir=None):
+            p = _resolve(name, defaults[name], exp_dir, dict(trial=trial_path, emb_dir=emb_dir, video_dir=video_dir,
+                                                             score_norm=score_norm, top_k=top_k, cohort_dir=cohort_dir,
+                                                             cohort_video_dir=cohort_video_dir))
+            norm = _norm_request(name, p, video=True)
             dev = _device(device)
             y, pairs = _read_trials(p["trial"])
             table, ia, ib = _audio_table(p, pairs, dev)
             vt = _video_table(p["video_dir"], [_pattern(p["pattern"], u) for u in table.utt_ids], dev)   # row i <-> audio row i
+            if norm is not None:     # the cohort fused by the same znorm_cat, one normalisation of the fused scores
+                s = scoring.feature_fusion_scores_normalised(table.emb, vt.emb, ia, ib, load_cohort(p["cohort_dir"], dev).emb,
+                                                             load_cohort(p["cohort_video_dir"], dev).emb, norm[0], norm[1])
+                return _finish(y, s, return_scores)
             return _finish(y, scoring.feature_fusion_scores(table.emb, vt.emb, ia, ib), return_scores)   # utils.py:465-473
         return f
 

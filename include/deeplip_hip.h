@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define DLIP_ABI_VERSION 57
+#define DLIP_ABI_VERSION 58
 #define DLIP_LIFT_WORDS 4098   /* a gradient's power-of-two lift: (2^e, 2^-e), then 2^-e repeated 2048 times (the post_scale vector of
                                   the convolution that consumes the lifted gradient); while it is formed the words behind the pair
                                   hold one maximum per workgroup of the producing pass */
@@ -361,7 +361,28 @@ int dlip_pair_cosine_f32(const float* emb, int32_t N, int32_t D, const int32_t* 
                          const int32_t* idx_b, float* score, int32_t n_trials, int32_t mode,
                          float eps, float weight, int32_t accumulate, dlip_stream_t stream);
 
-/* logits[b,k] = <normalize(e[b]), normalize(W[k])> (cosine logits, loss.py:44) when cosine != 0,
+/* (ABI 58) COHORT SCORE NORMALISATION of the trial scores above (Z-/T-/S-norm, adaptive S-norm with a top-K cohort).  The reference
+ * scores raw cosines only (models/fusion_models/utils.py:251-283, :331-522); the normalised forms are build-owned, DESIGN.md 3f.
+ *
+ * dlip_topk_stats_f32: s is a score matrix of R rows with pitch ld (floats): row r is s[r*ld .. r*ld+N), columns [N, ld) are never
+ * read (a GEMM's padded output width).  mean[r] / sd[r] = mean and POPULATION deviation (divisor K) of the K largest values of row r,
+ * ties at the K-th value counted exactly: the selection is exact (radix select over order-preserving keys of the row held in LDS),
+ * both statistics accumulate in fp64 (the deviation centred on the mean, from the on-chip copy) and are rounded to fp32 once.
+ * 1 <= K <= N <= 32768 (a 32768-float row is 128 KiB of the CU's 160 KiB LDS), ld >= N; anything else, a null pointer or R <= 0 is
+ * DLIP_EINVAL before any launch.  Inputs are taken to be finite; a non-finite value cannot hang or fault the kernel (the keys stay
+ * totally ordered), what it yields is unspecified. */
+int dlip_topk_stats_f32(const float* s, int32_t R, int32_t N, int64_t ld, int32_t K, float* mean, float* sd,
+                        dlip_stream_t stream);
+
+/* out[i] = weight * z(s[i]) (accumulate != 0: out[i] += ...), with za = (s[i] - mu[idx_a[i]]) / max(sd[idx_a[i]], eps), zb likewise
+ * through idx_b, and z = za (mode 0, Z-norm), zb (mode 1, T-norm) or (za + zb) / 2 (mode 2, S-norm).  mu / sd [U] are the per-utterance
+ * cohort statistics of dlip_topk_stats_f32; weight / accumulate as in dlip_pair_cosine_f32, so the two halves of a score fusion are
+ * normalised separately and added.  out may be s.  An index outside [0, U) is the caller's error (its trial comes out NaN, nothing is
+ * read out of bounds); hosts that hold the indices validate them first. */
+int dlip_score_norm_f32(const float* s, const int32_t* idx_a, const int32_t* idx_b, int32_t n, const float* mu, const float* sd,
+                        int32_t U, int32_t mode, float eps, float weight, int32_t accumulate, float* out, dlip_stream_t stream);
+
+/* logits[b,k] =<normalize(e[b]), normalize(W[k])> (cosine logits, loss.py:44) when cosine != 0,
  * else <e[b], W[k]> + bias[k] (loss.py:14); argmax[b] = first index of the row maximum
  * (torch.max(logits,1)[1]; train_fusion.py:296), int64.  K <= 1024. */
 int dlip_logits_argmax_f32(const float* e, const float* W, const float* bias, float* logits,

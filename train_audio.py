@@ -127,6 +127,7 @@ class Trainer(object):
         self.optim = self._make_sgd(groups, o)
         self._steps = None          # ShapeKeyedSteps, built with the first recorded step
         self._extractor = None      # one RaggedExtractor for every list and epoch of this trainer (its recorded plans are kept)
+        self._cohort = None         # (key, EmbeddingTable): the score-normalisation cohort of the current weights (build_cohort)
         self.lr_scheduler = torch.optim.lr_scheduler.MultiStepLR(self.optim, milestones=self.train_opts["lr_decay_step"], gamma=0.1)
         self.epoch, self.current_epoch = self.train_opts["epoch"], 0
         self.log_time = time.asctime(time.localtime(time.time())).replace(" ", "_")[4:]
@@ -397,6 +398,53 @@ class Trainer(object):
         if ddist.active():
             torch.distributed.barrier()
 
+    def score_norm(self):
+        """The run's score normalisation (build-owned): ``test.score_norm`` (none | znorm | tnorm | snorm | asnorm,
+        default none), ``test.score_norm_top_k`` (asnorm's cohort cut, default 300) and ``test.cohort`` (speaker_mean: one row per
+        training speaker, the mean of that speaker's x-vectors; utterances: every training x-vector) -> (kind or None, top_k, form)."""
+        kind = scoring.score_norm_kind(self.test_opts.get("score_norm", "none"))
+        form = str(self.test_opts.get("cohort", "speaker_mean"))
+        if form not in ("speaker_mean", "utterances"):
+            raise ValueError("test.cohort: {!r} is neither 'speaker_mean' nor 'utterances'".format(form))
+        return kind, int(self.test_opts.get("score_norm_top_k", 300)), form
+
+    def build_cohort(self, batch=64):
+        """The normalisation cohort of this run, from the training list's x-vectors (``extract_train_xv``): speaker means over the
+        training set's own labels, or the utterances themselves; L2-normalised where the test x-vectors are; rank 0 writes it
+        under exp/<run>/cohort_xv/ (one file per row).  None when no normalisation is set.  Kept until the weights change."""
+        from deeplip_amd import holders, packing
+        kind, _, form = self.score_norm()
+        if kind is None:
+            return None
+        key = (form, holders.PACK_GEN[0], packing.state_version(self.model, self.device))
+        if self._cohort is not None and self._cohort[0] == key:
+            return self._cohort[1]
+        train = self.extract_train_xv(batch)
+        if form == "speaker_mean":
+            lab = self.trainset.labels(np.arange(len(self.trainset)))
+            emb = scoring.speaker_mean_cohort(train.emb, lab)
+            ids = ["spk{:05d}.npy".format(int(l)) for l in scoring.speaker_groups(lab)[2]]
+        else:
+            emb, ids = train.emb, train.utt_ids
+        if self.train_opts["loss"] != "CrossEntropy":       # as _xvectors normalises the test lists
+            emb = ops.l2_normalize(emb)
+        table = scoring.EmbeddingTable(ids, emb)
+        self._store("cohort_xv", table)
+        self._cohort = (key, table)
+        return table
+
+    def _point_score_norm(self, fns):
+        """Point the cosine entry points ``fns`` at this run's normalisation and cohort store (they are called with one argument)."""
+        from deeplip_amd import scoring_entry as se
+        kind, top_k, _ = self.score_norm()
+        if kind is None:
+            return
+        self.build_cohort()
+        if not self.test_opts.get("write_store", True):
+            return
+        for fn in fns:
+            se.set_paths(fn, score_norm=kind, top_k=top_k, cohort_dir="exp/{}/cohort_xv".format(self.log_time))
+
     def extract_test_xv(self, batch=64):
         """x-vectors of the test set, L2-normalised (train_audio.py:343-373) -> EmbeddingTable (+ exp/<run>/test_xv/)."""
         self._load_for_extract()
@@ -444,6 +492,7 @@ class Trainer(object):
             torch.distributed.barrier()
         for fn in (("eer",) if name == "eer" else ("eer_cos_" + name, "eer_plda_" + name)):
             se.set_paths(fn, trial=path)
+        self._point_score_norm(("eer",) if name == "eer" else ("eer_cos_" + name,))     # the PLDA entry points refuse one
 
     def train_plda(self, n_principal_components=20):
         """train_audio.py:298-341: x-vectors of the LombardGRID development list -> exp/<run>/dev_xv_lomgrid/<basename>.npy, labels
@@ -498,7 +547,11 @@ class Trainer(object):
     def eer(self):
         y, pairs = synthetic_trials(self.voxtestset, self.data_opts["trials"], self.data_opts["trial_targets"])
         ia, ib = self.table.trial_indices(pairs)
-        return scoring.eer_from_scores(y, scoring.cosine_scores(self.table.emb, ia, ib).cpu().numpy())
+        s = scoring.cosine_scores(self.table.emb, ia, ib)
+        kind, top_k, _ = self.score_norm()
+        if kind is not None:
+            s = scoring.normalised_scores(self.table.emb, ia, ib, self.build_cohort().emb, kind, top_k, scores=s)
+        return scoring.eer_from_scores(y, s.cpu().numpy())
 
 
 def _self_launch(gpus, config, overrides, key="train.gpus_id"):
