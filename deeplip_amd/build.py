@@ -1,7 +1,7 @@
 """Build libdeeplip_hip.so (gfx950) in-tree with hipcc.
 
     python -m deeplip_amd.build            # rebuild if sources are newer than the library
-    python -m deeplip_amd.build --lab      # libdeeplip_hip_lab.so: -DDLIP_LAB (experimental tiles, in-kernel stamps);
+    python -m deeplip_amd.build --lab      # libdeeplip_hip_lab.so: -DDLIP_LAB (the product kernels with in-kernel stamps);
                                            # used by tools/ through DLIP_LIB_PATH, never by the product
 
 hipcc cross-compiles without a GPU.  The library lands in deeplip_amd/lib/ so that it travels
@@ -137,7 +137,7 @@ if __name__ == "__main__":
 # What profiles/traffic_latest.json (PMC bytes per launch of the dominant kernel) is stamped with, and what bench.py compares the
 # stamp to: the sources the dominant kernel's translation unit is compiled from.  Entry points added elsewhere (an ABI bump) do not
 # change that kernel; an edit of a header it includes does.
-DOMINANT_KERNEL_SOURCES = ("conv_igemm_f16x3_dma.hip", "conv_dma_common.h", "conv_dma_hooks.h", "conv_dma_hook_consts.inc", "conv_common.h", "dlip_common.h")
+DOMINANT_KERNEL_SOURCES = ("conv_igemm_f16x3_dma.hip", "conv_dma_common.h", "conv_dma_hooks.h", "conv_dispatch.h", "conv_common.h", "dlip_common.h")
 
 
 def dominant_kernel_sha() -> str:

@@ -16,11 +16,8 @@ int dlip_dbg_value[DLIP_DBG_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1
 
 extern "C" int dlip_debug_set(int32_t key, int32_t value) {
   DLIP_CHECK_ARG(key >= 0 && key < DLIP_DBG_COUNT);
-#ifndef DLIP_LAB
-  // key 7 (the rows kernel's general mode: built, measured slower than the ring kernel on the trunk, round 4) exists in the lab
-  // library only; resetting it (-1 / 0) is always fine
+  // key 7 is reserved (it forced the rows kernel's general mode, retired: EXPERIMENTS.md R8.2); resetting it (-1 / 0) is always fine
   DLIP_CHECK_ARG(!(key == DLIP_DBG_ROWS2D && value > 0));
-#endif
   dlip_dbg_value[key] = value;
   return DLIP_OK;
 }

@@ -1,9 +1,8 @@
 // The convolution files' calls into each other: the ONE declaration of every function that one of them defines and another
 // calls.  Included by the callers AND by the defining files, so a definition that drifts from its prototype is a compile error
 // (the names are extern "C": nothing is mangled, a mismatch would link and read garbage).
-// conv_igemm_f16x3_dma.hip may not include this header yet: the traffic profile is stamped with its bytes (build.DOMINANT_KERNEL_SOURCES); it keeps three local prototypes.
-// `args` is a const ConvArgs*, type-erased: ConvArgs lives in an unnamed namespace of conv_common.h (a dominant-kernel source too),
-// so it crosses a translation-unit boundary as an opaque pointer.
+// `args` is a const ConvArgs*, type-erased: ConvArgs lives in an unnamed namespace of conv_common.h, so it crosses a
+// translation-unit boundary as an opaque pointer.
 #pragma once
 #include <stddef.h>
 #include "deeplip_hip.h"
@@ -20,14 +19,9 @@ DLIP_INTERNAL int dlip_conv_split_workspace(void* stream, size_t slab_floats, fl
 // conv_win_f16x3.hip: the window kernel
 DLIP_INTERNAL int dlip_conv_win_ok(const void* args);
 DLIP_INTERNAL int dlip_conv_f16x3_win_launch(const void* args, void* stream, int out_split);
-// conv_rows_f16x3.hip: the rows kernel ...
+// conv_rows_f16x3.hip: the rows kernel
 DLIP_INTERNAL int dlip_conv_rows_ok(const void* args);
 DLIP_INTERNAL int dlip_conv_f16x3_rows_launch(const void* args, void* stream, int epi);
 DLIP_INTERNAL int dlip_conv_rows_plan(const dlip_conv_desc* d, int* bm);
 DLIP_INTERNAL long long dlip_conv_rows_tiles(const dlip_conv_desc* d);
 DLIP_INTERNAL int dlip_conv_rows_pool_plan(const dlip_conv_desc* d, int* bm);
-// ... and its general mode (compiled under -DDLIP_LAB only: the product library's three decline every launch)
-DLIP_INTERNAL int dlip_conv_rows2d_ok(const void* args, int epi);
-DLIP_INTERNAL int dlip_conv_rows2d_plan(const dlip_conv_desc* d, int c2, int* bm);
-DLIP_INTERNAL int dlip_conv_f16x3_rows2d_launch(const void* args, void* stream, int epi);
-DLIP_INTERNAL int dlip_conv_rows_declined(void);

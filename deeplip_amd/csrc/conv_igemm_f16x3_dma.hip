@@ -30,6 +30,7 @@
 // Fragment layout, accumulator initialisation and the LDS image are those of conv_igemm_f16x3.hip.
 #include "conv_common.h"
 #include "conv_dma_common.h"
+#include "conv_dispatch.h"
 #include "conv_dma_hooks.h"
 #include <algorithm>
 #include <cstdio>
@@ -103,12 +104,9 @@ struct ConvGroups {
 //   0  fp32 rows of y;  1  split-format rows of y (reports |v| >= 65520 to the range-status word);
 //   2  no y: per tile and row-group segment, the column sums of v and v^2 in fp64 (a.pool)
 // DUAL: the reduction continues over a second source x2 (1x1, strided) after the taps of x.
-// VAR: 0 in the product except bit 12 (filters of more than 32 taps: below).  The lab build (conv_dma_hooks.h) uses bit 2 (every
-// wave issues its pieces at the top of the slice), 6 (256x256 tile), 7 (window mode), 9 / 11 (ping-pong without priority / with the
-// group-major MFMA order), 10 (the lock-step loop on 256x128: the ping-pong loop's reference).  The experiments of rounds 2 / 3 that
-// lost -- a static priority for the second half of the waves, that half issuing half a slice late, the halves taking turns as a
-// slice's issuer, the pieces spread one by one behind MFMA quarter-groups -- are in DESIGN.md section 4 with their numbers and in
-// the history of this file, no longer in its text.
+// VAR: 0, or 4096 (bit 12: filters of more than 32 taps, below).  The other bits selected experiments that lost; they are retired
+// (EXPERIMENTS.md R8.2; DESIGN.md section 4 has their numbers).  The parameter stays an int in this position:
+// deeplip_amd/pmc.py and the committed profiles parse the kernel's name by position.
 struct StreamKG : StreamK {
   ConvGroups grp;
 };
@@ -138,18 +136,15 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N, OCC) void conv_igemm_f16x3_d
   constexpr int STAGE_B = (BM + BN) * ROWB;
   constexpr int LDK = 32;             // dwords per LDS row
   constexpr int PF = NSTAGE - 1;      // slices in flight ahead of the one being multiplied
-#include "conv_dma_hook_consts.inc"   // product: `constexpr bool WIN = false; constexpr int RING_W = 0;`
-  constexpr int RING = WIN ? RING_W : NSTAGE * STAGE_B;   // bytes; the epilogue parameter table (5 x BN floats) sits behind it
-  // The eight-wave 256x128 tile runs the ping-pong main loop (below); VAR bit 10 keeps the lock-step loop (lab reference),
-  // bit 9 drops the matrix phase's priority (lab), bit 11 keeps the group-major MFMA order inside the matrix phase (lab).
-  constexpr bool PINGPONG = BM == 256 && BN == 128 && NW == 8 && NSTAGE == 3 && (VAR & ~(512 | 2048 | 4096)) == 0;
+  constexpr int RING = NSTAGE * STAGE_B;   // bytes; the epilogue parameter table (5 x BN floats) sits behind it
+  static_assert(VAR == 0 || VAR == 4096, "VAR: bit 12 only");
+  // The eight-wave 256x128 tile runs the ping-pong main loop (below); the four-wave tiles the lock-step loop.
+  constexpr bool PINGPONG = BM == 256 && BN == 128 && NW == 8 && NSTAGE == 3;
   // VAR bit 12: filters with MORE THAN 32 TAPS.  The product's per-row validity mask has one bit per tap (R S <= 32); a weight
   // gradient run as a convolution -- input x as [C][H][W][N], "filter" = the output gradient as [K][Ho][Wo][N], the images as the
   // reduction's channels (deeplip_amd.autograd_video.wgrad_as_conv) -- has Ho x Wo taps (484 on layer 1).  This variant keeps each
   // row's window origin (hi0, wi0) in registers and tests a tap's row / column against the image when the piece is issued.
   constexpr bool BIGTAPS = (VAR & 4096) != 0;
-  constexpr bool PP_PRIO = (VAR & 512) == 0;
-  constexpr bool PP_ACC_MAJOR = (VAR & 2048) == 0;   // (bit 11: the group-major MFMA order, lab reference)
   constexpr int AQ = A_PER, BQ = B_PER;   // rows a lane addresses: its own passes
   extern __shared__ __attribute__((aligned(16))) float smem[];
 
@@ -267,9 +262,6 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N, OCC) void conv_igemm_f16x3_d
 
     f32x4 acc[MI][NI];
 #define DLIP_FENCE() __builtin_amdgcn_sched_barrier(0)
-    if constexpr (WIN) {
-#include "conv_dma_hook_window.inc"
-    } else {
     // Per-row gather state, branch-free: byte offset of the row's window origin and a bit per filter tap
     // that stays inside the image (columns and rows tested separately: R + S steps, not R x S).
     int a_off[AQ];
@@ -449,7 +441,6 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N, OCC) void conv_igemm_f16x3_d
     // ---- main loop: per slice 3 groups of MI x NI instructions.  Group order lo*hi, hi*hi, hi*lo:
     // the last group needs neither the activation-lo nor the weight-hi fragments, so the NEXT slice's first
     // group's fragments are read (behind the barrier) into registers the tail of this slice does not use. ----
-#include "conv_dma_hook_tile256.inc"   // product: nothing
     if constexpr (PINGPONG) {
       // PING-PONG main loop (round 3; the eight-wave 256x128 tile).  The loop below (still what the four-wave tiles run) keeps the
       // two waves of a SIMD in LOCK STEP: both read their
@@ -485,38 +476,23 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N, OCC) void conv_igemm_f16x3_d
         for (int ni = 0; ni < NI; ++ni) fbl[ni] = *reinterpret_cast<const f16x8*>(Bw + ni * 16 * LDK + klo);
       };
       auto mfma_all = [&]() {
-        if constexpr (PP_PRIO) __builtin_amdgcn_s_setprio(2);   // the matrix phase outranks its SIMD partner's load phase
-        if constexpr (PP_ACC_MAJOR) {
-          // ACCUMULATOR-MAJOR: the three products of one accumulator back to back.  A wave that is ALONE on its SIMD's matrix pipe
-          // -- as it is here -- issues v_mfma_f32_16x16x32_f16 every 16.4 cycles when consecutive instructions accumulate into the
-          // same registers, and only every 24.4 when each goes to another accumulator (tools/probes/mfma_rate.hip: 16 accumulators
-          // group by group 24.43, one chain 16.58, chains of three 16.42 cycles per MFMA; two waves per SIMD reach 16.3 either
-          // way, which is why the lock-step loop never saw it).  Per accumulator the order is still lo*hi, hi*hi, hi*lo: same bits.
+        __builtin_amdgcn_s_setprio(2);   // the matrix phase outranks its SIMD partner's load phase
+        // ACCUMULATOR-MAJOR: the three products of one accumulator back to back.  A wave that is ALONE on its SIMD's matrix pipe
+        // -- as it is here -- issues v_mfma_f32_16x16x32_f16 every 16.4 cycles when consecutive instructions accumulate into the
+        // same registers, and only every 24.4 when each goes to another accumulator (tools/probes/mfma_rate.hip: 16 accumulators
+        // group by group 24.43, one chain 16.58, chains of three 16.42 cycles per MFMA; two waves per SIMD reach 16.3 either
+        // way, which is why the lock-step loop never saw it).  Per accumulator the order is still lo*hi, hi*hi, hi*lo: same bits.
 #pragma unroll
-          for (int mi = 0; mi < MI; ++mi) {
+        for (int mi = 0; mi < MI; ++mi) {
 #pragma unroll
-            for (int ni = 0; ni < NI; ++ni) {
-              acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fbh[ni], fal[mi], acc[mi][ni], 0, 0, 0);
-              acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fbh[ni], fah[mi], acc[mi][ni], 0, 0, 0);
-              acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fbl[ni], fah[mi], acc[mi][ni], 0, 0, 0);
-            }
-            DLIP_FENCE();
+          for (int ni = 0; ni < NI; ++ni) {
+            acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fbh[ni], fal[mi], acc[mi][ni], 0, 0, 0);
+            acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fbh[ni], fah[mi], acc[mi][ni], 0, 0, 0);
+            acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fbl[ni], fah[mi], acc[mi][ni], 0, 0, 0);
           }
-        } else {
-#pragma unroll
-        for (int grp = 0; grp < 3; ++grp) {
-#pragma unroll
-          for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni) {
-              const f16x8 av = grp == 0 ? fal[mi] : fah[mi];
-              const f16x8 bv = grp == 2 ? fbl[ni] : fbh[ni];
-              acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bv, av, acc[mi][ni], 0, 0, 0);
-            }
           DLIP_FENCE();
         }
-        }
-        if constexpr (PP_PRIO) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
       };
       int st_iss = (PF > 1 && kn > 1) ? 2 % NSTAGE : 1 % NSTAGE;   // stage the next issue goes to (the prologue issued slices 0, 1)
       auto load_phase = [&](int s) {
@@ -575,8 +551,7 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N, OCC) void conv_igemm_f16x3_d
           DLIP_BSTAMP(5);
         }
       }
-    } else
-    {
+    } else {
       f16x8 fal[MI], fah[MI], fbh[NI], fbl[NI];
       auto read_first = [&](int stage) {   // what group 0 needs: activation lo, weight hi
         const float* Aw = smem + stage * (STAGE_B / 4) + a_frag;
@@ -620,9 +595,8 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N, OCC) void conv_igemm_f16x3_d
         // WHERE the slice's LDS-DMA pieces go out.  At the very top of the slice, right behind the barrier that frees their stage
         // (`early`), a layer that runs back to back takes 2-3 % less time on 128x128 and the two-stage 128x64 than with the pieces in
         // the MFMA shadow of groups 0 / 1 (tools/bench_dma.py; -6.5 % on 128x128's launches in the step); the three-stage 128x64
-        // never had it (+1 %).  (The 256x128 tile runs the ping-pong loop above; its lock-step form, the lab build's reference,
-        // keeps its pieces in the shadow: at the board's power limit the burst at the top cost the step 1.3 %.)
-        constexpr bool early = (VAR & 4) != 0 || (BM == 128 && BN == 128) || (BM == 128 && BN == 64 && NSTAGE == 2);
+        // never had it (+1 %).  (The 256x128 tile runs the ping-pong loop above.)
+        constexpr bool early = (BM == 128 && BN == 128) || (BM == 128 && BN == 64 && NSTAGE == 2);
         DLIP_SSTAMP(0);
         if (early && moreP) {
           advance();
@@ -656,7 +630,6 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N, OCC) void conv_igemm_f16x3_d
         DLIP_SSTAMP(6);
         st_cur = st_nxt;
       }
-    }
     }
 #undef DLIP_FENCE
     DLIP_STAMP(4);
@@ -1038,8 +1011,6 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(const ConvArgs a, cons
   *reinterpret_cast<f32x4*>(a.y + (size_t)m * a.ldy + k) = y;
 }
 
-#include "conv_dma_lab_menu.inc"   // lab build: the stamped launch path (nothing in the product build)
-
 // Per-stream workspace of the balanced split: ticket counters (zeroed once; every launch leaves them
 // zero) + slabs.  Launches on one stream are ordered, so they can share it; another stream needs its own.
 // The caller normally owns it (dlip_conv_workspace_bytes / dlip_conv_set_workspace: the Python
@@ -1218,10 +1189,7 @@ int launch_one(const ConvArgs& a, hipStream_t st, const ConvGroups* groups = nul
   const double nk_mean = GROUPED ? (double)groups->slices / groups->tiles : (double)a.nk;
   if (tiles <= 0 || tiles > 0x7FFFFFFFll) return DLIP_EINVAL;
   if (EPI == 2 && a.pool_group < BM) return DLIP_EINVAL;   // a tile may contain at most one row-group boundary
-  constexpr bool WIN = (VAR & 128) != 0;   // window mode: two window slots + NSTAGE weight stages (kernel comment)
-  constexpr size_t win_ring0 = (size_t)2 * (BM + 48) * ROWB + (size_t)NSTAGE * BN * ROWB;
-  constexpr size_t win_ring = win_ring0 > (size_t)BM * BN * 4 ? win_ring0 : (size_t)BM * BN * 4;
-  constexpr size_t lds = (WIN ? win_ring : (size_t)NSTAGE * (BM + BN) * ROWB) + 5 * BN * sizeof(float);   // ring + epilogue parameter table
+  constexpr size_t lds = (size_t)NSTAGE * (BM + BN) * ROWB + 5 * BN * sizeof(float);   // ring + epilogue parameter table
   constexpr int threads = 64 * WAVES_M * WAVES_N;
   static_assert(lds <= 160 * 1024, "LDS ring exceeds a CU");
   auto kern = conv_igemm_f16x3_dma_kernel<BM, BN, WAVES_M, WAVES_N, EPI, NSTAGE, OCC, DUAL, VAR, GROUPED>;
@@ -1322,17 +1290,9 @@ int launch_one(const ConvArgs& a, hipStream_t st, const ConvGroups* groups = nul
 template <int BM, int BN, int WAVES_M, int WAVES_N, int NSTAGE, int OCC, int VAR = 0>
 int launch_dma(const ConvArgs& a, hipStream_t st, int epi) {
   const bool dual = a.x2 != nullptr;
-  if constexpr (VAR == 128) {   // window mode (product): fp32 / split output
-    if (epi == 2 || dual) return DLIP_EINVAL;
-    return epi ? launch_one<BM, BN, WAVES_M, WAVES_N, NSTAGE, OCC, 1, false, VAR>(a, st)
-               : launch_one<BM, BN, WAVES_M, WAVES_N, NSTAGE, OCC, 0, false, VAR>(a, st);
-  } else if constexpr (VAR == 4096) {   // more than 32 filter taps (the weight gradient as a convolution): fp32 output, one source
+  if constexpr (VAR == 4096) {   // more than 32 filter taps (the weight gradient as a convolution): fp32 output, one source
     if (epi != 0 || dual) return DLIP_EINVAL;
     return launch_one<BM, BN, WAVES_M, WAVES_N, NSTAGE, OCC, 0, false, VAR>(a, st);
-  } else if constexpr (VAR != 0) {   // lab experiments: plain launches only
-    if (epi == 2 || dual) return DLIP_EINVAL;
-    return epi ? launch_one<BM, BN, WAVES_M, WAVES_N, NSTAGE, OCC, 1, false, VAR>(a, st)
-               : launch_one<BM, BN, WAVES_M, WAVES_N, NSTAGE, OCC, 0, false, VAR>(a, st);
   }
   if (epi == 2) {
     // (the product tiles 0 and 5: the whole fp32 tile image must fit the ring in one band)
@@ -1350,9 +1310,8 @@ int launch_dma(const ConvArgs& a, hipStream_t st, int epi) {
 }  // namespace
 
 // Tile menu of the DMA kernel (index = what dlip_conv_plan reports via dlip_conv_dma_tile; dlip_debug_set
-// (DLIP_DBG_DMA_TILE) forces one for tests and A/B runs).  0..5 are the product instances; a lab build
-// (python -m deeplip_amd.build --lab: -DDLIP_LAB, libdeeplip_hip_lab.so) appends its experiments (conv_dma_hooks.h).
-const TileCfg kDmaCfg[] = {{128, 128}, {128, 64}, {64, 128}, {64, 64}, {128, 64}, {256, 128} DLIP_LAB_TILE_CFGS};
+// (DLIP_DBG_DMA_TILE) forces one for tests and A/B runs).
+const TileCfg kDmaCfg[] = {{128, 128}, {128, 64}, {64, 128}, {64, 64}, {128, 64}, {256, 128}};
 constexpr int NUM_DMA_ALL = (int)(sizeof(kDmaCfg) / sizeof(kDmaCfg[0]));
 
 // Tile choice (measured per layer with tools/bench_dma.py, MI355X, balanced split on).  The cost of a slice
@@ -1393,7 +1352,7 @@ static int dma_pick(long long M, int K, int nk, int epi) {
   return 0;
 }
 
-// The split workspace of `stream` for another kernel of the library (conv_rows_f16x3.hip's general mode): 1 and the block, or 0
+// The split workspace of `stream` for another kernel of the library (encoder_train_ops.hip takes its ticket words): 1 and the block, or 0
 // when there is none of that size (same rules as for this kernel's own launches: never allocated inside a stream capture).
 extern "C" __attribute__((visibility("hidden"))) int dlip_conv_split_workspace(void* stream, size_t slab_floats, float** slabs, int** counters,
                                                                                int* counter_words) {
@@ -1406,10 +1365,6 @@ extern "C" __attribute__((visibility("hidden"))) int dlip_conv_split_workspace(v
   *counter_words = kMaxSplitTiles;
   return 1;
 }
-
-extern "C" int dlip_conv_rows2d_ok(const void* args, int epi);                                // conv_rows_f16x3.hip
-extern "C" int dlip_conv_f16x3_rows2d_launch(const void* args, void* stream, int epi);
-extern "C" int dlip_conv_rows_declined(void);
 
 // Library-internal entry points (hidden): ConvArgs lives in an unnamed namespace, so it crosses the
 // translation-unit boundary as an opaque pointer.
@@ -1424,13 +1379,6 @@ extern "C" __attribute__((visibility("hidden"))) void dlip_conv_dma_tile(long lo
 extern "C" __attribute__((visibility("hidden"))) int dlip_conv_f16x3_dma_launch(const void* args, void* stream, int epi) {
   const ConvArgs& a = *static_cast<const ConvArgs*>(args);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  // (round 4) the rows kernel's general mode (160 x 256 tiles, continuous slice stream, epilogue from registers, the same balanced
-  // split), when FORCED (dlip_debug_set(7, 1); measured slower than this kernel on the trunk: conv_rows_f16x3.hip); it declines when
-  // the stream has no split workspace for it
-  if (dlip_conv_rows2d_ok(args, epi)) {
-    const int rc = dlip_conv_f16x3_rows2d_launch(args, stream, epi);
-    if (rc != dlip_conv_rows_declined()) return rc;
-  }
   // The many-tap instances are also the ONLY ones that honour the slice / tap strides of slice-major operand images
   // (dlip_wgrad_conv_f16x3: cs_x, wt, cs_w, Hs); a weight gradient with 32 taps or fewer -- layer 4's 3x3 output-gradient maps: 9 taps --
   // used to fall through to the pixel-major instances below and read its slice-major images as if they were pixel-major: wrong
@@ -1449,7 +1397,6 @@ extern "C" __attribute__((visibility("hidden"))) int dlip_conv_f16x3_dma_launch(
     case 2: return launch_dma<64, 128, 2, 2, 3, 2>(a, st, epi);
     case 3: return launch_dma<64, 64, 2, 2, 3, 2>(a, st, epi);
     case 4: return launch_dma<128, 64, 2, 2, 2, 3>(a, st, epi);
-    DLIP_LAB_DISPATCH_CASES   // (lab build: tiles 6.. of its menu; nothing in the product build)
     default:
       return launch_dma<256, 128, 4, 2, 3, 1, 0>(a, st, epi);
   }
@@ -1488,8 +1435,8 @@ extern "C" int64_t dlip_conv_workspace_bytes(void) {
   int dev = 0, cus = 0;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
     return -1;
-  // counters + two slabs per resident workgroup: one per CU x 160x256 fp32 (the rows kernel's general mode) is the largest product on
-  // the menu (this kernel's own: 2 per CU x 128x128)
+  // counters + two slabs of 160x256 fp32 per CU.  This kernel's own launches need at most 2 per CU x 128x128 or 1 per CU x 256x128;
+  // the size is kept as it is because it decides which launches can split (a larger tile this sized for is retired)
   return (int64_t)kMaxSplitTiles * 4 + (int64_t)2 * cus * 160 * 256 * 4;
 }
 

@@ -42,15 +42,7 @@ struct RowsSched {
   int items;      // tiles of the launch: tiles_m * tiles_n, row block major (the column blocks of a row block are neighbours)
   int tiles_n;
   unsigned long long* span;   // NULL, or this launch's {first start, last end} in 100 MHz ticks (dlip_span_scope_*)
-  // MODE 1 (balanced split, the ring kernel's stream-K): the items * nk slices of the launch cut into G equal ranges, one per
-  // workgroup; a tile shared by several ranges goes through fp32 slabs (two per workgroup: its first and its last segment) and
-  // ticket words (8 per tile: one per wave position) in the ring kernel's per-stream workspace
-  int iters;      // items * nk; iters * G < 2^31 (32-bit arithmetic and magic-number division throughout: the 64-bit quotients'
-  int G;          // expansion left the cursor state in vector registers and on the stack)
-  FastDiv div_G, div_iters, div_nk;
-  float* slabs;
-  int* counters;
-  // MODE 0 (round 5), the SHORT LAST ROUND: row tiles t_full.. (items item_short0..) are 32 * nmi_short rows high instead of 32 MI, so
+  // (round 5) the SHORT LAST ROUND: row tiles t_full.. (items item_short0..) are 32 * nmi_short rows high instead of 32 MI, so
   // that the rows left over after the launch's full rounds of tiles spread over ALL workgroups as one round of shorter tiles (B = 256:
   // 948 tiles of 160 rows on 256 CUs = 3 full rounds + a fourth that is 70 % full -> 3 rounds + one of 128-row tiles: 3.8 tile
   // times instead of 4).  A short tile keeps the LDS image of a full one: its wave row w holds rows w * 16 nmi_short .. of the tile
@@ -64,18 +56,9 @@ struct RowsSched {
 
 constexpr int ROWS_BN = 256;
 
-// The kernel's ConvArgs as the kernarg segment holds it (first explicit argument: offset 0), behind an opaque asm: what is read
-// through this pointer is (re)loaded where it is used -- scalar loads, once per tile -- instead of being kept in scalar registers
-// for the whole kernel.  The general mode's tile set-up and epilogue need ~45 argument words and seven buffer descriptors between
-// them; held across the main loop they spilled ~300 scalar registers into vector lanes and, from there, loop state into scratch.
-typedef const ConvArgs __attribute__((address_space(4))) RowsKArgs;
-__device__ __forceinline__ RowsKArgs* rows_kargs() {
-  RowsKArgs* p = (RowsKArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(p));
-  return p;
-}
-
-// ... and the RowsSched behind it (second explicit argument: at the next 8-byte boundary)
+// The kernel's RowsSched as the kernarg segment holds it (second explicit argument: at the next 8-byte boundary behind ConvArgs),
+// behind an opaque asm: what is read through this pointer is (re)loaded where it is used -- scalar loads, once per tile -- instead
+// of being kept in scalar registers for the whole kernel.
 typedef const RowsSched __attribute__((address_space(4))) RowsKSched;
 __device__ __forceinline__ RowsKSched* rows_ksched() {
   typedef const char __attribute__((address_space(4))) KChar;
@@ -86,25 +69,14 @@ __device__ __forceinline__ RowsKSched* rows_ksched() {
 
 // EPI: 0 fp32 rows of y; 1 split-format rows of y (reports range); 2 no y: per HALF tile (the 16 MI rows of a wave row) and
 // row-group segment the fp64 column sums of v and v^2 (a.pool, the ring kernel's pooled epilogue with tile rows = 16 MI)
-// MODE: 0 the speech encoder's form (file comment): every tap a plain row offset, whole tiles per workgroup, tiles g, g + G, ...
-//       1 (round 4) the trunk's deep layers on the same loop: 2-D filters with padding / stride / dilation (a bit per tap and row,
-//         ORed into the piece's offset as bit 31 -- the ring kernel's), an optional residual in the split format (two 16-B loads
-//         per pixel block, the window kernel's), the ring kernel's BALANCED SPLIT -- every workgroup one contiguous range of the
-//         launch's tiles x slices -- and, DUAL, its second reduction source (dlip_conv2_nhwc_f16x3).  The hand-off of a shared
-//         tile is PER WAVE: the ping-pong halves never meet at a common barrier, and wave w of the finisher needs exactly the
-//         accumulators of wave w of the other parts -- so each wave publishes its own quads (sc1 stores, vmcnt(0), one relaxed
-//         ticket on the tile's word for its position) and the wave that finds its position complete adds the others' in part
-//         order and runs the epilogue; different waves of a tile may finish in different workgroups, the bits do not depend on it.
 // TAIL: the launch has a short last round (RowsSched); instances without it carry none of its code.
-template <int MI, int EPI, int MODE = 0, bool DUAL = false, bool TAIL = false>
+template <int MI, int EPI, bool TAIL = false>
 __global__ __launch_bounds__(512, 2) void conv_rows_f16x3_kernel(const ConvArgs a, const RowsSched sc) {
-  static_assert(MODE == 1 || !DUAL, "the second source exists in the general mode only");
-  static_assert(!TAIL || (MODE == 0 && EPI != 2), "short tiles: the speech encoder's form, fp32 or split output");
+  static_assert(!TAIL || EPI != 2, "short tiles: fp32 or split output");
   // (TAIL) the four schedule words are re-read from the kernel-argument segment (scalar loads) where a tile begins or ends: held in
   // scalar registers across the main loop they cost the split-output instances 40 SGPR spills and the B = 64 step 1 % (the
   // paired-lanes lesson again)
 #define ROWS_SC(f) (rows_ksched()->f)
-  static_assert(MODE == 0 || EPI != 2, "no pooled epilogue in the general mode");
   constexpr int NW = 8, BN = ROWS_BN, BM = 32 * MI, NI = 4;
   constexpr int WM = BM / 2;                       // rows of a wave's tile (16 MI); WN = 64
   constexpr int A_PIECES = BM / 8, B_PER = 4;      // 1-KiB pieces of a slice's activation rows; weight pieces per wave
@@ -122,17 +94,9 @@ __global__ __launch_bounds__(512, 2) void conv_rows_f16x3_kernel(const ConvArgs 
   const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
   const int g = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);   // neighbours in tile order share an XCD (L2)
   const int nk = a.nk;
-  int total, item0 = g, k0 = 0;                           // slices of this workgroup's stream; its first tile and slice
-  if constexpr (MODE == 1) {
-    const int it_begin = dlip_div(g * sc.iters, sc.div_G);
-    total = __builtin_amdgcn_readfirstlane(dlip_div((g + 1) * sc.iters, sc.div_G) - it_begin);
-    if (total <= 0) return;
-    item0 = __builtin_amdgcn_readfirstlane(dlip_div(it_begin, sc.div_nk));
-    k0 = __builtin_amdgcn_readfirstlane(it_begin - item0 * nk);
-  } else {
-    if (g >= sc.items) return;
-    total = ((sc.items - g + nwg - 1) / nwg) * nk;        // this workgroup's tiles: g, g + nwg, ...
-  }
+  if (g >= sc.items) return;
+  const int item0 = g;                                    // this workgroup's tiles: g, g + nwg, ...
+  const int total = ((sc.items - g + nwg - 1) / nwg) * nk;   // slices of its stream
 
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -148,6 +112,12 @@ __global__ __launch_bounds__(512, 2) void conv_rows_f16x3_kernel(const ConvArgs 
   const int csrc = ((lane & 7) ^ key_st) << 2;            // first channel (dword) of the chunk this lane fetches
   const u32x4 xr = make_rsrc_words(a.x, a.x_bytes);
   const u32x4 wr = make_rsrc_words(a.w, a.w_bytes);
+  // LEFT OVER from the retired general mode (EXPERIMENTS.md R8.2), with the dead branch of `issue`, the epilogue's local copies and
+  // five unused variables of `run_half` below: nothing reads or runs them, but taking them out changes which variables the lambdas
+  // capture, with that the order in which the optimiser creates the loop's phi nodes, and with that the schedule and the scalar
+  // spills of all fifteen instances (fp32 output at MI = 5: 20 -> 48 spills).  They leave with the next change that is allowed to
+  // move this kernel's machine code.
+  constexpr bool DUAL = false;
   u32x4 x2r = xr;
   if constexpr (DUAL) x2r = make_rsrc_words(a.x2, a.x2_bytes);
   const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
@@ -158,9 +128,6 @@ __global__ __launch_bounds__(512, 2) void conv_rows_f16x3_kernel(const ConvArgs 
   const int key_rd = (lrow >> 1) & 7;
   const int khi = (hq ^ key_rd) << 2, klo = ((4 + hq) ^ key_rd) << 2;
   const int x_ds = a.dw * a.ldx * 4;                      // bytes between two taps of a row
-  const int x_dr = a.dh * a.W * a.ldx * 4;                // (MODE 1) ... between two filter rows
-  const int ntaps = a.R * a.S;
-  const int nk1 = nk - (DUAL ? a.nk2 : 0);                // slices of the first source
 
   dlip_span_enter(sc.span, g);
 #ifdef DLIP_LAB
@@ -176,44 +143,24 @@ __global__ __launch_bounds__(512, 2) void conv_rows_f16x3_kernel(const ConvArgs 
   // (rows past M / weight rows past K carry the out-of-range offset itself: 2^31 plus any in-range tap offset is still beyond every
   // buffer, so a piece's address is ONE add -- the select per piece was two of every three vector instructions of a slice)
   uint32_t a_off[NA_A], b_off[B_PER];
-  uint32_t a_mask[MODE == 1 ? NA_A : 1];                  // (MODE 1) INVERTED: bit t set = tap t of that row is outside the image, or the row past M
-  uint32_t a2_off[DUAL ? NA_A : 1];                       // (DUAL) the row's pixel of the second source; out of range past M
-  int c_item = item0, c_k = k0, s_pos = 0, c0 = 0, x_tap = 0, w_tap = 0;
-  int tap = 0, x_row = 0;                                 // (MODE 1) tap index r S + s and the byte offset of filter row r
+  uint32_t a2_off[DUAL ? NA_A : 1];                       // (left over, see DUAL)
+  int c_item = item0, c_k = 0, s_pos = 0, c0 = 0, x_tap = 0, w_tap = 0;
   auto set_item = [&](int item) __attribute__((always_inline)) {
     const int tile_m = item / sc.tiles_n, tile_n = item - tile_m * sc.tiles_n;
-    [[maybe_unused]] RowsKArgs* ap = nullptr;
-    if constexpr (MODE == 1) ap = rows_kargs();
-    [[maybe_unused]] int t_base = tile_m * BM, t_half = WM;   // (MODE 0) the tile's first row, rows per wave row (RowsSched: short last round)
+    [[maybe_unused]] int t_base = tile_m * BM, t_half = WM;   // the tile's first row, rows per wave row (RowsSched: short last round)
     if constexpr (TAIL) {
       if (item >= ROWS_SC(item_short0)) { t_half = 16 * ROWS_SC(nmi_short); t_base = ROWS_SC(row_short0) + (tile_m - ROWS_SC(t_full)) * 2 * t_half; }
     }
 #pragma unroll
     for (int j = 0; j < NA_A; ++j) {
-      const int m = tile_m * BM + 8 * (wave + 8 * j) + prow;
-      if constexpr (MODE == 1) {
-        const int mc = m < ap->M ? m : ap->M - 1;
-        const int n = dlip_div(mc, FastDiv{ap->div_howo.mul, ap->div_howo.shift});
-        const int rem = mc - n * ap->HoWo;
-        const int ho = dlip_div(rem, FastDiv{ap->div_wo.mul, ap->div_wo.shift});
-        const int wo = rem - ho * ap->Wo;
-        const int hi0 = ho * ap->sh - ap->ph, wi0 = wo * ap->sw - ap->pw;   // window origin (may lie in the padding: the sum with a valid tap does not)
-        a_off[j] = (uint32_t)((((n * ap->H + hi0) * ap->W + wi0) * ap->ldx + csrc) * 4);
-        if constexpr (DUAL) a2_off[j] = m < ap->M ? (uint32_t)((((n * ap->H2 + ho * ap->s2h) * ap->W2 + wo * ap->s2w) * ap->ldx2 + csrc) * 4) : DLIP_OOB_OFFSET;
-        uint32_t colbits = 0u, ok = 0u;                   // columns and rows tested separately: R + S steps, not R x S
-        for (int sx = 0; sx < ap->S; ++sx) colbits |= (uint32_t)((unsigned)(wi0 + sx * ap->dw) < (unsigned)ap->W) << sx;
-        for (int r = 0; r < ap->R; ++r) ok |= ((unsigned)(hi0 + r * ap->dh) < (unsigned)ap->H ? colbits : 0u) << (r * ap->S);
-        a_mask[j] = m < ap->M ? ~ok : ~0u;
-      } else {
-        const int lr = 8 * (wave + 8 * j) + prow;            // row of the LDS image; hr: within its wave row
-        const int hr = lr >= WM ? lr - WM : lr;
-        const int ms = t_base + (lr >= WM ? t_half : 0) + hr;
-        const bool in = hr < t_half && ms < a.M;
-        const int mc = in ? ms : 0;
-        const int n = dlip_div(mc, a.div_howo);
-        const int t = mc - n * a.HoWo;                       // H = 1: the row's first input pixel is n * W + t
-        a_off[j] = in ? (uint32_t)(((n * a.W + t) * a.ldx + csrc) * 4) : DLIP_OOB_OFFSET;
-      }
+      const int lr = 8 * (wave + 8 * j) + prow;              // row of the LDS image; hr: within its wave row
+      const int hr = lr >= WM ? lr - WM : lr;
+      const int ms = t_base + (lr >= WM ? t_half : 0) + hr;
+      const bool in = hr < t_half && ms < a.M;
+      const int mc = in ? ms : 0;
+      const int n = dlip_div(mc, a.div_howo);
+      const int t = mc - n * a.HoWo;                         // H = 1: the row's first input pixel is n * W + t
+      a_off[j] = in ? (uint32_t)(((n * a.W + t) * a.ldx + csrc) * 4) : DLIP_OOB_OFFSET;
     }
 #pragma unroll
     for (int j = 0; j < B_PER; ++j) {
@@ -221,62 +168,27 @@ __global__ __launch_bounds__(512, 2) void conv_rows_f16x3_kernel(const ConvArgs 
       b_off[j] = n < a.K ? (uint32_t)((n * a.rsc + csrc) * 4) : DLIP_OOB_OFFSET;
     }
   };
-  auto place = [&]() __attribute__((always_inline)) {     // byte offsets of the slice the cursor stands on
-    if constexpr (MODE == 1) {
-      x_tap = x_row + s_pos * x_ds + c0 * 4;
-      w_tap = (tap * a.Cw + c0) * 4;
-      if (DUAL && c0 >= a.Cw) { x_tap = (c0 - a.Cw) * 4; w_tap = (ntaps * a.Cw + c0 - a.Cw) * 4; }   // behind the taps of each weight row
-    } else {
-      x_tap = s_pos * x_ds + c0 * 4;
-      w_tap = (s_pos * a.Cw + c0) * 4;
-    }
-  };
   auto advance = [&]() __attribute__((always_inline)) {   // channel slice outer, tap inner (the ring kernel's reduction order)
-    if constexpr (MODE == 1) {
-      // (value selects on local copies, one store per variable: as an if / else chain storing to the cursor variables, the
-      // optimiser merged the branches' stores into stores through a pointer phi and the whole cursor stayed on the stack)
-      const bool second = DUAL && c0 >= a.Cw;            // second source: one slice per 32 channels
-      int ntap = tap + 1, nsp = s_pos + 1, nrow = x_row, nc0 = c0, nk_ = c_k + 1, nitem = c_item;
-      if (nsp == a.S) { nsp = 0; nrow += x_dr; }
-      if (ntap == ntaps) { ntap = 0; nsp = 0; nrow = 0; nc0 += BK; }
-      if (second) { ntap = tap; nsp = s_pos; nrow = x_row; nc0 = c0 + BK; }
-      if (nk_ == nk) { nk_ = 0; ntap = 0; nsp = 0; nrow = 0; nc0 = 0; ++nitem; }   // (the caller has run set_item for the next tile: enter_next)
-      c_k = nk_; tap = ntap; s_pos = nsp; x_row = nrow; c0 = nc0; c_item = nitem;
-      place();
-    } else {
-      if (++c_k == nk) {
-        c_k = 0; s_pos = 0; c0 = 0;
-        c_item += nwg;
-        set_item(c_item);
-      } else if (++s_pos == a.S) {
-        s_pos = 0; c0 += BK;
-      }
-      x_tap = s_pos * x_ds + c0 * 4;
-      w_tap = (s_pos * a.Cw + c0) * 4;
+    if (++c_k == nk) {
+      c_k = 0; s_pos = 0; c0 = 0;
+      c_item += nwg;
+      set_item(c_item);
+    } else if (++s_pos == a.S) {
+      s_pos = 0; c0 += BK;
     }
-  };
-  // MODE 1: the row set-up of the NEXT tile (two divisions and R + S mask steps per row) is done apart from advance(), at a point
-  // of the caller's choosing -- in the loop BEFORE the slice's fragment reads: behind them it sat on top of 72 live fragment
-  // registers and pushed loop state into scratch
-  auto enter_next = [&]() __attribute__((always_inline)) {
-    if constexpr (MODE == 1) { if (c_k + 1 == nk) set_item(c_item + 1); }
+    x_tap = s_pos * x_ds + c0 * 4;
+    w_tap = (s_pos * a.Cw + c0) * 4;
   };
   auto issue = [&](int stage, auto na) __attribute__((always_inline)) {
     const uint32_t base = piece0 + stage * STAGE_B;
-    if (DUAL && c0 >= a.Cw) {                              // (wave-uniform)
+    if (DUAL && c0 >= a.Cw) {                              // (left over, see DUAL: never taken)
 #pragma unroll
       for (int j = 0; j < na(); ++j)
         dma_piece(x2r, a2_off[DUAL ? j : 0] + (uint32_t)x_tap, base + j * 8192);
     } else {
 #pragma unroll
       for (int j = 0; j < na(); ++j) {
-        if constexpr (MODE == 1) {
-          // a tap outside the image: its bit of the inverted mask, shifted to bit 31, ORed into the offset -- beyond every buffer
-          const uint32_t oob = (a_mask[j] << (31 - tap)) & 0x80000000u;
-          dma_piece(xr, (a_off[j] + (uint32_t)x_tap) | oob, base + j * 8192);
-        } else {
-          dma_piece(xr, a_off[j] + (uint32_t)x_tap, base + j * 8192);
-        }
+        dma_piece(xr, a_off[j] + (uint32_t)x_tap, base + j * 8192);
       }
     }
 #pragma unroll
@@ -326,10 +238,10 @@ __global__ __launch_bounds__(512, 2) void conv_rows_f16x3_kernel(const ConvArgs 
   };
 
   // ---- epilogue of one tile, from this wave's accumulators straight to memory:
-  //      y = act(acc / wscale + bias [+ residual]) * post_scale + post_shift   (a residual in MODE 1 only; split format) ----
-  // (MODE 0: the descriptors are built once, here -- plain scalars, as the compiler keeps them best; MODE 1: inside the epilogue,
-  // re-read through rows_kargs().  An aggregate carrying the seven descriptors into the epilogue cost the speech-encoder layers
-  // 2 - 4 %: it lived in vector registers and came back through v_readfirstlane + hazard s_nops, same-box A/B at B = 256.)
+  //      y = act(acc / wscale + bias) * post_scale + post_shift ----
+  // (The descriptors are built once, here -- plain scalars, as the compiler keeps them best.  An aggregate carrying them into the
+  // epilogue cost the speech-encoder layers 2 - 4 %: it lived in vector registers and came back through v_readfirstlane + hazard
+  // s_nops, same-box A/B at B = 256.)
   const uint32_t kbytes0 = (uint32_t)a.K * 4u;
   const __amdgpu_buffer_rsrc_t yr0 = dlip_make_rsrc(a.y, a.y_bytes);
   const __amdgpu_buffer_rsrc_t scr0 = dlip_make_rsrc(a.wscale, kbytes0);
@@ -340,13 +252,13 @@ __global__ __launch_bounds__(512, 2) void conv_rows_f16x3_kernel(const ConvArgs 
   const bool has_slope0 = a.slope != nullptr;
   const bool has_post0 = a.pscale != nullptr;
   float amax = 0.f;
-  // (round 5) MODE 0, fp32 / split output: the epilogue's per-channel parameters {1 / wscale, bias, slope} of this workgroup's column
+  // (round 5) fp32 / split output: the epilogue's per-channel parameters {1 / wscale, bias, slope} of this workgroup's column
   // block, 3 KB of LDS behind the ring, written once.  A workgroup's tiles g, g + G, ... share their column block whenever the column
   // blocks divide G (K = 512: two blocks on 256 workgroups), and the epilogue took them from memory per tile: two dependent L2 round
   // trips (~2.4 k cycles) at the head of the interval in which its SIMD partner multiplies for 1.1 k -- in-kernel stamps at B = 256:
   // 16 x 2 632 cycles of slices per k = 1 tile, but 60.6 k per tile, the difference being the two halves' epilogues each stalling the
   // other.  A tile of another column block (tab_n differs) takes the parameters from memory as before.
-  constexpr bool TAB = MODE == 0 && EPI != 2;
+  constexpr bool TAB = EPI != 2;
   float* const ptab = smem + NSTAGE * (STAGE_B / 4);
   [[maybe_unused]] int tab_n = -1;
   if constexpr (TAB) {
@@ -366,23 +278,10 @@ __global__ __launch_bounds__(512, 2) void conv_rows_f16x3_kernel(const ConvArgs 
   auto epilogue_p = [&](int item, auto post_c) __attribute__((always_inline)) {
     typedef _Float16 h8 __attribute__((ext_vector_type(8)));
     constexpr bool post = decltype(post_c)::value;   // (compile-time inside: the runtime flag selected and computed both forms per value)
-    __amdgpu_buffer_rsrc_t yr = yr0, rr = yr0, scr = scr0, bir = bir0, slr = slr0, psr = psr0, ptr_ = ptr0;
-    bool has_res = false, has_slope = has_slope0;
-    int eM = a.M, eK = a.K, eldy = a.ldy, eldr = 0;
-    if constexpr (MODE == 1) {
-      RowsKArgs* ap = rows_kargs();
-      const uint32_t kbytes = (uint32_t)ap->K * 4u;
-      yr = dlip_make_rsrc(ap->y, ap->y_bytes);
-      has_res = ap->res != nullptr;
-      rr = dlip_make_rsrc(ap->res, has_res ? ap->r_bytes : 0u);
-      scr = dlip_make_rsrc(ap->wscale, kbytes);
-      bir = dlip_make_rsrc(ap->bias, ap->bias ? kbytes : 0u);
-      slr = dlip_make_rsrc(ap->slope, ap->slope ? kbytes : 0u);
-      psr = dlip_make_rsrc(ap->pscale, ap->pscale ? kbytes : 0u);
-      ptr_ = dlip_make_rsrc(ap->pshift, ap->pshift ? kbytes : 0u);
-      has_slope = ap->slope != nullptr;
-      eM = ap->M; eK = ap->K; eldy = ap->ldy; eldr = ap->ldr;
-    }
+    // (local copies: left over, see DUAL -- the general mode re-read these from the kernel arguments here)
+    __amdgpu_buffer_rsrc_t yr = yr0, scr = scr0, bir = bir0, slr = slr0, psr = psr0, ptr_ = ptr0;
+    bool has_slope = has_slope0;
+    int eM = a.M, eK = a.K, eldy = a.ldy;
     const int tile_m = item / sc.tiles_n, tile_n = item - tile_m * sc.tiles_n;
     int row0 = tile_m * BM + wm * WM + lrow;
     [[maybe_unused]] int e_nmi = MI;                  // (TAIL) 16-row blocks of this wave's rows that exist (short last round)
@@ -393,29 +292,10 @@ __global__ __launch_bounds__(512, 2) void conv_rows_f16x3_kernel(const ConvArgs 
     if constexpr (EPI == 1) {
       // after the swap, 16-lane row hq of the pair (2 p, 2 p + 1) holds channels 32 p + {0, 16, 8, 24}[hq] + 0..7 of its pixel
       const int cs = ((hq & 1) << 4) | ((hq & 2) << 2);
-      // the residual arrives in the shape the values leave in: per pixel block one 16-B piece of hi halves and one of lo halves,
-      // issued first thing for each 32-channel pair -- their latency passes under the parameter loads and the exchange (all
-      // NI / 2 pairs at once, as the window kernel does, is 80 registers at MI = 5: spills)
 #pragma unroll
       for (int p = 0; p < NI / 2; ++p) {
         const int kb = col0 + 32 * p;                    // first channel of the 32-channel block
         const int k0 = kb + cs;                          // first of this lane's 8 channels
-        // (MODE 1, no post-affine -- a launch with both stays on the ring kernel) residual pieces, RD pixel blocks ahead of their use
-        constexpr bool RES = MODE == 1 && !post;
-        constexpr int RD = 3;
-        h8 rh[RES ? RD : 1], rl[RES ? RD : 1];
-        auto load_res = [&](int mi) __attribute__((always_inline)) {
-          const int m = row0 + mi * 16;
-          const uint32_t off = (m < eM && kb < eK) ? (uint32_t)((m * eldr + kb) * 4 + cs * 2) : DLIP_OOB_OFFSET;
-          rh[mi % RD] = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(rr, (int)off, 0, 0));
-          rl[mi % RD] = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(rr, (int)(off == DLIP_OOB_OFFSET ? off : off + 64u), 0, 0));
-        };
-        if constexpr (RES) {
-          if (has_res) {
-#pragma unroll
-            for (int mi = 0; mi < RD && mi < MI; ++mi) load_res(mi);
-          }
-        }
         float inv[8], bi[8], sl[8], ps[8], pt[8];
         bool from_tab = false;
         if constexpr (TAB && !post) from_tab = tile_n == tab_n;      // (wave-uniform)
@@ -459,7 +339,6 @@ __global__ __launch_bounds__(512, 2) void conv_rows_f16x3_kernel(const ConvArgs 
 #pragma unroll
           for (int c = 0; c < 8; ++c) {
             float t = v[c] * inv[c] + bi[c];
-            if constexpr (RES) { if (has_res) t += (float)rh[mi % RD][c] + (float)rl[mi % RD][c]; }
             t = t >= 0.f ? t : t * sl[c];
             if (post) t = t * ps[c] + pt[c];
             hi[c] = (_Float16)t;
@@ -471,10 +350,6 @@ __global__ __launch_bounds__(512, 2) void conv_rows_f16x3_kernel(const ConvArgs 
           const uint32_t off = ok ? (uint32_t)((m * eldy + kb) * 4 + cs * 2) : DLIP_OOB_OFFSET;
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hi), yr, (int)off, 0, 0);
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, lo), yr, (int)(ok ? off + 64u : DLIP_OOB_OFFSET), 0, 0);
-          if constexpr (RES) {
-            DLIP_FENCE();
-            if (has_res && mi + RD < MI) load_res(mi + RD);
-          }
         }
         DLIP_FENCE();
       }
@@ -557,7 +432,7 @@ __global__ __launch_bounds__(512, 2) void conv_rows_f16x3_kernel(const ConvArgs 
 #pragma unroll
           for (int c = 0; c < 4; ++c) inv4[c] = k0 + c < eK ? 1.f / s4[c] : 0.f;
         }
-        // (MODE 0, a.stats: launch-uniform) column sums of what this wave writes -- the batch statistics of the BatchNorm behind a
+        // (a.stats: launch-uniform) column sums of what this wave writes -- the batch statistics of the BatchNorm behind a
         // TDNN convolution under model.train() (tdnn.py:35-43) -- taken here instead of by a pass over y: a lane adds its MI pixels
         // (fp32: 5 values), the 16 lanes of a channel quad meet by four DPP row steps (fp32, a fixed tree: deterministic), lane 0 of
         // the quad converts to fp64 and stores {sum, sum of squares} of its 4 channels for chunk 2 tile_m + wm; the finalize kernel
@@ -566,7 +441,7 @@ __global__ __launch_bounds__(512, 2) void conv_rows_f16x3_kernel(const ConvArgs 
         float st_s[4] = {0.f, 0.f, 0.f, 0.f}, st_q[4] = {0.f, 0.f, 0.f, 0.f};
         // (the pointer is re-read from the kernel arguments HERE: held in scalar registers across the main loop it cost the fp32
         // instances 30 extra SGPR spills -- the paired-lanes lesson of conv_igemm_f16x3_dma.hip)
-        double* const stats_p = MODE == 0 ? *reinterpret_cast<double* const volatile*>(&a.stats) : nullptr;
+        double* const stats_p = *reinterpret_cast<double* const volatile*>(&a.stats);
         const bool want_stats = stats_p != nullptr;
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi) {
@@ -574,17 +449,6 @@ __global__ __launch_bounds__(512, 2) void conv_rows_f16x3_kernel(const ConvArgs 
           const int m = row0 + mi * 16;
 #pragma unroll
           for (int c = 0; c < 4; ++c) v[c] = acc[mi][ni][c] * inv4[c] + b4[c];
-          if constexpr (MODE == 1) {
-            if (has_res) {   // the residual is in the split format: 4 hi halves, 4 lo halves of this lane's channels
-              typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-              const bool rok = m < eM && k0 < eK;
-              const uint32_t ro = rok ? (uint32_t)((m * eldr + (k0 & ~31)) * 4 + (k0 & 31) * 2) : DLIP_OOB_OFFSET;
-              const h4 r_hi = __builtin_bit_cast(h4, __builtin_amdgcn_raw_buffer_load_b64(rr, (int)ro, 0, 0));
-              const h4 r_lo = __builtin_bit_cast(h4, __builtin_amdgcn_raw_buffer_load_b64(rr, (int)(rok ? ro + 64u : DLIP_OOB_OFFSET), 0, 0));
-#pragma unroll
-              for (int c = 0; c < 4; ++c) v[c] += (float)r_hi[c] + (float)r_lo[c];
-            }
-          }
 #pragma unroll
           for (int c = 0; c < 4; ++c) {
             float t = v[c];
@@ -621,87 +485,16 @@ __global__ __launch_bounds__(512, 2) void conv_rows_f16x3_kernel(const ConvArgs 
   };
   auto epilogue = [&](int item) __attribute__((always_inline)) {
     bool has_post = has_post0;
-    if constexpr (MODE == 1) has_post = rows_kargs()->pscale != nullptr;
     if (has_post) epilogue_p(item, std::true_type{}); else epilogue_p(item, std::false_type{});
-  };
-  // End of a segment (this wave's view).  A whole tile: its epilogue.  MODE 1, a tile this range shares with others (`part`): the
-  // hand-off in the kernel comment -- peek at the tile's ticket word for this wave position; everybody else has published: this
-  // wave is the finisher and keeps its part in registers; otherwise publish (write-through stores, drained, then ONE relaxed
-  // ticket) and finish only if the ticket says the others arrived meanwhile.  The finisher acquires (agent scope: this CU's L1
-  // drops stale slab lines), adds the parts IN PART ORDER (its own from registers) one row of NI quads at a time, and runs the
-  // epilogue.  Returns whether the epilogue's stores were issued (the counted waits behind it leave NST of them in flight); on the
-  // publishing path everything this wave had in flight has been waited for.
-  auto finish_tile = [&](int item, bool part, bool first) __attribute__((always_inline)) -> bool {
-    if constexpr (MODE == 1) {
-      if (part) {                                          // (wave-uniform)
-        constexpr int WSLAB = BM * BN / NW;                // floats of one wave's share of a slab = MI NI 64 quads
-        const int t0 = item * nk;
-        const int gf = __builtin_amdgcn_readfirstlane(dlip_div((t0 + 1) * sc.G - 1, sc.div_iters));    // owner of the tile's first slice
-        const int gl = __builtin_amdgcn_readfirstlane(dlip_div((t0 + nk) * sc.G - 1, sc.div_iters));   // owner of its last slice
-        const int others = gl - gf;
-        // which of part p's two slabs holds this tile: only the first part's range can have begun before the tile
-        const int gf_slot = dlip_div(gf * sc.iters, sc.div_G) < t0 ? 1 : 0;
-        int* ctr = sc.counters + (size_t)item * NW + wave;
-        int seen = 0;
-        if (lane == 0) seen = __hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        bool fin = __builtin_amdgcn_readfirstlane(seen) == others;
-        if (!fin) {
-          const __amdgpu_buffer_rsrc_t sr = dlip_make_rsrc(sc.slabs + ((size_t)(2 * g + (first ? 0 : 1)) * NW + wave) * WSLAB, WSLAB * 4);
-#pragma unroll
-          for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni)
-              __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[mi][ni]), sr, ((mi * NI + ni) * 64 + lane) * 16, 0, 16);
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          int tk = 0;
-          if (lane == 0) tk = __hip_atomic_fetch_add(ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          fin = __builtin_amdgcn_readfirstlane(tk) == others;   // the other parts arrived between the peek and the ticket
-          if (!fin) return false;
-        }
-        if (lane == 0) __hip_atomic_store(ctr, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi) {
-          f32x4 t[NI];
-          for (int p = gf; p <= gl; ++p) {
-            const __amdgpu_buffer_rsrc_t pr =
-                dlip_make_rsrc(sc.slabs + ((size_t)(2 * p + (p == gf ? gf_slot : 0)) * NW + wave) * WSLAB, WSLAB * 4);
-            f32x4 v[NI];
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni) {
-              v[ni] = acc[mi][ni];
-              if (p != g) v[ni] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(pr, ((mi * NI + ni) * 64 + lane) * 16, 0, 16));
-            }
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-              for (int c = 0; c < 4; ++c) t[ni][c] = p == gf ? v[ni][c] : t[ni][c] + v[ni][c];
-            DLIP_FENCE();
-          }
-#pragma unroll
-          for (int ni = 0; ni < NI; ++ni) acc[mi][ni] = t[ni];
-        }
-      }
-    }
-    epilogue(item);
-    return true;
   };
 
   // ---- prologue: the first two slices of the stream in flight ----
   constexpr std::integral_constant<int, NA_A> na_a{};
   constexpr std::integral_constant<int, NA_B> na_b{};
   set_item(c_item);
-  if constexpr (MODE == 1) {                               // the range may begin inside a tile: stand the cursor on slice k0
-    if (DUAL && k0 >= nk1) { c0 = a.Cw + (k0 - nk1) * BK; tap = 0; } else { c0 = (k0 / ntaps) * BK; tap = k0 % ntaps; }
-    s_pos = tap % a.S;
-    x_row = (tap / a.S) * x_dr;
-    place();
-  }
   ROWS_STAMP(0);
   if (!half_b) issue(0, na_a); else issue(0, na_b);
   if (total > 1) {
-    enter_next();
     advance();
     if (!half_b) issue(1, na_a); else issue(1, na_b);
   }
@@ -720,17 +513,12 @@ __global__ __launch_bounds__(512, 2) void conv_rows_f16x3_kernel(const ConvArgs 
     constexpr bool FIRST = decltype(first_c)::value;
     static_assert(NL + NST < 64, "vmcnt is a 6-bit counter");
     int st_iss = total > 1 ? 2 : 1;                        // stage the next issue goes to (the prologue issued slices 0, 1)
-    // consumer side: the segment being multiplied (MODE 0: always a whole tile)
+    // consumer side: the tile being multiplied
     int kleft = nk, e_item = item0, done_item = -1;
     [[maybe_unused]] int cur_nmi = MI;                     // (TAIL) the height of the tile being multiplied, in 16-row blocks per wave
     if constexpr (TAIL) { if (e_item >= ROWS_SC(item_short0)) cur_nmi = ROWS_SC(nmi_short); }
     [[maybe_unused]] int rem = 0;
-    [[maybe_unused]] bool e_part = false, e_first = true, done_part = false, done_first = false;   // (wave-uniform; MODE 1)
-    if constexpr (MODE == 1) {
-      kleft = nk - k0 < total ? nk - k0 : total;
-      rem = total - kleft;
-      e_part = kleft != nk;
-    }
+    [[maybe_unused]] bool e_part = false, e_first = true, done_part = false, done_first = false;   // (left over, see DUAL)
     if (total > 1) wait_vmcnt<NL>(); else wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();                          // slice 0 is complete
     ROWS_STAMP(1);
@@ -740,17 +528,12 @@ __global__ __launch_bounds__(512, 2) void conv_rows_f16x3_kernel(const ConvArgs 
       bool did_epi = false;                                // (wave-uniform)
       ROWS_SSTAMP(0);
       if (done_item >= 0) {
-        if constexpr (MODE == 1) {
-          did_epi = finish_tile(done_item, done_part, done_first);
-        } else {
-          epilogue(done_item);
-          did_epi = true;
-        }
-        if (s == total) break;                             // the stream ends on a segment's last slice
+        epilogue(done_item);
+        did_epi = true;
+        if (s == total) break;                             // the stream ends on a tile's last slice
         zero_acc(); done_item = -1;
       }
       const bool more2 = s + 2 < total;
-      if (more2) enter_next();
       DLIP_FENCE();
       read_all(st_cur);                                    // the reads first: their latency passes under the piece issue below
       st_cur = st_cur + 1 == NSTAGE ? 0 : st_cur + 1;
@@ -775,20 +558,9 @@ __global__ __launch_bounds__(512, 2) void conv_rows_f16x3_kernel(const ConvArgs 
       ROWS_SSTAMP(3);
       mfma_all(cur_nmi);
       ROWS_SSTAMP(4);
-      if constexpr (MODE == 1) {
-        if (--kleft == 0) {
-          done_item = e_item; done_part = e_part; done_first = e_first;
-          ++e_item;
-          kleft = nk < rem ? nk : rem;
-          rem -= kleft;
-          e_part = kleft != nk;
-          e_first = false;
-        }
-      } else {
-        if (--kleft == 0) {
-          kleft = nk; done_item = e_item; e_item += nwg;
-          if constexpr (TAIL) { if (e_item >= ROWS_SC(item_short0)) cur_nmi = ROWS_SC(nmi_short); }
-        }
+      if (--kleft == 0) {
+        kleft = nk; done_item = e_item; e_item += nwg;
+        if constexpr (TAIL) { if (e_item >= ROWS_SC(item_short0)) cur_nmi = ROWS_SC(nmi_short); }
       }
       if (FIRST) {
         __builtin_amdgcn_s_barrier();                      // b(2s+1)
@@ -812,8 +584,6 @@ __global__ __launch_bounds__(512, 2) void conv_rows_f16x3_kernel(const ConvArgs 
   if (sc.stamps && tid == 0) sc.stamps[(size_t)g * 16 + 6] = __builtin_amdgcn_s_memrealtime() - sc.stamps[(size_t)g * 16 + 7];
 #endif
 }
-
-constexpr int kRowsDeclined = -1000;   // (internal) a MODE 1 launch that found no split workspace: the caller takes the ring kernel
 
 int rows_cus() {
   static int cus = 0;                                  // (one device kind per process: every MI355X has the same count)
@@ -842,14 +612,14 @@ RowsTail rows_tail(long long M, int tiles_n, int mi, int slots) {
   return t;
 }
 
-template <int MI, int EPI, int MODE = 0, bool DUAL = false, bool TAIL = false>
+template <int MI, int EPI, bool TAIL = false>
 int launch_rows(const ConvArgs& a, hipStream_t st) {
   constexpr int BM = 32 * MI;
-  constexpr size_t lds = (size_t)3 * (BM + ROWS_BN) * ROWB + (MODE == 0 && EPI != 2 ? 3 * ROWS_BN * sizeof(float) : 0);   // ring + the epilogue's parameter table
+  constexpr size_t lds = (size_t)3 * (BM + ROWS_BN) * ROWB + (EPI != 2 ? 3 * ROWS_BN * sizeof(float) : 0);   // ring + the epilogue's parameter table
   static_assert(lds <= 160 * 1024, "LDS ring exceeds a CU");
   ConvArgs b = a;
   b.tiles_n = (a.K + ROWS_BN - 1) / ROWS_BN;
-  auto kern = conv_rows_f16x3_kernel<MI, EPI, MODE, DUAL, TAIL>;
+  auto kern = conv_rows_f16x3_kernel<MI, EPI, TAIL>;
   static DlipKernelState ks;
   int e = ks.ensure_lds(reinterpret_cast<const void*>(kern), lds);
   if (e != DLIP_OK) return e;
@@ -872,28 +642,7 @@ int launch_rows(const ConvArgs& a, hipStream_t st) {
   if (items <= 0 || items > 0x3FFFFFFFll) return DLIP_EINVAL;
   sc.items = (int)items;
   sc.tiles_n = b.tiles_n;
-  sc.iters = 0; sc.G = 0; sc.slabs = nullptr; sc.counters = nullptr;
-  sc.div_G = sc.div_iters = sc.div_nk = FastDiv{0u, 0u};
-  long long grid = items < slots ? items : slots;
-  if constexpr (MODE == 1) {
-    // The ring kernel's balanced split: items x nk slices in G equal ranges, G = the resident workgroups (at least 16 slices
-    // each).  Ranges that end inside a tile need the split workspace (two slabs per workgroup, 8 ticket words per tile).
-    const long long iters = items * (long long)a.nk;
-    long long G = slots;
-    if (iters < 16 * G) G = iters / 16 > 0 ? iters / 16 : 1;
-    if ((iters + a.nk) * (G + 1) >= 0x7FFFFFFFll) return kRowsDeclined;   // the kernel's 32-bit range arithmetic
-    sc.iters = (int)iters;
-    sc.div_G = dlip_fastdiv((uint32_t)G);
-    sc.div_iters = dlip_fastdiv((uint32_t)iters);
-    sc.div_nk = dlip_fastdiv((uint32_t)a.nk);
-    if (items % G != 0) {
-      int max_words = 0;
-      if (!dlip_conv_split_workspace(st, (size_t)2 * G * BM * ROWS_BN, &sc.slabs, &sc.counters, &max_words) || items * 8 > max_words)
-        return kRowsDeclined;
-    }
-    sc.G = (int)G;
-    grid = G;
-  }
+  const long long grid = items < slots ? items : slots;
   sc.span = dlip_span_next();
 #ifdef DLIP_LAB
   sc.stamps = nullptr;
@@ -992,67 +741,6 @@ extern "C" __attribute__((visibility("hidden"))) long long dlip_conv_rows_tiles(
   return rows_tail(M, (d->K + ROWS_BN - 1) / ROWS_BN, bm / 32, rows_cus()).tiles_m;
 }
 
-// MODE 1: which launches of the LDS-DMA path (split input; dlip_conv_f16x3_dma_launch asks first) CAN take the rows kernel's general
-// mode: pixel-major operands, whole 32-channel slices, at most 32 taps, fp32 or split output (no pooled epilogue).
-// NOT CHOSEN BY THE LIBRARY: it runs only when forced (dlip_debug_set(7, 1): tests, A/B runs).  Built in round 4 to carry the
-// trunk's layers 3 and 4 (the ring kernel's 256 x 128 launches) on the 160 x 256 tile / continuous stream / register epilogue that
-// made the speech encoder's layers 25 % faster; measured on one box at B = 64 (tools/probes/rows2d_layers.py,
-// profiles/r4/rows2d_layers.txt): layer 3's convolutions 2 - 4 % SLOWER than the ring kernel (200 vs 196 us, with residual 214
-// vs 207), its stride-2 and two-source launches 4 - 11 % slower, layer 4's 6 - 18 % slower.  Why (tools/probes/rows_trunk_proxy.py):
-// on rows that fill whole rounds of tiles -- no split -- this mode does 436 - 450 TFLOP/s against the ring kernel's 410 - 423,
-// but the trunk's row counts need the balanced split (418 tiles on 256 CUs), and here a shared tile's hand-off costs 25 - 32 us per
-// launch against the ring kernel's ~10: each ping-pong half publishes / finishes in its own interval (store acknowledgements, a
-// ticket round trip, MI x parts serial slab reads), the other half waiting at the next barrier; and every workgroup enters the
-// reduction at its own slice, so layer 4's 4.7 MB of weights per 256-column block no longer stay in an XCD's 4 MiB L2 (the ring
-// kernel keeps an XCD on one 128-column block: 2.35 MB).  What would change it is in DESIGN.md section 9.
-// ROUND 5: a measured negative result belongs in the lab, not in the product library: the general mode's four instances (220-256
-// VGPRs, 65-83 SGPR spills) are compiled ONLY under -DDLIP_LAB (python -m deeplip_amd.build --lab; tests/test_kernels_gpu.py's
-// general-mode tests and tools/probes/rows2d_layers.py load that library through DLIP_LIB_PATH).  In libdeeplip_hip.so the three entry
-// points below decline every launch and dlip_debug_set refuses key 7.
-#ifdef DLIP_LAB
-static bool rows2d_ok(const ConvArgs& a, int epi) {
-  const int v = dlip_dbg_value[DLIP_DBG_ROWS2D];
-  if (v <= 0 || !dlip_conv_dma_enabled() || epi < 0 || epi > 1) return false;
-  if (a.Cw != a.C || (a.C & 31) != 0 || a.R * a.S > 32 || a.wscale == nullptr || a.pool != nullptr) return false;
-  if (a.cs_x != 128 || a.cs_w != 128 || a.wt != a.Cw * 4 || a.Hs != a.H) return false;       // slice-major images: ring kernel only
-  if (a.x2 != nullptr && (a.nk2 <= 0)) return false;
-  if (a.res != nullptr && a.pscale != nullptr) return false;                                    // (not compiled: registers)
-  const long long items = (((long long)a.M + 159) / 160) * ((a.K + ROWS_BN - 1) / ROWS_BN);
-  if (items * 8 > 65536) return false;
-  return true;
-}
-
-extern "C" __attribute__((visibility("hidden"))) int dlip_conv_rows2d_ok(const void* args, int epi) {
-  return rows2d_ok(*static_cast<const ConvArgs*>(args), epi) ? 1 : 0;
-}
-
-// Descriptor form (dlip_conv_plan / dlip_conv_kernel_kind, `dual` = a second source of c2 channels): 1 if a split-format launch of `d`
-// (with or without a residual) runs the general mode; *bm = its tile height.
-extern "C" __attribute__((visibility("hidden"))) int dlip_conv_rows2d_plan(const dlip_conv_desc* d, int c2, int* bm) {
-  const int v = dlip_dbg_value[DLIP_DBG_ROWS2D];
-  if (v <= 0 || !dlip_conv_dma_enabled() || (d->C & 31) != 0 || d->R * d->S > 32 || (c2 & 31) != 0) return 0;
-  const long long M = (long long)d->N * d->Ho * d->Wo;
-  const long long items = ((M + 159) / 160) * ((d->K + ROWS_BN - 1) / ROWS_BN);
-  if (items * 8 > 65536) return 0;
-  if (bm) *bm = 160;
-  return 1;
-}
-
-// returns kRowsDeclined when the split workspace is missing (stream capture before any eager launch, or an external block that
-// is too small): the caller then runs the ring kernel
-extern "C" __attribute__((visibility("hidden"))) int dlip_conv_f16x3_rows2d_launch(const void* args, void* stream, int epi) {
-  const ConvArgs& a = *static_cast<const ConvArgs*>(args);
-  hipStream_t st = dlip_hip_stream(stream);
-  if (a.x2 != nullptr) return epi ? launch_rows<5, 1, 1, true>(a, st) : launch_rows<5, 0, 1, true>(a, st);
-  return epi ? launch_rows<5, 1, 1, false>(a, st) : launch_rows<5, 0, 1, false>(a, st);
-}
-#else
-extern "C" __attribute__((visibility("hidden"))) int dlip_conv_rows2d_ok(const void*, int) { return 0; }
-extern "C" __attribute__((visibility("hidden"))) int dlip_conv_rows2d_plan(const dlip_conv_desc*, int, int*) { return 0; }
-extern "C" __attribute__((visibility("hidden"))) int dlip_conv_f16x3_rows2d_launch(const void*, void*, int) { return DLIP_EINVAL; }
-#endif
-extern "C" __attribute__((visibility("hidden"))) int dlip_conv_rows_declined(void) { return kRowsDeclined; }
-
 // The pooled epilogue on this kernel is correct and tested, and slower than the ring kernel's LDS-staged one: the fp64 column
 // sums taken straight from the accumulators cost ~13 us per tile in cross-lane work (64 doubles x 4 butterfly steps per channel
 // quad), tdnn.9 at B = 64: 130 us against 96 us on the ring kernel's <128,128,pool> instance (tools/bench_rows.py).  So a
@@ -1079,9 +767,9 @@ extern "C" __attribute__((visibility("hidden"))) int dlip_conv_f16x3_rows_launch
   // a launch with a short last round (rows_tail) runs the TAIL instance; everything else the instance without that code
   if (rows_tail(a.M, (a.K + ROWS_BN - 1) / ROWS_BN, mi, cus).nmi < mi) {
     switch (mi) {
-      case 3: return epi ? launch_rows<3, 1, 0, false, true>(a, st) : launch_rows<3, 0, 0, false, true>(a, st);
-      case 4: return epi ? launch_rows<4, 1, 0, false, true>(a, st) : launch_rows<4, 0, 0, false, true>(a, st);
-      default: return epi ? launch_rows<5, 1, 0, false, true>(a, st) : launch_rows<5, 0, 0, false, true>(a, st);
+      case 3: return epi ? launch_rows<3, 1, true>(a, st) : launch_rows<3, 0, true>(a, st);
+      case 4: return epi ? launch_rows<4, 1, true>(a, st) : launch_rows<4, 0, true>(a, st);
+      default: return epi ? launch_rows<5, 1, true>(a, st) : launch_rows<5, 0, true>(a, st);
     }
   }
   switch (mi) {

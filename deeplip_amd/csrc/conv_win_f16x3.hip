@@ -320,11 +320,6 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N, OCC) void conv_win_f16x3_ker
             if (wn == 4) wait_vmcnt<BASE + 4>(); else if (wn == 3) wait_vmcnt<BASE + 3>(); else if (wn == 2) wait_vmcnt<BASE + 2>();
             else if (wn == 1) wait_vmcnt<BASE + 1>(); else wait_vmcnt<BASE>();
           };
-#ifdef DLIP_LAB
-          // lab probe (DLIP_WIN_NOWAIT=1; WRONG results, timing only): what a slice costs when nobody waits for the next slice's weights --
-          // the ceiling of any deeper ring / earlier issue
-          if (a.n_inner == 77) wait_vmcnt<40>(); else
-#endif
           if (!first && c == 0 && tap == 0) wait_plus(std::integral_constant<int, B_PER + NSTORE>{});
           else if (moreP) wait_plus(std::integral_constant<int, B_PER>{});
           else wait_plus(std::integral_constant<int, 0>{});
@@ -499,7 +494,6 @@ int launch_win(const ConvArgs& a, hipStream_t st, bool out_split) {
   const long long grid = tiles < slots ? tiles : slots;
   b.span = dlip_span_next();
 #ifdef DLIP_LAB
-  b.n_inner = getenv("DLIP_WIN_NOWAIT") ? 77 : 0;
   if (getenv("DLIP_STAMP_PRINT")) {   // median cycles between the phase stamps of every workgroup's second tile
     static unsigned long long* dbuf = nullptr;
     if (!dbuf) (void)hipMalloc(reinterpret_cast<void**>(&dbuf), 2 * 4096 * 8 * 8);
@@ -589,7 +583,7 @@ extern "C" int dlip_conv_kernel_kind(const dlip_conv_desc* d) {
   if (d->C % 32 == 0 && dlip_conv_dma_enabled() &&
       win_shape_ok(d->stride_h, d->stride_w, d->H, d->W, d->Ho, d->Wo, d->R, d->S, d->dil_h, d->dil_w, d->pad_h, d->pad_w, d->K))
     return 1;
-  return (dlip_conv_rows_plan(d, nullptr) || dlip_conv_rows2d_plan(d, 0, nullptr)) ? 2 : 0;
+  return dlip_conv_rows_plan(d, nullptr) ? 2 : 0;
 }
 
 extern "C" __attribute__((visibility("hidden"))) int dlip_conv_f16x3_win_launch(const void* args, void* stream, int out_split) {

@@ -109,7 +109,7 @@ def conv_nhwc(x: Tensor, w_krsc: Tensor, bias: Optional[Tensor] = None, *, strid
         kind = lib().dlip_conv_kernel_kind(C.byref(d)) if mode == 3 else 0
         if kind == 1:
             kname, bm.value, bn.value = "conv_win_f16x3_kernel", 128, (128 if K > 64 else 64)
-        elif kind == 2:      # the rows kernel (its speech-encoder mode, or the general mode: 2-D filters / residual)
+        elif kind == 2:      # the rows kernel (the speech encoder's 1-D valid convolutions and k = 1 layers)
             kname = "conv_rows_f16x3_kernel"
         tok = hook.begin(f"{kname}<{bm.value},{bn.value}>", 2.0 * N * Ho * Wo * K * R * S * Cin)
     if stats is not None:

@@ -37,6 +37,16 @@ def test_binding_matches_header():
     assert b"invalid argument" in l.dlip_error_string(-1)
 
 
+def test_debug_key_7_is_reserved():
+    """Key 7 forced a retired experiment (the rows kernel's general mode): a positive value is refused, resetting it is accepted.
+    Host-only: dlip_debug_set makes no device call."""
+    from deeplip_amd import _lib
+    l = _lib.lib()
+    assert l.dlip_debug_set(_lib.DBG_ROWS2D, 1) != 0
+    assert l.dlip_debug_set(_lib.DBG_ROWS2D, 0) == 0
+    assert l.dlip_debug_set(_lib.DBG_ROWS2D, -1) == 0
+
+
 def test_ops_refuse_cpu_tensors():
     import torch
     from deeplip_amd import ops

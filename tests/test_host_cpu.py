@@ -179,3 +179,8 @@ def test_pmc_summary_parses_counter_csvs(tmp_path):
     assert pmc.short("void conv_win_f16x3_kernel<128, 64, 2, 2, true, 2>(ConvArgs)") == "conv_win_f16x3_kernel<128,64>"
     assert pmc.short("x::conv_igemm_f16x3_dma_kernel<256, 128, 4, 2, 2, 3, 1, false, 0>") == "conv_igemm_f16x3_dma_kernel<256,128,pool>"
     assert pmc.short("x::conv_igemm_f16x3_dma_kernel<256, 128, 4, 2, 1, 3, 1, true, 0>") == "conv_igemm_f16x3_dma_kernel<256,128,dual>"
+    # the rows kernel lost two template arguments (<MI, EPI, MODE, DUAL, TAIL> -> <MI, EPI, TAIL>): the same short key as before
+    rows_old = "void (anonymous namespace)::conv_rows_f16x3_kernel<5, 0, 0, false, false>((anonymous namespace)::ConvArgs, (anonymous namespace)::RowsSched)"
+    rows_new = "void (anonymous namespace)::conv_rows_f16x3_kernel<5, 0, false>((anonymous namespace)::ConvArgs, (anonymous namespace)::RowsSched)"
+    assert pmc.short(rows_new) == pmc.short(rows_old) == "conv_rows_f16x3_kernel<5,0>"
+    assert pmc.short(rows_new.replace("<5, 0, false>", "<4, 1, true>")) == pmc.short(rows_old.replace("<5, 0, 0, false, false>", "<4, 1, 0, false, true>")) == "conv_rows_f16x3_kernel<4,1>"

@@ -1333,9 +1333,9 @@ def test_conv_rows_pooled_epilogue(ops, case, mi, force_rows):
 
 # ---- round 4: the rows kernel's GENERAL mode (conv_rows_f16x3_kernel<5, EPI, 1, DUAL>): 2-D filters, residual, balanced split ----
 def test_conv_rows_general_mode_is_never_chosen_unforced(ops):
-    """The general mode measured slower than the ring kernel on every trunk layer (conv_rows_f16x3.hip): dlip_conv_kernel_kind /
-    dlip_conv_plan report the ring kernel's 256 x 128 tile for layers 3 and 4 at the bench's batch, and the rows kernel's
-    160 x 256 only while dlip_debug_set(7, 1) forces it."""
+    """The rows kernel's general mode measured slower than the ring kernel on every trunk layer and is retired (EXPERIMENTS.md):
+    dlip_conv_kernel_kind / dlip_conv_plan report the ring kernel's 256 x 128 tile for layers 3 and 4 at the bench's batch, and
+    dlip_debug_set(7, 1), which used to force the mode, is refused."""
     import ctypes as C
     from deeplip_amd import _lib
     from deeplip_amd.ops import ConvDesc
@@ -1351,16 +1351,10 @@ def test_conv_rows_general_mode_is_never_chosen_unforced(ops):
     assert kind(B, 6, 256, 256, ldr=256) == (0, 256, 128)
     assert kind(B, 3, 512, 512, ldr=512) == (0, 256, 128)
     assert kind(B, 11, 128, 128)[0] == 1                         # layer 2's same-size convolutions: the window kernel
-    if _lib.lib().dlip_debug_set(_lib.DBG_ROWS2D, 1) != 0:       # the product library: the mode is not even compiled in
-        _lib.debug_set(_lib.DBG_ROWS2D, 0)                       # (switching it OFF is always accepted)
-        assert kind(B, 6, 256, 256, ldr=256) == (0, 256, 128)
-        return
-    try:                                                         # the lab library (DLIP_LIB_PATH): forcing routes layers 3 / 4 there
-        assert kind(B, 6, 256, 256, ldr=256) == (2, 160, 256)
-        assert kind(B, 3, 512, 512, ldr=512) == (2, 160, 256)
-        assert kind(B, 11, 128, 128)[0] == 1                     # (the window kernel is asked first)
-    finally:
-        _lib.debug_set(_lib.DBG_ROWS2D, -1)
+    assert _lib.lib().dlip_debug_set(_lib.DBG_ROWS2D, 1) != 0   # forcing the retired mode is refused
+    _lib.debug_set(_lib.DBG_ROWS2D, 0)                           # (switching it OFF is always accepted)
+    assert kind(B, 6, 256, 256, ldr=256) == (0, 256, 128)
+    _lib.debug_set(_lib.DBG_ROWS2D, -1)
 
 
 @pytest.mark.parametrize("N,H,W,C,R,S,stride,pad,dil", [(3, 5, 6, 64, 3, 3, 1, 1, 1), (2, 1, 40, 128, 1, 3, 1, 0, 2), (2, 4, 4, 192, 3, 3, 2, 1, 1),

@@ -2,7 +2,6 @@
 # A/B two library builds on one box (device-to-device variance is ~10 %: only same-box numbers compare).
 #   here:  tools/ab.sh snapshot      -> builds the committed HEAD sources into deeplip_amd/lib/libdeeplip_hip_A.so
 #   box:   tools/ab.sh run [bench_dma.py args]   -> interleaved rounds, A = snapshot, B = working tree build
-# (the ring kernel's lock-step loop, round 3's `nopp` A/B, is tile 11 of the lab build now: python -m deeplip_amd.build --lab)
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 if [ "$1" = snapshot ]; then
   T=$(mktemp -d); git -C $R archive ${2:-HEAD} deeplip_amd/csrc include | tar -x -C $T

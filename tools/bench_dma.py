@@ -14,7 +14,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=64)
 ap.add_argument("--iters", type=int, default=20)
 ap.add_argument("--only", default="")
-ap.add_argument("--variants", default="-1", help="comma list of DMA tile ids (dlip_debug_set; -1 = built-in choice; 6..9 need the lab build via DLIP_LIB_PATH)")
+ap.add_argument("--variants", default="-1", help="comma list of DMA tile ids (dlip_debug_set; -1 = built-in choice, 0..5 = the tile menu)")
 ap.add_argument("--streamk", type=int, default=-1, help="balanced split: -1 built-in cost model, 0 never, 2 always (dlip_debug_set)")
 ap.add_argument("--ninner", type=int, default=-1, help="1: tile order with the output-channel block inner (experiment)")
 ap.add_argument("--win", type=int, default=-1, help="window kernel: -1 built-in rule, 0 off (ring kernel everywhere), 1 K <= 64 only")

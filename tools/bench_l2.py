@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Same-size 3x3 convolution at 128 -> 128 channels (layer 2, second block): 128-column window instance (dlip_debug_set
-DLIP_DBG_WIN = 2, experiment) vs the ring kernel; correctness on a small batch first, then timing at B = 64 clips."""
+"""Same-size 3x3 convolution at 128 -> 128 channels (layer 2, second block): the window kernel's 128-column instance (the built-in
+choice) vs the ring kernel (dlip_debug_set DLIP_DBG_WIN = 0); correctness on a small batch first, then timing at B = 64 clips."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -20,14 +20,14 @@ for (N, H, C, K) in [(40, 11, 128, 128), (64 * 29, 11, 128, 128)]:
     y = torch.empty(N, H, H, K, device="cuda")
     rs = ops.split_pack(torch.randn(N, H, H, K, device="cuda"))
     for res in (rs, None):
-        a = run(N, H, C, K, res, 2).clone(); r = run(N, H, C, K, res, 0).clone()
+        a = run(N, H, C, K, res, -1).clone(); r = run(N, H, C, K, res, 0).clone()
         torch.cuda.synchronize()
         ua, ur = ops.split_unpack(a), ops.split_unpack(r)
         print(f"N={N} res={res is not None}: max|win-ring|/max = {float((ua - ur).abs().max() / ur.abs().max()):.2e}", flush=True)
         if N < 100:
             continue
         for rnd in range(2):
-            for w in (2, 0):
+            for w in (-1, 0):
                 run(N, H, C, K, res, w)
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
