@@ -13,7 +13,7 @@ import torch  # must be imported first: the library binds to the HIP runtime tor
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DLIP_LIB_PATH") or os.path.join(_PKG, "lib", "libdeeplip_hip.so")  # env override: A/B builds
-ABI_VERSION = 58
+ABI_VERSION = 59
 LIFT_WORDS = 4098
 LIFT_BCAST = 2048
 
@@ -192,6 +192,13 @@ SIGNATURES = {
     "dlip_compact_bilinear_bwd_f32": [c_f] * 9 + [c_i32] * 6 + [c_stream],
     "dlip_time_tail_zero_f32": [c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_i32, c_stream],
     "dlip_avgpool_time_ragged_f32": [c_f, c_f, c_i32, c_f, c_i32, c_i32, c_i32, c_i32, c_stream],
+    "dlip_statpool_nhwc_f32": [c_f, c_f, c_i32, C.c_float, c_f, c_i32, c_i32, c_i32, c_i32, c_stream],
+    "dlip_statpool_nhwc_bwd_f32": [c_f, c_f, c_f, C.c_float, c_f, c_i32, c_i32, c_i32, c_i32, c_stream],
+    "dlip_swap_axes_nhwc_f32": [c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_stream],
+    "dlip_time_valid_lengths_i32": [c_f, c_i32, c_i32, c_f, c_i32, c_stream],
+    "dlip_attentive_stat_pool_eps_f32": [c_f, c_f, c_f, c_f, c_f, c_i32, C.c_float, c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_stream],
+    "dlip_attentive_stat_pool_eps_bwd_f32": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i32, C.c_float, c_f, c_f, c_f, c_f, c_i32, c_i32, c_i32,
+                                             c_i32, c_stream],
 }
 
 

@@ -718,20 +718,25 @@ class MeanStdPoolFn(Function):
 class AttnStatPoolFn(Function):
     """The tail of AttentiveStatPooling (models/audio_models/pooling.py:87-107) behind its hidden layer: e = relu(hidden) v + k,
     alpha = softmax over frames, y = [sum alpha x | sqrt(sum alpha x^2 - mean^2)].  x [B,T,C], hidden [B,T,H] (= x W^T + b from the
-    differentiable GEMM in front: W, b and the second path into x get their gradients there), v [H,1], k [1,1]."""
+    differentiable GEMM in front: W, b and the second path into x get their gradients there), v [H,1], k [1,1].  ``eps`` > 0 (the ResNet
+    speech encoder's head): std = sqrt(max(sum alpha x^2 - mean^2, 0) + eps), the _eps entry points (ABI 59); 0: the reference's expression."""
 
     @staticmethod
-    def forward(ctx, x, hidden, v, k):
+    def forward(ctx, x, hidden, v, k, eps=0.0):
         x, hidden = x.contiguous(), hidden.contiguous()
         B, T, C_ = x.shape
         H = hidden.shape[2]
-        y = torch.empty((B, 2 * C_), device=x.device, dtype=torch.float32)
         alpha = torch.empty((B, T), device=x.device, dtype=torch.float32)
         vv, kk = v.detach().contiguous(), k.detach().contiguous()
-        check(lib().dlip_attentive_stat_pool_f32(ptr(x), ptr(hidden), ptr(vv), ptr(kk), None, 0, ptr(y), ptr(alpha), B, T, C_, H,
-                                                 stream_handle()), "dlip_attentive_stat_pool_f32")
+        if eps:
+            y = ops.attentive_stat_pool_eps(x, hidden, vv, kk, eps, alpha_out=alpha)
+        else:
+            y = torch.empty((B, 2 * C_), device=x.device, dtype=torch.float32)
+            check(lib().dlip_attentive_stat_pool_f32(ptr(x), ptr(hidden), ptr(vv), ptr(kk), None, 0, ptr(y), ptr(alpha), B, T, C_, H,
+                                                     stream_handle()), "dlip_attentive_stat_pool_f32")
         ctx.save_for_backward(x, hidden, vv, alpha, y)
         ctx.shapes = (tuple(v.shape), tuple(k.shape))
+        ctx.eps = float(eps)
         return y
 
     @staticmethod
@@ -743,22 +748,72 @@ class AttnStatPoolFn(Function):
         dh = torch.empty_like(hidden)
         rde = torch.empty_like(hidden)
         de = torch.empty((B, T), device=x.device, dtype=torch.float32)
-        check(lib().dlip_attentive_stat_pool_bwd_f32(ptr(x), ptr(hidden), ptr(vv), ptr(alpha), ptr(y), ptr(dy.contiguous()), None, 0, ptr(dx),
-                                                     ptr(dh), ptr(rde), ptr(de), B, T, C_, H, stream_handle()), "dlip_attentive_stat_pool_bwd_f32")
+        if ctx.eps:
+            check(lib().dlip_attentive_stat_pool_eps_bwd_f32(ptr(x), ptr(hidden), ptr(vv), ptr(alpha), ptr(y), ptr(dy.contiguous()), None, 0,
+                                                             ctx.eps, ptr(dx), ptr(dh), ptr(rde), ptr(de), B, T, C_, H, stream_handle()),
+                  "dlip_attentive_stat_pool_eps_bwd_f32")
+        else:
+            check(lib().dlip_attentive_stat_pool_bwd_f32(ptr(x), ptr(hidden), ptr(vv), ptr(alpha), ptr(y), ptr(dy.contiguous()), None, 0, ptr(dx),
+                                                         ptr(dh), ptr(rde), ptr(de), B, T, C_, H, stream_handle()), "dlip_attentive_stat_pool_bwd_f32")
         dv = _colsum(rde.view(B * T, H)).view(ctx.shapes[0]) if ctx.needs_input_grad[2] else None
         dk = _colsum(de.view(B * T, 1)).view(ctx.shapes[1]) if ctx.needs_input_grad[3] else None
-        return dx, dh, dv, dk
+        return dx, dh, dv, dk, None
 
 
-def attentive_stat_pool(x, pool):
+def attentive_stat_pool(x, pool, eps=0.0):
     """AttentiveStatPooling.forward under model.train() (pooling.py:99-107) on channels-last x [B,T,C] -> [B,2C]: the hidden layer
     W x + b is the engine's differentiable 1 x 1 convolution (forward, data and weight gradient on the MFMA kernels), the rest
-    AttnStatPoolFn."""
+    AttnStatPoolFn (``eps``: its floored standard deviation)."""
     from . import autograd_video as av
     B, T, C_ = x.shape
     H = pool.hidden_size
-    hidden = av.conv(x.reshape(B, 1, T, C_), pool.W.view(H, C_, 1, 1), pool.b.reshape(-1)).reshape(B, T, H)
-    return AttnStatPoolFn.apply(x, hidden, pool.v, pool.k)
+    if H % 4:       # (the train-path convolution takes output widths in multiples of 4: any other hidden size is the nn.Linear Function's)
+        hidden = linear(x.reshape(B * T, C_), pool.W, pool.b.reshape(-1)).reshape(B, T, H)
+    else:
+        hidden = av.conv(x.reshape(B, 1, T, C_), pool.W.view(H, C_, 1, 1), pool.b.reshape(-1)).reshape(B, T, H)
+    return AttnStatPoolFn.apply(x, hidden, pool.v, pool.k, eps)
+
+
+class StatPoolNHWCFn(Function):
+    """Statistics pooling of the ResNet speech encoder's map [N,H,W,C] -> [N, 2 H C] = cat(mean, sqrt(unbiased variance + eps)) over W
+    (dlip_statpool_nhwc_f32 / _bwd_f32): one length per batch, as a training batch has."""
+
+    @staticmethod
+    def forward(ctx, x, eps):
+        x = x.contiguous()
+        y = ops.statpool_nhwc(x, None, 0, eps)
+        ctx.save_for_backward(x, y)
+        ctx.eps = float(eps)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, y = ctx.saved_tensors
+        N, H, W, C_ = x.shape
+        dx = torch.empty_like(x)
+        check(lib().dlip_statpool_nhwc_bwd_f32(ptr(x), ptr(y), ptr(dy.contiguous()), ctx.eps, ptr(dx), N, H, W, C_, stream_handle()),
+              "dlip_statpool_nhwc_bwd_f32")
+        return dx, None
+
+
+class SwapAxesNHWCFn(Function):
+    """[N,A,B,C] -> [N,B,A,C] (dlip_swap_axes_nhwc_f32); the backward is the same copy the other way."""
+
+    @staticmethod
+    def forward(ctx, x):
+        return ops.swap_axes_nhwc(x.contiguous())
+
+    @staticmethod
+    def backward(ctx, dy):
+        return ops.swap_axes_nhwc(dy.contiguous())
+
+
+def statpool_nhwc(x, eps):
+    return StatPoolNHWCFn.apply(x, eps)
+
+
+def swap_axes_nhwc(x):
+    return SwapAxesNHWCFn.apply(x)
 
 
 def materialize_pending(y, pending):

@@ -714,6 +714,62 @@ def avgpool_time_ragged(x: Tensor, lengths: Tensor, shift: int = 0) -> Tensor:
     return y
 
 
+def statpool_nhwc(x: Tensor, lengths: Optional[Tensor] = None, shift: int = 0, eps: float = 1e-5) -> Tensor:
+    """x [N,H,W,C] fp32 (W = time) -> [N, 2 H C] = cat(mean, sqrt(unbiased variance + eps)) over the valid frames w < Wb of image n, per
+    feature j = h C + c (dlip_statpool_nhwc_f32).  ``lengths`` (int32 CUDA [N], input frames) / ``shift``: Wb as time_tail_zero; None:
+    Wb = W, which must be >= 2."""
+    _req(x, "x")
+    _req(lengths, "lengths", torch.int32)
+    if x.dim() != 4 or x.shape[3] % 4 or not 0 <= int(shift) <= 16 or (lengths is not None and lengths.numel() != x.shape[0]):
+        raise ValueError("statpool_nhwc: x [N,H,W,C] with C % 4 == 0, one int32 length per image or none, 0 <= shift <= 16")
+    N, H, W, Cc = x.shape
+    if W < 2:
+        raise ValueError(f"statpool_nhwc: the unbiased standard deviation needs >= 2 frames, the map has {W}")
+    y = _empty((N, 2 * H * Cc), x.device)
+    check(lib().dlip_statpool_nhwc_f32(ptr(x), ptr(lengths), int(shift), float(eps), ptr(y), N, H, W, Cc, stream_handle()),
+          "dlip_statpool_nhwc_f32")
+    return y
+
+
+def swap_axes_nhwc(x: Tensor) -> Tensor:
+    """x [N,A,B,C] -> [N,B,A,C] (dlip_swap_axes_nhwc_f32): [N,H,W,C] -> [N,W,H,C], each frame's H C features contiguous, and back."""
+    _req(x, "x")
+    if x.dim() != 4 or x.shape[3] % 4:
+        raise ValueError("swap_axes_nhwc: x [N,A,B,C] with C % 4 == 0")
+    N, A, B, Cc = x.shape
+    y = _empty((N, B, A, Cc), x.device)
+    check(lib().dlip_swap_axes_nhwc_f32(ptr(x), ptr(y), N, A, B, Cc, stream_handle()), "dlip_swap_axes_nhwc_f32")
+    return y
+
+
+def time_valid_lengths(lengths: Tensor, shift: int, W: int) -> Tensor:
+    """int32 CUDA [N] input lengths -> the valid frames ((clamp(L, 1, W << shift) - 1) >> shift) + 1 on a W-frame axis behind ``shift``
+    stride-2 stages, formed on the device (dlip_time_valid_lengths_i32)."""
+    _req(lengths, "lengths", torch.int32)
+    if lengths is None or not 0 <= int(shift) <= 16 or W < 1:
+        raise ValueError("time_valid_lengths: int32 lengths, 0 <= shift <= 16, W >= 1")
+    out = _empty((lengths.numel(),), lengths.device, torch.int32)
+    check(lib().dlip_time_valid_lengths_i32(ptr(lengths), int(shift), int(W), ptr(out), lengths.numel(), stream_handle()),
+          "dlip_time_valid_lengths_i32")
+    return out
+
+
+def attentive_stat_pool_eps(x: Tensor, hidden: Tensor, v: Tensor, k: Tensor, eps: float, lengths: Optional[Tensor] = None,
+                            alpha_out: Optional[Tensor] = None) -> Tensor:
+    """x [B,T,C], hidden [B,T,Hd] (= x W^T + b) -> [B,2C] = cat(sum alpha x, sqrt(max(sum alpha x^2 - mean^2, 0) + eps)), alpha = softmax over
+    the first lengths[b] frames of relu(hidden) v + k (dlip_attentive_stat_pool_eps_f32)."""
+    for t, n in ((x, "x"), (hidden, "hidden"), (v, "v"), (k, "k"), (alpha_out, "alpha_out")):
+        _req(t, n)
+    _req(lengths, "lengths", torch.int32)
+    B, T, Cc = x.shape
+    if tuple(hidden.shape[:2]) != (B, T) or v.numel() != hidden.shape[2] or k.numel() != 1 or (lengths is not None and lengths.numel() != B):
+        raise ValueError("attentive_stat_pool_eps: x [B,T,C], hidden [B,T,Hd], v [Hd], k [1], one length per utterance or none")
+    y = _empty((B, 2 * Cc), x.device)
+    check(lib().dlip_attentive_stat_pool_eps_f32(ptr(x), ptr(hidden), ptr(v), ptr(k), ptr(lengths), 0, float(eps), ptr(y), ptr(alpha_out),
+                                                 B, T, Cc, hidden.shape[2], stream_handle()), "dlip_attentive_stat_pool_eps_f32")
+    return y
+
+
 def l1_sum(w: Tensor) -> Tensor:
     """sum |w| as a 0-d device tensor (dlip_l1_sum_f32: fp64 accumulation, fixed order)."""
     _req(w, "w")

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define DLIP_ABI_VERSION 58
+#define DLIP_ABI_VERSION 59
 #define DLIP_LIFT_WORDS 4098   /* a gradient's power-of-two lift: (2^e, 2^-e), then 2^-e repeated 2048 times (the post_scale vector of
                                   the convolution that consumes the lifted gradient); while it is formed the words behind the pair
                                   hold one maximum per workgroup of the producing pass */
@@ -1058,6 +1058,44 @@ int dlip_cmvn_nct_ragged_f32(const float* feat, const float* energy, const int32
                              int32_t C, int32_t ldf, int32_t normalize, dlip_stream_t stream);
 int dlip_delta_nct_ragged_f32(const float* x, const int32_t* frame_lengths, float* y, int32_t B, int32_t C, int32_t NF, int32_t order,
                               dlip_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 59) STATISTICS AND ATTENTIVE POOLING of the ResNet speech encoder (`arch: resnet`, `pooling: statistic | attentive_statistic`;
+ * conf/audio_config.yaml:102 names the key, no source ships upstream: deeplip_amd/audio_resnet.py and DESIGN.md 4b are the
+ * definition).  x is the trunk's last map, NHWC [N,H,W,C] fp32 with H = frequency and W = time; the pooled feature index is
+ * j = h C + c (the channels-last flatten), D = H C.  `lengths` / `shift` as in the ABI 56 block: utterance n is valid for its first
+ * Wb = ((clamp(lengths[n], 1, W << shift) - 1) >> shift) + 1 frames; lengths == NULL: Wb = W.  The map is post-ReLU, so a feature
+ * that is constant over time is ordinary: every standard deviation here carries eps > 0 UNDER the root, and the backward divides
+ * by a std >= sqrt(eps).  C % 4 == 0, every tensor 16-byte aligned, no atomics, the same bits on every run.
+ *
+ * dlip_statpool_nhwc_f32 (pooling.py:24-26 on the map): y [N, 2D] = mean_j = sum_{w < Wb} x / Wb | std_j = sqrt(sum_{w < Wb}
+ *   (x - mean)^2 / (Wb - 1) + eps), one pass over the map (no transposed or intermediate copy), fp64 sums in a fixed order.  The lengths
+ *   are clamped on the device and never read on the host: a recorded plan replays with a new vector.  Frames w >= Wb are never
+ *   loaded.  Wb == 1 gives std = sqrt(eps).  N, H <= 65535, 0 <= shift <= 16.
+ * dlip_statpool_nhwc_bwd_f32: dx = dmean / W + dstd (x - mean) / ((W - 1) std) with mean and std read from y; every element of dx is
+ *   written.  Rectangular batches only (a training batch is cropped to one length, datasets.py:112-115); W >= 2; eps > 0 is the
+ *   forward's (the std in y holds it: the argument is checked, not used in the arithmetic).
+ * dlip_swap_axes_nhwc_f32: y[n, b, a, :] = x[n, a, b, :] for x [N,A,B,C] -- the copy [N,H,W,C] -> [N,W,H C] that makes each frame's
+ *   D-vector contiguous for the attentive pooling's hidden-layer GEMM; its backward is the same call with A and B exchanged.
+ * dlip_time_valid_lengths_i32: valid[n] = Wb as above, on the device -- the frame counts the attentive pooling kernels take as `len`.
+ * dlip_attentive_stat_pool_eps_f32 / dlip_attentive_stat_pool_eps_bwd_f32 (pooling.py:87-107): dlip_attentive_stat_pool_f32 and its
+ *   backward with std = sqrt(max(sum_t alpha x^2 - mean^2, 0) + eps); the same kernels behind a template argument, the entry
+ *   points without eps keep their instruction sequence.  The backward takes the max as the identity (the weighted variance is >= 0
+ *   in exact arithmetic) and forms dx from the centred value: dx = alpha_t (dmean + dstd (x - mean) / std), in fp64.  LDS of the
+ *   backward: (3 C + T) floats <= 60 KiB.
+ * ------------------------------------------------------------------------------------------ */
+int dlip_statpool_nhwc_f32(const float* x, const int32_t* lengths, int32_t shift, float eps, float* y, int32_t N, int32_t H, int32_t W,
+                           int32_t C, dlip_stream_t stream);
+int dlip_statpool_nhwc_bwd_f32(const float* x, const float* y, const float* dy, float eps, float* dx, int32_t N, int32_t H, int32_t W,
+                               int32_t C, dlip_stream_t stream);
+int dlip_swap_axes_nhwc_f32(const float* x, float* y, int32_t N, int32_t A, int32_t B, int32_t C, dlip_stream_t stream);
+int dlip_time_valid_lengths_i32(const int32_t* lengths, int32_t shift, int32_t W, int32_t* valid, int32_t N, dlip_stream_t stream);
+int dlip_attentive_stat_pool_eps_f32(const float* x, const float* hidden, const float* v, const float* k, const int32_t* len,
+                                     int32_t len_add, float eps, float* y, float* alpha_out, int32_t B, int32_t T, int32_t C, int32_t Hd,
+                                     dlip_stream_t stream);
+int dlip_attentive_stat_pool_eps_bwd_f32(const float* x, const float* hidden, const float* v, const float* alpha, const float* y,
+                                         const float* dy, const int32_t* len, int32_t len_add, float eps, float* dx, float* dhidden,
+                                         float* rde, float* de, int32_t B, int32_t T, int32_t C, int32_t Hd, dlip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Step plans.  The reference drives its encoders from a Python loop, one utterance and one torch.nn layer

@@ -66,6 +66,19 @@ def build_criterion(train_opts, embedding_dim, n_spk):
     return CrossEntropy(embedding_dim, n_spk)
 
 
+def build_model(model_opts, data_opts):
+    """The encoder the ``model`` section names (train_audio.py:60-68).  The ResNet's statistics poolings size their vector by the feature
+    dimension, which the ``data`` section knows: it is filled into the ``resnet`` sub-dict when that leaves ``feat_dim`` out."""
+    arch = model_opts["arch"]
+    if arch in ("tdnn", "etdnn"):
+        return tdnn.SpeakerEmbNet(model_opts)
+    if arch == "resnet":                                                     # train_audio.py:64-66 (`import models.resnet`)
+        import models.resnet as resnet
+        model_opts[arch].setdefault("feat_dim", int(data_opts.get("feat_dim", 40)))
+        return resnet.SpeakerEmbNet(model_opts)
+    raise NotImplementedError("Other models are not implemented!")           # train_audio.py:67-68
+
+
 class Trainer(object):
     def __init__(self, config="conf/audio_config.yaml", overrides=None, arith_mode=None):
         with open(os.path.join(ROOT, config)) as f:
@@ -86,13 +99,7 @@ class Trainer(object):
         torch.cuda.set_device(self.device)
         self.rank, self.world = ddist.init_from_env(self.device)
         arch = self.model_opts["arch"]
-        if arch in ("tdnn", "etdnn"):
-            self.model = tdnn.SpeakerEmbNet(self.model_opts)
-        elif arch == "resnet":                                               # train_audio.py:64-66 (`import models.resnet`)
-            import models.resnet as resnet
-            self.model = resnet.SpeakerEmbNet(self.model_opts)
-        else:
-            raise NotImplementedError("Other models are not implemented!")   # train_audio.py:67-68
+        self.model = build_model(self.model_opts, self.data_opts)
         d = self.data_opts
         # the resnet takes [B,1,F,T] with F = the feature dimension of the data section (train_audio.py:183-184)
         F_ = self.model_opts[arch]["input_dim"] if arch != "resnet" else int(d.get("feat_dim", 40))
@@ -156,7 +163,7 @@ class Trainer(object):
             return [Ta]
         lo, hi = int(cf[0]), min(int(cf[1]), Ta)
         lo = min(lo, hi)
-        need = (self.model.frames_consumed() + 2) if hasattr(self.model, "frames_consumed") else 1
+        need = self._min_frames()
         if lo < need:
             raise ValueError(f"train.crop_frames: the encoder needs utterances of >= {need} frames")
         return rung_tops(lo, hi, float(self.train_opts.get("crop_ladder_waste", 0.10)), 4 if hi % 4 == 0 else 1)
@@ -367,9 +374,12 @@ class Trainer(object):
         return self._extractor[1]
 
     def _min_frames(self) -> int:
-        """The shortest utterance the encoder embeds: one frame for the ResNet (zero-padded convolutions, average pooling); for the
-        TDNNs the frames their valid convolutions consume + the two pooled frames the unbiased std needs (pooling.py:24-26)."""
-        return 1 if self.model_opts["arch"] == "resnet" else self.model.frames_consumed() + 2
+        """The shortest utterance the encoder embeds.  The ResNet says itself (min_frames(): one frame -- zero-padded convolutions --
+        or what leaves two frames on its last map under `pooling: statistic`); for the TDNNs the frames their valid convolutions
+        consume + the two pooled frames the unbiased std needs (pooling.py:24-26)."""
+        if hasattr(self.model, "min_frames"):
+            return int(self.model.min_frames())
+        return self.model.frames_consumed() + 2
 
     def close(self):
         """Release the recorded extraction plans (their arenas) and the recorded training steps."""
