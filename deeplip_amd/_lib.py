@@ -7,199 +7,23 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 import threading
 
 import torch  # must be imported first: the library binds to the HIP runtime torch already loaded
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DLIP_LIB_PATH") or os.path.join(_PKG, "lib", "libdeeplip_hip.so")  # env override: A/B builds
-ABI_VERSION = 59
-LIFT_WORDS = 4098
-LIFT_BCAST = 2048
+HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "deeplip_hip.h")   # what build.py compiles (and hashes) the library from
 
 _lock = threading.Lock()
 _lib = None
 _status = None
 _status_np = None
 
-c_f = C.c_void_p      # device float* (passed as integer address)
+c_f = C.c_void_p      # device pointer (passed as integer address); the three names tests spell expected argtypes with
 c_i32 = C.c_int32
 c_i64 = C.c_int64
-c_stream = C.c_void_p
-
-
-class ConvDesc(C.Structure):
-    """struct dlip_conv_desc"""
-    _fields_ = [(n, C.c_int32) for n in (
-        "N", "H", "W", "C", "K", "R", "S", "stride_h", "stride_w", "pad_h", "pad_w", "dil_h", "dil_w",
-        "Ho", "Wo", "ldx", "ldy", "ldr")]
-
-
-# name -> argtypes (restype is int for all but dlip_error_string); mirrors include/deeplip_hip.h
-SIGNATURES = {
-    "dlip_abi_version": [],
-    "dlip_conv_nhwc_f32": [C.POINTER(ConvDesc), c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_stream],
-    "dlip_conv_nhwc_f16x3": [C.POINTER(ConvDesc), c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i32, c_stream],
-    "dlip_conv2_nhwc_f16x3": [C.POINTER(ConvDesc), c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f,
-                              c_i32, c_stream],
-    "dlip_conv_pool_partial_bytes": [C.POINTER(ConvDesc), C.POINTER(C.c_int32)],
-    "dlip_conv_pool_f16x3": [C.POINTER(ConvDesc), c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i64, c_i32, c_f, c_i32, c_i32, c_stream],
-    "dlip_pool_finish_f32": [c_f, c_i64, c_i32, c_i32, c_i32, c_f, c_i32, c_i32, c_i32, c_i32, c_f, c_stream],
-    "dlip_set_status_words": [c_f],
-    "dlip_status_scope": [c_f],
-    "dlip_span_scope_begin": [c_f, c_f, c_i32],
-    "dlip_span_scope_end": [c_stream, C.POINTER(C.c_int32)],
-    "dlip_range_scope_begin": [c_f, c_i32],
-    "dlip_range_scope_end": [c_stream],
-    "dlip_debug_set": [c_i32, c_i32],
-    "dlip_bn_rows_chunks": [c_i32],
-    "dlip_bn_rows_train_fwd_f32": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i32, c_i32, C.c_float, C.c_float, C.c_float, c_i32, c_i32, c_f, c_stream],
-    "dlip_conv_stats_chunks": [C.POINTER(ConvDesc)],
-    "dlip_conv_nhwc_stats_f16x3": [C.POINTER(ConvDesc), c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i64, c_stream],
-    "dlip_bn_rows_train_bwd_f32": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i32, c_i32, C.c_float, c_i32, c_f, c_stream],
-    "dlip_bn_prelu_rows_train_fwd_f32": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i32, c_i32, C.c_float, C.c_float, c_f, c_stream],
-    "dlip_bn_prelu_maxpool_train_fwd_f32": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i64, c_i32, c_i32, c_i32, C.c_float, C.c_float, c_f, c_stream],
-    "dlip_bn_prelu_maxpool_train_bwd_f32": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i64, c_i32, c_i32, c_i32, c_f, c_stream],
-    "dlip_bn_add_prelu_rows_train_fwd_f32": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i32, c_i32, C.c_float, C.c_float, c_f, c_stream],
-    "dlip_bn_add_prelu_rows_train_bwd_f32": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i32, c_i32, c_f, c_stream],
-    "dlip_wgrad_operand_split_bn_f32": [c_f, c_f, c_i64, c_i64, c_i32, c_f, c_f, c_f, c_f, c_f, C.c_float, c_f, c_stream],
-    "dlip_wgrad_chwn_bn_f32": [c_f, c_f, c_i64, c_i32, c_i32, c_i32, c_i32, c_f, c_f, c_f, c_f, c_f, C.c_float, c_f, c_stream],
-    "dlip_meanstd_pool_bn_f32": [c_f, c_f, c_f, c_f, c_f, C.c_float, c_f, c_i32, c_i32, c_i32, c_stream],
-    "dlip_meanstd_pool_bwd_bn_f32": [c_f, c_f, c_f, c_f, c_f, C.c_float, c_f, c_f, c_f, c_i32, c_i32, c_i32, c_stream],
-    "dlip_meanstd_bwd_coef_f32": [c_f, c_f, c_f, c_i32, c_i32, c_i32, c_stream],
-    "dlip_bn_rows_train_bwd_ms_f32": [c_f, c_i32, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i32, c_i32, C.c_float, c_f, c_stream],
-    "dlip_bn_rows_train_bwd_sums_f32": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i32, c_i32, C.c_float, c_i32, c_f, c_f, c_i32,
-                                        c_stream],
-    "dlip_wgrad_operand_split_bnbwd_f32": [c_f, c_f, c_f, c_i64, c_i64, c_i32, c_f, c_f, c_f, c_f, c_f, c_f, c_i64, C.c_float, c_i32, c_f, c_f,
-                                           c_i32, c_f, c_i32, c_stream],
-    "dlip_wgrad_chwn_bnbwd_f32": [c_f, c_f, c_f, c_i64, c_i32, c_i32, c_i32, c_i32, c_f, c_f, c_f, c_f, c_f, c_f, c_i64, C.c_float, c_i32, c_f,
-                                  c_f, c_stream],
-    "dlip_bn_apply_rows_f32": [c_f, c_f, c_f, c_f, c_f, c_f, C.c_float, c_f, c_i32, c_i32, c_stream],
-    "dlip_dropout_keep_f32": [c_f, c_f, c_f, c_i64, C.c_float, C.c_float, c_stream],
-    "dlip_chomp_concat_f32": [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32), c_i32, c_f, c_i32, c_i32, c_i32, c_stream],
-    "dlip_upsample_zero_split_f32": [c_f, c_f, c_f, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_bn_prelu_rows_train_bwd_f32": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i32, c_i32, c_f, c_stream],
-    "dlip_colsum_rows_f32": [c_f, c_f, c_f, c_i32, c_i32, c_stream],
-    "dlip_meanstd_pool_bwd_f32": [c_f, c_f, c_f, c_f, c_i32, c_i32, c_i32, c_stream],
-    "dlip_permute3_f32": [c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_pow2_lift_f32": [c_f, c_f, c_i64, C.c_float, c_stream],
-    "dlip_pow2_scale_f32": [c_f, c_f, c_i64, C.c_float, c_stream],
-    "dlip_split_pack_scaled_pad_f32": [c_f, c_f, c_f, c_i64, c_i32, c_i32, c_stream],
-    "dlip_split_pack_scaled_f32": [c_f, c_f, c_f, c_i64, c_i32, c_stream],
-    "dlip_split_weights_rows_f32": [c_f, c_f, c_f, c_i32, c_i32, c_stream],
-    "dlip_split_weights_perm_f32": [c_f, c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_fill_from_scalar_f32": [c_f, c_f, c_i32, c_stream],
-    "dlip_aam_margin_f32": [c_f, c_f, c_f, c_f, c_i32, c_i32, C.c_float, c_i32, c_i32, c_stream],
-    "dlip_split_weights_multi_f32": [c_f, c_f, c_i32, c_i32, c_stream],
-    "dlip_wgrad_operand_split_f32": [c_f, c_f, c_i64, c_i64, c_i32, c_f, c_f, c_stream],
-    "dlip_wgrad_operand_f32": [c_f, c_f, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_f, c_stream],
-    "dlip_stem_wgrad_chwn_f32": [c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_wgrad_conv_f16x3": [c_f, c_f, c_f, c_f, c_f, c_f] + [c_i32] * 15 + [c_stream],
-    "dlip_wgrad_chwn_f32": [c_f, c_f, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_f, c_i32, c_f, c_stream],
-    "dlip_tap_gather_f32": [c_f, c_f, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_upsample_zero_f32": [c_f, c_f, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_prelu_rows_fwd_f32": [c_f, c_f, c_f, c_i64, c_i32, c_stream],
-    "dlip_add_prelu_rows_fwd_f32": [c_f, c_f, c_f, c_f, c_f, c_i64, c_i32, c_stream],
-    "dlip_prelu_rows_bwd_f32": [c_f, c_f, c_f, c_f, c_f, c_i64, c_i32, c_stream],
-    "dlip_maxpool3x3s2_bwd_f32": [c_f, c_f, c_f, c_i64, c_i32, c_i32, c_i32, c_stream],
-    "dlip_maxpool3x3s2_idx_f32": [c_f, c_f, C.c_void_p, c_i64, c_i32, c_i32, c_i32, c_stream],
-    "dlip_maxpool3x3s2_bwd_idx_f32": [C.c_void_p, c_f, c_f, c_i64, c_i32, c_i32, c_i32, c_stream],
-    "dlip_row_broadcast_f32": [c_f, c_f, c_f, c_i64, c_i32, c_i32, C.c_float, c_stream],
-    "dlip_stem_im2col_f32": [c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_stem_wgrad_operand_f32": [c_f, c_f, c_i64, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_split_stem_weights_f32": [c_f, c_f, c_f, c_i32, c_stream],
-    "dlip_mul_mask_f32": [c_f, c_f, c_f, c_i64, C.c_float, c_stream],
-    "dlip_conv_workspace_bytes": [],
-    "dlip_conv_set_workspace": [c_f, c_i64, c_stream],
-    "dlip_split_pack_f32": [c_f, c_f, C.c_int64, c_i32, c_stream],
-    "dlip_split_unpack_f32": [c_f, c_f, C.c_int64, c_i32, c_stream],
-    "dlip_conv_plan": [C.POINTER(ConvDesc), c_i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
-    "dlip_conv_kernel_kind": [C.POINTER(ConvDesc)],
-    "dlip_plan_begin": [c_stream],
-    "dlip_plan_end": [c_stream, C.POINTER(C.c_void_p)],
-    "dlip_plan_run": [C.c_void_p, c_stream],
-    "dlip_plan_launches": [C.c_void_p],
-    "dlip_plan_destroy": [C.c_void_p],
-    "dlip_stem3d_bn_act_f32": [c_f, c_f, c_f, c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_stem3d_bn_act_f16x3": [c_f, c_f, c_f, c_f, c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_stem3d_pool_f16x3": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_stem3d_pool_u8_f16x3": [c_f, c_i32, c_i32, c_i32, c_i32, c_i32, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_stem3d_pool_workspace_bytes": [c_i32, c_i32, c_i32, c_i32],
-    "dlip_selftest_lds_oob": [c_f, c_i32, c_stream],
-    "dlip_maxpool3x3s2_nhwc_f32": [c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_avgpool_nhwc_f32": [c_f, c_f, c_i32, c_i32, c_i32, c_stream],
-    "dlip_time_mean_f32": [c_f, c_f, c_i32, c_f, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_group_mean_f32": [c_f, c_f, c_f, c_i32, c_i32, c_stream],
-    "dlip_mask_frames_f32": [c_f, c_f, c_f, c_i32, c_i32, c_i32, c_stream],
-    "dlip_meanstd_pool_f32": [c_f, c_f, c_i32, c_f, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_attentive_stat_pool_f32": [c_f, c_f, c_f, c_f, c_f, c_i32, c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_attentive_stat_pool_bwd_f32": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i32, c_f, c_f, c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_nct_to_ntc_f32": [c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_ntc_to_nct_f32": [c_f, c_f, c_i32, c_i32, c_i32, c_stream],
-    "dlip_nct_to_ntc_split_f32": [c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_ingest_rgb_u8": [c_f, c_f, c_i64, c_i32, c_i32, c_stream],
-    "dlip_affine_act_f32": [c_f, c_f, c_f, c_f, c_i64, c_i32, C.c_float, c_i32, c_stream],
-    "dlip_znorm_cat_f32": [c_f, c_i32, c_f, c_i32, c_f, c_i32, c_i32, c_stream],
-    "dlip_znorm_cat_pooled_f32": [c_f, c_i32, c_f, c_i64, c_i32, c_i32, c_i32, c_f, c_i32, c_i32, c_f, c_i32, c_i32, c_stream],
-    "dlip_l2_normalize_f32": [c_f, c_f, c_i32, c_i32, C.c_float, c_stream],
-    "dlip_pair_cosine_f32": [c_f, c_i32, c_i32, c_f, c_f, c_f, c_i32, c_i32, C.c_float, C.c_float, c_i32, c_stream],
-    "dlip_topk_stats_f32": [c_f, c_i32, c_i32, c_i64, c_i32, c_f, c_f, c_stream],
-    "dlip_score_norm_f32": [c_f, c_f, c_f, c_i32, c_f, c_f, c_i32, c_i32, C.c_float, C.c_float, c_i32, c_f, c_stream],
-    "dlip_plda_llr_f32": [c_f, c_i32, c_i32, c_f, c_f, c_f, c_f, c_i32, c_stream],
-    "dlip_logits_argmax_f32": [c_f, c_f, c_f, c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_margin_ce_loss_f32": [c_f, c_f, c_f, c_i32, c_i32, C.c_float, C.c_float, c_stream],
-    "dlip_lowfer_cat_f32": [c_f, c_f, c_f, c_i32, c_i32, c_stream],
-    "dlip_frame_preemph_f32": [c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, C.c_float, c_stream],
-    "dlip_powspec_f32": [c_f, c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_powspec_dft64_f32": [c_f, c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_powspec_wave_fft64_f32": [c_f, c_f, c_f, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, C.c_double, c_i32, c_i32, c_stream],
-    "dlip_log_floor_f32": [c_f, c_f, c_i64, c_stream],
-    "dlip_cmvn_nct_f32": [c_f, c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_delta_nct_f32": [c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_wave_frame_lengths_i32": [c_f, c_f, c_i32, c_i64, c_i32, c_i32, c_stream],
-    "dlip_frame_preemph_ragged_f32": [c_f, c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, C.c_float, c_stream],
-    "dlip_powspec_wave_fft64_ragged_f32": [c_f, c_f, c_f, c_f, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, C.c_double, c_i32, c_i32, c_stream],
-    "dlip_cmvn_nct_ragged_f32": [c_f, c_f, c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_delta_nct_ragged_f32": [c_f, c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_crop_normalize_u8": [c_f, c_f, c_f, c_i32, c_f, c_i64, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_bn1d_train_fwd_f32": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i32, c_i32, C.c_float, C.c_float, C.c_float, c_stream],
-    "dlip_bn1d_train_bwd_f32": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i32, c_i32, c_stream],
-    "dlip_lrelu_bwd_f32": [c_f, c_f, c_f, c_i64, C.c_float, c_stream],
-    "dlip_l1_sum_f32": [c_f, c_f, c_i64, c_stream],
-    "dlip_l1_sign_f32": [c_f, c_f, c_f, C.c_float, c_i64, c_stream],
-    "dlip_colsum_f32": [c_f, c_f, c_i32, c_i32, c_stream],
-    "dlip_margin_ce_bwd_f32": [c_f, c_f, c_f, c_i32, c_i32, C.c_float, C.c_float, C.c_float, c_f, c_stream],
-    "dlip_l2_normalize_bwd_f32": [c_f, c_f, c_f, c_i32, c_i32, C.c_float, c_stream],
-    "dlip_gemm_small_f32": [c_f, c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_shuffle_stem24_f32": [c_f, c_f, c_f, c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_shuffle_dwpw_f32": [c_f, c_f, c_f, c_f, c_f, c_f, c_f] + [c_i32] * 12 + [c_stream],
-    "dlip_tcn_dw_fwd_f32": [c_f, c_i32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
-                            C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_tcn_dw_dgrad_f32": [C.POINTER(C.c_void_p), c_i32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
-                              C.POINTER(C.c_int32), c_f, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_tcn_dw_wgrad_chunks": [c_i32],
-    "dlip_tcn_dw_wgrad_f32": [c_f, c_i32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
-                              C.POINTER(C.c_int32), c_i32, c_i32, c_i32, c_i32, c_f, c_i64, c_stream],
-    "dlip_avgpool3_nhwc_f32": [c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_triplet_mine_f32": [c_f, c_f, C.c_float, c_i32, c_f, c_f, c_f, c_f, c_i32, c_i32, c_stream],
-    "dlip_triplet_loss_f32": [c_f, c_f, c_f, c_f, C.c_float, c_i32, c_f, c_f, c_f, c_f, c_f, c_i32, c_stream],
-    "dlip_triplet_loss_bwd_f32": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i32, c_i32, c_stream],
-    "dlip_bilinear_pool_f32": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_bilinear_pool_bwd_w_f32": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_bilinear_pool_bwd_x_f32": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_bilinear_finish_f32": [c_f, c_f, c_f, c_f, c_i32, c_i32, C.c_float, c_stream],
-    "dlip_compact_bilinear_f32": [c_f] * 11 + [c_i32] * 6 + [c_stream],
-    "dlip_compact_bilinear_bwd_f32": [c_f] * 9 + [c_i32] * 6 + [c_stream],
-    "dlip_time_tail_zero_f32": [c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_avgpool_time_ragged_f32": [c_f, c_f, c_i32, c_f, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_statpool_nhwc_f32": [c_f, c_f, c_i32, C.c_float, c_f, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_statpool_nhwc_bwd_f32": [c_f, c_f, c_f, C.c_float, c_f, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_swap_axes_nhwc_f32": [c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_time_valid_lengths_i32": [c_f, c_i32, c_i32, c_f, c_i32, c_stream],
-    "dlip_attentive_stat_pool_eps_f32": [c_f, c_f, c_f, c_f, c_f, c_i32, C.c_float, c_f, c_f, c_i32, c_i32, c_i32, c_i32, c_stream],
-    "dlip_attentive_stat_pool_eps_bwd_f32": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i32, C.c_float, c_f, c_f, c_f, c_f, c_i32, c_i32, c_i32,
-                                             c_i32, c_stream],
-}
 
 
 class DeepLipHipError(RuntimeError):
@@ -210,6 +34,75 @@ class DeepLipRangeError(DeepLipHipError):
     """An activation left the range of the split-fp16 ("f16x3") arithmetic (|v| >= 65520): the results of the
     launches since the last check are invalid.  Recourse: pack that model in the exact mode,
     ``deeplip_amd.packing.set_precision("f32")`` (same engine, fp32 MFMA)."""
+
+
+class ConvDesc(C.Structure):
+    """struct dlip_conv_desc (_fields_: the header's, set below)"""
+
+
+# ---- the binding is DERIVED from include/deeplip_hip.h: its prototypes, integer #defines, enums and dlip_conv_desc ----
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "float": C.c_float,
+            "double": C.c_double, "dlip_stream_t": C.c_void_p, "dlip_plan_t": C.c_void_p}
+_PARAM = re.compile(r"(DLIP_HOST )?(?:const )?(\w+) ?(\*(?: ?const ?\*)?)?(?: ?\w+)?")   # [DLIP_HOST] [const] T [* | * const*] [name]
+
+
+def _argtype(decl: str, proto: str):
+    """ctypes class of one parameter declaration (whitespace normalised, no space in front of a '*')."""
+    m = _PARAM.fullmatch(decl)
+    host, base, stars = m.groups() if m else (None, None, None)
+    if stars and not host:
+        return C.c_void_p                               # a device pointer, whatever it points to: passed as an integer address
+    if stars and stars != "*":
+        return C.POINTER(C.c_void_p)                    # DLIP_HOST T* const*: a host array of device pointers
+    if stars and base == "dlip_conv_desc":
+        return C.POINTER(ConvDesc)
+    if stars and base in _SCALARS:
+        return C.POINTER(_SCALARS[base])                # DLIP_HOST T*: a host array or out-parameter
+    if not stars and not host and base in _SCALARS:
+        return _SCALARS[base]
+    raise DeepLipHipError(f"deeplip_hip.h: no ctypes mapping for parameter '{decl}' of {proto}")
+
+
+def parse_header(text: str):
+    """(constants, dlip_conv_desc fields, prototypes) of a header written like include/deeplip_hip.h: {DLIP_NAME: int} from the
+    integer #defines and the enums, [(field, ctype)], {dlip_name: (restype, argtypes)}.  A type outside the closed table above
+    raises: a new one must fail here, at import, not bind as something else."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    consts = {n: int(v) for n, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(DLIP_\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", text, flags=re.M)}
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)   # preprocessor lines would otherwise run into the next prototype's return type
+    for body in re.findall(r"\benum\s*\{(.*?)\}", text, flags=re.S):
+        consts.update((n, int(v)) for n, v in re.findall(r"(DLIP_\w+)\s*=\s*(-?\d+)", body))
+    fields = []
+    for body in re.findall(r"struct\s+dlip_conv_desc\s*\{(.*?)\}", text, flags=re.S):
+        for typ, names in re.findall(r"(\w+)\s+([\w\s,]+);", body):
+            fields += [(n.strip(), _SCALARS[typ]) for n in names.split(",")]
+    protos = {}
+    for stmt in text.split(";"):
+        if "(" not in stmt:
+            continue                                    # typedefs, struct fields, enums, the extern "C" braces
+        stmt = re.sub(r"\s*\*", "*", " ".join(stmt.split()))
+        m = re.fullmatch(r"(?:[^()]*[{}] ?)?([\w ]+?\*?) ?\b(dlip_\w+) ?\(([^()]*)\)", stmt)
+        if m is None:
+            raise DeepLipHipError(f"deeplip_hip.h: not a prototype: '{stmt}'")
+        ret, name, args = m.groups()
+        restype = C.c_char_p if ret == "const char*" else _SCALARS.get(ret)
+        if restype is None:
+            raise DeepLipHipError(f"deeplip_hip.h: no ctypes mapping for the return type '{ret}' of {name}")
+        args = [a.strip() for a in args.split(",")] if args.strip() not in ("", "void") else []
+        protos[name] = (restype, [_argtype(a, name) for a in args])
+    return consts, fields, protos
+
+
+if not os.path.exists(HEADER_PATH):
+    raise DeepLipHipError(f"{HEADER_PATH} not found: deeplip_amd binds libdeeplip_hip.so from the header it is built from "
+                          "(a source tree: include/ beside the package). deeplip_amd has no CPU fallback.")
+with open(HEADER_PATH) as _f:
+    HEADER, ConvDesc._fields_, PROTOTYPES = parse_header(_f.read())
+# name -> argtypes of every launch entry point (the two that return text are bound from PROTOTYPES like the rest)
+SIGNATURES = {n: a for n, (_, a) in PROTOTYPES.items() if n not in ("dlip_source_sha", "dlip_error_string")}
+ABI_VERSION = HEADER["DLIP_ABI_VERSION"]
+LIFT_WORDS = HEADER["DLIP_LIFT_WORDS"]
+LIFT_BCAST = HEADER["DLIP_LIFT_BCAST"]
 
 
 def lib() -> C.CDLL:
@@ -225,17 +118,10 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} not found: build it with `python -m deeplip_amd.build` "
                 "(or __graft_entry__.build()). deeplip_amd has no CPU fallback.")
         l = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, args in SIGNATURES.items():
+        for name, (restype, args) in PROTOTYPES.items():
             fn = getattr(l, name)  # AttributeError if the ABI lost a symbol
             fn.argtypes = args
-            fn.restype = C.c_int
-        l.dlip_conv_workspace_bytes.restype = C.c_int64
-        l.dlip_conv_pool_partial_bytes.restype = C.c_int64
-        l.dlip_stem3d_pool_workspace_bytes.restype = C.c_int64
-        l.dlip_source_sha.argtypes = []
-        l.dlip_source_sha.restype = C.c_char_p
-        l.dlip_error_string.argtypes = [C.c_int]
-        l.dlip_error_string.restype = C.c_char_p
+            fn.restype = restype
         v = l.dlip_abi_version()
         if v != ABI_VERSION:
             raise DeepLipHipError(f"libdeeplip_hip.so ABI {v} != binding ABI {ABI_VERSION}; rebuild")
@@ -282,7 +168,7 @@ def ensure_conv_workspace() -> None:
 
 
 # ---- diagnostic overrides (tests, tools): dlip_debug_set ----
-DBG_CONV_TILE, DBG_DMA_TILE, DBG_DMA_ENABLE, DBG_STREAMK, DBG_WIN, DBG_NINNER, DBG_ROWS, DBG_ROWS2D, DBG_BN_FUSED, DBG_ROWS_TAIL, DBG_GROUPED = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
+globals().update((n[5:], v) for n, v in HEADER.items() if n.startswith("DLIP_DBG_"))   # DBG_CONV_TILE .. DBG_GROUPED: the header's keys
 
 
 DEBUG = {}          # what this process set through debug_set (key -> value; -1 / absent = the built-in choice)
@@ -294,9 +180,9 @@ def debug_set(key: int, value: int = -1) -> None:
 
 
 # ---- range status of the f16x3 arithmetic: eight words in host-pinned, device-visible memory ----
-_STATUS_NAMES = ("a convolution / linear epilogue", "the fused stem + pool", "split_pack (a model input or gradient operand)",
-                 "statistics pooling")
-_ST_LOW = 4
+_STATUS_NAMES = {HEADER["DLIP_ST_CONV"]: "a convolution / linear epilogue", HEADER["DLIP_ST_STEM"]: "the fused stem + pool",
+                 HEADER["DLIP_ST_PACK"]: "split_pack (a model input or gradient operand)", HEADER["DLIP_ST_POOL"]: "statistics pooling"}
+_ST_LOW = HEADER["DLIP_ST_LOW"]
 
 
 def status_words():
@@ -312,7 +198,7 @@ def status_words():
 
 
 def _range_error(words) -> "DeepLipRangeError":
-    high = [n for n, v in zip(_STATUS_NAMES, words[:4]) if v]
+    high = [n for w, n in sorted(_STATUS_NAMES.items()) if words[w]]
     recourse = ("results since the last check are invalid. Run that model in the exact mode -- arith 'f32' (deeplip_amd.arith / "
                 "--arith / model.arith / DLIP_ARITH), i.e. deeplip_amd.packing.set_precision('f32'): exact fp32 MFMA, same engine; "
                 "arith 'auto' does it by itself for the batch concerned.")
@@ -320,7 +206,7 @@ def _range_error(words) -> "DeepLipRangeError":
         return DeepLipRangeError("f16x3 arithmetic: an activation with |v| >= 65520 (not representable as hi + lo fp16) was "
                                  f"produced by {', '.join(high)}; " + recourse)
     fam = words[_ST_LOW] - 1
-    who = _STATUS_NAMES[fam] if 0 <= fam < len(_STATUS_NAMES) else "a split-format producer"
+    who = _STATUS_NAMES.get(fam, "a split-format producer")
     return DeepLipRangeError(f"f16x3 arithmetic: {who} produced a tensor whose largest magnitude is below 2^-2 = 0.25: its "
                              "lo halves are fp16 subnormals and the result is no longer fp32-grade (relative error 3e-8 / max|v|); "
                              + recourse)
@@ -387,7 +273,7 @@ def check_range(sync: bool = False) -> None:
 
 # ---- low-side range scopes: one evidence word per split-producing launch (dlip_range_scope_*) ----
 _SCOPE_SLOTS = 128           # launches per scope (a B = 64 fused step makes ~40)
-_EVID_WORDS = 1024           # int32 words of evidence per launch (32 cache lines: DLIP_EVID_WORDS)
+_EVID_WORDS = HEADER["DLIP_EVID_WORDS"]     # int32 words of evidence per launch (32 cache lines)
 _RING_CHUNKS = 16
 _rings = {}                  # (device index, stream handle) -> [ring tensor, next chunk]
 _scope_depth = threading.local()

@@ -19,13 +19,11 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
   } while (0)
 
 // Diagnostic overrides (dlip_debug_set, include/deeplip_hip.h): -1 = the built-in choice.  Plain ints read on
-// the launch path -- the library itself reads no environment variable there.
-enum { DLIP_DBG_CONV_TILE = 0, DLIP_DBG_DMA_TILE = 1, DLIP_DBG_DMA_ENABLE = 2, DLIP_DBG_STREAMK = 3, DLIP_DBG_WIN = 4, DLIP_DBG_NINNER = 5, DLIP_DBG_ROWS = 6, DLIP_DBG_ROWS2D = 7, DLIP_DBG_BN_FUSED = 8, DLIP_DBG_ROWS_TAIL = 9, DLIP_DBG_GROUPED = 10, DLIP_DBG_COUNT = 11 };
+// the launch path -- the library itself reads no environment variable there.  The keys are the header's DLIP_DBG_* enum.
 extern "C" __attribute__((visibility("hidden"))) int dlip_dbg_value[DLIP_DBG_COUNT];
 
 // Range-status words (dlip_set_status_words): where the f16x3 kernels report an activation the split format
-// cannot hold.  NULL = not registered (nothing is reported).  One word per kernel family.
-enum { DLIP_ST_CONV = 0, DLIP_ST_STEM = 1, DLIP_ST_PACK = 2, DLIP_ST_POOL = 3, DLIP_ST_LOW = 4, DLIP_ST_COUNT = 8 };
+// cannot hold.  NULL = not registered (nothing is reported).  One word per kernel family: the header's DLIP_ST_* enum.
 extern "C" __attribute__((visibility("hidden"))) int32_t* dlip_status_words(void);
 #define DLIP_F16_OVERFLOW 65520.0f   // the smallest magnitude that rounds to infinity in fp16
 // Low side of the split format.  hi keeps 11 significant bits down to 6.1e-5, but lo = v - hi is ~2^-11 |v|: it is a NORMAL
@@ -59,8 +57,6 @@ __attribute__((visibility("hidden"))) DlipRange dlip_range_for(int family);
 //              The first version OR-ed bits atomically into ONE word per launch: the 16 k waves of an element-wise pass (or
 //              the first round of a GEMM) finishing together queued at that word's L2 channel -- 12 ns per atomic, and
 //              plain loads of one hot line were no better: the 22 us stem pre-pass became a 100 us one.
-#define DLIP_EVID_LINES 32
-#define DLIP_EVID_WORDS (DLIP_EVID_LINES * 32)   // int32 words of evidence per launch (32 lines of 128 B)
 __device__ __forceinline__ void dlip_report_range(float amax, const DlipRange r) {
   if (r.status != nullptr && __builtin_amdgcn_ballot_w64(!(amax < DLIP_F16_OVERFLOW)) != 0ull) {
     if ((threadIdx.x & 63) == 0) __hip_atomic_store(r.status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);

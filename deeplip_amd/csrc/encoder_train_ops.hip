@@ -20,7 +20,6 @@
 namespace {
 
 constexpr int CHUNK_ROWS = 512;
-constexpr int DLIP_LIFT_BCAST = 2048;   // include/deeplip_hip.h: DLIP_LIFT_WORDS = 2 + max(4096 workgroup maxima, this many copies of 2^-e)
 
 __device__ __forceinline__ float lrelu(float v, float slope) { return v >= 0.f ? v : v * slope; }
 

@@ -11,7 +11,11 @@
  *
  * Conventions
  *   - plain pointers and sizes only; every pointer is DEVICE memory owned by the caller
- *     (kernels never allocate, free or synchronise);
+ *     (kernels never allocate, free or synchronise), except the parameters marked DLIP_HOST:
+ *     descriptors, out-parameters and per-branch arrays the CPU reads or writes during the call;
+ *   - this header is the ONE definition of the ABI: deeplip_amd/_lib.py derives its ctypes binding and
+ *     the shared constants from it (prototypes, `#define DLIP_X <integer>`, anonymous enums,
+ *     dlip_conv_desc), so keep declarations in the plain style used below;
  *   - activations are channels-last (NHWC / N-T-C), fp32; weights are pre-packed by the
  *     caller to [K][R][S][C] ("KRSC", BN already folded in fp64 on the host);
  *   - every call is asynchronous on `stream` (a hipStream_t; NULL = the null stream);
@@ -29,9 +33,11 @@ extern "C" {
 #endif
 
 #define DLIP_ABI_VERSION 59
-#define DLIP_LIFT_WORDS 4098   /* a gradient's power-of-two lift: (2^e, 2^-e), then 2^-e repeated 2048 times (the post_scale vector of
-                                  the convolution that consumes the lifted gradient); while it is formed the words behind the pair
-                                  hold one maximum per workgroup of the producing pass */
+#define DLIP_HOST              /* marks a pointer parameter that the CPU dereferences during the call (HOST memory, not device) */
+#define DLIP_LIFT_BCAST 2048
+#define DLIP_LIFT_WORDS 4098   /* a gradient's power-of-two lift: (2^e, 2^-e), then 2^-e repeated DLIP_LIFT_BCAST times (the post_scale
+                                  vector of the convolution that consumes the lifted gradient); while it is formed the words behind the
+                                  pair hold one maximum per workgroup of the producing pass: 2 + max(4096 maxima, DLIP_LIFT_BCAST) */
 
 #define DLIP_OK 0
 #define DLIP_EINVAL (-1)  /* inconsistent shapes / null pointers / unsupported alignment */
@@ -74,7 +80,7 @@ typedef struct dlip_conv_desc {
   int32_t ldx, ldy, ldr;       /* pixel strides in floats          */
 } dlip_conv_desc;
 
-int dlip_conv_nhwc_f32(const dlip_conv_desc* d, const float* x, const float* w_krsc,
+int dlip_conv_nhwc_f32(DLIP_HOST const dlip_conv_desc* d, const float* x, const float* w_krsc,
                        const float* bias, const float* residual, const float* slope,
                        const float* post_scale, const float* post_shift, float* y,
                        dlip_stream_t stream);
@@ -93,7 +99,7 @@ int dlip_conv_nhwc_f32(const dlip_conv_desc* d, const float* x, const float* w_k
  * producer's epilogue, instead of once per filter tap in every consumer. */
 #define DLIP_SPLIT_IN 1
 #define DLIP_SPLIT_OUT 2
-int dlip_conv_nhwc_f16x3(const dlip_conv_desc* d, const float* x, const void* w_split,
+int dlip_conv_nhwc_f16x3(DLIP_HOST const dlip_conv_desc* d, const float* x, const void* w_split,
                          const float* w_scale, const float* bias, const float* residual,
                          const float* slope, const float* post_scale, const float* post_shift,
                          float* y, int32_t flags, dlip_stream_t stream);
@@ -113,11 +119,11 @@ int dlip_conv_nhwc_f16x3(const dlip_conv_desc* d, const float* x, const void* w_
  * dlip_conv_stats_chunks(d): how many chunks such a launch of `d` writes, or 0 when this shape has no statistics epilogue (today:
  * the rows kernel's shapes -- 1-D valid convolutions and k = 1 GEMMs; the caller then launches the plain convolution).  Within a
  * chunk (half a tile: <= 80 rows) the sums are fp32 in a fixed order; across chunks the finalize kernel adds in fp64. */
-int32_t dlip_conv_stats_chunks(const dlip_conv_desc* d);
-int dlip_conv_nhwc_stats_f16x3(const dlip_conv_desc* d, const float* x, const void* w_split, const float* w_scale,
+int32_t dlip_conv_stats_chunks(DLIP_HOST const dlip_conv_desc* d);
+int dlip_conv_nhwc_stats_f16x3(DLIP_HOST const dlip_conv_desc* d, const float* x, const void* w_split, const float* w_scale,
                                const float* bias, const float* slope, float* y, double* stats, int64_t stats_bytes,
                                dlip_stream_t stream);
-int dlip_conv2_nhwc_f16x3(const dlip_conv_desc* d, const float* x, const float* x2, int32_t H2, int32_t W2,
+int dlip_conv2_nhwc_f16x3(DLIP_HOST const dlip_conv_desc* d, const float* x, const float* x2, int32_t H2, int32_t W2,
                           int32_t C2, int32_t ldx2, int32_t stride2_h, int32_t stride2_w, const void* w_split,
                           const float* w_scale, const float* bias, const float* residual, const float* slope,
                           const float* post_scale, const float* post_shift, float* y, int32_t flags,
@@ -145,8 +151,8 @@ int dlip_conv2_nhwc_f16x3(const dlip_conv_desc* d, const float* x, const float* 
  * zeroes the padding frames, dlip_stem3d_pool_f16x3).  The speech side starts one stage earlier since ABI 57: a zero-padded batch of
  * waveforms + sample counts goes through the front-end's ragged entry points (dlip_wave_frame_lengths_i32 and the *_ragged_f32
  * kernels further down), which hand the frame counts on as this very length vector. */
-int64_t dlip_conv_pool_partial_bytes(const dlip_conv_desc* d, int32_t* tile_rows);
-int dlip_conv_pool_f16x3(const dlip_conv_desc* d, const float* x, const void* w_split, const float* w_scale,
+int64_t dlip_conv_pool_partial_bytes(DLIP_HOST const dlip_conv_desc* d, DLIP_HOST int32_t* tile_rows);
+int dlip_conv_pool_f16x3(DLIP_HOST const dlip_conv_desc* d, const float* x, const void* w_split, const float* w_scale,
                          const float* bias, const float* residual, const float* slope, const float* post_scale,
                          const float* post_shift, double* partials, int64_t partial_bytes, int32_t group_rows,
                          const int32_t* group_len, int32_t len_mul, int32_t len_add, dlip_stream_t stream);
@@ -178,13 +184,13 @@ int dlip_split_unpack_f32(const float* x, float* y, int64_t rows, int32_t C, dli
  * fp32 activations (split_f16 = 1) or on split-format activations (split_f16 = 3: the LDS-DMA
  * kernel) will use for `d` -- i.e. which conv_igemm_*_kernel<BM,BN,..> instance a profiler will
  * show.  Host-only, no launch. */
-int dlip_conv_plan(const dlip_conv_desc* d, int32_t split_f16, int32_t* bm, int32_t* bn);
+int dlip_conv_plan(DLIP_HOST const dlip_conv_desc* d, int32_t split_f16, DLIP_HOST int32_t* bm, DLIP_HOST int32_t* bn);
 /* 1 if a split-format (DLIP_SPLIT_IN) launch of `d` runs on the window kernel (conv_win_f16x3_kernel<128,64> for K <= 64, <128,128> above: same-size
  * stride-1 3x3 convolutions with K <= 128 -- one activation window per channel slice in LDS instead of one fetch per
  * tap), 2 if on the rows kernel (conv_rows_f16x3_kernel; dlip_conv_plan then reports its BM x 256 tile): without a residual the
  * speech encoder's 1-D valid convolutions and k = 1 GEMMs over all frames), 0 if on the LDS-DMA ring kernel dlip_conv_plan describes.
  * Host-only. */
-int dlip_conv_kernel_kind(const dlip_conv_desc* d);
+int dlip_conv_kernel_kind(DLIP_HOST const dlip_conv_desc* d);
 
 /* ------------------------------------------------------------------------------------------
  * Video stem: Conv3d(1->K, 5x7x7, stride (1,2,2), pad (2,3,3), no bias) + BatchNorm3d + PReLU|ReLU
@@ -800,8 +806,8 @@ int dlip_dropout_keep_f32(const float* x, const float* u, float* y, int64_t n, f
  * (tcn.py:96-108) of n_branches <= 4 tensors z_j [B, lengths[j], widths[j]] (HOST arrays of pointers / sizes; lengths[j] - T even,
  * widths multiples of 4): cat[b, t, off_j + c] = z_j[b, t + (lengths[j] - T) / 2, c].  backward != 0: the reverse -- `branches` are
  * written from cat (= the gradient of the concatenation), zeros in the chomped rows. */
-int dlip_chomp_concat_f32(const float* const* branches, const int32_t* lengths, const int32_t* widths, int32_t n_branches, float* cat,
-                          int32_t B, int32_t T, int32_t backward, dlip_stream_t stream);
+int dlip_chomp_concat_f32(DLIP_HOST const float* const* branches, DLIP_HOST const int32_t* lengths, DLIP_HOST const int32_t* widths,
+                          int32_t n_branches, float* cat, int32_t B, int32_t T, int32_t backward, dlip_stream_t stream);
 /* y = x * mask * scale (nn.Dropout forward / backward, tcn.py:80,85). */
 int dlip_mul_mask_f32(const float* x, const float* mask, float* y, int64_t n, float scale, dlip_stream_t stream);
 
@@ -815,6 +821,7 @@ int dlip_mul_mask_f32(const float* x, const float* mask, float* y, int64_t n, fl
  * re-pack that model in the exact "f32" mode (same engine).  words = int32[8] {conv, stem, split_pack, pooling, low side (below),
  * 3 reserved}, zeroed by the caller; NULL unregisters (nothing is reported).  One block per process (one process per GPU).
  * ------------------------------------------------------------------------------------------ */
+enum { DLIP_ST_CONV = 0, DLIP_ST_STEM = 1, DLIP_ST_PACK = 2, DLIP_ST_POOL = 3, DLIP_ST_LOW = 4, DLIP_ST_COUNT = 8 };   /* the words */
 int dlip_set_status_words(int32_t* words);
 /* (ABI 45) A status block for the launches of the CALLING THREAD alone: until dlip_status_scope(NULL), every producer this thread
  * launches (and the verdict kernel of a range scope it closes) reports to `words` (int32[8], host-pinned and device-visible, or
@@ -850,8 +857,10 @@ int dlip_status_scope(int32_t* words);
  * caller) and re-arms the record -- recorded into a plan, every replay accumulates; *used = records taken.  Outside a scope the
  * kernels time nothing. */
 int dlip_span_scope_begin(uint64_t* pairs, uint64_t* acc, int32_t n);
-int dlip_span_scope_end(dlip_stream_t stream, int32_t* used);
+int dlip_span_scope_end(dlip_stream_t stream, DLIP_HOST int32_t* used);
 
+#define DLIP_EVID_WORDS 1024                     /* int32 words of low-side evidence per launch: */
+#define DLIP_EVID_LINES (DLIP_EVID_WORDS / 32)   /* 32 cache lines of 128 B */
 int dlip_range_scope_begin(int32_t* slots, int32_t n);
 int dlip_range_scope_end(dlip_stream_t stream);
 
@@ -870,6 +879,8 @@ int dlip_range_scope_end(dlip_stream_t stream);
  * 10 the LDS-DMA kernel's border groups (a padded convolution on the 256 x 128 tile run as its padding-free sub-convolutions in one
  * launch: 0 = never, 1 = whenever the construction applies; built in where a launch's share of padding taps is large enough);
  * value -1 restores the built-in choice. */
+enum { DLIP_DBG_CONV_TILE = 0, DLIP_DBG_DMA_TILE = 1, DLIP_DBG_DMA_ENABLE = 2, DLIP_DBG_STREAMK = 3, DLIP_DBG_WIN = 4, DLIP_DBG_NINNER = 5,
+       DLIP_DBG_ROWS = 6, DLIP_DBG_ROWS2D = 7, DLIP_DBG_BN_FUSED = 8, DLIP_DBG_ROWS_TAIL = 9, DLIP_DBG_GROUPED = 10, DLIP_DBG_COUNT = 11 };
 int dlip_debug_set(int32_t key, int32_t value);
 
 /* ------------------------------------------------------------------------------------------
@@ -918,15 +929,17 @@ int dlip_avgpool3_nhwc_f32(const float* x, float* y, int32_t N, int32_t H, int32
  *   fixed-order fp64 sum of the chunks rounded once to fp32 -- two launches, no atomics, the same bits on every run.  workspace:
  *   sum_r dlip_tcn_dw_wgrad_chunks(B * t_out_r) * k_r * C doubles (workspace_len = its size in doubles).
  * ------------------------------------------------------------------------------------------ */
-int dlip_tcn_dw_fwd_f32(const float* x, int32_t n, const float* const* w, const float* const* bias, const float* const* slope,
-                        float* const* y, const int32_t* k, const int32_t* pad, const int32_t* t_out, int32_t B, int32_t T,
-                        int32_t C, int32_t d, dlip_stream_t stream);
-int dlip_tcn_dw_dgrad_f32(const float* const* dz, int32_t n, const float* const* w, const int32_t* k, const int32_t* pad,
-                          const int32_t* t_out, float* dx, int32_t B, int32_t T, int32_t C, int32_t d, dlip_stream_t stream);
+int dlip_tcn_dw_fwd_f32(const float* x, int32_t n, DLIP_HOST const float* const* w, DLIP_HOST const float* const* bias,
+                        DLIP_HOST const float* const* slope, DLIP_HOST float* const* y, DLIP_HOST const int32_t* k,
+                        DLIP_HOST const int32_t* pad, DLIP_HOST const int32_t* t_out, int32_t B, int32_t T, int32_t C, int32_t d,
+                        dlip_stream_t stream);
+int dlip_tcn_dw_dgrad_f32(DLIP_HOST const float* const* dz, int32_t n, DLIP_HOST const float* const* w, DLIP_HOST const int32_t* k,
+                          DLIP_HOST const int32_t* pad, DLIP_HOST const int32_t* t_out, float* dx, int32_t B, int32_t T, int32_t C,
+                          int32_t d, dlip_stream_t stream);
 int dlip_tcn_dw_wgrad_chunks(int32_t rows);
-int dlip_tcn_dw_wgrad_f32(const float* x, int32_t n, const float* const* dz, float* const* dw, const int32_t* k, const int32_t* pad,
-                          const int32_t* t_out, int32_t B, int32_t T, int32_t C, int32_t d, double* workspace,
-                          int64_t workspace_len, dlip_stream_t stream);
+int dlip_tcn_dw_wgrad_f32(const float* x, int32_t n, DLIP_HOST const float* const* dz, DLIP_HOST float* const* dw,
+                          DLIP_HOST const int32_t* k, DLIP_HOST const int32_t* pad, DLIP_HOST const int32_t* t_out, int32_t B, int32_t T,
+                          int32_t C, int32_t d, double* workspace, int64_t workspace_len, dlip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * (ABI 53) Online triplet loss with negative mining on the device: OnlineTriplet (models/audio_models/loss.py:18-31) and the
@@ -1112,7 +1125,7 @@ int dlip_attentive_stat_pool_eps_bwd_f32(const float* x, const float* hidden, co
  * dlip_plan_launches = kernel launches the plan holds.  dlip_plan_destroy(NULL) is a no-op.
  * ------------------------------------------------------------------------------------------ */
 int dlip_plan_begin(dlip_stream_t stream);
-int dlip_plan_end(dlip_stream_t stream, dlip_plan_t* plan);
+int dlip_plan_end(dlip_stream_t stream, DLIP_HOST dlip_plan_t* plan);
 int dlip_plan_run(dlip_plan_t plan, dlip_stream_t stream);
 int dlip_plan_launches(dlip_plan_t plan);
 int dlip_plan_destroy(dlip_plan_t plan);
