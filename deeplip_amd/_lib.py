@@ -103,6 +103,8 @@ SIGNATURES = {n: a for n, (_, a) in PROTOTYPES.items() if n not in ("dlip_source
 ABI_VERSION = HEADER["DLIP_ABI_VERSION"]
 LIFT_WORDS = HEADER["DLIP_LIFT_WORDS"]
 LIFT_BCAST = HEADER["DLIP_LIFT_BCAST"]
+# waveform augmentation (deeplip_amd/augment.py): the FIR kernel's tile, its tap chunk and the longest room response it takes
+DLIP_FIR_TILE, DLIP_FIR_TAP_CHUNK, DLIP_FIR_MAX_TAPS = (HEADER[n] for n in ("DLIP_FIR_TILE", "DLIP_FIR_TAP_CHUNK", "DLIP_FIR_MAX_TAPS"))
 
 
 def lib() -> C.CDLL:

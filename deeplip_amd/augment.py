@@ -1,0 +1,207 @@
+"""Waveform augmentation on the device, in front of ``AudioFrontend``.
+
+What an x-vector recipe does to a training utterance before the features are taken: the reference's
+``AddNoise`` / ``NormalizeUtterance`` (models/video_models/preprocess.py:141-179) and the four augmentation kinds its training
+lists carry (train_audio.py:454: 'reverb', 'music', 'babble', 'noise' -- one convolution with a room impulse response, three additive
+mixtures at an SNR).  ``WaveAugment`` keeps the noise bank and the room responses on the device, draws the random choices on the
+host (``draw``) and applies them with the ``dlip_wave_*`` kernels (``__call__``: launches only) in Kaldi's order -- reverberation,
+additive noise, utterance normalisation -- on a batch ``wave [B, S]`` (+ ``lengths``), each row as if it were alone.
+
+Two deliberate differences from the reference, which divides by zero in both places: a noise slice of zero power leaves the row
+untouched, and a row of zero standard deviation normalises to zeros.
+"""
+from __future__ import annotations
+
+import warnings
+from typing import Dict, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+from ._lib import check, lib, ptr, stream_handle
+
+SNR_PASS = 9999                     # preprocess.py:168: the level that means "leave the signal alone"
+AUGMENT_KEYS = ("snr_levels", "p_reverb", "keep_power", "normalize", "max_taps")
+
+
+def parse_augment_section(section) -> Optional[dict]:
+    """The keyword arguments of ``WaveAugment`` an ``augment:`` config section names (``data.augment`` of conf/audio_config.yaml), or
+    None for an absent / empty one.  Unknown keys, a ``p_reverb`` outside [0, 1], an empty ``snr_levels`` and a ``max_taps`` outside
+    [1, DLIP_FIR_MAX_TAPS] raise ValueError."""
+    if section is None or section is False:
+        return None
+    if not isinstance(section, dict):
+        raise ValueError(f"augment: expected a mapping of {list(AUGMENT_KEYS)}, got {type(section).__name__}")
+    unknown = sorted(set(section) - set(AUGMENT_KEYS))
+    if unknown:
+        raise ValueError(f"augment: unknown key(s) {unknown}; expected {list(AUGMENT_KEYS)}")
+    out = {}
+    if "snr_levels" in section:
+        levels = section["snr_levels"]
+        if not isinstance(levels, (list, tuple)) or len(levels) == 0:
+            raise ValueError("augment.snr_levels: expected a non-empty list of SNR levels in dB (9999 = no noise)")
+        out["snr_levels"] = tuple(float(v) for v in levels)
+    p = float(section.get("p_reverb", 0.0))
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"augment.p_reverb: {p} is not a probability")
+    out["p_reverb"] = p
+    out["keep_power"] = bool(section.get("keep_power", True))
+    out["normalize"] = bool(section.get("normalize", False))
+    taps = int(section.get("max_taps", _lib.DLIP_FIR_MAX_TAPS))
+    if not 1 <= taps <= _lib.DLIP_FIR_MAX_TAPS:
+        raise ValueError(f"augment.max_taps: {taps} is outside [1, {_lib.DLIP_FIR_MAX_TAPS}] (the FIR kernel's cap)")
+    out["max_taps"] = taps
+    return out
+
+
+class WaveAugment:
+    """``noise``: a 1-D float array (the bank additive noise is cut from), uploaded once.  ``rirs``: a sequence of 1-D room impulse
+    responses of differing length, packed to ``[R, Lmax]`` + ``rir_len`` + ``rir_peak`` (the tap of the direct path, argmax |h|);
+    responses longer than ``max_taps`` are truncated (with a warning) and their peak is taken inside the kept part; ``rir_peaks``
+    names the direct-path taps explicitly.
+    ``snr_levels``: the levels (dB) one is drawn from per row, 9999 = no noise.  ``p_reverb``: the probability a row is reverberated.
+    ``keep_power``: the reverberated row is rescaled to the power it had.  ``normalize``: (x - mean) / std per row at the end."""
+
+    def __init__(self, noise=None, snr_levels: Sequence[float] = (-5, 0, 5, 10, 15, 20, SNR_PASS), rirs=None, p_reverb: float = 0.0,
+                 keep_power: bool = True, normalize: bool = False, max_taps: int = 8192, device="cuda", rir_peaks=None):
+        if len(snr_levels) == 0:
+            raise ValueError("WaveAugment: snr_levels is empty")
+        if not 0.0 <= float(p_reverb) <= 1.0:
+            raise ValueError(f"WaveAugment: p_reverb {p_reverb} is not a probability")
+        if not 1 <= int(max_taps) <= _lib.DLIP_FIR_MAX_TAPS:
+            raise ValueError(f"WaveAugment: max_taps must lie in [1, {_lib.DLIP_FIR_MAX_TAPS}] (the FIR kernel's cap), got {max_taps}")
+        self.snr_levels = tuple(float(v) for v in snr_levels)
+        self.p_reverb, self.keep_power, self.normalize, self.max_taps = float(p_reverb), bool(keep_power), bool(normalize), int(max_taps)
+        self.device = torch.device(device)
+        self.noise = None
+        if noise is not None:
+            self.noise = np.array(noise, dtype=np.float32)             # (a copy: the caller's array may be read-only)
+            if self.noise.ndim != 1 or self.noise.size == 0:
+                raise ValueError("WaveAugment: noise must be a non-empty 1-D array")
+        self.rir = self.rir_len = self.rir_peak = None
+        self.truncated = []                                            # indices of the responses cut to max_taps
+        if rirs is not None and len(rirs) > 0:
+            hs = []
+            for i, h in enumerate(rirs):
+                h = np.asarray(h, dtype=np.float32)
+                if h.ndim != 1 or h.size == 0:
+                    raise ValueError(f"WaveAugment: room response {i} must be a non-empty 1-D array")
+                if h.size > self.max_taps:
+                    self.truncated.append(i)
+                    h = h[:self.max_taps]
+                hs.append(h)
+            if self.truncated:
+                warnings.warn(f"WaveAugment: room response(s) {self.truncated} are longer than max_taps = {self.max_taps} and were "
+                              "truncated to it (their direct-path tap is taken inside the kept part)")
+            self.rir_len = np.array([h.size for h in hs], dtype=np.int32)
+            self.rir_peak = np.array([int(np.argmax(np.abs(h))) for h in hs], dtype=np.int32)
+            if rir_peaks is not None:                                  # the direct-path taps, where they are not the largest ones
+                self.rir_peak = np.asarray(rir_peaks, dtype=np.int32).reshape(-1)
+                if self.rir_peak.size != len(hs) or (self.rir_peak < 0).any() or (self.rir_peak >= self.rir_len).any():
+                    raise ValueError("WaveAugment: rir_peaks must hold one tap index inside each (kept) response")
+            self.rir = np.zeros((len(hs), int(self.rir_len.max())), dtype=np.float32)
+            for i, h in enumerate(hs):
+                self.rir[i, :h.size] = h
+        if self.p_reverb > 0.0 and self.rir is None:
+            raise ValueError("WaveAugment: p_reverb > 0 needs rirs")
+        self._dev = None                                               # the device copies, made on the first call
+        if torch.cuda.is_available() and self.device.type == "cuda":
+            self._upload()
+
+    def _upload(self):
+        if self._dev is None:
+            up = lambda a: None if a is None else torch.from_numpy(a).to(self.device)
+            self._dev = {k: up(getattr(self, k)) for k in ("noise", "rir", "rir_len", "rir_peak")}
+        return self._dev
+
+    # ------------------------------------------------------------------------------------------------------------ host: the draws
+    def draw(self, lengths, rng: np.random.Generator) -> Dict[str, np.ndarray]:
+        """The random choices of one batch, host only: ``snr_db`` float32 [B] (uniform over ``snr_levels``; all 9999 without a bank),
+        ``noise_start`` int64 [B] (uniform over [0, len(noise) - n], preprocess.py:172; 0 for rows at 9999) and ``rir_idx`` int32 [B]
+        (with probability ``p_reverb`` a response drawn uniformly, else -1).  A bank shorter than a row raises ValueError."""
+        lens = np.asarray(lengths.tolist() if hasattr(lengths, "tolist") else list(lengths), dtype=np.int64).reshape(-1)
+        B = lens.size
+        if self.noise is None:
+            snr = np.full(B, SNR_PASS, dtype=np.float32)
+        else:
+            snr = np.asarray(self.snr_levels, dtype=np.float32)[rng.integers(0, len(self.snr_levels), size=B)]
+        start = np.zeros(B, dtype=np.int64)
+        for b in np.nonzero(snr < SNR_PASS)[0]:
+            room = self.noise.size - int(lens[b])
+            if room < 0:
+                raise ValueError(f"WaveAugment.draw: row {int(b)} holds {int(lens[b])} samples, the noise bank only {self.noise.size}")
+            start[b] = rng.integers(0, room + 1)
+        ridx = np.full(B, -1, dtype=np.int32)
+        if self.rir is not None and self.p_reverb > 0.0:
+            hit = rng.random(B) < self.p_reverb
+            ridx = np.where(hit, rng.integers(0, self.rir.shape[0], size=B), -1).astype(np.int32)
+        return {"snr_db": snr, "noise_start": start, "rir_idx": ridx}
+
+    # ---------------------------------------------------------------------------------------------------------- device: the stages
+    def __call__(self, wave: torch.Tensor, lengths=None, params=None, rng: Optional[np.random.Generator] = None) -> torch.Tensor:
+        """wave [B, S] float32 (cuda) -> the augmented batch [B, S] (a new tensor; samples past a row's length are zeros).
+
+        ``lengths``: as ``AudioFrontend``'s (host values are validated, an int32 device tensor is clamped by the kernels and never
+        read on the host).  ``params``: what ``draw`` returned -- numpy arrays (copied in without synchronising) or device tensors of
+        the same dtypes (a recorded step plan's inputs); None draws them here from ``rng``, which needs host lengths.  Launches only:
+        nothing below synchronises or allocates outside ``ops._empty``, so the call records into a step plan."""
+        ops._req(wave, "WaveAugment: wave")
+        if wave.dim() != 2:
+            raise ValueError(f"WaveAugment: expected wave [B, S], got {tuple(wave.shape)}")
+        B, S = wave.shape
+        dev = wave.device
+        lens = ops.lengths_i32(lengths, dev, n=B, lo=1, hi=S)
+        if params is None:
+            if isinstance(lengths, torch.Tensor) and lengths.is_cuda:
+                raise ValueError("WaveAugment: lengths on the device are never read on the host; pass params=draw(host_lengths, rng)")
+            params = self.draw([S] * B if lengths is None else lengths, rng if rng is not None else np.random.default_rng())
+        unknown = sorted(set(params) - {"snr_db", "noise_start", "rir_idx"})
+        if unknown:
+            raise ValueError(f"WaveAugment: unknown params {unknown}")
+        d = self._upload()
+        nbytes = int(lib().dlip_wave_reverb_workspace_bytes(B, S))
+        if nbytes <= 0:
+            raise _lib.DeepLipHipError(f"dlip_wave_reverb_workspace_bytes refused B = {B}, S = {S}")
+        ws = ops._empty((nbytes // 8,), dev, torch.float64)
+        cur = wave
+        if d["rir"] is None and isinstance(params.get("rir_idx"), np.ndarray) and (params["rir_idx"] >= 0).any():
+            raise ValueError("WaveAugment: params ask for reverberation but no rirs were given")
+        ridx = self._param(params, "rir_idx", torch.int32, B, dev) if d["rir"] is not None else None
+        if ridx is not None:
+            y = ops._empty((B, S), dev)
+            R, Lmax = d["rir"].shape
+            check(lib().dlip_wave_reverb_f32(ptr(cur), ptr(lens), ptr(d["rir"]), ptr(d["rir_len"]), ptr(d["rir_peak"]), ptr(ridx), ptr(y),
+                                             ptr(ws), nbytes, B, S, R, Lmax, int(self.keep_power), stream_handle()), "dlip_wave_reverb_f32")
+            cur = y
+        snr = self._param(params, "snr_db", torch.float32, B, dev)
+        if snr is not None and d["noise"] is not None:
+            start = self._param(params, "noise_start", torch.int64, B, dev)
+            if start is None:
+                raise ValueError("WaveAugment: params carry snr_db but no noise_start")
+            z = ops._empty((B, S), dev)
+            check(lib().dlip_wave_add_noise_f32(ptr(cur), ptr(lens), ptr(d["noise"]), d["noise"].numel(), ptr(start), ptr(snr), ptr(z),
+                                                ptr(ws), nbytes, B, S, stream_handle()), "dlip_wave_add_noise_f32")
+            cur = z
+        if self.normalize:
+            out = ops._empty((B, S), dev)
+            check(lib().dlip_wave_normalize_f32(ptr(cur), ptr(lens), ptr(out), ptr(ws), nbytes, B, S, stream_handle()),
+                  "dlip_wave_normalize_f32")
+            cur = out
+        if cur is wave:
+            raise ValueError("WaveAugment: nothing to apply (no noise bank, no room responses, normalize off)")
+        return cur
+
+    @staticmethod
+    def _param(params, name, dtype, B, dev):
+        v = params.get(name)
+        if v is None:
+            return None
+        if isinstance(v, torch.Tensor):
+            if not v.is_cuda:
+                v = v.to(dev, non_blocking=True)
+        else:
+            v = torch.from_numpy(np.ascontiguousarray(v)).to(dev, non_blocking=True)
+        if v.dtype != dtype or v.numel() != B:
+            raise TypeError(f"WaveAugment: params[{name!r}] must hold {B} values of {dtype}, got {v.numel()} of {v.dtype}")
+        return v.contiguous()

@@ -145,6 +145,38 @@ class SyntheticAVSet:
         return np.stack(clips), np.asarray(ptr, dtype=np.int32)
 
 
+def noise_bank(seconds: float = 5.0, rate: int = 16000, key: str = "augment.noise", seed: int = wg.DEFAULT_SEED) -> np.ndarray:
+    """A noise recording for deeplip_amd.augment.WaveAugment: [seconds * rate] float32 coloured noise -- white noise through a
+    one-pole low-pass (most of its power below 1 kHz, as room and babble noise have) under a slow amplitude swell, so that two
+    slices of it differ in power as slices of a real recording do."""
+    n = int(round(seconds * rate))
+    w = wg.gen(key, (n,), seed).astype(np.float64)
+    x = np.empty(n)
+    acc = 0.0
+    for i in range(n):                       # y[i] = 0.9 y[i-1] + w[i]
+        acc = 0.9 * acc + w[i]
+        x[i] = acc
+    x *= 0.1 * (1.0 + 0.5 * np.sin(2.0 * np.pi * np.arange(n) / (0.7 * rate)))
+    return x.astype(np.float32)
+
+
+def room_responses(n: int = 6, rate: int = 16000, key: str = "augment.rir", seed: int = wg.DEFAULT_SEED,
+                   longest: int = 9000) -> List[np.ndarray]:
+    """``n`` synthetic room impulse responses of differing length: a unit direct path after a small delay (0 .. 3 ms), then noise
+    decaying exponentially (60 dB over the response's length).  The lengths run from 50 ms up to ``longest`` samples -- by default
+    longer than WaveAugment's ``max_taps`` of 8192, so the set exercises the truncation."""
+    out = []
+    shortest = int(0.05 * rate)
+    for i in range(n):
+        L = longest if i == n - 1 else int(shortest * (longest / shortest) ** (i / max(n - 1, 1)))
+        delay = (7 * i) % max(int(0.003 * rate), 1)
+        h = 0.1 * wg.gen(f"{key}.{i}", (L,), seed).astype(np.float64) * np.exp(-6.9 * np.arange(L) / L)
+        h[:delay] = 0.0
+        h[delay] = 1.0
+        out.append(h.astype(np.float32))
+    return out
+
+
 def frames_u8_from_clips(clips: np.ndarray, rgb: bool = True) -> np.ndarray:
     """Normalised float clips [G,1,T,H,W] -> the uint8 frames a loader would have held before dataloaders.py:17-24 normalised
     them: gray = round(255 * (x * 0.165 + 0.421)), as [G,T,3,H,W] RGB with R = G = B (BASELINE.json's input shape) or

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define DLIP_ABI_VERSION 59
+#define DLIP_ABI_VERSION 60
 #define DLIP_HOST              /* marks a pointer parameter that the CPU dereferences during the call (HOST memory, not device) */
 #define DLIP_LIFT_BCAST 2048
 #define DLIP_LIFT_WORDS 4098   /* a gradient's power-of-two lift: (2^e, 2^-e), then 2^-e repeated DLIP_LIFT_BCAST times (the post_scale
@@ -1109,6 +1109,45 @@ int dlip_attentive_stat_pool_eps_f32(const float* x, const float* hidden, const 
 int dlip_attentive_stat_pool_eps_bwd_f32(const float* x, const float* hidden, const float* v, const float* alpha, const float* y,
                                          const float* dy, const int32_t* len, int32_t len_add, float eps, float* dx, float* dhidden,
                                          float* rde, float* de, int32_t B, int32_t T, int32_t C, int32_t Hd, dlip_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 60) WAVEFORM AUGMENTATION in front of the audio front-end: what an x-vector recipe does to a training utterance before the
+ * features are taken.  wave [B,S] fp32 + `lengths` (device int32 [B], nullable): row b holds n = clamp(lengths[b], 1, S) samples
+ * (S when lengths == NULL) and is computed as if it were alone.  Every sum that decides a row's values (powers, mean, variance) is
+ * taken in fp64 per tile of DLIP_FIR_TILE samples in a fixed order and the tiles are met front to back over the row's own
+ * ceil(n / DLIP_FIR_TILE) tiles: no atomics, the same bits whatever B, S and the neighbours are.  Input samples t >= n are never
+ * read; output samples t >= n are written as zeros.  Index and length vectors are clamped on the device and never read on the
+ * host: a recorded plan replays with new vectors.  The three calls run in Kaldi's order (reverb, additive, normalise).
+ *
+ * dlip_wave_reverb_workspace_bytes: bytes of the caller-owned workspace the three calls below take (two doubles per row and tile;
+ *   8-byte aligned; each call fills and reads it within its own launches, so one block serves them in turn); negative on bad sizes.
+ * dlip_wave_reverb_f32 (train_audio.py:454: the 'reverb' kind of the training lists' augmentation, Kaldi's convolution with a room
+ *   impulse response): rows with rir_idx[b] >= 0 (clamped to R - 1): h = rir[r, :len], len = clamp(rir_len[r], 1, Lmax), d =
+ *   clamp(rir_peak[r], 0, len - 1) the tap of the direct path;  y[t] = sum_k h[k] x[t + d - k], 0 <= t < n, x zero outside [0, n) --
+ *   as long as the input and aligned with it.  Exact fp32 (one fmaf per product, taps ascending) on the vector ALUs: a workgroup
+ *   owns DLIP_FIR_TILE consecutive outputs of one row and walks the taps in chunks of DLIP_FIR_TAP_CHUNK, the tile's input window
+ *   of each chunk staged in LDS.  keep_power != 0: y *= sqrt(Px / Py), P the mean square over [0, n), gain 1 when Py == 0 (a second
+ *   launch).  Rows with rir_idx[b] < 0 pass through bit for bit.  rir [R, Lmax]; Lmax <= DLIP_FIR_MAX_TAPS, else DLIP_EINVAL;
+ *   y must not be x; B <= 65535.
+ * dlip_wave_add_noise_f32 (models/video_models/preprocess.py:150-179 AddNoise.__call__; train_audio.py:454 'music' / 'babble' /
+ *   'noise'): rows with snr_db[b] < 9999: c = bank[st : st + n], st = clamp(noise_start[b], 0, bank_len - n) (an int64 vector: a
+ *   noise corpus exceeds 2^31 samples);  z = y + c sqrt((Py / Pc) / 10^(snr_db[b] / 10)).  Rows at the sentinel 9999 pass through
+ *   bit for bit, and so do rows whose slice has Pc == 0 (the reference divides by zero there).  Two launches.
+ * dlip_wave_normalize_f32 (preprocess.py:141-147 NormalizeUtterance.__call__): (z - mean) / std with the population standard
+ *   deviation of the row's n samples; std == 0 gives zeros (the reference divides by zero).  Two launches.
+ * ------------------------------------------------------------------------------------------ */
+#define DLIP_FIR_TILE 2048
+#define DLIP_FIR_TAP_CHUNK 256
+#define DLIP_FIR_MAX_TAPS 8192
+int64_t dlip_wave_reverb_workspace_bytes(int64_t B, int64_t S);
+int dlip_wave_reverb_f32(const float* x, const int32_t* lengths, const float* rir, const int32_t* rir_len, const int32_t* rir_peak,
+                         const int32_t* rir_idx, float* y, void* workspace, int64_t workspace_bytes, int32_t B, int32_t S, int32_t R,
+                         int32_t Lmax, int32_t keep_power, dlip_stream_t stream);
+int dlip_wave_add_noise_f32(const float* y, const int32_t* lengths, const float* bank, int64_t bank_len, const int64_t* noise_start,
+                            const float* snr_db, float* z, void* workspace, int64_t workspace_bytes, int32_t B, int32_t S,
+                            dlip_stream_t stream);
+int dlip_wave_normalize_f32(const float* z, const int32_t* lengths, float* out, void* workspace, int64_t workspace_bytes, int32_t B,
+                            int32_t S, dlip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Step plans.  The reference drives its encoders from a Python loop, one utterance and one torch.nn layer

@@ -79,6 +79,18 @@ def build_model(model_opts, data_opts):
     raise NotImplementedError("Other models are not implemented!")           # train_audio.py:67-68
 
 
+def parse_wave_training(data_opts):
+    """(train_from_waves, augment keyword arguments or None) of a ``data`` section (host only).  ``data.augment`` is the section
+    deeplip_amd.augment.parse_augment_section checks -- unknown keys, ``p_reverb`` outside [0, 1] and an empty ``snr_levels`` raise
+    ValueError -- and needs ``data.train_from_waves``: there is no waveform to augment on the feature path."""
+    from deeplip_amd.augment import parse_augment_section
+    from_waves = bool(data_opts.get("train_from_waves", False))
+    aug = parse_augment_section(data_opts.get("augment"))
+    if aug is not None and not from_waves:
+        raise ValueError("data.augment: waveform augmentation needs data.train_from_waves: true")
+    return from_waves, aug
+
+
 class Trainer(object):
     def __init__(self, config="conf/audio_config.yaml", overrides=None, arith_mode=None):
         with open(os.path.join(ROOT, config)) as f:
@@ -91,6 +103,9 @@ class Trainer(object):
             d[leaf] = v
         self.train_opts, self.model_opts = opts["train"], opts["model"]
         self.data_opts, self.test_opts = opts["data"], opts["test"]
+        # data.train_from_waves / data.augment (build-owned, off by default): batches of WAVEFORMS, augmented on the device and turned
+        # into features by the GPU front-end in front of the unchanged step (_train_epoch).  Parsed before anything touches the GPU.
+        self.train_from_waves, self.augment_opts = parse_wave_training(self.data_opts)
         # the arithmetic of the engine (--arith > $DLIP_ARITH > model.arith > auto), before the first weight pack
         self.arith = arith.configure(arith_mode, self.model_opts.get("arith"))
         if not torch.cuda.is_available():
@@ -144,6 +159,30 @@ class Trainer(object):
             self.log_time = name[0]
         ddist.broadcast_params(list(self.model.parameters()) + list(self.criterion.parameters()))
         self.buckets = None         # built on the first training step (gradient views need the final placement)
+        self._wave_fe, self._augment = self._wave_stages(arch, F_) if self.train_from_waves else (None, None)
+
+    def _wave_stages(self, arch, feat_dim):
+        """data.train_from_waves: the loaders' feature extraction (models/audio_models/datasets.py:65-83) as the GPU front-end -- MFCC
+        with as many coefficients as the TDNNs take, fbank with ``feat_dim`` bands for ``arch: resnet`` -- and, with ``data.augment``,
+        the waveform augmentation in front of it (train_audio.py:454; a synthetic noise bank and synthetic room responses)."""
+        from deeplip_amd.augment import WaveAugment
+        from deeplip_amd.frontend import AudioFrontend
+        from deeplip_amd.synthetic import noise_bank, room_responses
+        d = self.data_opts
+        feat = d.get("feat_type", "mfcc" if arch != "resnet" else "fbank")
+        fe = AudioFrontend(feat, rate=int(d.get("rate", 16000)), win_len=float(d.get("win_len", 0.025)),
+                           win_shift=float(d.get("win_shift", 0.01)), nfft=int(d.get("nfft", 512)), num_cep=feat_dim, device=self.device,
+                           **({} if feat == "mfcc" else {"num_bin": feat_dim}))
+        if fe.feat_dim != feat_dim:
+            raise ValueError(f"data.train_from_waves: the front-end yields {fe.feat_dim} features, the encoder takes {feat_dim}")
+        if self.augment_opts is None:
+            return fe, None
+        import warnings
+        with warnings.catch_warnings():                # (the synthetic set holds one response longer than max_taps on purpose)
+            warnings.simplefilter("ignore")
+            longest = fe.frame_len + (int(d["audio_frames"]) - 1) * fe.frame_step          # samples of the longest crop
+            aug = WaveAugment(noise=noise_bank(max(5.0, 1.25 * longest / fe.rate), rate=fe.rate), rirs=room_responses(rate=fe.rate), device=self.device, **self.augment_opts)
+        return fe, aug
 
     def _make_sgd(self, groups, o):
         if self.graph_step:
@@ -227,25 +266,50 @@ class Trainer(object):
             if hb is None:
                 idx = rng.integers(0, len(self.trainset), bs)
                 T = int(ladder[int(rng.integers(0, len(ladder)))])
-                t0_ = int(rng.integers(0, Ta - T + 1))
-                xb = np.ascontiguousarray(self.trainset.audio(idx)[:, :, t0_:t0_ + T])       # the batch's one crop (datasets.py:112-115)
-                hb = (torch.from_numpy(xb).pin_memory(), torch.from_numpy(self.trainset.labels(idx)).pin_memory())
+                extra = ()
+                if self.train_from_waves:
+                    # the same crop as WAVEFORMS: frame_len + (T - 1) frame_step samples (T frames) cut from the zero-padded batch at
+                    # an offset that fits the shortest row -- a rectangular batch; the augmentation's choices are drawn beside it
+                    fl, fs = self._wave_fe.frame_len, self._wave_fe.frame_step
+                    Sb = fl + (T - 1) * fs
+                    wl = self.trainset.wave_len(fl, fs)[idx]
+                    wav, _ = self.trainset.waves_padded(idx, S=max(int(wl.max()), Sb), frame_len=fl, frame_step=fs)
+                    s0 = int(rng.integers(0, max(int(wl.min()) - Sb, 0) + 1))
+                    xb = np.ascontiguousarray(wav[:, s0:s0 + Sb])
+                    if self._augment is not None:
+                        p = self._augment.draw([Sb] * bs, rng)
+                        extra = tuple(torch.from_numpy(p[n]).pin_memory() for n in ("snr_db", "noise_start", "rir_idx"))
+                else:
+                    t0_ = int(rng.integers(0, Ta - T + 1))
+                    xb = np.ascontiguousarray(self.trainset.audio(idx)[:, :, t0_:t0_ + T])   # the batch's one crop (datasets.py:112-115)
+                hb = (torch.from_numpy(xb).pin_memory(), torch.from_numpy(self.trainset.labels(idx)).pin_memory()) + extra
                 if n_cache > 0:
                     cache[k] = hb
             with torch.cuda.stream(copy_stream):
-                x, lab = hb[0].to(self.device, non_blocking=True), hb[1].to(self.device, non_blocking=True)
+                x, lab, *extra = (h.to(self.device, non_blocking=True) for h in hb)
                 ev = torch.cuda.Event()
                 ev.record(copy_stream)
-            return x, lab, ev
+            return x, lab, ev, extra
+
+        def features(wave, extra):
+            """data.train_from_waves: augmentation (when configured) and front-end, eager launches in front of the step."""
+            with torch.no_grad():
+                if self._augment is not None:
+                    wave = self._augment(wave, params=dict(zip(("snr_db", "noise_start", "rir_idx"), extra)))
+                return self._wave_fe(wave)
 
         staged = stage(0) if steps > 0 else None
         torch.cuda.synchronize(self.device)
         t0 = time.perf_counter()
         for i in range(steps):
-            x, lab, ev = staged
+            x, lab, ev, extra = staged
             cur = torch.cuda.current_stream(self.device)
             cur.wait_event(ev)
             x.record_stream(cur); lab.record_stream(cur)
+            if self.train_from_waves:
+                for t in extra:
+                    t.record_stream(cur)
+                x = features(x, extra)
             if recorded:
                 # keyed by the crop length (the shape) AND the margin the criterion bakes into the recorded launches
                 loss, logits = self._steps.step(x, lab, key=float(getattr(self.criterion, "margin", 0.0)))
@@ -266,6 +330,8 @@ class Trainer(object):
         quality = {"triplets": correct / max(steps * self.world, 1)} if self.triplet else {"acc": correct / n}
         self.last_epoch_stats = {"loss": tot / n, **quality, "utt_per_s": n / dt, "steps": steps, "bs": bs * self.world,
                                  "step_mode": (self._steps.mode if recorded else "eager"), "crop_ladder": [int(t) for t in ladder]}
+        if self.train_from_waves:
+            self.last_epoch_stats.update(from_waves=True, augment=None if self.augment_opts is None else dict(self.augment_opts))
         self.model.eval()
         return tot / n
 
