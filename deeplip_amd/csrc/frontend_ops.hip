@@ -123,6 +123,40 @@ __global__ __launch_bounds__(256) void powspec_dft64_kernel(const float* __restr
   if (threadIdx.x == 0) energy[r] = t == 0.0 ? 2.220446049250313e-16f : (float)t;
 }
 
+// THE FFT CORE of the two waveform kernels below (power spectrum, log-magnitude STFT): sample j of the frame, an fp64 value that
+// `sample(j)` forms, goes into LDS at the bit-reversed position (imaginary part 0), the nfft / 2 twiddles exp(-2 pi i j / nfft) into a
+// table (sincospi), and log2(nfft) radix-2 decimation-in-time stages of nfft / 2 butterflies (one per thread and stage at nfft / 2
+// threads) leave the spectrum in re / im in natural order.  Every thread of the workgroup calls it; it ends behind a barrier.
+template <class Sample>
+__device__ __forceinline__ void fft64_frame_lds(double* re, double* im, double* cs, double* sn, int nfft, int lg, Sample sample) {
+  const int half = nfft >> 1;
+  for (int j = threadIdx.x; j < nfft; j += blockDim.x) {
+    const double v = sample(j);
+    const int br = (int)(__brev((unsigned)j) >> (32 - lg));
+    re[br] = v;
+    im[br] = 0.0;
+    if (j < half) {
+      double s, c;
+      sincospi(-2.0 * (double)j / (double)nfft, &s, &c);       // exp(-2 pi i j / nfft)
+      cs[j] = c;
+      sn[j] = s;
+    }
+  }
+  __syncthreads();
+  for (int st = 1; st <= lg; ++st) {
+    const int len = 1 << st, hl = len >> 1, tw = nfft >> st;
+    for (int t = threadIdx.x; t < half; t += blockDim.x) {
+      const int pos = t & (hl - 1), i0 = ((t >> (st - 1)) << st) + pos, i1 = i0 + hl;
+      const double wr = cs[pos * tw], wi = sn[pos * tw];
+      const double br_ = re[i1] * wr - im[i1] * wi, bi_ = re[i1] * wi + im[i1] * wr;
+      const double ar = re[i0], ai = im[i0];
+      re[i0] = ar + br_; im[i0] = ai + bi_;
+      re[i1] = ar - br_; im[i1] = ai - bi_;
+    }
+    __syncthreads();
+  }
+}
+
 // Power spectrum STRAIGHT FROM THE WAVEFORM, in the reference's own precision: python_speech_features pre-emphasises, frames and
 // transforms in fp64 (numpy), so a band that holds 1e-12 of a frame's energy -- the lowest one-bin mel filter next to DC in a frame where
 // pre-emphasis leaves nothing -- is still resolved there, while fp32 pre-emphasis alone puts rounding noise at -143 dB of the frame under
@@ -155,34 +189,12 @@ __global__ __launch_bounds__(512) void powspec_wave_fft64_kernel(const float* __
       return;
     }
   }
-  const int half = nfft >> 1;
-  for (int j = threadIdx.x; j < nfft; j += blockDim.x) {
+  fft64_frame_lds(re, im, cs, sn, nfft, lg, [&](int j) {
     const long long n = (long long)f * step + j;
     double v = 0.0;
     if (j < L && n < S) v = n == 0 ? (double)xb[0] : (double)xb[n] - coef * (double)xb[n - 1];
-    const int br = (int)(__brev((unsigned)j) >> (32 - lg));
-    re[br] = v;
-    im[br] = 0.0;
-    if (j < half) {
-      double s, c;
-      sincospi(-2.0 * (double)j / (double)nfft, &s, &c);       // exp(-2 pi i j / nfft)
-      cs[j] = c;
-      sn[j] = s;
-    }
-  }
-  __syncthreads();
-  for (int st = 1; st <= lg; ++st) {
-    const int len = 1 << st, hl = len >> 1, tw = nfft >> st;
-    for (int t = threadIdx.x; t < half; t += blockDim.x) {
-      const int pos = t & (hl - 1), i0 = ((t >> (st - 1)) << st) + pos, i1 = i0 + hl;
-      const double wr = cs[pos * tw], wi = sn[pos * tw];
-      const double br_ = re[i1] * wr - im[i1] * wi, bi_ = re[i1] * wi + im[i1] * wr;
-      const double ar = re[i0], ai = im[i0];
-      re[i0] = ar + br_; im[i0] = ai + bi_;
-      re[i1] = ar - br_; im[i1] = ai - bi_;
-    }
-    __syncthreads();
-  }
+    return v;
+  });
   double e = 0.0;
   for (int k = threadIdx.x; k < NBp; k += blockDim.x) {
     float p = 0.f;
@@ -201,6 +213,66 @@ __global__ __launch_bounds__(512) void powspec_wave_fft64_kernel(const float* __
     for (int w = 0; w < (int)(blockDim.x + 63) / 64; ++w) t += part[w];
     energy[r] = t == 0.0 ? 2.220446049250313e-16f : (float)t;
   }
+}
+
+// LOG-MAGNITUDE SPECTROGRAM straight from the waveform: the loaders' `stft` feature type (models/audio_models/datasets.py:72-76:
+// librosa.stft(y, n_fft, hop_length, win_length) -> magphase -> log1p, with librosa's defaults center=True, pad_mode="reflect",
+// window="hann").  The geometry is the loader's: hop and win truncate rate * win_shift / rate * win_len (datasets.py:73), a signal of
+// s samples has 1 + s / hop frames, and frame t covers the reflect-padded signal from t hop - nfft / 2 on.
+__device__ __forceinline__ long long stft_clamp_len(int v, int nfft, long long hi) {
+  const long long lo = (nfft >> 1) + 1;           // one reflection per side reaches every sample of a frame: the host checks S >= lo
+  return v < lo ? lo : (v > hi ? hi : v);
+}
+
+__global__ __launch_bounds__(256) void stft_frame_lengths_kernel(const int32_t* __restrict__ slen, int32_t* __restrict__ flen, int B,
+                                                                 long long S, int nfft, int hop) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b < B) flen[b] = 1 + (int)(stft_clamp_len(slen[b], nfft, S) / hop);
+}
+
+// One workgroup per (row, frame), as powspec_wave_fft64_kernel and through the same FFT core, fp64 inside: sample j of frame f is
+// y[reflect(f hop + j - nfft / 2)] (about 0 and about S - 1, the edge sample not repeated) times the periodic Hann window of `win`
+// points centred in the nfft-point frame (0.5 - 0.5 cos(2 pi k / win) at j = lp + k, lp = (nfft - win) / 2, zero elsewhere; cospi, so
+// the value is the fp64 one); bins k < F leave as (float)log1p(sqrt(re^2 + im^2)), the one rounding to fp32 of the pipeline; the pad
+// columns F .. Fp - 1 are zeros.  The reflected index stays inside the row: f hop <= S (the host checks NF == 1 + S / hop) and
+// S >= nfft / 2 + 1 give 0 <= n < S after one reflection.
+// kRagged: the row ends at S_b = clamp(slen[b], nfft / 2 + 1, S), has 1 + S_b / hop frames and is reflected about ITS OWN end; samples
+// >= S_b are never read.  A frame past the row's count leaves a zero row; that exit depends on blockIdx alone and sits in front of the
+// first barrier.
+template <bool kRagged>
+__global__ __launch_bounds__(512) void stft_logmag_wave_kernel(const float* __restrict__ x, const int32_t* __restrict__ slen,
+                                                               float* __restrict__ out, long long S, int NF, int win, int hop, int nfft,
+                                                               int lg, int F, int Fp) {
+  extern __shared__ double sh[];          // [nfft] re | [nfft] im | [nfft / 2] cos | [nfft / 2] sin
+  double* re = sh;
+  double* im = sh + nfft;
+  double* cs = sh + 2 * nfft;
+  double* sn = cs + nfft / 2;
+  const long long r = blockIdx.x;
+  const int f = (int)(r % NF);
+  const float* xb = x + (r / NF) * S;
+  if (kRagged) {
+    S = stft_clamp_len(slen[r / NF], nfft, S);
+    if (f >= 1 + (int)(S / hop)) {
+      for (int k = threadIdx.x; k < Fp; k += blockDim.x) out[r * Fp + k] = 0.f;
+      return;
+    }
+  }
+  const int lp = (nfft - win) >> 1;
+  const long long start = (long long)f * hop - (nfft >> 1);
+  fft64_frame_lds(re, im, cs, sn, nfft, lg, [&](int j) {
+    const int k = j - lp;
+    double v = 0.0;
+    if (k >= 0 && k < win) {
+      long long n = start + j;
+      if (n < 0) n = -n;
+      else if (n >= S) n = 2 * (S - 1) - n;
+      v = (double)xb[n] * (0.5 - 0.5 * cospi(2.0 * (double)k / (double)win));
+    }
+    return v;
+  });
+  for (int k = threadIdx.x; k < Fp; k += blockDim.x)
+    out[r * Fp + k] = k < F ? (float)log1p(sqrt(re[k] * re[k] + im[k] * im[k])) : 0.f;
 }
 
 // y = log(x == 0 ? eps : x) elementwise (base.logfbank / base.mfcc)
@@ -378,6 +450,43 @@ extern "C" int dlip_powspec_wave_fft64_ragged_f32(const float* x, const int32_t*
                                                   int32_t NBp, dlip_stream_t stream) {
   DLIP_CHECK_ARG(sample_len);
   return powspec_wave_fft64(x, sample_len, pw, energy, B, S, NF, frame_len, frame_step, nfft, preemph, NB, NBp, stream);
+}
+
+static bool stft_geometry_ok(int64_t S, int32_t n_fft, int32_t hop) {
+  return n_fft >= 128 && n_fft <= 1024 && (n_fft & (n_fft - 1)) == 0 && hop >= 1 && S >= n_fft / 2 + 1;
+}
+
+static int stft_logmag_wave(const float* x, const int32_t* slen, float* out, int64_t B, int64_t S, int32_t NF, int32_t win, int32_t hop,
+                            int32_t n_fft, int32_t F, int32_t Fp, dlip_stream_t stream) {
+  DLIP_CHECK_ARG(x && out && B > 0 && stft_geometry_ok(S, n_fft, hop) && win >= 1 && win <= n_fft);
+  DLIP_CHECK_ARG((int64_t)NF == 1 + S / hop && F == n_fft / 2 + 1 && Fp >= F);
+  DLIP_CHECK_ARG(B * (long long)NF < (1ll << 31));
+  int lg = 0;
+  while ((1 << lg) < n_fft) ++lg;
+  const int threads = n_fft / 2;           // 64 .. 512: one butterfly per thread and stage
+  const size_t lds = (size_t)(3 * n_fft) * sizeof(double);
+  hipLaunchKernelGGL(slen ? stft_logmag_wave_kernel<true> : stft_logmag_wave_kernel<false>, dim3((unsigned)(B * NF)),
+                     dim3((unsigned)threads), lds, dlip_hip_stream(stream), x, slen, out, (long long)S, NF, win, hop, n_fft, lg, F, Fp);
+  return dlip_launch_status();
+}
+
+extern "C" int dlip_stft_logmag_wave_f32(const float* x, float* out, int64_t B, int64_t S, int32_t NF, int32_t win, int32_t hop,
+                                         int32_t n_fft, int32_t F, int32_t Fp, dlip_stream_t stream) {
+  return stft_logmag_wave(x, nullptr, out, B, S, NF, win, hop, n_fft, F, Fp, stream);
+}
+
+extern "C" int dlip_stft_logmag_wave_ragged_f32(const float* x, const int32_t* sample_len, float* out, int64_t B, int64_t S, int32_t NF,
+                                                int32_t win, int32_t hop, int32_t n_fft, int32_t F, int32_t Fp, dlip_stream_t stream) {
+  DLIP_CHECK_ARG(sample_len);
+  return stft_logmag_wave(x, sample_len, out, B, S, NF, win, hop, n_fft, F, Fp, stream);
+}
+
+extern "C" int dlip_stft_frame_lengths_i32(const int32_t* sample_len, int32_t* frame_lengths, int32_t B, int64_t S, int32_t n_fft,
+                                           int32_t hop, dlip_stream_t stream) {
+  DLIP_CHECK_ARG(sample_len && frame_lengths && B > 0 && stft_geometry_ok(S, n_fft, hop));
+  hipLaunchKernelGGL(stft_frame_lengths_kernel, dim3((B + 255) / 256), dim3(256), 0, dlip_hip_stream(stream), sample_len, frame_lengths,
+                     B, (long long)S, n_fft, hop);
+  return dlip_launch_status();
 }
 
 extern "C" int dlip_log_floor_f32(const float* x, float* y, int64_t n, dlip_stream_t stream) {

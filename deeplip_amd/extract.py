@@ -34,20 +34,31 @@ class RaggedExtractor:
     rows [B,D]`` are launch-only step functions (deeplip_amd/plan.py).  Under ``run(waves=True)`` audio_fn is called as
     ``audio_fn(wave [B,S], sample_lengths int32 [B])``: the front-end with ``lengths`` and the encoder on its frame lengths."""
 
+    # the front-end given as ``wave_geometry``; None: framesig's arithmetic on (frame_len, frame_step).  (A class-level default beside
+    # the one __init__ sets: an extractor assembled field by field from the older attribute set keeps that arithmetic.)
+    wave_frontend = None
+
     def __init__(self, audio_fn: Optional[Callable], video_fn: Optional[Callable], device, batch: int = 32, clip_batch: Optional[int] = None,
                  waste: float = 0.10, audio_quantum: int = 4, video_quantum: int = 1, max_arena_bytes: int = 64 << 30,
                  audio_min_frames: int = 1, video_min_frames: int = 1, fallback="auto",
-                 wave_geometry: Tuple[int, int] = (400, 160)):
+                 wave_geometry=(400, 160)):
         """``audio_min_frames`` / ``video_min_frames``: the shortest item the encoders can embed -- for the E-TDNN
         ``frames_consumed() + 2`` = 24 (its valid convolutions take 22 frames off an utterance and the unbiased standard deviation of
         the statistics pooling needs two pooled frames, pooling.py:24-26), one frame for a lip clip.  Checked HERE, on the host,
         where the lengths are: the kernels only clamp a length to [0, T] and a pooled count of 0 (or 1 under the std) would come
         back as NaN / Inf rows in the embedding table with no error.  ``fallback``: see ExtractPipeline (per-batch f32 re-run).
-        ``wave_geometry``: (frame_len, frame_step) in samples of the front-end inside ``audio_fn``, for ``run(waves=True)``."""
+        ``wave_geometry``: (frame_len, frame_step) in samples of the front-end inside ``audio_fn``, for ``run(waves=True)`` --
+        sigproc.framesig's arithmetic -- or the front-end itself (any object with ``frame_len``, ``frame_step``,
+        ``frames_for_samples(n)`` and ``samples_for_frames(T)``; optionally ``min_samples``, checked on the host in ``run``), whose
+        own frame count then decides: the ``stft`` feature type counts 1 + n // hop frames."""
         self.device, self.batch, self.clip_batch, self.waste = device, int(batch), int(clip_batch or batch), float(waste)
         self.aq, self.vq = audio_quantum, video_quantum
         self.audio_min_frames, self.video_min_frames = int(audio_min_frames), int(video_min_frames)
-        self.frame_len, self.frame_step = int(wave_geometry[0]), int(wave_geometry[1])
+        if hasattr(wave_geometry, "frames_for_samples"):
+            self.wave_frontend = wave_geometry
+            self.frame_len, self.frame_step = int(wave_geometry.frame_len), int(wave_geometry.frame_step)
+        else:
+            self.frame_len, self.frame_step = int(wave_geometry[0]), int(wave_geometry[1])
         self.pa = BucketedExtract(audio_fn, device=device, max_arena_bytes=max_arena_bytes // 4, fallback=fallback) if audio_fn is not None else None
         self.pv = BucketedExtract(video_fn, device=device, max_arena_bytes=max_arena_bytes, fallback=fallback) if video_fn is not None else None
         self.stats: dict = {}
@@ -57,14 +68,27 @@ class RaggedExtractor:
             if p is not None:
                 p.close()
 
+    # ------------------------------------------------------------------ samples <-> frames of the front-end inside audio_fn
+    def _frames_for(self, n: int) -> int:
+        if self.wave_frontend is not None:
+            return int(self.wave_frontend.frames_for_samples(int(n)))
+        from .frontend import num_frames
+        return num_frames(int(n), self.frame_len, self.frame_step)
+
+    def _samples_for(self, T: int) -> int:
+        if self.wave_frontend is not None:
+            return int(self.wave_frontend.samples_for_frames(int(T)))
+        return self.frame_len + (int(T) - 1) * self.frame_step
+
     # ------------------------------------------------------------------ one modality: host batches in submission order
     def _audio_host(self, dataset, lo: int, b: Batch):
         x, L = dataset.audio_padded([lo + int(i) for i in b.idx], T=b.T)
         return (pin(torch.from_numpy(x)), pin(torch.from_numpy(L)))
 
     def _wave_host(self, dataset, lo: int, b: Batch):
-        """A rung of T frames pads to the S samples that frame into exactly T (num_frames(S) = T): the front-end's output is [n,F,T]."""
-        S = self.frame_len + (b.T - 1) * self.frame_step
+        """A rung of T frames pads to the S samples that frame into exactly T (frames_for_samples(S) = T, the longest such signal): the
+        front-end's output is [n,F,T]."""
+        S = self._samples_for(b.T)
         x, L = dataset.waves_padded([lo + int(i) for i in b.idx], S=S, frame_len=self.frame_len, frame_step=self.frame_step)
         return (pin(torch.from_numpy(x)), pin(torch.from_numpy(L)))
 
@@ -87,9 +111,15 @@ class RaggedExtractor:
         dev = self.device
         xa = xv = None
         if waves and self.pa is not None:
-            from .frontend import num_frames
             slen = dataset.wave_len(self.frame_len, self.frame_step)[lo:hi]
-            alen = np.array([num_frames(int(s), self.frame_len, self.frame_step) for s in slen], dtype=np.int64)
+            alen = np.array([self._frames_for(int(s)) for s in slen], dtype=np.int64)
+            # the sample counts travel as a device vector, which the kernels clamp and do not refuse: the front-end's shortest
+            # utterance (stft: nfft // 2 + 1 samples, one reflection per side) is checked HERE, where the lengths are
+            need = int(getattr(self.wave_frontend, "min_samples", 1))
+            short = np.flatnonzero(np.asarray(slen) < need)
+            if short.size:
+                raise ValueError(f"RaggedExtractor: utterance {lo + int(short[0])} has {int(slen[int(short[0])])} samples; the front-end "
+                                 f"needs >= {need}; {short.size} such utterance(s) in the list")
         else:
             alen = np.asarray(dataset.audio_len[lo:hi])
         if n and self.pa is not None:

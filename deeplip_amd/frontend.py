@@ -7,6 +7,8 @@ produce with python_speech_features (models/audio_models/datasets.py:65-83: ``mf
 per-utterance mean/variance normalisation of datasets.py:52-53.  The 512-point real DFT, the mel
 filterbank and the DCT-II(+lifter) are three fp32 MFMA GEMMs against constant matrices built once
 on the host in fp64; framing/pre-emphasis, power spectrum, log and CMVN are small HIP kernels.
+The loaders' fourth feature type, ``stft`` (datasets.py:72-76: log1p of the magnitude of librosa.stft), is one kernel from the
+waveform to the log-magnitude rows, in fp64, with the same CMVN and deltas behind it.
 
 ``VideoFrontend`` is the test-time pipeline of models/video_models/dataloaders.py:11-22
 (Normalize(0,255) -> CenterCrop(88) -> Normalize(0.421, 0.165)) on uint8 gray or RGB frames plus the
@@ -64,9 +66,12 @@ class AudioFrontend:
                  nfft: int = 512, num_bin: int = 26, num_cep: int = 24, preemph: float = 0.97, ceplifter: int = 22,
                  energy: bool = True, normalize: bool = True, delta: bool = False, dft64: Optional[bool] = None, device="cuda",
                  dft: Optional[str] = None):
-        if feat_type not in ("mfcc", "fbank", "logfbank"):
+        if feat_type not in ("mfcc", "fbank", "logfbank", "stft"):
             raise NotImplementedError("Other features are not implemented!")   # datasets.py:75-76
         self.feat_type, self.rate, self.nfft = feat_type, rate, nfft
+        if feat_type == "stft":
+            self._init_stft(win_len, win_shift, normalize, delta, dft64, dft, device)
+            return
         # sigproc.framesig rounds half UP: 22.05 kHz steps by 220.5 -> 221 samples and 44.1 kHz frames 1102.5 -> 1103, where
         # round() (half to even) gave 220 and 1102 -- another number of frames than the reference's loader produces
         self.frame_len = round_half_up(win_len * rate)
@@ -115,9 +120,93 @@ class AudioFrontend:
             d = np.zeros((num_cep, self.nfp)); d[:, :num_bin] = dct * lift[:, None]                        # lifter folded in
             self.w_dct = torch.from_numpy(d).float().contiguous().to(self.device)
 
+    def _init_stft(self, win_len, win_shift, normalize, delta, dft64, dft, device):
+        """``stft`` (datasets.py:72-76): librosa.stft(y, n_fft, hop_length=int(rate * win_shift), win_length=int(rate * win_len)) ->
+        magphase -> log1p.  hop and window TRUNCATE, as the loader's own line does (22.05 kHz: 220 and 551, where framesig's
+        round_half_up gives 221 and 551); num_bin / num_cep / preemph / ceplifter / energy do not enter, and no mel, DFT or DCT matrix
+        is built or uploaded: one kernel goes from the waveform to log1p|X| (dlip_stft_logmag_wave_f32, fp64 inside), CMVN and deltas
+        are the other feature types' kernels.  ``frame_len`` / ``frame_step`` name the window and the hop in samples, the numbers a
+        loader's crop is cut by (collate_fn, datasets.py:113-115)."""
+        nfft, rate = self.nfft, self.rate
+        self.hop, self.win_length = int(rate * win_shift), int(rate * win_len)
+        if self.win_length < 1 or self.hop < 1:
+            raise ValueError(f"AudioFrontend: int(rate * win_len) and int(rate * win_shift) must be at least one sample, got "
+                             f"{self.win_length} and {self.hop}")
+        if nfft < 128 or nfft > 1024 or nfft & (nfft - 1):
+            raise ValueError(f"AudioFrontend: feat_type 'stft' needs nfft to be a power of two in 128 .. 1024, got nfft={nfft}")
+        if nfft < self.win_length:
+            raise ValueError(f"AudioFrontend: nfft must be >= the window ({self.win_length} samples = win_len {win_len} s at {rate} Hz), "
+                             f"got nfft={nfft}")
+        if dft64 is not None or dft not in (None, "fft64"):
+            raise ValueError(f"AudioFrontend: feat_type 'stft' has the one transform 'fft64' (dft=None or 'fft64', dft64=None), got "
+                             f"dft={dft!r}, dft64={dft64!r}")
+        self.frame_len, self.frame_step = self.win_length, self.hop
+        self.normalize, self.delta = normalize, delta
+        self.dft, self.dft64 = "fft64", False
+        self.device = torch.device(device)
+        nb = nfft // 2 + 1
+        self.nb, self.nbp = nb, (nb + 3) // 4 * 4
+
     @property
     def feat_dim(self) -> int:
+        if self.feat_type == "stft":
+            return (3 if self.delta else 1) * self.nb
         return (3 if self.delta else 1) * (self.num_cep if self.feat_type == "mfcc" else self.num_bin)
+
+    @property
+    def min_samples(self) -> int:
+        """The shortest utterance the front-end takes: one sample, resp. nfft // 2 + 1 for ``stft`` (one reflection per side)."""
+        return self.nfft // 2 + 1 if self.feat_type == "stft" else 1
+
+    def frames_for_samples(self, n: int) -> int:
+        """Frames of an n-sample utterance: sigproc.framesig's count, resp. librosa.stft's 1 + n // hop (center=True)."""
+        if self.feat_type == "stft":
+            return 1 + int(n) // self.hop
+        return num_frames(int(n), self.frame_len, self.frame_step)
+
+    def samples_for_frames(self, T: int) -> int:
+        """The longest signal that has T frames: a batch padded to it comes out [B, F, T]."""
+        if self.feat_type == "stft":
+            return int(T) * self.hop - 1
+        return self.frame_len + (int(T) - 1) * self.frame_step
+
+    def _call_stft(self, wave: torch.Tensor, lengths=None):
+        ops._req(wave, "AudioFrontend('stft'): wave")
+        B, S = wave.shape
+        lo = self.min_samples                   # one reflection per side must reach every sample of a frame
+        if S < lo:
+            raise ValueError(f"AudioFrontend('stft'): the batch must be at least nfft // 2 + 1 = {lo} samples wide, got {S}")
+        lens = ops.lengths_i32(lengths, wave.device, n=B, lo=lo, hi=S)
+        NF = 1 + S // self.hop
+        C_ = self.nb
+        geom = (NF, self.win_length, self.hop, self.nfft, C_, self.nbp)
+        feat = ops._empty((B * NF, self.nbp), wave.device)
+        out = ops._empty((B, C_, NF), wave.device)
+        nf = None
+        if lens is None:
+            check(lib().dlip_stft_logmag_wave_f32(ptr(wave), ptr(feat), B, S, *geom, stream_handle()), "dlip_stft_logmag_wave_f32")
+            check(lib().dlip_cmvn_nct_f32(ptr(feat), None, ptr(out), B, NF, C_, self.nbp, int(self.normalize), stream_handle()),
+                  "dlip_cmvn_nct_f32")
+        else:
+            check(lib().dlip_stft_logmag_wave_ragged_f32(ptr(wave), ptr(lens), ptr(feat), B, S, *geom, stream_handle()),
+                  "dlip_stft_logmag_wave_ragged_f32")
+            nf = ops._empty((B,), wave.device, torch.int32)
+            check(lib().dlip_stft_frame_lengths_i32(ptr(lens), ptr(nf), B, S, self.nfft, self.hop, stream_handle()),
+                  "dlip_stft_frame_lengths_i32")
+            check(lib().dlip_cmvn_nct_ragged_f32(ptr(feat), None, ptr(nf), ptr(out), B, NF, C_, self.nbp, int(self.normalize),
+                                                 stream_handle()), "dlip_cmvn_nct_ragged_f32")
+        return self._deltas(out, nf, B, C_, NF, lens is None)
+
+    def _deltas(self, out, nf, B, C_, NF, rect):
+        if self.delta:
+            out3 = ops._empty((B, 3 * C_, NF), out.device)
+            if rect:
+                check(lib().dlip_delta_nct_f32(ptr(out), ptr(out3), B, C_, NF, 2, stream_handle()), "dlip_delta_nct_f32")
+            else:
+                check(lib().dlip_delta_nct_ragged_f32(ptr(out), ptr(nf), ptr(out3), B, C_, NF, 2, stream_handle()),
+                      "dlip_delta_nct_ragged_f32")
+            out = out3
+        return out if rect else (out, nf)
 
     def __call__(self, wave: torch.Tensor, lengths=None):
         """wave [B, S] float32 (cuda) -> features [B, F, NF] float32.
@@ -130,6 +219,8 @@ class AudioFrontend:
         are validated here; a device vector is clamped by the kernels and never read on the host, and nothing below synchronises, so
         the call records into a step plan (deeplip_amd/plan.py) and ``frame_lengths`` is the encoders' ``lengths``."""
         wave = wave.contiguous().float()
+        if self.feat_type == "stft":
+            return self._call_stft(wave, lengths)
         B, S = wave.shape
         lens = ops.lengths_i32(lengths, wave.device, n=B, lo=1, hi=S)           # None: the rectangular batch, no length is read
         NF = num_frames(S, self.frame_len, self.frame_step)
@@ -185,15 +276,7 @@ class AudioFrontend:
                   "dlip_wave_frame_lengths_i32")
             check(lib().dlip_cmvn_nct_ragged_f32(ptr(feat), ptr(en), ptr(nf), ptr(out), B, NF, C_, feat.shape[1], int(self.normalize),
                                                  stream_handle()), "dlip_cmvn_nct_ragged_f32")
-        if self.delta:
-            out3 = ops._empty((B, 3 * C_, NF), wave.device)
-            if lens is None:
-                check(lib().dlip_delta_nct_f32(ptr(out), ptr(out3), B, C_, NF, 2, stream_handle()), "dlip_delta_nct_f32")
-            else:
-                check(lib().dlip_delta_nct_ragged_f32(ptr(out), ptr(nf), ptr(out3), B, C_, NF, 2, stream_handle()),
-                      "dlip_delta_nct_ragged_f32")
-            out = out3
-        return out if lens is None else (out, nf)
+        return self._deltas(out, nf, B, C_, NF, lens is None)
 
 
 class VideoFrontend:

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define DLIP_ABI_VERSION 60
+#define DLIP_ABI_VERSION 61
 #define DLIP_HOST              /* marks a pointer parameter that the CPU dereferences during the call (HOST memory, not device) */
 #define DLIP_LIFT_BCAST 2048
 #define DLIP_LIFT_WORDS 4098   /* a gradient's power-of-two lift: (2^e, 2^-e), then 2^-e repeated DLIP_LIFT_BCAST times (the post_scale
@@ -1148,6 +1148,34 @@ int dlip_wave_add_noise_f32(const float* y, const int32_t* lengths, const float*
                             dlip_stream_t stream);
 int dlip_wave_normalize_f32(const float* z, const int32_t* lengths, float* out, void* workspace, int64_t workspace_bytes, int32_t B,
                             int32_t S, dlip_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 61) LOG-MAGNITUDE SPECTROGRAMS from the waveform: the loaders' fourth feature type, `stft` (models/audio_models/datasets.py:72-76:
+ * librosa.stft(y, n_fft, hop_length, win_length) -> magphase -> log1p -> transpose; librosa's defaults center=True,
+ * pad_mode="reflect", window="hann").  x [B,S] fp32; hop = int(rate * win_shift) and win = int(rate * win_len) TRUNCATE
+ * (datasets.py:73), where the other three feature types round half up.  With lp = (n_fft - win) / 2 and the periodic Hann window
+ * w[lp + k] = 0.5 - 0.5 cos(2 pi k / win), 0 <= k < win (zero elsewhere):
+ *
+ * dlip_stft_logmag_wave_f32 (models/audio_models/datasets.py:72-76): out[b NF + t, k] = log1p(|sum_j w[j] y[refl(t hop + j - n_fft / 2)]
+ *   exp(-2 pi i j k / n_fft)|), k < F = n_fft / 2 + 1, NF = 1 + S / hop; refl reflects about 0 and about S - 1 without repeating the
+ *   edge sample.  One launch, one workgroup per (row, frame), window, radix-2 FFT, modulus and log1p in fp64: the result is the
+ *   reference's value but for the final rounding to fp32.  out [B NF, Fp], Fp >= F, pad columns zero.  DLIP_EINVAL unless n_fft is a
+ *   power of two in 128 .. 1024, 1 <= win <= n_fft, hop >= 1, S >= n_fft / 2 + 1 (one reflection per side suffices),
+ *   NF == 1 + S / hop, F == n_fft / 2 + 1, Fp >= F, B NF < 2^31.
+ * dlip_stft_logmag_wave_ragged_f32 (models/audio_models/datasets.py:72-76, one utterance at a time: train_fusion.py:334-349): row b
+ *   ends at S_b = clamp(sample_len[b], n_fft / 2 + 1, S) (device int32 [B], never read on the host), has NF_b = 1 + S_b / hop frames and
+ *   is reflected about its own end; samples >= S_b are never read; frames t >= NF_b are zero rows.  Frame t < NF_b holds the bits the
+ *   rectangular entry point gives for the S_b-sample signal alone.
+ * dlip_stft_frame_lengths_i32 (models/audio_models/datasets.py:72-76: the frame count of librosa.stft): frame_lengths[b] = NF_b on the
+ *   device, the counterpart of dlip_wave_frame_lengths_i32 -- the `frame_lengths` of dlip_cmvn_nct_ragged_f32 /
+ *   dlip_delta_nct_ragged_f32 (datasets.py:52-63 behind the spectrogram, unchanged) and the encoders' `lengths`.
+ * ------------------------------------------------------------------------------------------ */
+int dlip_stft_logmag_wave_f32(const float* x, float* out, int64_t B, int64_t S, int32_t NF, int32_t win, int32_t hop, int32_t n_fft,
+                              int32_t F, int32_t Fp, dlip_stream_t stream);
+int dlip_stft_logmag_wave_ragged_f32(const float* x, const int32_t* sample_len, float* out, int64_t B, int64_t S, int32_t NF,
+                                     int32_t win, int32_t hop, int32_t n_fft, int32_t F, int32_t Fp, dlip_stream_t stream);
+int dlip_stft_frame_lengths_i32(const int32_t* sample_len, int32_t* frame_lengths, int32_t B, int64_t S, int32_t n_fft, int32_t hop,
+                                dlip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Step plans.  The reference drives its encoders from a Python loop, one utterance and one torch.nn layer

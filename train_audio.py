@@ -170,9 +170,12 @@ class Trainer(object):
         from deeplip_amd.synthetic import noise_bank, room_responses
         d = self.data_opts
         feat = d.get("feat_type", "mfcc" if arch != "resnet" else "fbank")
-        fe = AudioFrontend(feat, rate=int(d.get("rate", 16000)), win_len=float(d.get("win_len", 0.025)),
-                           win_shift=float(d.get("win_shift", 0.01)), nfft=int(d.get("nfft", 512)), num_cep=feat_dim, device=self.device,
-                           **({} if feat == "mfcc" else {"num_bin": feat_dim}))
+        geom = dict(rate=int(d.get("rate", 16000)), win_len=float(d.get("win_len", 0.025)), win_shift=float(d.get("win_shift", 0.01)),
+                    nfft=int(d.get("nfft", 512)), device=self.device)
+        if feat == "stft":              # log-magnitude spectrogram (datasets.py:72-76): nfft // 2 + 1 bins, nothing else to choose
+            fe = AudioFrontend("stft", **geom)
+        else:
+            fe = AudioFrontend(feat, num_cep=feat_dim, **geom, **({} if feat == "mfcc" else {"num_bin": feat_dim}))
         if fe.feat_dim != feat_dim:
             raise ValueError(f"data.train_from_waves: the front-end yields {fe.feat_dim} features, the encoder takes {feat_dim}")
         if self.augment_opts is None:
@@ -269,7 +272,8 @@ class Trainer(object):
                 extra = ()
                 if self.train_from_waves:
                     # the same crop as WAVEFORMS: frame_len + (T - 1) frame_step samples (T frames) cut from the zero-padded batch at
-                    # an offset that fits the shortest row -- a rectangular batch; the augmentation's choices are drawn beside it
+                    # an offset that fits the shortest row -- a rectangular batch; the augmentation's choices are drawn beside it.
+                    # (feat_type stft: the loader cuts the same samples, datasets.py:113-115, and librosa.stft makes T + 2 frames of them)
                     fl, fs = self._wave_fe.frame_len, self._wave_fe.frame_step
                     Sb = fl + (T - 1) * fs
                     wl = self.trainset.wave_len(fl, fs)[idx]

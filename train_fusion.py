@@ -474,7 +474,7 @@ class Trainer(object):
                 def audio_fn(wave, sample_len):  # front-end and encoder in one recorded step; the frame lengths stay on the device
                     feats, n_frames = fe(wave, sample_len)
                     return self.model_audio.extract_embedding(feats, lengths=n_frames)[0]
-                geom = {"wave_geometry": (fe.frame_len, fe.frame_step)}
+                geom = {"wave_geometry": fe if fe.feat_type == "stft" else (fe.frame_len, fe.frame_step)}
             ex = RaggedExtractor(audio_fn,
                                  lambda v, l: self.model_video.embed(v, lengths=l),                        # :346-348 (mean over T)
                                  self.device, batch=batch, audio_min_frames=1 if arch == "resnet" else self.model_audio.frames_consumed() + 2,
@@ -484,10 +484,18 @@ class Trainer(object):
 
     def _test_frontend(self, arch):
         """The loaders' feature extraction (data.python_data_config; models/audio_models/datasets.py:65-83) as the GPU front-end, with as
-        many coefficients / bands as the speech encoder takes."""
+        many coefficients / bands as the speech encoder takes; ``feat_type: stft`` yields nfft // 2 + 1 bins, which the encoder's
+        feat_dim must equal."""
         from deeplip_amd.frontend import AudioFrontend
         o = self.feat_opts
         feat = o.get("feat_type", "mfcc" if arch != "resnet" else "fbank")
+        if feat == "stft":
+            fe = AudioFrontend("stft", rate=int(o.get("rate", 16000)), win_len=float(o.get("win_len", 0.025)),
+                               win_shift=float(o.get("win_shift", 0.01)), nfft=int(o.get("nfft", 512)), device=self.device)
+            if fe.feat_dim != self.feat_dim:
+                raise ValueError(f"data.python_data_config.test_from_waves: the front-end yields {fe.feat_dim} features, the encoder "
+                                 f"takes {self.feat_dim}")
+            return fe
         return AudioFrontend(feat, rate=int(o.get("rate", 16000)), win_len=float(o.get("win_len", 0.025)), win_shift=float(o.get("win_shift", 0.01)),
                              nfft=int(o.get("nfft", 512)), num_cep=self.feat_dim, device=self.device,
                              **({} if feat == "mfcc" else {"num_bin": self.feat_dim}))
