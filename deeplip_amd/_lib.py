@@ -106,6 +106,9 @@ LIFT_BCAST = HEADER["DLIP_LIFT_BCAST"]
 # waveform augmentation (deeplip_amd/augment.py): the FIR kernel's tile, its tap chunk and the longest room response it takes
 DLIP_FIR_TILE, DLIP_FIR_TAP_CHUNK, DLIP_FIR_MAX_TAPS = (HEADER[n] for n in ("DLIP_FIR_TILE", "DLIP_FIR_TAP_CHUNK", "DLIP_FIR_MAX_TAPS"))
 
+# sliding-window CMN (deeplip_amd/voiced_frames.py): the kernel's tile of output frames and the longest window it takes
+DLIP_CMN_TILE, DLIP_CMN_MAX_WINDOW = HEADER["DLIP_CMN_TILE"], HEADER["DLIP_CMN_MAX_WINDOW"]
+
 
 def lib() -> C.CDLL:
     """Load (once) and return the HIP library; raises if it is missing -- never falls back."""

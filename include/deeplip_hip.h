@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define DLIP_ABI_VERSION 61
+#define DLIP_ABI_VERSION 62
 #define DLIP_HOST              /* marks a pointer parameter that the CPU dereferences during the call (HOST memory, not device) */
 #define DLIP_LIFT_BCAST 2048
 #define DLIP_LIFT_WORDS 4098   /* a gradient's power-of-two lift: (2^e, 2^-e), then 2^-e repeated DLIP_LIFT_BCAST times (the post_scale
@@ -1175,6 +1175,51 @@ int dlip_stft_logmag_wave_f32(const float* x, float* out, int64_t B, int64_t S, 
 int dlip_stft_logmag_wave_ragged_f32(const float* x, const int32_t* sample_len, float* out, int64_t B, int64_t S, int32_t NF,
                                      int32_t win, int32_t hop, int32_t n_fft, int32_t F, int32_t Fp, dlip_stream_t stream);
 int dlip_stft_frame_lengths_i32(const int32_t* sample_len, int32_t* frame_lengths, int32_t B, int64_t S, int32_t n_fft, int32_t hop,
+                                dlip_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 62) SLIDING-WINDOW CMN AND ENERGY-VAD FRAME SELECTION behind the front-end: the stage the reference's own speech pipeline
+ * spells out (conf/audio_config.yaml:21 `plda_input` and :25 `nn_input`: `apply-cmvn-sliding --norm-vars=false --center=true
+ * --cmn-window=300 ... | select-voiced-frames ... vad.scp`).  No source for these tools ships upstream: parity is UNPINNED, and this
+ * block with DESIGN.md 4f is the definition, restated from Kaldi's published SlidingWindowCmn and ComputeVadEnergy.
+ * x [B, C, NF] fp32, time contiguous (the front-end's output); `lengths` (device int32 [B], nullable): row b holds
+ * n = clamp(lengths[b], 1, NF) frames (NF when NULL), clamped on the device and never read on the host -- a recorded plan replays
+ * with a new vector -- and is computed as if it were alone: frames t >= n are never loaded (the padding may hold anything), full
+ * lengths give the bits of lengths == NULL, no atomics, the same bits on every run.
+ *
+ * dlip_vad_energy_select_i32 (Kaldi compute-vad-energy + the index side of select-voiced-frames): e[t] = log_energy[b energy_stride + t]
+ *   (a row of x is passed without a copy: log_energy = x + energy_row NF, energy_stride = C NF);
+ *   thr = fp32(energy_threshold + energy_mean_scale (sum_{t<n} e[t]) / n), the sum in fp64 in an order n alone decides, rounded once
+ *   (energy_mean_scale == 0: thr = fp32(energy_threshold), no sum);  for t < n: den = |[t - context, t + context] within [0, n)|,
+ *   num = how many of those frames have e > thr, voiced[t] = (float)num >= (float)den * proportion_threshold (the product in fp32,
+ *   Kaldi's BaseFloat).  `voiced` (uint8 [B, NF], nullable) is an external decision (`vad.scp`) taken instead; log_energy may then be
+ *   NULL.  V = the row's voiced frames; V < min_keep: the row keeps all its n frames and fallback[b] = 1 (Kaldi drops an utterance
+ *   without voiced frames; a batch cannot drop a row and the host never sees V), else 0.  out_len[b] = V, or n for a fallback row;
+ *   pos [B, NF] = the destination column of frame t (kept frames packed to the front in order), -1 for a dropped frame and for
+ *   t >= n.  One workgroup per row.  DLIP_EINVAL: context < 0, min_keep < 1, proportion_threshold outside [0, 1], B or NF < 1, NF > 2^30,
+ *   neither log_energy nor voiced, energy_stride < NF.
+ * dlip_cmn_sliding_select_f32 (Kaldi apply-cmvn-sliding, then the data side of select-voiced-frames): the window of frame t is
+ *     center:  begin = t - window / 2 (integer division), end = begin + window;     else:  begin = t - window, end = t + 1
+ *     if begin < 0: end -= begin, begin = 0;      if !center and end > t: end = max(t + 1, min_window)
+ *     if end > n: begin -= end - n, end = n, if begin < 0: begin = 0
+ *   v[t] = x[t] - mean(x[begin:end]); norm_vars != 0: v[t] *= max(sum x^2 / w - mean^2, 1e-10)^(-1/2), 0 where w = end - begin = 1.
+ *   The window ALWAYS runs over the row's n frames of x, before the selection.  Sums in fp64 in an order (t, n, window, center,
+ *   min_window) alone decide -- a workgroup owns the DLIP_CMN_TILE frames t belongs to, forms the fp64 prefix sums of the frames its
+ *   windows reach over, less the first of them (thread by thread front to back, the threads' totals in thread order: mean and
+ *   variance do not move with that pivot and the prefixes stay the size of the signal's variation) and takes a window's sum as
+ *   the difference of two of them; a window of at most 16 frames is summed frame by frame -- and the result is rounded to fp32 once.  pos / out_len from the call above: y[b, c, pos[t]] = v[t] for pos[t] >= 0, columns >= out_len[b] exact
+ *   zeros; both NULL: no selection (y[b, c, t] = v[t], zeros from n on).  window == 0: the selection alone, kept values copied
+ *   bit for bit.  y must not be x.  DLIP_EINVAL: window outside [0, DLIP_CMN_MAX_WINDOW], min_window outside
+ *   [1, DLIP_CMN_MAX_WINDOW], B, C or NF < 1, only one of pos / out_len given.
+ * ------------------------------------------------------------------------------------------ */
+#define DLIP_CMN_TILE 1024
+#define DLIP_CMN_MAX_WINDOW 768
+int dlip_vad_energy_select_i32(const float* log_energy, int64_t energy_stride, const uint8_t* voiced, const int32_t* lengths,
+                               double energy_threshold, double energy_mean_scale, int32_t context, float proportion_threshold,
+                               int32_t min_keep, int32_t* pos, int32_t* out_len, int32_t* fallback, int32_t B, int32_t NF,
+                               dlip_stream_t stream);
+int dlip_cmn_sliding_select_f32(const float* x, const int32_t* lengths, const int32_t* pos, const int32_t* out_len, float* y, int32_t B,
+                                int32_t C, int32_t NF, int32_t window, int32_t center, int32_t min_window, int32_t norm_vars,
                                 dlip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------

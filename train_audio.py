@@ -106,6 +106,10 @@ class Trainer(object):
         # data.train_from_waves / data.augment (build-owned, off by default): batches of WAVEFORMS, augmented on the device and turned
         # into features by the GPU front-end in front of the unchanged step (_train_epoch).  Parsed before anything touches the GPU.
         self.train_from_waves, self.augment_opts = parse_wave_training(self.data_opts)
+        # data.voiced_frames (build-owned, absent = off): sliding-window CMN + energy-VAD frame selection in front of the encoder on the
+        # feature-fed ragged test lists -- the `nn_input` / `plda_input` pipe (conf/audio_config.yaml:21,25; deeplip_amd/voiced_frames.py).
+        from deeplip_amd.voiced_frames import parse_voiced_frames_section
+        self.voiced_frames_opts = parse_voiced_frames_section(self.data_opts.get("voiced_frames"))
         # the arithmetic of the engine (--arith > $DLIP_ARITH > model.arith > auto), before the first weight pack
         self.arith = arith.configure(arith_mode, self.model_opts.get("arith"))
         if not torch.cuda.is_available():
@@ -407,6 +411,8 @@ class Trainer(object):
         rows = []
         ce = self.train_opts["loss"] == "CrossEntropy"
         self.model.eval()
+        if self.voiced_frames_opts is not None and not dataset.ragged:
+            raise ValueError("data.voiced_frames needs data.test_ragged: true (the stage hands the encoder one length per utterance)")
         with torch.no_grad():
             if dataset.ragged:
                 # utterances at their own lengths (train_audio.py:343-373 feeds them one by one): length-bucketed batches,
@@ -438,10 +444,28 @@ class Trainer(object):
             self._extractor[1].close()
             self._extractor = None
         if self._extractor is None:
-            ex = RaggedExtractor(lambda a, l: torch.cat(self.model.extract_embedding(a, lengths=l), dim=1), None, self.device, batch=batch,
-                                 audio_min_frames=self._min_frames())
+            stage = self._voiced_frames_stage()
+
+            def audio_fn(a, l):
+                if stage is not None:   # conf/audio_config.yaml:25: sliding CMN, then the voiced frames alone (a shorter row per utterance)
+                    a, l = stage(a, l)
+                return torch.cat(self.model.extract_embedding(a, lengths=l), dim=1)
+            ex = RaggedExtractor(audio_fn, None, self.device, batch=batch, audio_min_frames=self._min_frames())
             self._extractor = (key, ex)
         return self._extractor[1]
+
+    def _voiced_frames_stage(self):
+        """The VoicedFrames stage of data.voiced_frames (None: off).  ``min_keep`` defaults to the encoder's minimum frame count: a row
+        the VAD leaves fewer frames keeps all of its frames, which the extractor has checked on the host."""
+        if self.voiced_frames_opts is None:
+            return None
+        from deeplip_amd.voiced_frames import VoicedFrames
+        o = dict(self.voiced_frames_opts)
+        if o["min_keep"] is None:
+            o["min_keep"] = self._min_frames()
+        if o["min_keep"] < self._min_frames():
+            raise ValueError(f"data.voiced_frames.min_keep: {o['min_keep']} is below the {self._min_frames()} frames the encoder needs")
+        return VoicedFrames(**o)
 
     def _min_frames(self) -> int:
         """The shortest utterance the encoder embeds.  The ResNet says itself (min_frames(): one frame -- zero-padded convolutions --

@@ -65,6 +65,15 @@ class Trainer(object):
         self.train_opts, self.model_opts = opts["train"], opts["model"]
         self.data_opts, self.test_opts = opts["data"], opts["test"]
         self.mode = mode
+        # data.python_data_config.voiced_frames (build-owned, absent = off): sliding-window CMN + energy-VAD frame selection between the
+        # front-end and the speech encoder of the test lists (conf/audio_config.yaml:21,25 `apply-cmvn-sliding | select-voiced-frames`;
+        # deeplip_amd/voiced_frames.py).  Parsed before anything touches the GPU; it sits behind the front-end, so it needs test_from_waves.
+        from deeplip_amd.voiced_frames import parse_voiced_frames_section
+        pdc = self.data_opts.get("python_data_config") or {}
+        self.voiced_frames_opts = parse_voiced_frames_section(pdc.get("voiced_frames"))
+        if self.voiced_frames_opts is not None and not pdc.get("test_from_waves", False):
+            raise ValueError("data.python_data_config.voiced_frames needs data.python_data_config.test_from_waves: true (the stage "
+                             "sits between the front-end and the speech encoder)")
         self._extractor = None      # one RaggedExtractor for every list / epoch of this trainer (keeps its recorded plans)
         self._host_cache = {} if self.test_opts.get("cache_host_batches", False) else None
         self._steps = self._enc_pipe = self.buckets = None
@@ -468,16 +477,20 @@ class Trainer(object):
             arch = self.model_opts["audio_config"]["arch"]
             audio_fn = lambda a, l: self.model_audio.extract_embedding(a, lengths=l)[0]                    # train_fusion.py:338
             geom = {}
+            min_frames = 1 if arch == "resnet" else self.model_audio.frames_consumed() + 2
             if self.test_from_waves:
                 fe = self._test_frontend(arch)
+                stage = self._voiced_frames_stage(min_frames)
 
                 def audio_fn(wave, sample_len):  # front-end and encoder in one recorded step; the frame lengths stay on the device
                     feats, n_frames = fe(wave, sample_len)
+                    if stage is not None:        # conf/audio_config.yaml:25: sliding CMN, then the voiced frames alone (a shorter row)
+                        feats, n_frames = stage(feats, n_frames)
                     return self.model_audio.extract_embedding(feats, lengths=n_frames)[0]
                 geom = {"wave_geometry": fe if fe.feat_type == "stft" else (fe.frame_len, fe.frame_step)}
             ex = RaggedExtractor(audio_fn,
                                  lambda v, l: self.model_video.embed(v, lengths=l),                        # :346-348 (mean over T)
-                                 self.device, batch=batch, audio_min_frames=1 if arch == "resnet" else self.model_audio.frames_consumed() + 2,
+                                 self.device, batch=batch, audio_min_frames=min_frames,
                                  max_arena_bytes=int(self.test_opts.get("max_arena_gb", 64)) << 30, **geom)
             self._extractor = (key, ex)
         return self._extractor[1]
@@ -489,16 +502,33 @@ class Trainer(object):
         from deeplip_amd.frontend import AudioFrontend
         o = self.feat_opts
         feat = o.get("feat_type", "mfcc" if arch != "resnet" else "fbank")
+        # voiced_frames with a CMN window: the sliding mean replaces the whole-utterance CMVN (raw features leave the front-end)
+        vf = self.voiced_frames_opts
+        norm = {} if vf is None or vf["cmn_window"] is None else {"normalize": False}
         if feat == "stft":
             fe = AudioFrontend("stft", rate=int(o.get("rate", 16000)), win_len=float(o.get("win_len", 0.025)),
-                               win_shift=float(o.get("win_shift", 0.01)), nfft=int(o.get("nfft", 512)), device=self.device)
+                               win_shift=float(o.get("win_shift", 0.01)), nfft=int(o.get("nfft", 512)), device=self.device, **norm)
             if fe.feat_dim != self.feat_dim:
                 raise ValueError(f"data.python_data_config.test_from_waves: the front-end yields {fe.feat_dim} features, the encoder "
                                  f"takes {self.feat_dim}")
             return fe
         return AudioFrontend(feat, rate=int(o.get("rate", 16000)), win_len=float(o.get("win_len", 0.025)), win_shift=float(o.get("win_shift", 0.01)),
-                             nfft=int(o.get("nfft", 512)), num_cep=self.feat_dim, device=self.device,
+                             nfft=int(o.get("nfft", 512)), num_cep=self.feat_dim, device=self.device, **norm,
                              **({} if feat == "mfcc" else {"num_bin": self.feat_dim}))
+
+    def _voiced_frames_stage(self, min_frames):
+        """The VoicedFrames stage of data.python_data_config.voiced_frames (None: off).  ``min_keep`` defaults to the encoder's minimum
+        frame count: a row the VAD leaves fewer frames keeps all of its frames, which the extractor has checked on the host."""
+        if self.voiced_frames_opts is None:
+            return None
+        from deeplip_amd.voiced_frames import VoicedFrames
+        o = dict(self.voiced_frames_opts)
+        if o["min_keep"] is None:
+            o["min_keep"] = int(min_frames)
+        if o["min_keep"] < min_frames:
+            raise ValueError(f"data.python_data_config.voiced_frames.min_keep: {o['min_keep']} is below the {min_frames} frames the "
+                             "speech encoder needs")
+        return VoicedFrames(**o)
 
     def close(self):
         """Release the recorded plans (extraction arenas, the training pipeline) this trainer holds."""
