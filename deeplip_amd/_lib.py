@@ -109,6 +109,11 @@ DLIP_FIR_TILE, DLIP_FIR_TAP_CHUNK, DLIP_FIR_MAX_TAPS = (HEADER[n] for n in ("DLI
 # sliding-window CMN (deeplip_amd/voiced_frames.py): the kernel's tile of output frames and the longest window it takes
 DLIP_CMN_TILE, DLIP_CMN_MAX_WINDOW = HEADER["DLIP_CMN_TILE"], HEADER["DLIP_CMN_MAX_WINDOW"]
 
+# waveform resampling (deeplip_amd/resample.py): the kernel's longest tile of outputs, its LDS budget in words (polyphase table + a
+# tile's input span) and the largest up / down factor it takes
+DLIP_RESAMPLE_TILE, DLIP_RESAMPLE_LDS_WORDS, DLIP_RESAMPLE_MAX_FACTOR = (HEADER[n] for n in ("DLIP_RESAMPLE_TILE", "DLIP_RESAMPLE_LDS_WORDS",
+                                                                                          "DLIP_RESAMPLE_MAX_FACTOR"))
+
 
 def lib() -> C.CDLL:
     """Load (once) and return the HIP library; raises if it is missing -- never falls back."""

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define DLIP_ABI_VERSION 62
+#define DLIP_ABI_VERSION 63
 #define DLIP_HOST              /* marks a pointer parameter that the CPU dereferences during the call (HOST memory, not device) */
 #define DLIP_LIFT_BCAST 2048
 #define DLIP_LIFT_WORDS 4098   /* a gradient's power-of-two lift: (2^e, 2^-e), then 2^-e repeated DLIP_LIFT_BCAST times (the post_scale
@@ -1221,6 +1221,49 @@ int dlip_vad_energy_select_i32(const float* log_energy, int64_t energy_stride, c
 int dlip_cmn_sliding_select_f32(const float* x, const int32_t* lengths, const int32_t* pos, const int32_t* out_len, float* y, int32_t B,
                                 int32_t C, int32_t NF, int32_t window, int32_t center, int32_t min_window, int32_t norm_vars,
                                 dlip_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 63) WAVEFORM RESAMPLING in front of the audio front-end: the rate conversion of the reference's test loader
+ * (models/audio_models/datasets.py:459-463: `librosa.resample(data, rate, self.rate)` for a file whose rate differs from the configured
+ * one) and the speed perturbation of an x-vector recipe (sox `speed 0.9 / 1.0 / 1.1`, the third augmentation beside reverberation and
+ * additive noise) are one operation, a rational polyphase FIR resampler.  For a row of n samples, a ratio up / down in lowest terms
+ * and a prototype filter h[0 .. L) with centre c = (L - 1) / 2 (integer division):
+ *
+ *     n_out = ceil(n up / down),   y[m] = sum_i x[i] h[c + m down - i up],  0 <= m < n_out,  x = 0 outside [0, n),  h = 0 outside [0, L)
+ *
+ * -- scipy.signal.resample_poly(x, up, down) when h is scipy's default design (deeplip_amd/resample.py: design).  Parity with
+ * librosa's own filter (resampy's `kaiser_best`) is UNPINNED: nothing upstream pins the result.  In polyphase form, with q = c + m down,
+ * r = q mod up, i_hi = q div up and K = ceil(L / up):  y[m] = sum_{j < K} tab[r][j] x[i_hi - j],  tab[r][j] = h[r + j up].
+ *
+ * dlip_wave_resample_f32 (models/audio_models/datasets.py:459-463): wave [B, S] fp32 + `lengths` (device int32 [B], nullable): row b
+ *   holds n = clamp(lengths[b], 1, S) samples (S when NULL); input samples t >= n are never read.  The bank of Q ratios lives on the
+ *   device: `bank` int32 [Q, 4] = (up, down, c, K) per ratio and `tabs` fp32 [Q, tab_stride], ratio q's table at tabs + q tab_stride
+ *   as [up][Kp] words, Kp = K | 1 (the phase stride is odd: lanes on different phases spread over the LDS banks; the pad word is
+ *   never read).  `ratio_idx` int32 [B]: the row's ratio, clamped to Q - 1; < 0: the row passes through, min(n, S_out) samples copied
+ *   bit for bit.  out [B, S_out]: row b gets n_out = min(ceil(n up / down), S_out) samples and exact zeros from n_out to S_out;
+ *   out_lengths[b] = n_out (device int32 [B], never read on the host: a recorded plan replays with new lengths and indices).  Exact
+ *   fp32 on the vector ALUs: one fmaf per product, j ascending from an accumulator of 0.f, the same for every output -- a row has
+ *   the same bits whatever B, S, S_out, Q, `tile` and its neighbours are.  Every index product (m down, n up, q) is formed in 64
+ *   bits.  A 256-lane workgroup owns tiles of `tile` consecutive outputs of one row (256, 512 or DLIP_RESAMPLE_TILE; consecutive
+ *   lanes consecutive outputs) and stages the row's table (`tab_stride` words of LDS) and each tile's input span (`span_words`) in
+ *   LDS.  A descriptor read on the device is not trusted: one with up or down outside [1, DLIP_RESAMPLE_MAX_FACTOR], c < 0, K < 1,
+ *   up Kp > tab_stride or a tile span above span_words makes its rows pass through.  DLIP_EINVAL: tab_stride + span_words >
+ *   DLIP_RESAMPLE_LDS_WORDS (a ratio that does not fit), another tile, B outside [1, 65535], S or S_out outside [1, 2^31 - 1 - tile],
+ *   Q < 1, out == wave.
+ * dlip_wave_resample_fits (host only, no launch): the longest tile (DLIP_RESAMPLE_TILE, 512 or 256) at which the ratio up / down
+ *   with an L-tap prototype fits the kernel's LDS budget -- up Kp + span <= DLIP_RESAMPLE_LDS_WORDS -- or 0 where none does (or up
+ *   or down lies outside [1, DLIP_RESAMPLE_MAX_FACTOR]).  A bank runs at the shortest tile of its ratios.
+ * dlip_wave_resample_span_words (host only): ceil((tile - 1) down / up) + K, the input words a tile of one ratio reaches over;
+ *   `span_words` of a launch is the largest over its bank.  Negative on bad arguments.
+ * ------------------------------------------------------------------------------------------ */
+#define DLIP_RESAMPLE_TILE 1024
+#define DLIP_RESAMPLE_LDS_WORDS 15360
+#define DLIP_RESAMPLE_MAX_FACTOR 4096
+int32_t dlip_wave_resample_fits(int32_t up, int32_t down, int32_t L);
+int64_t dlip_wave_resample_span_words(int32_t up, int32_t down, int32_t K, int32_t tile);
+int dlip_wave_resample_f32(const float* wave, const int32_t* lengths, const float* tabs, const int32_t* bank, const int32_t* ratio_idx,
+                           float* out, int32_t* out_lengths, int32_t B, int64_t S, int64_t S_out, int32_t Q, int32_t tab_stride,
+                           int32_t span_words, int32_t tile, dlip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Step plans.  The reference drives its encoders from a Python loop, one utterance and one torch.nn layer

@@ -91,6 +91,17 @@ def parse_wave_training(data_opts):
     return from_waves, aug
 
 
+def parse_speed_perturb(data_opts):
+    """The keyword arguments of ``deeplip_amd.resample.SpeedPerturb`` a ``data`` section names (``data.speed_perturb``, a sibling of
+    ``data.augment``; host only), or None for an absent one.  Unknown keys and speeds outside [0.5, 2.0] raise ValueError, and so does
+    the section without ``data.train_from_waves``: there is no waveform to perturb on the feature path."""
+    from deeplip_amd.resample import parse_speed_perturb_section
+    sp = parse_speed_perturb_section(data_opts.get("speed_perturb"))
+    if sp is not None and not bool(data_opts.get("train_from_waves", False)):
+        raise ValueError("data.speed_perturb: speed perturbation needs data.train_from_waves: true")
+    return sp
+
+
 class Trainer(object):
     def __init__(self, config="conf/audio_config.yaml", overrides=None, arith_mode=None):
         with open(os.path.join(ROOT, config)) as f:
@@ -106,6 +117,8 @@ class Trainer(object):
         # data.train_from_waves / data.augment (build-owned, off by default): batches of WAVEFORMS, augmented on the device and turned
         # into features by the GPU front-end in front of the unchanged step (_train_epoch).  Parsed before anything touches the GPU.
         self.train_from_waves, self.augment_opts = parse_wave_training(self.data_opts)
+        # data.speed_perturb (build-owned, absent = off): each training row resampled at a drawn speed in front of the augmentation
+        self.speed_opts = parse_speed_perturb(self.data_opts)
         # data.voiced_frames (build-owned, absent = off): sliding-window CMN + energy-VAD frame selection in front of the encoder on the
         # feature-fed ragged test lists -- the `nn_input` / `plda_input` pipe (conf/audio_config.yaml:21,25; deeplip_amd/voiced_frames.py).
         from deeplip_amd.voiced_frames import parse_voiced_frames_section
@@ -164,6 +177,10 @@ class Trainer(object):
         ddist.broadcast_params(list(self.model.parameters()) + list(self.criterion.parameters()))
         self.buckets = None         # built on the first training step (gradient views need the final placement)
         self._wave_fe, self._augment = self._wave_stages(arch, F_) if self.train_from_waves else (None, None)
+        self._speed = None
+        if self.speed_opts is not None:
+            from deeplip_amd.resample import SpeedPerturb
+            self._speed = SpeedPerturb(device=self.device, **self.speed_opts)
 
     def _wave_stages(self, arch, feat_dim):
         """data.train_from_waves: the loaders' feature extraction (models/audio_models/datasets.py:65-83) as the GPU front-end -- MFCC
@@ -264,6 +281,7 @@ class Trainer(object):
             copy_stream = self._copy_stream = torch.cuda.Stream(device=self.device)
         cache = self.__dict__.setdefault("_batch_cache", {})
         n_cache = int(self.train_opts.get("data_cache", 0) or 0)
+        speed_out = self.__dict__.setdefault("_speed_out", {})       # data.speed_perturb: width of a staged cut -> samples of its crop
 
         def stage(i):
             """Batch i -> the device, copies on their own stream behind the running step.  ``train.data_cache: N``: the synthetic
@@ -280,13 +298,18 @@ class Trainer(object):
                     # (feat_type stft: the loader cuts the same samples, datasets.py:113-115, and librosa.stft makes T + 2 frames of them)
                     fl, fs = self._wave_fe.frame_len, self._wave_fe.frame_step
                     Sb = fl + (T - 1) * fs
+                    # data.speed_perturb: the cut is as wide as the fastest speed needs to leave Sb samples (features() cuts there)
+                    Sc = Sb if self._speed is None else self._speed.in_samples(Sb)
                     wl = self.trainset.wave_len(fl, fs)[idx]
-                    wav, _ = self.trainset.waves_padded(idx, S=max(int(wl.max()), Sb), frame_len=fl, frame_step=fs)
-                    s0 = int(rng.integers(0, max(int(wl.min()) - Sb, 0) + 1))
-                    xb = np.ascontiguousarray(wav[:, s0:s0 + Sb])
+                    wav, _ = self.trainset.waves_padded(idx, S=max(int(wl.max()), Sc), frame_len=fl, frame_step=fs)
+                    s0 = int(rng.integers(0, max(int(wl.min()) - Sc, 0) + 1))
+                    xb = np.ascontiguousarray(wav[:, s0:s0 + Sc])
                     if self._augment is not None:
                         p = self._augment.draw([Sb] * bs, rng)
                         extra = tuple(torch.from_numpy(p[n]).pin_memory() for n in ("snr_db", "noise_start", "rir_idx"))
+                    if self._speed is not None:         # drawn last: a run without the section keeps its random stream
+                        speed_out[Sc] = Sb
+                        extra += (torch.from_numpy(self._speed.draw(bs, rng)["speed_idx"]).pin_memory(),)
                 else:
                     t0_ = int(rng.integers(0, Ta - T + 1))
                     xb = np.ascontiguousarray(self.trainset.audio(idx)[:, :, t0_:t0_ + T])   # the batch's one crop (datasets.py:112-115)
@@ -300,8 +323,12 @@ class Trainer(object):
             return x, lab, ev, extra
 
         def features(wave, extra):
-            """data.train_from_waves: augmentation (when configured) and front-end, eager launches in front of the step."""
+            """data.train_from_waves: speed perturbation and augmentation (when configured) and front-end, eager launches in front of
+            the step -- Kaldi's order: the row is resampled to exactly the crop's samples, then reverberated / mixed."""
             with torch.no_grad():
+                if self._speed is not None:
+                    *extra, speed_idx = extra
+                    wave, _ = self._speed(wave, params={"speed_idx": speed_idx}, out_samples=speed_out[wave.shape[1]])
                 if self._augment is not None:
                     wave = self._augment(wave, params=dict(zip(("snr_db", "noise_start", "rir_idx"), extra)))
                 return self._wave_fe(wave)
@@ -340,6 +367,8 @@ class Trainer(object):
                                  "step_mode": (self._steps.mode if recorded else "eager"), "crop_ladder": [int(t) for t in ladder]}
         if self.train_from_waves:
             self.last_epoch_stats.update(from_waves=True, augment=None if self.augment_opts is None else dict(self.augment_opts))
+            if self.speed_opts is not None:
+                self.last_epoch_stats.update(speed_perturb=dict(self.speed_opts))
         self.model.eval()
         return tot / n
 

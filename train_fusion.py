@@ -74,6 +74,19 @@ class Trainer(object):
         if self.voiced_frames_opts is not None and not pdc.get("test_from_waves", False):
             raise ValueError("data.python_data_config.voiced_frames needs data.python_data_config.test_from_waves: true (the stage "
                              "sits between the front-end and the speech encoder)")
+        # data.python_data_config.source_rate (build-owned, absent = off): the test lists' recordings are at this rate and are resampled
+        # to `rate` on the device in front of the front-end (models/audio_models/datasets.py:459-463; deeplip_amd/resample.py)
+        self.source_rate = pdc.get("source_rate")
+        if self.source_rate is not None:
+            if isinstance(self.source_rate, bool) or int(self.source_rate) != self.source_rate or int(self.source_rate) < 1:
+                raise ValueError(f"data.python_data_config.source_rate: {self.source_rate!r} is not a sampling rate")
+            self.source_rate = int(self.source_rate)
+            if not pdc.get("test_from_waves", False):
+                raise ValueError("data.python_data_config.source_rate needs data.python_data_config.test_from_waves: true (there is no "
+                                 "waveform to resample on the feature path)")
+            if self.source_rate == int(pdc.get("rate", 16000)):
+                raise ValueError(f"data.python_data_config.source_rate equals rate ({self.source_rate}): nothing to resample (leave the "
+                                 "key out instead)")
         self._extractor = None      # one RaggedExtractor for every list / epoch of this trainer (keeps its recorded plans)
         self._host_cache = {} if self.test_opts.get("cache_host_batches", False) else None
         self._steps = self._enc_pipe = self.buckets = None
@@ -482,12 +495,22 @@ class Trainer(object):
                 fe = self._test_frontend(arch)
                 stage = self._voiced_frames_stage(min_frames)
 
+                rs = None
+                if self.source_rate is not None:
+                    from deeplip_amd.resample import Resample
+                    rs = Resample(self.source_rate, fe.rate, device=self.device)
+
                 def audio_fn(wave, sample_len):  # front-end and encoder in one recorded step; the frame lengths stay on the device
+                    if rs is not None:           # datasets.py:459-463: the recording's rate -> the configured one (a row of another length)
+                        wave, sample_len = rs(wave, sample_len)
                     feats, n_frames = fe(wave, sample_len)
                     if stage is not None:        # conf/audio_config.yaml:25: sliding CMN, then the voiced frames alone (a shorter row)
                         feats, n_frames = stage(feats, n_frames)
                     return self.model_audio.extract_embedding(feats, lengths=n_frames)[0]
                 geom = {"wave_geometry": fe if fe.feat_type == "stft" else (fe.frame_len, fe.frame_step)}
+                if rs is not None:               # every sample count the extractor handles is at the source rate
+                    from deeplip_amd.resample import ResampledGeometry
+                    geom = {"wave_geometry": ResampledGeometry(fe, rs)}
             ex = RaggedExtractor(audio_fn,
                                  lambda v, l: self.model_video.embed(v, lengths=l),                        # :346-348 (mean over T)
                                  self.device, batch=batch, audio_min_frames=min_frames,
