@@ -66,6 +66,67 @@ class AttentiveStatPooling(nn.Module):
         return self.run_ntc(ops.nct_to_ntc(x.contiguous()))
 
 
+class MultiHeadAttention(nn.Module):
+    """``pooling: multi_head_attention`` (pooling.py:62-71 is an empty TODO class upstream; this is the definition):
+    ``head`` attentive statistics poolings of their own hidden width over the same frames, concatenated -- [B,C,T] -> [B, head 2C] =
+    cat_h [mean_h | std_h], std = sqrt(max(sum alpha x^2 - mean^2, 0) + POOL_EPS).  ``hidden_size``: an int (every head that width) or a
+    sequence of ``head`` widths.  The heads' parameters are stacked: W [S,C], b [1,S], v [S,1], k [1,head] with S the sum of the widths;
+    head h owns rows off_h : off_{h+1} of the first three and column h of k.  hidden = W x + b is ONE GEMM launch for all heads; scores,
+    softmax and the weighted statistics read hidden and x once (dlip_mh_attn_scores_f32 / dlip_mh_attn_stat_pool_f32)."""
+
+    def __init__(self, input_size, head=4, hidden_size=(100, 200, 300, 400)):
+        super().__init__()
+        if isinstance(head, bool) or not isinstance(head, int) or not 1 <= head <= ops.MH_MAX_HEADS:
+            raise ValueError(f"MultiHeadAttention: head is an int in [1, {ops.MH_MAX_HEADS}], got {head!r}")
+        if isinstance(hidden_size, int) and not isinstance(hidden_size, bool):
+            widths = [hidden_size] * head
+        elif isinstance(hidden_size, (list, tuple)) and all(isinstance(w, int) and not isinstance(w, bool) for w in hidden_size):
+            widths = list(hidden_size)
+        else:
+            raise ValueError(f"MultiHeadAttention: hidden_size is an int or a sequence of {head} ints, got {hidden_size!r}")
+        if len(widths) != head:
+            raise ValueError(f"MultiHeadAttention: {len(widths)} hidden sizes for {head} heads")
+        if any(w < 1 for w in widths):
+            raise ValueError(f"MultiHeadAttention: every hidden size must be positive, got {widths}")
+        self.input_size, self.head, self.hidden_sizes = int(input_size), head, tuple(widths)
+        offs = [0]
+        for w in widths:
+            offs.append(offs[-1] + w)
+        self.offsets = tuple(offs)
+        self.hidden_size = S = offs[-1]
+        self.W = nn.Parameter(torch.empty(S, self.input_size))
+        self.b = nn.Parameter(torch.empty(1, S))
+        self.v = nn.Parameter(torch.empty(S, 1))
+        self.k = nn.Parameter(torch.empty(1, head))
+        # (the kernels read the head boundaries on the device; not a part of the state dict)
+        self.register_buffer("head_off", torch.tensor(offs, dtype=torch.int32), persistent=False)
+        with torch.no_grad():       # every head's slice on its own block: a head's init does not depend on its neighbours
+            for h in range(head):
+                lo, hi = offs[h], offs[h + 1]
+                nn.init.xavier_normal_(self.W[lo:hi])
+                nn.init.xavier_normal_(self.b[:, lo:hi])
+                nn.init.xavier_normal_(self.v[lo:hi])
+                nn.init.xavier_normal_(self.k[:, h:h + 1])
+
+    @property
+    def output_size(self) -> int:
+        return self.head * 2 * self.input_size
+
+    def run_ntc(self, x_ntc: Tensor, lengths: Optional[Tensor] = None, len_add: int = 0) -> Tensor:
+        """x [B,T,C] -> [B, head 2C]; ``lengths`` (int32 CUDA [B]): attention and statistics over the first lengths[b] + len_add frames."""
+        from .audio_resnet import POOL_EPS
+        B, T, C_ = x_ntc.shape
+        ops.mh_attn_check(self.head, T, C_)
+        hidden = ops.linear(x_ntc.reshape(B * T, C_), self.W.detach().contiguous(), self.b.detach().reshape(-1).contiguous())
+        alpha = ops.mh_attn_scores(hidden.view(B, T, self.hidden_size), self.v.detach().reshape(-1).contiguous(),
+                                   self.k.detach().reshape(-1).contiguous(), self.head_off, lengths, len_add)
+        return ops.mh_attn_stat_pool(x_ntc, alpha, POOL_EPS, lengths, len_add)
+
+    def forward(self, x):
+        """[B,C,T] (reference layout) -> [B, head 2C]."""
+        return self.run_ntc(ops.nct_to_ntc(x.contiguous()))
+
+
 class TDNN_Block(nn.Module):
     """tdnn.py:7-43.  ``dilation`` is the context list, e.g. [-2,0,2] -> kernel 3, dilation 2."""
 
@@ -154,9 +215,15 @@ class SpeakerEmbNet(nn.Module):
             self.pooling = Marker("AdaptiveAvgPool1d(1)")
         elif opts["pooling"] == "attentive_statistic":
             self.pooling = AttentiveStatPooling(hidden_dim[-1], attention_hidden_size)
+        elif opts["pooling"] == "multi_head_attention":
+            # (build-owned keys: attention_heads, default 4; attention_hidden_size an int -- every head that width -- or a list)
+            ahs = attention_hidden_size if isinstance(attention_hidden_size, int) else list(attention_hidden_size)
+            self.pooling = MultiHeadAttention(hidden_dim[-1], opts.get("attention_heads", 4), ahs)
         else:
             raise NotImplementedError("Other pooling method has not implemented.")
-        if opts["pooling"] in ("statistic", "attentive_statistic"):
+        if opts["pooling"] == "multi_head_attention":
+            self.fc1 = LinearParams(self.pooling.output_size, embedding_dim)
+        elif opts["pooling"] in ("statistic", "attentive_statistic"):
             self.fc1 = LinearParams(hidden_dim[-1] * 2, embedding_dim)
         elif opts["pooling"] == "average":
             self.fc1 = LinearParams(hidden_dim[-1], embedding_dim)
@@ -171,7 +238,7 @@ class SpeakerEmbNet(nn.Module):
         layer i + 1; the last one also scales the pooled statistics that fc1 reads).  Zero unless a calibration set it."""
         if packing.PRECISION != "f16x3":
             return 0
-        if name == f"t{len(self.tdnn) - 1}" and self.pooling_type == "attentive_statistic":
+        if name == f"t{len(self.tdnn) - 1}" and self.pooling_type in ("attentive_statistic", "multi_head_attention"):
             return 0            # (the attention scores are not homogeneous in their input: that tensor stays unscaled)
         return packing.act_exponents(self).get(name, 0)
 
@@ -212,8 +279,9 @@ class SpeakerEmbNet(nn.Module):
         layer differentiable.  Each step is a torch.autograd Function whose forward and backward are dlip_*
         launches (deeplip_amd/autograd.py: TDNNBlockTrainFn, MeanStdPoolFn, LinearFn, BNRowsActFn)."""
         from . import autograd as ag
-        if self.pooling_type not in ("statistic", "attentive_statistic"):
-            raise NotImplementedError("train-mode encoder: pooling 'statistic' (the shipped configs) or 'attentive_statistic'")
+        if self.pooling_type not in ("statistic", "attentive_statistic", "multi_head_attention"):
+            raise NotImplementedError("train-mode encoder: pooling 'statistic' (the shipped configs), 'attentive_statistic' or "
+                                      "'multi_head_attention'")
         if self.input_dim % 4:
             raise ValueError("train-mode encoder: input_dim must be a multiple of 4")
         # [B,T,F] channels-last; F zero-padded to a multiple of 32 when the first layer can then run on the split-fp16 kernels
@@ -233,8 +301,12 @@ class SpeakerEmbNet(nn.Module):
                 hand_over = ag.POOL_BWD_ON_LOAD and h.shape[0] * T_out > ag.BN_SMALL_ROWS and T_out > 1 and blk.bn_first and ag.BN_ON_LOAD
             h, pend = ag.tdnn_block_train(h, blk, pending=pend, defer=(2 if hand_over else True) if (i + 1 < n or last_on_load) else False)
         # (pooling.py:24-26 | :87-107: attention scores, softmax over frames, weighted mean and std, all differentiable)
-        h = (ag.meanstd_pool(h, pending=pend, hand_over=hand_over and pend is not None) if self.pooling_type == "statistic"
-             else ag.attentive_stat_pool(h, self.pooling))
+        if self.pooling_type == "statistic":
+            h = ag.meanstd_pool(h, pending=pend, hand_over=hand_over and pend is not None)
+        elif self.pooling_type == "attentive_statistic":
+            h = ag.attentive_stat_pool(h, self.pooling)
+        else:
+            h = ag.mh_attentive_stat_pool(h, self.pooling)
         x_a = ag.linear(h, self.fc1.weight, self.fc1.bias)
         h = ag.bn_rows_act_train(x_a, self.bn1, LRELU, act_first=not self.bn_first)
         xv = ag.linear(h, self.fc2.weight, self.fc2.bias)

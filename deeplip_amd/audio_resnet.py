@@ -20,6 +20,8 @@ Poolings (k = number of stride-2 stages, F' = ((F - 1) >> k) + 1, 
                           sqrt(unbiased variance + POOL_EPS) -> P = 2 D; needs Wb >= 2
     attentive_statistic   deeplip_amd.audio.AttentiveStatPooling(D, attention_hidden_size) over the frames' D-vectors, with
                           std = sqrt(max(sum alpha x^2 - mean^2, 0) + POOL_EPS) -> P = 2 D
+    multi_head_attention  deeplip_amd.audio.MultiHeadAttention(D, attention_heads, attention_hidden_size): n such poolings of their own
+                          hidden width over the same D-vectors, concatenated -> P = n 2 D
 The last map is post-ReLU: a good share of its features is exactly constant over time (zero), where a standard deviation without a
 floor has a 0/0 gradient.  POOL_EPS under the root is part of the definition, in eval and in training.  D depends on the feature
 dimension, so both statistics poolings need ``feat_dim`` in the options.
@@ -44,7 +46,7 @@ from .video import BasicBlock, _basic_block_train, _cached_pack, downsample_basi
 
 Tensor = torch.Tensor
 POOL_EPS = 1e-5          # under the root of both statistics poolings' standard deviation
-POOLINGS = ("average", "statistic", "attentive_statistic")
+POOLINGS = ("average", "statistic", "attentive_statistic", "multi_head_attention")
 
 
 def attentive_pool_nhwc(h: Tensor, pool, lens: Optional[Tensor] = None, shift: int = 0) -> Tensor:
@@ -64,6 +66,21 @@ def attentive_pool_nhwc_train(h: Tensor, pool) -> Tensor:
     from . import autograd as ag
     N, H, W, C_ = h.shape
     return ag.attentive_stat_pool(ag.swap_axes_nhwc(h).view(N, W, H * C_), pool, POOL_EPS)
+
+
+def mh_attentive_pool_nhwc(h: Tensor, pool, lens: Optional[Tensor] = None, shift: int = 0) -> Tensor:
+    """attentive_pool_nhwc for ``pool`` = deeplip_amd.audio.MultiHeadAttention of input size H C: [N,H,W,C] -> [N, heads 2 H C]."""
+    N, H, W, C_ = h.shape
+    xt = ops.swap_axes_nhwc(h).view(N, W, H * C_)
+    valid = None if lens is None else ops.time_valid_lengths(lens, shift, W)
+    return pool.run_ntc(xt, valid)
+
+
+def mh_attentive_pool_nhwc_train(h: Tensor, pool) -> Tensor:
+    """The same under model.train() (one length per batch)."""
+    from . import autograd as ag
+    N, H, W, C_ = h.shape
+    return ag.mh_attentive_stat_pool(ag.swap_axes_nhwc(h).view(N, W, H * C_), pool)
 
 
 class SpeakerEmbNet(nn.Module):
@@ -113,6 +130,11 @@ class SpeakerEmbNet(nn.Module):
             if self.pooling_type == "attentive_statistic":
                 from .audio import AttentiveStatPooling
                 self.pooling = AttentiveStatPooling(self.pool_dim, int(o.get("attention_hidden_size", 64)))
+            elif self.pooling_type == "multi_head_attention":
+                from .audio import MultiHeadAttention
+                ahs = o.get("attention_hidden_size", 64)
+                self.pooling = MultiHeadAttention(self.pool_dim, o.get("attention_heads", 4), ahs if isinstance(ahs, int) else list(ahs))
+                pooled = self.pooling.output_size
         if self.fc_layers == 1:
             self.fc = LinearParams(pooled, self.embedding_dim)
         else:                                   # ("bn1" is the stem's)
@@ -170,8 +192,10 @@ class SpeakerEmbNet(nn.Module):
             if h.shape[2] < 2:
                 raise ValueError(f"resnet speech encoder: pooling 'statistic' needs utterances of >= {self.min_frames()} frames")
             pooled = ag.statpool_nhwc(h, POOL_EPS)
-        else:
+        elif self.pooling_type == "attentive_statistic":
             pooled = attentive_pool_nhwc_train(h, self.pooling)
+        else:
+            pooled = mh_attentive_pool_nhwc_train(h, self.pooling)
         if self.fc_layers == 1:
             e = ag.linear(pooled, self.fc.weight, self.fc.bias)
             return e, e
@@ -197,7 +221,9 @@ class SpeakerEmbNet(nn.Module):
             if h.shape[2] < 2:
                 raise ValueError(f"resnet speech encoder: pooling 'statistic' needs utterances of >= {self.min_frames()} frames")
             return ops.statpool_nhwc(h, lens, shift, POOL_EPS)
-        return attentive_pool_nhwc(h, self.pooling, lens, shift)
+        if self.pooling_type == "attentive_statistic":
+            return attentive_pool_nhwc(h, self.pooling, lens, shift)
+        return mh_attentive_pool_nhwc(h, self.pooling, lens, shift)
 
     @arith.guarded_eval
     def extract_embedding(self, x: Tensor, lengths=None) -> Tuple[Tensor, Tensor]:

@@ -774,6 +774,59 @@ def attentive_stat_pool(x, pool, eps=0.0):
     return AttnStatPoolFn.apply(x, hidden, pool.v, pool.k, eps)
 
 
+class MHAttnStatPoolFn(Function):
+    """The tail of audio.MultiHeadAttention behind its hidden layer (dlip_mh_attn_scores_f32, dlip_mh_attn_stat_pool_f32 and
+    dlip_mh_attn_stat_pool_bwd_f32): x [B,T,C], hidden [B,T,S] (= x W^T + b of all heads from the differentiable GEMM in
+    front: W, b and the second path into x get their gradients there), v [S,1], k [1,n], head_off int32 [n+1] -> y [B, n 2C].  x is read
+    once in the forward and twice in the backward for all heads; dx arrives summed over the heads."""
+
+    @staticmethod
+    def forward(ctx, x, hidden, v, k, head_off, eps):
+        x, hidden = x.contiguous(), hidden.contiguous()
+        B, T, C_ = x.shape
+        n = k.numel()
+        ops.mh_attn_check(n, T, C_)
+        vv, kk = v.detach().reshape(-1).contiguous(), k.detach().reshape(-1).contiguous()
+        alpha = ops.mh_attn_scores(hidden, vv, kk, head_off)
+        y = ops.mh_attn_stat_pool(x, alpha, eps)
+        ctx.save_for_backward(x, hidden, vv, alpha, y, head_off)
+        ctx.shapes = (tuple(v.shape), tuple(k.shape))
+        ctx.eps = float(eps)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, hidden, vv, alpha, y, head_off = ctx.saved_tensors
+        B, T, C_ = x.shape
+        S, n = hidden.shape[2], alpha.shape[1]
+        dx = torch.empty_like(x)
+        dh = torch.empty_like(hidden)
+        rde = torch.empty_like(hidden)
+        de = torch.empty((B, n, T), device=x.device, dtype=torch.float32)
+        dek = torch.empty((B, n), device=x.device, dtype=torch.float32)
+        check(lib().dlip_mh_attn_stat_pool_bwd_f32(ptr(x), ptr(hidden), ptr(vv), ptr(head_off), ptr(alpha), ptr(y), ptr(dy.contiguous()), None, 0,
+                                                   ctx.eps, ptr(dx), ptr(dh), ptr(rde), ptr(de), ptr(dek), B, T, C_, S, n, stream_handle()),
+              "dlip_mh_attn_stat_pool_bwd_f32")
+        dv = _colsum(rde.view(B * T, S)).view(ctx.shapes[0]) if ctx.needs_input_grad[2] else None
+        dk = _colsum(dek).view(ctx.shapes[1]) if ctx.needs_input_grad[3] else None
+        return dx, dh, dv, dk, None, None
+
+
+def mh_attentive_stat_pool(x, pool):
+    """audio.MultiHeadAttention under model.train() on channels-last x [B,T,C] -> [B, n 2C]: the hidden layer W x + b of ALL heads is the
+    engine's differentiable 1 x 1 convolution (or, for a summed hidden width that is no multiple of 4, the nn.Linear Function -- the
+    choice attentive_stat_pool makes), the rest MHAttnStatPoolFn."""
+    from . import autograd_video as av
+    from .audio_resnet import POOL_EPS
+    B, T, C_ = x.shape
+    S = pool.hidden_size
+    if S % 4:
+        hidden = linear(x.reshape(B * T, C_), pool.W, pool.b.reshape(-1)).reshape(B, T, S)
+    else:
+        hidden = av.conv(x.reshape(B, 1, T, C_), pool.W.view(S, C_, 1, 1), pool.b.reshape(-1)).reshape(B, T, S)
+    return MHAttnStatPoolFn.apply(x, hidden, pool.v, pool.k, pool.head_off, POOL_EPS)
+
+
 class StatPoolNHWCFn(Function):
     """Statistics pooling of the ResNet speech encoder's map [N,H,W,C] -> [N, 2 H C] = cat(mean, sqrt(unbiased variance + eps)) over W
     (dlip_statpool_nhwc_f32 / _bwd_f32): one length per batch, as a training batch has."""

@@ -770,6 +770,55 @@ def attentive_stat_pool_eps(x: Tensor, hidden: Tensor, v: Tensor, k: Tensor, eps
     return y
 
 
+# ---- multi-head attentive statistics pooling (csrc/mh_attn_pool_ops.hip, ABI 64): deeplip_amd.audio.MultiHeadAttention ----
+MH_MAX_HEADS = 8
+MH_LDS_BYTES = 160 * 1024        # 3 n C floats of the backward's first pass
+
+
+def mh_attn_check(n: int, T: int, C: int) -> None:
+    """The limits of the dlip_mh_attn_* entry points as a ValueError that names them (the library answers DLIP_EINVAL)."""
+    if not 1 <= n <= MH_MAX_HEADS:
+        raise ValueError(f"multi-head attentive pooling: 1 <= heads <= {MH_MAX_HEADS}, got {n}")
+    if T > 16000:
+        raise ValueError(f"multi-head attentive pooling: at most 16000 frames, got {T}")
+    if C % 4 or 12 * n * C > MH_LDS_BYTES:
+        raise ValueError(f"multi-head attentive pooling: C % 4 == 0 and 12 heads C <= {MH_LDS_BYTES} bytes of LDS, got heads {n}, C {C}")
+
+
+def mh_attn_scores(hidden: Tensor, v: Tensor, k: Tensor, head_off: Tensor, lengths: Optional[Tensor] = None, len_add: int = 0) -> Tensor:
+    """hidden [B,T,S] (= x W^T + b of all heads), v [S], k [n], head_off int32 CUDA [n+1] (prefix sums of the head widths) -> alpha [B,n,T]:
+    per head the softmax over the first lengths[b] + len_add frames of relu(hidden[..., head]) v[head] + k[h]; zeros behind
+    (dlip_mh_attn_scores_f32)."""
+    for t, nm in ((hidden, "hidden"), (v, "v"), (k, "k")):
+        _req(t, nm)
+    _req(head_off, "head_off", torch.int32)
+    _req(lengths, "lengths", torch.int32)
+    B, T, S = hidden.shape
+    n = k.numel()
+    if head_off is None or head_off.numel() != n + 1 or v.numel() != S or (lengths is not None and lengths.numel() != B):
+        raise ValueError("mh_attn_scores: hidden [B,T,S], v [S], k [n], head_off [n+1], one length per utterance or none")
+    alpha = _empty((B, n, T), hidden.device)
+    check(lib().dlip_mh_attn_scores_f32(ptr(hidden), ptr(v), ptr(k), ptr(head_off), ptr(lengths), int(len_add), ptr(alpha), B, T, S, n,
+                                        stream_handle()), "dlip_mh_attn_scores_f32")
+    return alpha
+
+
+def mh_attn_stat_pool(x: Tensor, alpha: Tensor, eps: float, lengths: Optional[Tensor] = None, len_add: int = 0) -> Tensor:
+    """x [B,T,C], alpha [B,n,T] -> [B, n 2C] = cat over heads of (sum alpha x | sqrt(max(sum alpha x^2 - mean^2, 0) + eps)), x read once
+    for all heads (dlip_mh_attn_stat_pool_f32)."""
+    _req(x, "x")
+    _req(alpha, "alpha")
+    _req(lengths, "lengths", torch.int32)
+    B, T, Cc = x.shape
+    if alpha.dim() != 3 or alpha.shape[0] != B or alpha.shape[2] != T or (lengths is not None and lengths.numel() != B):
+        raise ValueError("mh_attn_stat_pool: x [B,T,C], alpha [B,n,T], one length per utterance or none")
+    n = alpha.shape[1]
+    y = _empty((B, n * 2 * Cc), x.device)
+    check(lib().dlip_mh_attn_stat_pool_f32(ptr(x), ptr(alpha), ptr(lengths), int(len_add), float(eps), ptr(y), B, T, Cc, n, stream_handle()),
+          "dlip_mh_attn_stat_pool_f32")
+    return y
+
+
 def l1_sum(w: Tensor) -> Tensor:
     """sum |w| as a 0-d device tensor (dlip_l1_sum_f32: fp64 accumulation, fixed order)."""
     _req(w, "w")

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define DLIP_ABI_VERSION 63
+#define DLIP_ABI_VERSION 64
 #define DLIP_HOST              /* marks a pointer parameter that the CPU dereferences during the call (HOST memory, not device) */
 #define DLIP_LIFT_BCAST 2048
 #define DLIP_LIFT_WORDS 4098   /* a gradient's power-of-two lift: (2^e, 2^-e), then 2^-e repeated DLIP_LIFT_BCAST times (the post_scale
@@ -1264,6 +1264,46 @@ int64_t dlip_wave_resample_span_words(int32_t up, int32_t down, int32_t K, int32
 int dlip_wave_resample_f32(const float* wave, const int32_t* lengths, const float* tabs, const int32_t* bank, const int32_t* ratio_idx,
                            float* out, int32_t* out_lengths, int32_t B, int64_t S, int64_t S_out, int32_t Q, int32_t tab_stride,
                            int32_t span_words, int32_t tile, dlip_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 64) MULTI-HEAD ATTENTIVE STATISTICS POOLING of both speech encoders (`pooling: multi_head_attention`, conf/audio_config.yaml:71,
+ * conf/fusion_config.yaml:58; upstream `MultiHeadAttention(input_size, head=4, hidden_size=[100,200,300,400])` is an empty TODO class,
+ * models/audio_models/pooling.py:62-71: deeplip_amd/audio.py and DESIGN.md 4h are the definition).  n heads of widths Hd_h, S = sum Hd_h,
+ * head_off = their prefix sums (DEVICE int32 [n + 1], head_off[0] = 0, head_off[n] = S; every value is clamped to [0, S] where it is
+ * read, so a wrong array leaves no row).  x [B,T,C] fp32 channels-last, hidden [B,T,S] = x W^T + b for ALL heads (one GEMM in front),
+ * v [S], k [n].  With L_b = clamp(len[b] + len_add, 0, T) valid frames (len / len_add as dlip_meanstd_pool_f32; NULL: T):
+ *     e[b,h,t]     = relu(hidden[b,t,off_h:off_{h+1}]) . v[off_h:off_{h+1}] + k[h]
+ *     alpha[b,h,:] = softmax over t < L_b of e[b,h,:]            (zeros for t >= L_b)
+ *     m_h[c] = sum_t alpha x,   s_h[c] = sqrt(max(sum_t alpha x^2 - m_h^2, 0) + eps),   y[b] = cat_h [m_h | s_h]       [B, n 2C]
+ * -- the concatenation of n dlip_attentive_stat_pool_eps_f32 results, from one read of hidden and one read of x.  Exact fp32 data, fp64
+ * wherever a sum runs over frames, channels or hidden units, no atomics, the same bits on every run; padding frames of x and hidden are
+ * never loaded.  1 <= n <= 8, T <= 16000, B <= 65535.
+ *
+ * dlip_mh_attn_scores_f32: alpha [B,n,T] from hidden.  One wave per frame reads the row's S floats once (segmented dot products); the
+ *   softmax runs on a (head, utterance) grid with its maximum and its sum reduced across the workgroup.  S >= n.
+ * dlip_mh_attn_stat_pool_f32: y from x and alpha on a (C / 64, utterance) grid like dlip_meanstd_pool_f32's: alpha is staged in LDS 256
+ *   frames at a time, each x element is loaded once and feeds the 2 n accumulators of all heads.  C % 4 == 0, x 16-byte aligned,
+ *   eps > 0, and the backward's LDS bound below (what could not be differentiated is refused here already).
+ * dlip_mh_attn_stat_pool_bwd_f32: the single-head backward above in its floored, centred form per head, with g_q,h = ds_h / (2 s_h):
+ *     dalpha[b,h,t]   = sum_c x (dm_h + g_q,h (x - 2 m_h))                         pass 1 over x, all heads at once
+ *     de [B,n,T]      = alpha (dalpha - sum_t' alpha dalpha)                       (zeros behind L_b);  dek [B,n] = sum_t de (its column
+ *                                                                                    sums over B = dk)
+ *     dx [B,T,C]      = sum_h alpha[b,h,t] (dm_h + 2 g_q,h (x - m_h))              pass 2 over x; summed over heads in fp64, written ONCE,
+ *                                                                                    zeros in padding frames
+ *     dhidden [B,T,S] = de[b,h(j),t] v_j [hidden > 0],   rde [B,T,S] = de[b,h(j),t] relu(hidden)       (column sums of rde = dv)
+ *   Pass 1 runs on a (row range, utterance) grid with dm | g_q | m of every head in LDS: 3 n C floats <= 160 KiB (n = 4: C <= 3412, n = 8:
+ *   C <= 1704; the E-TDNN's C = 1500 at n = 4 takes 70 KiB).  x, y, dy, dx 16-byte aligned, C % 4 == 0, S >= n, eps > 0 (the forward's;
+ *   checked, the std in y holds it).
+ * DLIP_EINVAL before any launch: n outside [1, 8], T > 16000, B > 65535, the LDS bound, C % 4, alignment, a null pointer.
+ * ------------------------------------------------------------------------------------------ */
+int dlip_mh_attn_scores_f32(const float* hidden, const float* v, const float* k, const int32_t* head_off, const int32_t* len,
+                            int32_t len_add, float* alpha, int32_t B, int32_t T, int32_t S, int32_t n, dlip_stream_t stream);
+int dlip_mh_attn_stat_pool_f32(const float* x, const float* alpha, const int32_t* len, int32_t len_add, float eps, float* y, int32_t B,
+                               int32_t T, int32_t C, int32_t n, dlip_stream_t stream);
+int dlip_mh_attn_stat_pool_bwd_f32(const float* x, const float* hidden, const float* v, const int32_t* head_off, const float* alpha,
+                                   const float* y, const float* dy, const int32_t* len, int32_t len_add, float eps, float* dx,
+                                   float* dhidden, float* rde, float* de, float* dek, int32_t B, int32_t T, int32_t C, int32_t S, int32_t n,
+                                   dlip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Step plans.  The reference drives its encoders from a Python loop, one utterance and one torch.nn layer

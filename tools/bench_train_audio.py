@@ -18,12 +18,16 @@ ap.add_argument("--batch", type=int, default=64)
 ap.add_argument("--dim", type=int, default=24)
 ap.add_argument("--steps", type=int, default=5)
 ap.add_argument("--dbg", action="append", default=[], metavar="KEY=VALUE", help="dlip_debug_set(KEY, VALUE) before anything is launched (A/B runs)")
+ap.add_argument("--pooling", default="statistic", help="statistic | attentive_statistic | multi_head_attention (what the option costs a step)")
+ap.add_argument("--attention-hidden", type=int, nargs="+", default=[64], help="attention_hidden_size: one int, or one width per head")
+ap.add_argument("--attention-heads", type=int, default=4)
 a = ap.parse_args()
 for _kv in a.dbg:
     from deeplip_amd import _lib as _dl
     _dl.debug_set(int(_kv.split("=")[0]), int(_kv.split("=")[1]))
 et = {"input_dim": a.dim, "hidden_dim": [512] * 9 + [1500], "context": ETDNN_CONTEXT, "tdnn_layers": 10, "embedding_dim": 512,
-      "pooling": "statistic", "attention_hidden_size": 64, "bn_first": True}
+      "pooling": a.pooling, "attention_hidden_size": a.attention_hidden[0] if len(a.attention_hidden) == 1 else a.attention_hidden,
+      "attention_heads": a.attention_heads, "bn_first": True}
 net = SpeakerEmbNet({"arch": "etdnn", "etdnn": et})
 sd = wg.fill_state_dict({k: tuple(v.shape) for k, v in net.state_dict().items()}, prefix="audio.")
 net.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
