@@ -105,6 +105,8 @@ LIFT_WORDS = HEADER["DLIP_LIFT_WORDS"]
 LIFT_BCAST = HEADER["DLIP_LIFT_BCAST"]
 # waveform augmentation (deeplip_amd/augment.py): the FIR kernel's tile, its tap chunk and the longest room response it takes
 DLIP_FIR_TILE, DLIP_FIR_TAP_CHUNK, DLIP_FIR_MAX_TAPS = (HEADER[n] for n in ("DLIP_FIR_TILE", "DLIP_FIR_TAP_CHUNK", "DLIP_FIR_MAX_TAPS"))
+# ... and the transform route (reverb="fft"): the overlap-save block and the longest room response that route takes
+DLIP_OLS_BLOCK, DLIP_OLS_MAX_TAPS = HEADER["DLIP_OLS_BLOCK"], HEADER["DLIP_OLS_MAX_TAPS"]
 
 # sliding-window CMN (deeplip_amd/voiced_frames.py): the kernel's tile of output frames and the longest window it takes
 DLIP_CMN_TILE, DLIP_CMN_MAX_WINDOW = HEADER["DLIP_CMN_TILE"], HEADER["DLIP_CMN_MAX_WINDOW"]

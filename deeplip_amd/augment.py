@@ -22,13 +22,22 @@ from . import _lib, ops
 from ._lib import check, lib, ptr, stream_handle
 
 SNR_PASS = 9999                     # preprocess.py:168: the level that means "leave the signal alone"
-AUGMENT_KEYS = ("snr_levels", "p_reverb", "keep_power", "normalize", "max_taps")
+AUGMENT_KEYS = ("snr_levels", "p_reverb", "keep_power", "normalize", "max_taps", "reverb")
+REVERB_ROUTES = ("fir", "fft")      # the direct FIR kernel | the partitioned overlap-save transform route (4i)
+
+
+def reverb_cap(route: str) -> int:
+    """The longest room response the reverberation route takes; an unknown route raises ValueError."""
+    if route not in REVERB_ROUTES:
+        raise ValueError(f"reverb: expected one of {list(REVERB_ROUTES)}, got {route!r}")
+    return _lib.DLIP_FIR_MAX_TAPS if route == "fir" else _lib.DLIP_OLS_MAX_TAPS
 
 
 def parse_augment_section(section) -> Optional[dict]:
     """The keyword arguments of ``WaveAugment`` an ``augment:`` config section names (``data.augment`` of conf/audio_config.yaml), or
-    None for an absent / empty one.  Unknown keys, a ``p_reverb`` outside [0, 1], an empty ``snr_levels`` and a ``max_taps`` outside
-    [1, DLIP_FIR_MAX_TAPS] raise ValueError."""
+    None for an absent / empty one.  Unknown keys, a ``p_reverb`` outside [0, 1], an empty ``snr_levels``, a ``reverb`` other than
+    ``fir`` / ``fft`` and a ``max_taps`` outside [1, the cap of the chosen route] raise ValueError.  ``reverb`` appears in the result
+    only when the section names it."""
     if section is None or section is False:
         return None
     if not isinstance(section, dict):
@@ -48,10 +57,16 @@ def parse_augment_section(section) -> Optional[dict]:
     out["p_reverb"] = p
     out["keep_power"] = bool(section.get("keep_power", True))
     out["normalize"] = bool(section.get("normalize", False))
-    taps = int(section.get("max_taps", _lib.DLIP_FIR_MAX_TAPS))
-    if not 1 <= taps <= _lib.DLIP_FIR_MAX_TAPS:
-        raise ValueError(f"augment.max_taps: {taps} is outside [1, {_lib.DLIP_FIR_MAX_TAPS}] (the FIR kernel's cap)")
+    route = section.get("reverb", "fir")
+    if route not in REVERB_ROUTES:
+        raise ValueError(f"augment.reverb: expected one of {list(REVERB_ROUTES)}, got {route!r}")
+    cap = reverb_cap(route)
+    taps = int(section.get("max_taps", cap))
+    if not 1 <= taps <= cap:
+        raise ValueError(f"augment.max_taps: {taps} is outside [1, {cap}] (the cap of reverb: {route})")
     out["max_taps"] = taps
+    if "reverb" in section:
+        out["reverb"] = route
     return out
 
 
@@ -61,16 +76,25 @@ class WaveAugment:
     responses longer than ``max_taps`` are truncated (with a warning) and their peak is taken inside the kept part; ``rir_peaks``
     names the direct-path taps explicitly.
     ``snr_levels``: the levels (dB) one is drawn from per row, 9999 = no noise.  ``p_reverb``: the probability a row is reverberated.
-    ``keep_power``: the reverberated row is rescaled to the power it had.  ``normalize``: (x - mean) / std per row at the end."""
+    ``keep_power``: the reverberated row is rescaled to the power it had.  ``normalize``: (x - mean) / std per row at the end.
+    ``reverb``: the route that convolves -- ``"fir"``, the direct kernel (responses up to DLIP_FIR_MAX_TAPS, cost linear in their
+    length), or ``"fft"``, the partitioned overlap-save route (up to DLIP_OLS_MAX_TAPS; DESIGN.md section 4i says from which length
+    on it is the faster one).  The two agree to fp32 rounding, not bit for bit, so the choice is the caller's and never depends on
+    a response's length.  ``max_taps`` defaults to the cap of the chosen route."""
 
     def __init__(self, noise=None, snr_levels: Sequence[float] = (-5, 0, 5, 10, 15, 20, SNR_PASS), rirs=None, p_reverb: float = 0.0,
-                 keep_power: bool = True, normalize: bool = False, max_taps: int = 8192, device="cuda", rir_peaks=None):
+                 keep_power: bool = True, normalize: bool = False, max_taps: Optional[int] = None, device="cuda", rir_peaks=None,
+                 reverb: str = "fir"):
         if len(snr_levels) == 0:
             raise ValueError("WaveAugment: snr_levels is empty")
         if not 0.0 <= float(p_reverb) <= 1.0:
             raise ValueError(f"WaveAugment: p_reverb {p_reverb} is not a probability")
-        if not 1 <= int(max_taps) <= _lib.DLIP_FIR_MAX_TAPS:
-            raise ValueError(f"WaveAugment: max_taps must lie in [1, {_lib.DLIP_FIR_MAX_TAPS}] (the FIR kernel's cap), got {max_taps}")
+        cap = reverb_cap(reverb)
+        if max_taps is None:
+            max_taps = cap
+        if not 1 <= int(max_taps) <= cap:
+            raise ValueError(f"WaveAugment: max_taps must lie in [1, {cap}] (the cap of reverb={reverb!r}), got {max_taps}")
+        self.reverb = reverb
         self.snr_levels = tuple(float(v) for v in snr_levels)
         self.p_reverb, self.keep_power, self.normalize, self.max_taps = float(p_reverb), bool(keep_power), bool(normalize), int(max_taps)
         self.device = torch.device(device)
@@ -113,6 +137,18 @@ class WaveAugment:
         if self._dev is None:
             up = lambda a: None if a is None else torch.from_numpy(a).to(self.device)
             self._dev = {k: up(getattr(self, k)) for k in ("noise", "rir", "rir_len", "rir_peak")}
+            self._dev["spectra"] = None
+            if self.reverb == "fft" and self.rir is not None:      # the responses' partition spectra: one launch, once per bank
+                R, Lmax = self.rir.shape
+                nbytes = int(lib().dlip_wave_rir_spectra_bytes(R, Lmax))
+                if nbytes <= 0:
+                    raise _lib.DeepLipHipError(f"dlip_wave_rir_spectra_bytes refused R = {R}, Lmax = {Lmax}")
+                sp = torch.empty(nbytes // 4, dtype=torch.float32, device=self.device)
+                with torch.cuda.device(self.device):
+                    check(lib().dlip_wave_rir_spectra_f32(ptr(self._dev["rir"]), ptr(self._dev["rir_len"]), ptr(sp), nbytes, R, Lmax,
+                                                          stream_handle()), "dlip_wave_rir_spectra_f32")
+                    torch.cuda.current_stream().synchronize()      # as the copies above: whichever stream calls later finds them made
+                self._dev["spectra"] = sp
         return self._dev
 
     # ------------------------------------------------------------------------------------------------------------ host: the draws
@@ -163,7 +199,14 @@ class WaveAugment:
         nbytes = int(lib().dlip_wave_reverb_workspace_bytes(B, S))
         if nbytes <= 0:
             raise _lib.DeepLipHipError(f"dlip_wave_reverb_workspace_bytes refused B = {B}, S = {S}")
-        ws = ops._empty((nbytes // 8,), dev, torch.float64)
+        if self.reverb == "fft" and d["rir"] is not None:              # the power partials and, behind them, the input spectra
+            nbytes_fft = int(lib().dlip_wave_reverb_fft_workspace_bytes(B, S, d["rir"].shape[1]))
+            if nbytes_fft < nbytes:
+                raise _lib.DeepLipHipError(f"dlip_wave_reverb_fft_workspace_bytes refused B = {B}, S = {S}, Lmax = {d['rir'].shape[1]}")
+            ws_fft = ops._empty((nbytes_fft // 8,), dev, torch.float64)
+            ws = ws_fft[:nbytes // 8]
+        else:
+            ws = ops._empty((nbytes // 8,), dev, torch.float64)
         cur = wave
         if d["rir"] is None and isinstance(params.get("rir_idx"), np.ndarray) and (params["rir_idx"] >= 0).any():
             raise ValueError("WaveAugment: params ask for reverberation but no rirs were given")
@@ -171,8 +214,13 @@ class WaveAugment:
         if ridx is not None:
             y = ops._empty((B, S), dev)
             R, Lmax = d["rir"].shape
-            check(lib().dlip_wave_reverb_f32(ptr(cur), ptr(lens), ptr(d["rir"]), ptr(d["rir_len"]), ptr(d["rir_peak"]), ptr(ridx), ptr(y),
-                                             ptr(ws), nbytes, B, S, R, Lmax, int(self.keep_power), stream_handle()), "dlip_wave_reverb_f32")
+            if self.reverb == "fft":
+                check(lib().dlip_wave_reverb_fft_f32(ptr(cur), ptr(lens), ptr(d["spectra"]), ptr(d["rir_len"]), ptr(d["rir_peak"]), ptr(ridx),
+                                                     ptr(y), ptr(ws_fft), nbytes_fft, B, S, R, Lmax, int(self.keep_power), stream_handle()),
+                      "dlip_wave_reverb_fft_f32")
+            else:
+                check(lib().dlip_wave_reverb_f32(ptr(cur), ptr(lens), ptr(d["rir"]), ptr(d["rir_len"]), ptr(d["rir_peak"]), ptr(ridx), ptr(y),
+                                                 ptr(ws), nbytes, B, S, R, Lmax, int(self.keep_power), stream_handle()), "dlip_wave_reverb_f32")
             cur = y
         snr = self._param(params, "snr_db", torch.float32, B, dev)
         if snr is not None and d["noise"] is not None:

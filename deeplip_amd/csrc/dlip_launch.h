@@ -24,6 +24,11 @@ inline bool dlip_aligned128(const P*... p) { return dlip_aligned<128>(p...); }
 
 inline hipStream_t dlip_hip_stream(dlip_stream_t stream) { return static_cast<hipStream_t>(stream); }
 
+// keep_power of the reverberation routes (wave_augment_ops.hip): y *= sqrt(Px / Py) per reverberated row, the sums taken per
+// DLIP_FIR_TILE tile in the FIR kernel's order; `part` holds two doubles per (row, tile).  Called by wave_reverb_fft_ops.hip.
+__attribute__((visibility("hidden"))) void dlip_wave_reverb_keep_power(const float* x, const int32_t* lengths, const int32_t* rir_idx,
+                                                                       float* y, double* part, int B, int S, hipStream_t stream);
+
 // Ragged batches through stride-2 stages (the ResNet speech encoder): utterance frames valid on a W-frame time axis that `shift`
 // stride-2 convolutions (kernel 3, padding 1: L -> (L - 1) / 2 + 1) stand in front of, from the INPUT length `len` -- clamped to
 // [1, W << shift], so the result lies in [1, W] whatever the vector holds.  Device code of layout_ops / pool_ops.

@@ -183,6 +183,37 @@ __global__ __launch_bounds__(kThreads) void reverb_gain_kernel(float* __restrict
   }
 }
 
+// The FIR kernel's power partials for a y that another kernel made (the transform route, wave_reverb_fft_ops.hip): the same lanes own
+// the same samples and the sums meet in the same order, so keep_power is one computation whichever route convolved.
+__global__ __launch_bounds__(kThreads) void reverb_power_kernel(const float* __restrict__ x, const int32_t* __restrict__ lengths,
+                                                                 const int32_t* __restrict__ rir_idx, const float* __restrict__ y,
+                                                                 double* __restrict__ part, int S, int ntiles) {
+  __shared__ double red[8];
+  const long long b = blockIdx.y;
+  const int t0 = (int)blockIdx.x * kTile;
+  const int n = row_len(lengths, b, S);
+  if (t0 >= n || rir_idx[b] < 0) return;
+  const float* xb = x + b * S;
+  const float* yb = y + b * S;
+  const int lb = (int)threadIdx.x * kPer;
+  double px = 0.0, py = 0.0;
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {
+    const int t = t0 + lb + j;
+    if (t < n) {
+      const double xv = (double)xb[t], yv = (double)yb[t];
+      px += xv * xv;
+      py += yv * yv;
+    }
+  }
+  block_sum2(px, py, red);
+  if (threadIdx.x == 0) {
+    double* p = part + (b * ntiles + blockIdx.x) * 2;
+    p[0] = px;
+    p[1] = py;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------------------------------ noise
 // The slice of row b: bank[st .. st + n), st = clamp(start[b], 0, max(bank_len - n, 0)); words past the bank's end read as zero.
 __device__ __forceinline__ long long noise_start(const int64_t* __restrict__ start, long long b, long long bank_len, int n) {
@@ -348,6 +379,14 @@ extern "C" int dlip_wave_reverb_f32(const float* x, const int32_t* lengths, cons
   if (keep_power)
     hipLaunchKernelGGL(reverb_gain_kernel, dim3(nt, B), dim3(kThreads), 0, dlip_hip_stream(stream), y, lengths, rir_idx, part, S, nt);
   return dlip_launch_status();
+}
+
+// keep_power behind the transform route (declared in dlip_launch.h): the partials of (x, y), then the gain.  Two launches.
+void dlip_wave_reverb_keep_power(const float* x, const int32_t* lengths, const int32_t* rir_idx, float* y, double* part, int B, int S,
+                                 hipStream_t stream) {
+  const int nt = tiles_of(S);
+  hipLaunchKernelGGL(reverb_power_kernel, dim3(nt, B), dim3(kThreads), 0, stream, x, lengths, rir_idx, y, part, S, nt);
+  hipLaunchKernelGGL(reverb_gain_kernel, dim3(nt, B), dim3(kThreads), 0, stream, y, lengths, rir_idx, part, S, nt);
 }
 
 extern "C" int dlip_wave_add_noise_f32(const float* y, const int32_t* lengths, const float* bank, int64_t bank_len,

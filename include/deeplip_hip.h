@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define DLIP_ABI_VERSION 64
+#define DLIP_ABI_VERSION 65
 #define DLIP_HOST              /* marks a pointer parameter that the CPU dereferences during the call (HOST memory, not device) */
 #define DLIP_LIFT_BCAST 2048
 #define DLIP_LIFT_WORDS 4098   /* a gradient's power-of-two lift: (2^e, 2^-e), then 2^-e repeated DLIP_LIFT_BCAST times (the post_scale
@@ -1306,7 +1306,40 @@ int dlip_mh_attn_stat_pool_bwd_f32(const float* x, const float* hidden, const fl
                                    dlip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
- * Step plans.  The reference drives its encoders from a Python loop, one utterance and one torch.nn layer
+ * (ABI 65) REVERBERATION WITH LONG ROOM RESPONSES: the definition of dlip_wave_reverb_f32 (ABI 60) -- y[t] = sum_k h[k] x[t + d - k],
+ * 0 <= t < n, x zero outside [0, n), d the tap of the direct path, optional keep_power, zero tail, pass-through rows bit for bit --
+ * computed as a uniformly partitioned overlap-save convolution in fp32: P = DLIP_OLS_BLOCK new samples per step, transform length
+ * 2P, partition boundaries anchored at sample 0 of the row and tap 0 of the response, so a row's bits depend on (x[:n], h, d) alone,
+ * never on B, S, Lmax or the neighbours.  Responses up to DLIP_OLS_MAX_TAPS (4.1 s at 16 kHz); cost per output block proportional to
+ * the response's own ceil(len / P) partitions.  The two routes agree to fp32 rounding, not bit for bit: the caller chooses one.
+ *
+ * dlip_wave_rir_spectra_bytes (train_audio.py:454; host only): bytes of the spectra block of a bank rir [R, Lmax] -- the twiddle table
+ *   (P complex words) and P complex words per (response, partition of Lmax); negative on bad sizes (Lmax > DLIP_OLS_MAX_TAPS).
+ * dlip_wave_rir_spectra_f32 (train_audio.py:454: the room responses of the 'reverb' kind, transformed once per bank): fills `spectra`
+ *   (8-byte aligned, caller-owned) from rir [R, Lmax] and rir_len (clamped to [1, Lmax] on the device); partition p of response r =
+ *   the half spectrum of h_r[pP : (p + 1)P) zero-padded to 2P, bins 0 and P sharing one word, scaled by 1 / P.  One launch.
+ * dlip_wave_reverb_fft_workspace_bytes (train_audio.py:454; host only): bytes of the caller-owned workspace of the call below: the
+ *   power partials of dlip_wave_reverb_workspace_bytes(B, S), then the input spectra, P complex words per (row, block of S);
+ *   negative on bad sizes.
+ * dlip_wave_reverb_fft_f32 (train_audio.py:454: the 'reverb' kind, as dlip_wave_reverb_f32): lengths, rir_idx, rir_len and rir_peak are
+ *   clamped on the device exactly as there.  Launches: the input spectra of the reverberated rows (samples t >= n are never read);
+ *   one workgroup per (row, output block) accumulates X[k - p] H[p] over the response's own partitions, p ascending, inverts in LDS
+ *   and writes y[j - d] and the zero tail; keep_power != 0 adds the FIR route's own power sums (per DLIP_FIR_TILE tile, same order)
+ *   and its gain launch: 2 launches, 4 with keep_power.  No atomics.  DLIP_EINVAL before any launch for Lmax > DLIP_OLS_MAX_TAPS,
+ *   null pointers, y == x, a short or misaligned (8-byte) workspace or spectra block; B <= 65535.
+ * ------------------------------------------------------------------------------------------ */
+#define DLIP_OLS_BLOCK 2048
+#define DLIP_OLS_MAX_TAPS 65536
+int64_t dlip_wave_rir_spectra_bytes(int32_t R, int32_t Lmax);
+int dlip_wave_rir_spectra_f32(const float* rir, const int32_t* rir_len, void* spectra, int64_t spectra_bytes, int32_t R, int32_t Lmax,
+                              dlip_stream_t stream);
+int64_t dlip_wave_reverb_fft_workspace_bytes(int64_t B, int64_t S, int32_t Lmax);
+int dlip_wave_reverb_fft_f32(const float* x, const int32_t* lengths, const void* spectra, const int32_t* rir_len,
+                             const int32_t* rir_peak, const int32_t* rir_idx, float* y, void* workspace, int64_t workspace_bytes, int32_t B,
+                             int32_t S, int32_t R, int32_t Lmax, int32_t keep_power, dlip_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Step plans. The reference drives its encoders from a Python loop, one utterance and one torch.nn layer
  * at a time (train_fusion.py:338-358 extraction, :262-293 training step); here a step is ~45 short kernels
  * and the host must not sit between them.  A plan records every dlip_* launch made on `stream` between
  * dlip_plan_begin and dlip_plan_end (HIP stream capture, thread-local mode -> an instantiated hipGraph) and
