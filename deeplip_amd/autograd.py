@@ -285,6 +285,83 @@ def aam_margin(logits, labels, margin, easy=False):
     return AAMMarginFn.apply(logits, labels.contiguous(), margin, easy)
 
 
+class RowNormFn(Function):
+    """r = max(|x_u|, eps) per row -- the norm L2NormalizeFn divides by, the same bits -- and dx = dr x / r (zeros on a row at the clamp)."""
+
+    @staticmethod
+    def forward(ctx, x, eps):
+        x = x.contiguous()
+        r = ops.row_norm(x, eps)
+        ctx.save_for_backward(x, r)
+        ctx.eps = eps
+        return r
+
+    @staticmethod
+    def backward(ctx, dr):
+        x, r = ctx.saved_tensors
+        dx = torch.empty_like(x)
+        check(lib().dlip_row_norm_bwd_f32(ptr(x), ptr(r), ptr(dr.contiguous()), ptr(dx), x.shape[0], x.shape[1], ctx.eps, stream_handle()),
+              "dlip_row_norm_bwd_f32")
+        return dx, None
+
+
+def row_norm(x, eps=1e-12):
+    return RowNormFn.apply(x, eps)
+
+
+class ASoftmaxLogitsFn(Function):
+    """The A-Softmax logits (deeplip_amd.loss.ASoftmax; dlip_asoftmax_logits_f32): z = r c off the target, r (lambda c + psi(c)) / (1 + lambda)
+    on it.  ``lam`` is the criterion's 1-element device buffer: both launches read it through the pointer, it gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, r, labels, lam, m, r_floor):
+        logits, r = logits.contiguous(), r.contiguous()
+        ctx.save_for_backward(logits, r, labels, lam)
+        ctx.cfg = (int(m), float(r_floor))
+        return ops.asoftmax_logits(logits, r, labels, lam, m, r_floor)
+
+    @staticmethod
+    def backward(ctx, dz):
+        logits, r, labels, lam = ctx.saved_tensors
+        m, r_floor = ctx.cfg
+        dc = torch.empty_like(logits)
+        dr = torch.empty_like(r)
+        check(lib().dlip_asoftmax_logits_f32(ptr(logits), ptr(r), ptr(labels), ptr(lam), ptr(dz.contiguous()), ptr(dc), ptr(dr),
+                                             logits.shape[0], logits.shape[1], m, r_floor, 1, stream_handle()), "dlip_asoftmax_logits_f32")
+        return dc, dr, None, None, None, None
+
+
+def asoftmax_logits(logits, r, labels, lam, m, r_floor=1e-12):
+    return ASoftmaxLogitsFn.apply(logits, r, labels.contiguous(), lam, int(m), float(r_floor))
+
+
+class ContrastiveLossFn(Function):
+    """Contrastive (deeplip_amd.loss) with the pairs selected on the device: forward = dlip_contrastive_loss_f32, backward =
+    dlip_triplet_loss_bwd_f32 on its signed weights (deeplip_amd/pairs.py).  Returns (loss, n_pairs): 0-dim fp32 and 0-dim int32 device
+    tensors, nothing is read back."""
+
+    @staticmethod
+    def forward(ctx, embeddings, labels, margin, mode):
+        from . import pairs as pr
+        x = embeddings.contiguous()
+        p = pr.loss_forward(x, labels, margin, mode)
+        ctx.save_for_backward(x, p.g, p.rownorm, p.w, p.n)
+        ctx.mark_non_differentiable(p.n)
+        return p.loss, p.n
+
+    @staticmethod
+    def backward(ctx, dloss, _dn):
+        from . import pairs as pr
+        x, g, rownorm, w, n = ctx.saved_tensors
+        dl = dloss.reshape(1).to(torch.float32).contiguous()       # stays on the device: no host read-back per step
+        dx = pr.loss_backward(x, pr.PairLoss(None, n, g, rownorm, w, None), dl)
+        return dx, None, None, None
+
+
+def contrastive_loss(embeddings, labels, margin, mode):
+    return ContrastiveLossFn.apply(embeddings, labels, float(margin), int(mode))
+
+
 def linear(x, w, b=None):
     return LinearFn.apply(x, w, b)
 

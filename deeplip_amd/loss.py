@@ -1,5 +1,6 @@
 """Speaker-classification criteria on the HIP engine: mirror of the reference's
-``models/audio_models/loss.py`` (LMCL = CosFace / AM-softmax, CrossEntropy, OnlineTriplet).
+``models/audio_models/loss.py`` (LMCL = CosFace / AM-softmax, CrossEntropy, OnlineTriplet), plus the build's own definitions of the
+three classes upstream leaves empty (AAMSoftmax, ASoftmax, Contrastive).
 
 ``forward(embeddings, labels) -> (loss, logits)`` exactly as the reference; both values come from
 ``dlip_logits_argmax_f32`` + ``dlip_margin_ce_loss_f32``.  ``predict`` adds the first-max argmax
@@ -138,16 +139,96 @@ class OnlineTriplet(nn.Module):
         return loss, n
 
 
-class _Stub(nn.Module):
-    """ASoftmax / AAMSoftmax / Contrastive are empty TODO stubs upstream (loss.py:53-75)."""
+class ASoftmax(nn.Module):
+    """A-Softmax (SphereFace, Liu et al. 2017).  Upstream `ASoftmax` is an empty TODO stub (loss.py:53-59) that the config comment
+    nevertheless lists (conf/audio_config.yaml:130), so the definition is the build's own (parity unpinned) behind the
+    interface of the reference's LMCL: ``forward(embeddings, labels) -> (loss, cosine logits)``.
 
-    def forward(self, x):
-        pass
+    With c_bj = cos(theta_bj) the cosine logits and r_b = |x_b| (clamped below as ``l2_normalize`` clamps it) the cross-entropy sees
+    z_bj = r_b c_bj off the target and z_by = r_b (lambda c + psi(c)) / (1 + lambda) on it, psi(c) = (-1)^k T_m(c) - 2k, T_m the
+    Chebyshev polynomial (c, 2c^2 - 1, 4c^3 - 3c, 8c^4 - 8c^2 + 1 for m = 1 .. 4), k = #{ j in 1 .. m-1 : c <= cos(j pi / m) }, c
+    clamped to [-1, 1].  loss = mean_b CE(z_b, y_b): no scale ``s``, no L1 term.  psi is continuous and psi' vanishes at every
+    branch point, so no case is fragile.
+
+    lambda lives in a 1-element fp32 device buffer (non-persistent: the state dict holds ``weights`` alone, as LMCL's) that the
+    kernels read through the pointer, so a recorded step follows the schedule without being recorded again.  ``anneal(it=None)``
+    writes max(lambda_min, lambda_base (1 + gamma it)^(-power)) into it on the current stream (call it outside a capture);
+    ``it=None`` advances the criterion's own counter and uses the new count (SphereFace's order: the first step runs at it = 1).
+    ``forward`` never changes lambda; ``set_lambda(value)`` fixes it by hand.  ``margin`` = m (the trainer keys recorded steps by it)."""
+
+    def __init__(self, embedding_size, num_classes, m=4, lambda_min=5.0, lambda_base=1000.0, gamma=0.12, power=1.0):
+        super().__init__()
+        if isinstance(m, bool) or m not in (1, 2, 3, 4):
+            raise ValueError(f"ASoftmax: m = {m!r}, supported 1, 2, 3, 4")
+        self.embedding_size, self.num_classes = embedding_size, num_classes
+        self.m = self.margin = int(m)
+        self.lambda_min, self.lambda_base, self.gamma, self.power = float(lambda_min), float(lambda_base), float(gamma), float(power)
+        self.it = 0
+        self.weights = nn.Parameter(torch.Tensor(num_classes, embedding_size))
+        nn.init.kaiming_normal_(self.weights)
+        self.register_buffer("lam", torch.full((1,), self.schedule(0), dtype=torch.float32), persistent=False)
+
+    def schedule(self, it) -> float:
+        """lambda at iteration ``it``: max(lambda_min, lambda_base (1 + gamma it)^(-power))."""
+        return max(self.lambda_min, self.lambda_base * (1.0 + self.gamma * float(it)) ** (-self.power))
+
+    def anneal(self, it=None) -> float:
+        if it is None:
+            self.it += 1
+            it = self.it
+        return self.set_lambda(self.schedule(it))
+
+    def set_lambda(self, value) -> float:
+        self.lam.fill_(float(value))         # one fill launch on the current stream: nothing is read back
+        return float(value)
+
+    def predict(self, embeddings, labels=None):
+        w = self.weights.detach().contiguous()
+        x = embeddings.detach().contiguous()
+        logits, amax = ops.logits_argmax(x, w, cosine=True)
+        loss = None
+        if labels is not None:
+            lab = labels.to(torch.int64).contiguous()
+            loss = ops.margin_ce_loss(ops.asoftmax_logits(logits, ops.row_norm(x), lab, self.lam, self.m), lab, 1.0, 0.0)
+        return loss, logits, amax
+
+    def forward(self, embeddings, labels):
+        if torch.is_grad_enabled() and (self.weights.requires_grad or embeddings.requires_grad):
+            from . import autograd as ag
+            logits = ag.linear(ag.l2_normalize(embeddings), ag.l2_normalize(self.weights))
+            lab = labels.to(torch.int64)
+            z = ag.asoftmax_logits(logits, ag.row_norm(embeddings), lab, self.lam, self.m)
+            return ag.margin_ce_loss(z, lab, 1.0, 0.0), logits
+        loss, logits, _ = self.predict(embeddings, labels)
+        return loss, logits
 
 
-class ASoftmax(_Stub):
-    pass
+class Contrastive(nn.Module):
+    """Online contrastive loss on cosines, the pairs selected on the device.  Upstream `Contrastive` is an empty TODO stub
+    (loss.py:69-75) that the config comment lists (conf/audio_config.yaml:130); the definition is the build's own (parity unpinned;
+    DESIGN.md 3g): the cosine form of adambielski/siamese-triplet's ``OnlineContrastiveLoss(margin, pair_selector)`` -- the source of
+    the reference's triplet selectors --, i.e. torch.nn.CosineEmbeddingLoss on the selected pairs: a positive pair (one label) costs
+    1 - cos_ij, a negative pair relu(cos_ij - margin), cos_ij = x_i.x_j / (max(|x_i|, 1e-8) max(|x_j|, 1e-8)); ``loss`` is the mean
+    over all selected pairs (inactive negatives count in the denominator).
 
+    ``forward(embeddings, labels) -> (loss, n_pairs)``: 0-dim fp32 and int32 device tensors with OnlineTriplet's contract -- nothing is
+    read back, so a recorded training step can contain the criterion (``int(n_pairs)`` synchronises, keep it out of a step).  Zero
+    selected pairs: loss = 0, n_pairs = 0, an all-zero gradient.  ``pair_selector``: one of deeplip_amd.pairs' selectors.  No
+    parameters.  CPU tensors are refused (DeepLipHipError); E % 4 != 0, B > 1024 and float labels raise ValueError before any launch."""
 
-class Contrastive(_Stub):
-    pass
+    def __init__(self, margin, pair_selector):
+        super().__init__()
+        from . import pairs as pr
+        if not isinstance(pair_selector, pr.PairSelector) or pair_selector.mode is None:
+            raise TypeError("Contrastive: pair_selector must be one of deeplip_amd.pairs' selectors (AllPairSelector, "
+                            "HardNegativePairSelector)")
+        self.margin = margin
+        self.pair_selector = pair_selector
+
+    def forward(self, embeddings, labels):
+        from . import autograd as ag, pairs as pr, triplet as tp
+        tp.check_inputs(embeddings, labels)
+        if torch.is_grad_enabled() and embeddings.requires_grad:
+            return ag.contrastive_loss(embeddings, labels, self.margin, self.pair_selector.mode)
+        p = pr.loss_forward(embeddings, labels, float(self.margin), self.pair_selector.mode)
+        return p.loss, p.n

@@ -1050,6 +1050,24 @@ def margin_ce_loss(logits: Tensor, labels: Tensor, scale: float = 1.0, margin: f
     return loss[0]
 
 
+def row_norm(x: Tensor, eps: float = 1e-12) -> Tensor:
+    """r [U] = max(|x_u|, eps): the norm ``l2_normalize`` divides by, the same bits."""
+    _req(x, "x")
+    r = _empty((x.shape[0],), x.device)
+    check(lib().dlip_row_norm_f32(ptr(x), ptr(r), x.shape[0], x.shape[1], eps, stream_handle()), "dlip_row_norm_f32")
+    return r
+
+
+def asoftmax_logits(logits: Tensor, r: Tensor, labels: Tensor, lam: Tensor, m: int, r_floor: float = 1e-12) -> Tensor:
+    """The A-Softmax logits z [B,K] from cosine logits, the rows' norms, int64 labels and the 1-element device buffer ``lam``
+    (dlip_asoftmax_logits_f32, forward mode)."""
+    _req(logits, "logits"); _req(r, "r"); _req(labels, "labels", torch.int64); _req(lam, "lam")
+    z = _empty(logits.shape, logits.device)
+    check(lib().dlip_asoftmax_logits_f32(ptr(logits), ptr(r), ptr(labels), ptr(lam), None, ptr(z), None, logits.shape[0], logits.shape[1],
+                                         int(m), float(r_floor), 0, stream_handle()), "dlip_asoftmax_logits_f32")
+    return z
+
+
 def lowfer_cat(e1: Tensor, e2: Tensor) -> Tensor:
     _req(e1, "e1"); _req(e2, "e2")
     B, D = e1.shape

@@ -145,15 +145,24 @@ class StepPlan:
         with torch.cuda.stream(self.stream), torch.no_grad():
             self._pass("collect")                 # warm-up: packs weights, registers the workspace, fills the arena
             self.stream.synchronize()
-            check(lib().dlip_plan_begin(self.stream.cuda_stream), "dlip_plan_begin")
+            # (Python's cyclic collector stays off while the stream captures: a dead trainer's recorded graph destroyed in here makes a
+            # HIP call the capture refuses, thrown from a destructor -- the process aborts; see TrainStepGraph._capture)
+            import gc
+            gc_was_on = gc.isenabled()
+            gc.disable()
             try:
-                out = self._pass("replay")
-            except BaseException:
-                h = C.c_void_p()
-                lib().dlip_plan_end(self.stream.cuda_stream, C.byref(h))   # leave capture mode before propagating
-                lib().dlip_plan_destroy(h)
-                raise
-            check(lib().dlip_plan_end(self.stream.cuda_stream, C.byref(self._handle)), "dlip_plan_end")
+                check(lib().dlip_plan_begin(self.stream.cuda_stream), "dlip_plan_begin")
+                try:
+                    out = self._pass("replay")
+                except BaseException:
+                    h = C.c_void_p()
+                    lib().dlip_plan_end(self.stream.cuda_stream, C.byref(h))   # leave capture mode before propagating
+                    lib().dlip_plan_destroy(h)
+                    raise
+                check(lib().dlip_plan_end(self.stream.cuda_stream, C.byref(self._handle)), "dlip_plan_end")
+            finally:
+                if gc_was_on:
+                    gc.enable()
         if self.arena.cursor != len(self.arena.bufs):
             raise DeepLipHipError("StepPlan: the recorded pass made fewer allocations than the warm-up pass")
         self.outputs = out

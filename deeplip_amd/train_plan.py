@@ -161,8 +161,21 @@ class TrainStepGraph:
             torch.cuda.synchronize(self.device)
             poll_ms = float(os.environ.get("TORCH_NCCL_WATCHDOG_SLEEP_INTERVAL_MS", os.environ.get("DLIP_WATCHDOG_POLL_MS", "100")))
             time.sleep(5 * poll_ms / 1e3)
-        with torch.cuda.graph(g, stream=self.stream, capture_error_mode=mode):
-            out = self.fn(*self.static)
+        # Python's cyclic collector stays off while the stream captures.  A dead reference cycle may hold an earlier plan's CUDAGraph (a
+        # trainer and its ShapeKeyedSteps point at each other, so a dropped trainer waits for the collector): collected INSIDE the
+        # capture, that graph's destructor makes a HIP call the capturing stream refuses ("operation not permitted when stream is
+        # capturing") and throws from a destructor -- the process aborts.  torch.cuda.graph collects on entry only on request
+        # (torch.compiler.config.force_cudagraph_gc).  Nothing is collected here either: what is dead goes when the collector next runs
+        # by itself, outside the capture, as it did whenever it did not happen to run in here.
+        import gc
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(g, stream=self.stream, capture_error_mode=mode):
+                out = self.fn(*self.static)
+        finally:
+            if gc_was_on:
+                gc.enable()
         return g, out
 
     def _give_up(self, reason: str):

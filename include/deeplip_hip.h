@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define DLIP_ABI_VERSION 65
+#define DLIP_ABI_VERSION 66
 #define DLIP_HOST              /* marks a pointer parameter that the CPU dereferences during the call (HOST memory, not device) */
 #define DLIP_LIFT_BCAST 2048
 #define DLIP_LIFT_WORDS 4098   /* a gradient's power-of-two lift: (2^e, 2^-e), then 2^-e repeated DLIP_LIFT_BCAST times (the post_scale
@@ -1337,6 +1337,39 @@ int64_t dlip_wave_reverb_fft_workspace_bytes(int64_t B, int64_t S, int32_t Lmax)
 int dlip_wave_reverb_fft_f32(const float* x, const int32_t* lengths, const void* spectra, const int32_t* rir_len,
                              const int32_t* rir_peak, const int32_t* rir_idx, float* y, void* workspace, int64_t workspace_bytes, int32_t B,
                              int32_t S, int32_t R, int32_t Lmax, int32_t keep_power, dlip_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 66) THE A-SOFTMAX AND CONTRASTIVE CRITERIA: the last two names of `train.loss` (conf/audio_config.yaml:130: "CrossEntropy,
+ * A-Softmax, LMCL(AM-Softmax), AAM-Softmax, Contrastive, Triplet") that were empty stubs -- `ASoftmax` (models/audio_models/loss.py:53-59)
+ * and `Contrastive` (loss.py:69-75).  Upstream has no implementation: parity unpinned, the definitions are the build's own.
+ *
+ * dlip_asoftmax_logits_f32 (loss.py:53-59; SphereFace, Liu et al. 2017): c [B,K] cosine logits, r [B] = the rows' clamped norms
+ *   (dlip_row_norm_f32), labels int64 [B], lambda = ONE float in device memory, read by the kernel (a recorded step follows the annealing
+ *   schedule through the pointer), m = 1 .. 4.  backward == 0: out = z [B,K], z_bj = r_b c_bj off the target, z_by = r_b (lambda c +
+ *   psi(c)) / (1 + lambda) on it, psi(c) = (-1)^k T_m(c) - 2k, k = #{ j in 1 .. m-1 : c <= cos(j pi / m) }, c clamped to [-1, 1], T_m the
+ *   Chebyshev polynomial (dz, dr unused, may be NULL).  backward != 0: out = dc [B,K] (= r_b dz_bj, times (lambda + psi'(c)) / (1 + lambda)
+ *   on the target) and dr [B] = sum_j dz_bj z_bj / r_b, summed in fp64 in a fixed order; 0 on a row with r_b <= r_floor (the clamp).
+ * dlip_row_norm_f32 / dlip_row_norm_bwd_f32: r [U] = max(|x_u|, eps) with the sum, order and rounding of dlip_l2_normalize_f32 (the same
+ *   bits as the norm it divides by); dx [U,D] = dr_u x_u / r_u, zeros on a row at the clamp (r_u <= eps).
+ *
+ * dlip_contrastive_loss_f32 (loss.py:69-75; the cosine form of adambielski/siamese-triplet's OnlineContrastiveLoss = torch.nn.
+ *   CosineEmbeddingLoss on pairs selected on the device): x [B,E] and labels int32 [B] under the limits of dlip_triplet_mine_f32, whose Gram
+ *   launch fills g [B,B] = x x^T and rownorm [B].  mode 0: every pair a < j; mode 1 (hard negative): every positive pair a < p and, per
+ *   anchor row a with P_a later positives, the min(P_a, #negatives after a) negatives n > a of highest cosine, the lower index winning
+ *   ties (exact, by rank counting).  A positive pair costs 1 - cos, a selected negative relu(cos - margin); loss[0] = the mean over all
+ *   selected pairs, n_pairs[0] = their number N (N == 0: loss = 0).  Scratch the caller owns: rowsum [B] fp64, rowcnt [B].  w [B,B] int32,
+ *   every element written: -1 positive pair, +1 selected negative with an active hinge, 0 otherwise -- the `wcount` that
+ *   dlip_triplet_loss_bwd_f32 takes as it is (with n_triplets = n_pairs): that launch IS this loss's backward.  sel (nullable) [B,B] int32,
+ *   every element written: 1 positive pair, 2 selected negative, 0 otherwise.  Launches: Gram, rows, finish.  No atomics.
+ * ------------------------------------------------------------------------------------------ */
+int dlip_asoftmax_logits_f32(const float* c, const float* r, const int64_t* labels, const float* lambda, const float* dz, float* out,
+                             float* dr, int32_t B, int32_t K, int32_t m, float r_floor, int32_t backward, dlip_stream_t stream);
+int dlip_row_norm_f32(const float* x, float* r, int32_t U, int32_t D, float eps, dlip_stream_t stream);
+int dlip_row_norm_bwd_f32(const float* x, const float* r, const float* dr, float* dx, int32_t U, int32_t D, float eps,
+                          dlip_stream_t stream);
+int dlip_contrastive_loss_f32(const float* x, const int32_t* labels, float margin, int32_t mode, float* g, float* rownorm, double* rowsum,
+                              int32_t* rowcnt, int32_t* w, int32_t* sel, float* loss, int32_t* n_pairs, int32_t B, int32_t E,
+                              dlip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Step plans. The reference drives its encoders from a Python loop, one utterance and one torch.nn layer

@@ -12,6 +12,7 @@ from deeplip_amd.scoring_entry import AUDIO_DEFAULTS as _DEFAULTS, make_entry_po
 from deeplip_amd.triplet import (AllTripletSelector, FunctionNegativeTripletSelector, HardestNegativeTripletSelector,  # noqa: F401
                                  RandomNegativeTripletSelector, SemihardNegativeTripletSelector, TripletSelector, hardest_negative,
                                  random_hard_negative, semihard_negative)      # utils.py:18-142, mined on the device
+from deeplip_amd.pairs import AllPairSelector, HardNegativePairSelector, PairSelector, make_pair_selector  # noqa: F401  (Contrastive's selectors)
 import numpy as np
 
 

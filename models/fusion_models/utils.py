@@ -9,6 +9,7 @@ available as ``eer_cos`` / ``score_fusion`` / ``feature_fusion_scores``."""
 from deeplip_amd.scoring import (EmbeddingTable, cosine_scores, eer_cos, eer_from_scores,  # noqa: F401
                                  feature_fusion_scores, read_trial_list, roc_curve, score_fusion)
 from deeplip_amd.scoring_entry import FUSION_DEFAULTS as _DEFAULTS, make_entry_points as _make, set_paths  # noqa: F401
+from deeplip_amd.pairs import AllPairSelector, HardNegativePairSelector, PairSelector, make_pair_selector  # noqa: F401  (Contrastive's selectors)
 import numpy as np
 
 

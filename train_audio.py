@@ -40,14 +40,19 @@ sys.path.insert(0, ROOT)
 from deeplip_amd import _lib, arith, dist as ddist, ops, scoring, weightgen as wg  # noqa: E402
 from deeplip_amd.synthetic import SyntheticAVSet, synthetic_trials  # noqa: E402
 from models.audio_models import tdnn  # noqa: E402
-from models.audio_models.loss import AAMSoftmax, LMCL, CrossEntropy, OnlineTriplet  # noqa: E402
+from models.audio_models.loss import AAMSoftmax, ASoftmax, Contrastive, LMCL, CrossEntropy, OnlineTriplet  # noqa: E402
 
 
 def build_criterion(train_opts, embedding_dim, n_spk):
     """The criterion ``train.loss`` names (train_audio.py:90-97; host-side construction, no GPU needed).  ``LMCL`` and ``AAMSoftmax``
     start at ``train.margin[0]``; ``Triplet`` (conf/audio_config.yaml:130 lists it, the reference's trainer never builds it) is
     OnlineTriplet on the build-owned block ``train.triplet: {margin: 0.2, selector: hardest | semihard | random | all}`` (absent
-    block or key: those defaults; one margin for mining and loss); every other value is CrossEntropy, as upstream."""
+    block or key: those defaults; one margin for mining and loss).  ``ASoftmax`` and its config spelling ``A-Softmax`` (a stub upstream,
+    loss.py:53-59) build deeplip_amd.loss.ASoftmax from the build-owned block ``train.asoftmax: {m: 4, lambda_min: 5.0, lambda_base: 1000.0,
+    gamma: 0.12, power: 1.0}``; ``OnlineContrastive`` builds deeplip_amd.loss.Contrastive from ``train.contrastive: {margin: 0.5, selector:
+    hard_negative | all}``.  Every other value is CrossEntropy, as upstream -- INCLUDING the config comment's own ``Contrastive``: the
+    reference's trainer falls through to CrossEntropy for it and that behaviour is kept, which is why the value that builds the
+    contrastive criterion carries the ``Online`` prefix."""
     kind = train_opts["loss"]
     if kind == "LMCL":
         return LMCL(embedding_dim, n_spk, train_opts["scale"], train_opts["margin"][0])
@@ -63,6 +68,22 @@ def build_criterion(train_opts, embedding_dim, n_spk):
             raise ValueError("train.loss: Triplet has no parameters of its own: train.freeze_encoder would leave nothing to train")
         margin = float(t.get("margin", 0.2))
         return OnlineTriplet(margin, make_selector(str(t.get("selector", "hardest")), margin))
+    if kind in ("ASoftmax", "A-Softmax"):
+        a = train_opts.get("asoftmax") or {}
+        known = ("m", "lambda_min", "lambda_base", "gamma", "power")
+        unknown = sorted(set(a) - set(known))
+        if unknown:
+            raise ValueError(f"train.asoftmax: unknown key(s) {unknown}; expected {', '.join(known)}")
+        return ASoftmax(embedding_dim, n_spk, **{k: a[k] for k in known if k in a})
+    if kind == "OnlineContrastive":
+        from deeplip_amd.pairs import make_pair_selector
+        t = train_opts.get("contrastive") or {}
+        unknown = sorted(set(t) - {"margin", "selector"})
+        if unknown:
+            raise ValueError(f"train.contrastive: unknown key(s) {unknown}; expected margin, selector")
+        if train_opts.get("freeze_encoder", False):
+            raise ValueError("train.loss: OnlineContrastive has no parameters of its own: train.freeze_encoder would leave nothing to train")
+        return Contrastive(float(t.get("margin", 0.5)), make_pair_selector(str(t.get("selector", "hard_negative"))))
     return CrossEntropy(embedding_dim, n_spk)
 
 
@@ -152,13 +173,14 @@ class Trainer(object):
         self.criterion = build_criterion(self.train_opts, E, d["n_spk"]).to(self.device)
         if isinstance(self.criterion, (LMCL, AAMSoftmax)):
             self.init_margin, self.end_margin = self.train_opts["margin"]
-        self.triplet = isinstance(self.criterion, OnlineTriplet)
+        self.triplet = isinstance(self.criterion, (OnlineTriplet, Contrastive))     # no parameters, no logits: (loss, count of tuples)
+        self.tuples = "pairs" if isinstance(self.criterion, Contrastive) else "triplets"
         o = self.train_opts["sgd"]
         self.freeze_encoder = bool(self.train_opts.get("freeze_encoder", False))
         groups = [{"params": self.criterion.parameters()}] if self.freeze_encoder else \
                  [{"params": self.model.parameters()}, {"params": self.criterion.parameters()}]   # train_audio.py:112
         if self.triplet:
-            groups = groups[:1]         # OnlineTriplet has no parameters: the optimiser gets the model's alone
+            groups = groups[:1]         # OnlineTriplet / Contrastive have no parameters: the optimiser gets the model's alone
         # train.graph_step (default on): the optimisation step is recorded once per crop length and replayed as one HIP graph
         # (deeplip_amd/train_plan.py); a recorded step reads its learning rate from a device tensor, which MultiStepLR updates in
         # place, and takes the fused SGD kernel.  train.graph_step: false keeps the loop of eager launches.
@@ -333,6 +355,7 @@ class Trainer(object):
                     wave = self._augment(wave, params=dict(zip(("snr_db", "noise_start", "rir_idx"), extra)))
                 return self._wave_fe(wave)
 
+        anneal = getattr(self.criterion, "anneal", None)
         staged = stage(0) if steps > 0 else None
         torch.cuda.synchronize(self.device)
         t0 = time.perf_counter()
@@ -345,6 +368,8 @@ class Trainer(object):
                 for t in extra:
                     t.record_stream(cur)
                 x = features(x, extra)
+            if anneal is not None:
+                anneal()                 # ASoftmax: lambda of this step, written on the device in front of the step, outside the recorded graph
             if recorded:
                 # keyed by the crop length (the shape) AND the margin the criterion bakes into the recorded launches
                 loss, logits = self._steps.step(x, lab, key=float(getattr(self.criterion, "margin", 0.0)))
@@ -362,7 +387,7 @@ class Trainer(object):
         dt = time.perf_counter() - t0
         tot, correct, n = ddist.allreduce_metrics([tot, correct, n], self.device)
         # Triplet: there are no logits, hence no accuracy; the statistics carry the mean number of triplets per step (and rank) instead
-        quality = {"triplets": correct / max(steps * self.world, 1)} if self.triplet else {"acc": correct / n}
+        quality = {self.tuples: correct / max(steps * self.world, 1)} if self.triplet else {"acc": correct / n}
         self.last_epoch_stats = {"loss": tot / n, **quality, "utt_per_s": n / dt, "steps": steps, "bs": bs * self.world,
                                  "step_mode": (self._steps.mode if recorded else "eager"), "crop_ladder": [int(t) for t in ladder]}
         if self.train_from_waves:
@@ -378,7 +403,7 @@ class Trainer(object):
             self._adjust_margin()
             loss = self._train_epoch()
             st = self.last_epoch_stats
-            quality = "triplets/step {:.0f}".format(st["triplets"]) if self.triplet else "acc {:.3f}".format(st["acc"])
+            quality = "{}/step {:.0f}".format(self.tuples, st[self.tuples]) if self.triplet else "acc {:.3f}".format(st["acc"])
             print("Epoch {} loss {:.4f} {} ({:.0f} utt/s, {} steps of {})".format(epoch, loss, quality, st["utt_per_s"],
                                                                               st["steps"], st["bs"]), flush=True)
             self.lr_scheduler.step()
