@@ -36,9 +36,22 @@ class MeanStdPooling(nn.Module):
         return ops.meanstd_pool(x_ntc)
 
 
+def attentive_pool_ntc(pool, x_ntc: Tensor, lengths: Optional[Tensor], len_add: int, eps: float) -> Tensor:
+    """The eval-mode route of both attentive poolings: x [B,T,C] -> [B, heads 2C].  hidden = W x + b is ONE GEMM launch for all heads;
+    scores, softmax and the weighted statistics read hidden and x once (dlip_mh_attn_scores_f32 / dlip_mh_attn_stat_pool_f32)."""
+    B, T, C_ = x_ntc.shape
+    ops.mh_attn_check(pool.head, T, C_)
+    hidden = ops.linear(x_ntc.reshape(B * T, C_), pool.W.detach().contiguous(), pool.b.detach().reshape(-1).contiguous())
+    alpha = ops.mh_attn_scores(hidden.view(B, T, pool.hidden_size), pool.v.detach().reshape(-1).contiguous(),
+                               pool.k.detach().reshape(-1).contiguous(), pool.head_off, lengths, len_add)
+    return ops.mh_attn_stat_pool(x_ntc, alpha, eps, lengths, len_add)
+
+
 class AttentiveStatPooling(nn.Module):
-    """pooling.py:73-107: attention over frames, then attention-weighted mean and std.
-    hidden = W x + b is one GEMM launch; score / softmax / weighted statistics one fused kernel."""
+    """pooling.py:73-107: attention over frames, then attention-weighted mean and std -- one head of the kernels MultiHeadAttention runs
+    (DESIGN.md 4h).  ``eps`` = 0 is the reference's std = sqrt(sum alpha x^2 - mean^2); the ResNet speech encoder's head passes POOL_EPS
+    (std = sqrt(max(sum alpha x^2 - mean^2, 0) + eps), deeplip_amd/audio_resnet.py)."""
+    head, head_off = 1, None        # (one head owns every hidden column: the kernels take no offsets array)
 
     def __init__(self, input_size, hidden_size):
         super().__init__()
@@ -50,16 +63,9 @@ class AttentiveStatPooling(nn.Module):
         for p in self.parameters():
             nn.init.xavier_normal_(p)
 
-    def run_ntc(self, x_ntc: Tensor, lengths: Optional[Tensor] = None, len_add: int = 0) -> Tensor:
+    def run_ntc(self, x_ntc: Tensor, lengths: Optional[Tensor] = None, len_add: int = 0, eps: float = 0.0) -> Tensor:
         """x [B,T,C] -> [B,2C]; ``lengths`` (int32 CUDA [B]): attention and statistics over the first lengths[b] + len_add frames."""
-        from ._lib import check, lib, ptr, stream_handle
-        B, T, C_ = x_ntc.shape
-        hidden = ops.linear(x_ntc.reshape(B * T, C_), self.W.detach().contiguous(), self.b.detach().reshape(-1).contiguous())
-        y = ops._empty((B, 2 * C_), x_ntc.device)
-        check(lib().dlip_attentive_stat_pool_f32(ptr(x_ntc), ptr(hidden), ptr(self.v.detach().contiguous()),
-                                                 ptr(self.k.detach().contiguous()), ptr(lengths), len_add, ptr(y), None, B, T, C_,
-                                                 self.hidden_size, stream_handle()), "dlip_attentive_stat_pool_f32")
-        return y
+        return attentive_pool_ntc(self, x_ntc, lengths, len_add, eps)
 
     def forward(self, x):
         """[B,C,T] (reference layout) -> [B,2C]."""
@@ -115,12 +121,7 @@ class MultiHeadAttention(nn.Module):
     def run_ntc(self, x_ntc: Tensor, lengths: Optional[Tensor] = None, len_add: int = 0) -> Tensor:
         """x [B,T,C] -> [B, head 2C]; ``lengths`` (int32 CUDA [B]): attention and statistics over the first lengths[b] + len_add frames."""
         from .audio_resnet import POOL_EPS
-        B, T, C_ = x_ntc.shape
-        ops.mh_attn_check(self.head, T, C_)
-        hidden = ops.linear(x_ntc.reshape(B * T, C_), self.W.detach().contiguous(), self.b.detach().reshape(-1).contiguous())
-        alpha = ops.mh_attn_scores(hidden.view(B, T, self.hidden_size), self.v.detach().reshape(-1).contiguous(),
-                                   self.k.detach().reshape(-1).contiguous(), self.head_off, lengths, len_add)
-        return ops.mh_attn_stat_pool(x_ntc, alpha, POOL_EPS, lengths, len_add)
+        return attentive_pool_ntc(self, x_ntc, lengths, len_add, POOL_EPS)
 
     def forward(self, x):
         """[B,C,T] (reference layout) -> [B, head 2C]."""

@@ -50,15 +50,14 @@ POOLINGS = ("average", "statistic", "attentive_statistic", "multi_head_attention
 
 
 def attentive_pool_nhwc(h: Tensor, pool, lens: Optional[Tensor] = None, shift: int = 0) -> Tensor:
-    """Eval-mode attentive statistics pooling of the map h [N,H,W,C] fp32 -> [N, 2 H C]: ``pool`` (deeplip_amd.audio.AttentiveStatPooling of
-    input size H C) over the D-vectors of each utterance's valid frames (``lens`` int32 CUDA input lengths / ``shift`` as ops.time_tail_zero;
-    the frame counts are formed on the device)."""
+    """Eval-mode attentive statistics pooling of the map h [N,H,W,C] fp32 -> [N, heads 2 H C]: ``pool`` (deeplip_amd.audio.AttentiveStatPooling
+    or MultiHeadAttention of input size H C) over the D-vectors of each utterance's valid frames (``lens`` int32 CUDA input lengths /
+    ``shift`` as ops.time_tail_zero; the frame counts are formed on the device), every standard deviation with POOL_EPS."""
+    from .audio import attentive_pool_ntc
     N, H, W, C_ = h.shape
     xt = ops.swap_axes_nhwc(h).view(N, W, H * C_)              # each frame's D-vector contiguous: the hidden layer is one GEMM
-    hidden = ops.linear(xt.view(N * W, H * C_), pool.W.detach().contiguous(), pool.b.detach().reshape(-1).contiguous())
     valid = None if lens is None else ops.time_valid_lengths(lens, shift, W)
-    return ops.attentive_stat_pool_eps(xt, hidden.view(N, W, pool.hidden_size), pool.v.detach().reshape(-1).contiguous(),
-                                       pool.k.detach().reshape(-1).contiguous(), POOL_EPS, lengths=valid)
+    return attentive_pool_ntc(pool, xt, valid, 0, POOL_EPS)
 
 
 def attentive_pool_nhwc_train(h: Tensor, pool) -> Tensor:
@@ -66,21 +65,6 @@ def attentive_pool_nhwc_train(h: Tensor, pool) -> Tensor:
     from . import autograd as ag
     N, H, W, C_ = h.shape
     return ag.attentive_stat_pool(ag.swap_axes_nhwc(h).view(N, W, H * C_), pool, POOL_EPS)
-
-
-def mh_attentive_pool_nhwc(h: Tensor, pool, lens: Optional[Tensor] = None, shift: int = 0) -> Tensor:
-    """attentive_pool_nhwc for ``pool`` = deeplip_amd.audio.MultiHeadAttention of input size H C: [N,H,W,C] -> [N, heads 2 H C]."""
-    N, H, W, C_ = h.shape
-    xt = ops.swap_axes_nhwc(h).view(N, W, H * C_)
-    valid = None if lens is None else ops.time_valid_lengths(lens, shift, W)
-    return pool.run_ntc(xt, valid)
-
-
-def mh_attentive_pool_nhwc_train(h: Tensor, pool) -> Tensor:
-    """The same under model.train() (one length per batch)."""
-    from . import autograd as ag
-    N, H, W, C_ = h.shape
-    return ag.mh_attentive_stat_pool(ag.swap_axes_nhwc(h).view(N, W, H * C_), pool)
 
 
 class SpeakerEmbNet(nn.Module):
@@ -192,10 +176,8 @@ class SpeakerEmbNet(nn.Module):
             if h.shape[2] < 2:
                 raise ValueError(f"resnet speech encoder: pooling 'statistic' needs utterances of >= {self.min_frames()} frames")
             pooled = ag.statpool_nhwc(h, POOL_EPS)
-        elif self.pooling_type == "attentive_statistic":
-            pooled = attentive_pool_nhwc_train(h, self.pooling)
         else:
-            pooled = mh_attentive_pool_nhwc_train(h, self.pooling)
+            pooled = attentive_pool_nhwc_train(h, self.pooling)
         if self.fc_layers == 1:
             e = ag.linear(pooled, self.fc.weight, self.fc.bias)
             return e, e
@@ -221,9 +203,7 @@ class SpeakerEmbNet(nn.Module):
             if h.shape[2] < 2:
                 raise ValueError(f"resnet speech encoder: pooling 'statistic' needs utterances of >= {self.min_frames()} frames")
             return ops.statpool_nhwc(h, lens, shift, POOL_EPS)
-        if self.pooling_type == "attentive_statistic":
-            return attentive_pool_nhwc(h, self.pooling, lens, shift)
-        return mh_attentive_pool_nhwc(h, self.pooling, lens, shift)
+        return attentive_pool_nhwc(h, self.pooling, lens, shift)
 
     @arith.guarded_eval
     def extract_embedding(self, x: Tensor, lengths=None) -> Tuple[Tensor, Tensor]:

@@ -792,70 +792,12 @@ class MeanStdPoolFn(Function):
         return dx, None, None
 
 
-class AttnStatPoolFn(Function):
-    """The tail of AttentiveStatPooling (models/audio_models/pooling.py:87-107) behind its hidden layer: e = relu(hidden) v + k,
-    alpha = softmax over frames, y = [sum alpha x | sqrt(sum alpha x^2 - mean^2)].  x [B,T,C], hidden [B,T,H] (= x W^T + b from the
-    differentiable GEMM in front: W, b and the second path into x get their gradients there), v [H,1], k [1,1].  ``eps`` > 0 (the ResNet
-    speech encoder's head): std = sqrt(max(sum alpha x^2 - mean^2, 0) + eps), the _eps entry points (ABI 59); 0: the reference's expression."""
-
-    @staticmethod
-    def forward(ctx, x, hidden, v, k, eps=0.0):
-        x, hidden = x.contiguous(), hidden.contiguous()
-        B, T, C_ = x.shape
-        H = hidden.shape[2]
-        alpha = torch.empty((B, T), device=x.device, dtype=torch.float32)
-        vv, kk = v.detach().contiguous(), k.detach().contiguous()
-        if eps:
-            y = ops.attentive_stat_pool_eps(x, hidden, vv, kk, eps, alpha_out=alpha)
-        else:
-            y = torch.empty((B, 2 * C_), device=x.device, dtype=torch.float32)
-            check(lib().dlip_attentive_stat_pool_f32(ptr(x), ptr(hidden), ptr(vv), ptr(kk), None, 0, ptr(y), ptr(alpha), B, T, C_, H,
-                                                     stream_handle()), "dlip_attentive_stat_pool_f32")
-        ctx.save_for_backward(x, hidden, vv, alpha, y)
-        ctx.shapes = (tuple(v.shape), tuple(k.shape))
-        ctx.eps = float(eps)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, hidden, vv, alpha, y = ctx.saved_tensors
-        B, T, C_ = x.shape
-        H = hidden.shape[2]
-        dx = torch.empty_like(x)
-        dh = torch.empty_like(hidden)
-        rde = torch.empty_like(hidden)
-        de = torch.empty((B, T), device=x.device, dtype=torch.float32)
-        if ctx.eps:
-            check(lib().dlip_attentive_stat_pool_eps_bwd_f32(ptr(x), ptr(hidden), ptr(vv), ptr(alpha), ptr(y), ptr(dy.contiguous()), None, 0,
-                                                             ctx.eps, ptr(dx), ptr(dh), ptr(rde), ptr(de), B, T, C_, H, stream_handle()),
-                  "dlip_attentive_stat_pool_eps_bwd_f32")
-        else:
-            check(lib().dlip_attentive_stat_pool_bwd_f32(ptr(x), ptr(hidden), ptr(vv), ptr(alpha), ptr(y), ptr(dy.contiguous()), None, 0, ptr(dx),
-                                                         ptr(dh), ptr(rde), ptr(de), B, T, C_, H, stream_handle()), "dlip_attentive_stat_pool_bwd_f32")
-        dv = _colsum(rde.view(B * T, H)).view(ctx.shapes[0]) if ctx.needs_input_grad[2] else None
-        dk = _colsum(de.view(B * T, 1)).view(ctx.shapes[1]) if ctx.needs_input_grad[3] else None
-        return dx, dh, dv, dk, None
-
-
-def attentive_stat_pool(x, pool, eps=0.0):
-    """AttentiveStatPooling.forward under model.train() (pooling.py:99-107) on channels-last x [B,T,C] -> [B,2C]: the hidden layer
-    W x + b is the engine's differentiable 1 x 1 convolution (forward, data and weight gradient on the MFMA kernels), the rest
-    AttnStatPoolFn (``eps``: its floored standard deviation)."""
-    from . import autograd_video as av
-    B, T, C_ = x.shape
-    H = pool.hidden_size
-    if H % 4:       # (the train-path convolution takes output widths in multiples of 4: any other hidden size is the nn.Linear Function's)
-        hidden = linear(x.reshape(B * T, C_), pool.W, pool.b.reshape(-1)).reshape(B, T, H)
-    else:
-        hidden = av.conv(x.reshape(B, 1, T, C_), pool.W.view(H, C_, 1, 1), pool.b.reshape(-1)).reshape(B, T, H)
-    return AttnStatPoolFn.apply(x, hidden, pool.v, pool.k, eps)
-
-
 class MHAttnStatPoolFn(Function):
-    """The tail of audio.MultiHeadAttention behind its hidden layer (dlip_mh_attn_scores_f32, dlip_mh_attn_stat_pool_f32 and
-    dlip_mh_attn_stat_pool_bwd_f32): x [B,T,C], hidden [B,T,S] (= x W^T + b of all heads from the differentiable GEMM in
-    front: W, b and the second path into x get their gradients there), v [S,1], k [1,n], head_off int32 [n+1] -> y [B, n 2C].  x is read
-    once in the forward and twice in the backward for all heads; dx arrives summed over the heads."""
+    """The tail of audio.AttentiveStatPooling (n = 1; pooling.py:87-107) and audio.MultiHeadAttention behind the hidden layer
+    (dlip_mh_attn_scores_f32, dlip_mh_attn_stat_pool_f32 and dlip_mh_attn_stat_pool_bwd_f32): x [B,T,C], hidden [B,T,S]
+    (= x W^T + b of all heads from the differentiable GEMM in front: W, b and the second path into x get their gradients there), v [S,1],
+    k [1,n], head_off int32 [n+1] (None for one head) -> y [B, n 2C].  x is read once in the forward and twice in the backward for all
+    heads; dx arrives summed over the heads.  ``eps`` > 0: std = sqrt(max(sum alpha x^2 - mean^2, 0) + eps); 0: the reference's expression."""
 
     @staticmethod
     def forward(ctx, x, hidden, v, k, head_off, eps):
@@ -889,19 +831,24 @@ class MHAttnStatPoolFn(Function):
         return dx, dh, dv, dk, None, None
 
 
-def mh_attentive_stat_pool(x, pool):
-    """audio.MultiHeadAttention under model.train() on channels-last x [B,T,C] -> [B, n 2C]: the hidden layer W x + b of ALL heads is the
-    engine's differentiable 1 x 1 convolution (or, for a summed hidden width that is no multiple of 4, the nn.Linear Function -- the
-    choice attentive_stat_pool makes), the rest MHAttnStatPoolFn."""
+def attentive_stat_pool(x, pool, eps=0.0):
+    """audio.AttentiveStatPooling.forward (pooling.py:99-107) or audio.MultiHeadAttention.forward under model.train() on channels-last
+    x [B,T,C] -> [B, heads 2C]: the hidden layer W x + b of ALL heads is the engine's differentiable 1 x 1 convolution (forward, data and
+    weight gradient on the MFMA kernels), the rest MHAttnStatPoolFn.  ``eps`` = 0: the reference's unfloored standard deviation."""
     from . import autograd_video as av
-    from .audio_resnet import POOL_EPS
     B, T, C_ = x.shape
     S = pool.hidden_size
-    if S % 4:
+    if S % 4:       # (the train-path convolution takes output widths in multiples of 4: any other hidden size is the nn.Linear Function's)
         hidden = linear(x.reshape(B * T, C_), pool.W, pool.b.reshape(-1)).reshape(B, T, S)
     else:
         hidden = av.conv(x.reshape(B, 1, T, C_), pool.W.view(S, C_, 1, 1), pool.b.reshape(-1)).reshape(B, T, S)
-    return MHAttnStatPoolFn.apply(x, hidden, pool.v, pool.k, pool.head_off, POOL_EPS)
+    return MHAttnStatPoolFn.apply(x, hidden, pool.v, pool.k, pool.head_off, eps)
+
+
+def mh_attentive_stat_pool(x, pool):
+    """``pooling: multi_head_attention`` under model.train(): attentive_stat_pool with the definition's floor."""
+    from .audio_resnet import POOL_EPS
+    return attentive_stat_pool(x, pool, POOL_EPS)
 
 
 class StatPoolNHWCFn(Function):

@@ -1,11 +1,11 @@
-// Multi-head attentive statistics pooling (ABI 64; `pooling: multi_head_attention`) on channels-last activations:
-// n attention heads of their own hidden width over one frame tensor x [B,T,C], y [B, n 2C] = cat_h [mean_h | std_h].  Head h owns the
-// columns off[h] .. off[h+1] of hidden [B,T,S] (ONE GEMM for all heads, in front of these kernels) and of v; the offsets travel as a
-// device int32 [n+1] array and are clamped to [0, S] where they are read, so no column index leaves a hidden row whatever it holds.
+// Attentive statistics pooling (`pooling: attentive_statistic` is n = 1, ABI 67; `pooling: multi_head_attention`, ABI 64)
+// on channels-last activations: n attention heads of their own hidden width over one frame tensor x [B,T,C], y [B, n 2C] =
+// cat_h [mean_h | std_h].  Head h owns the columns off[h] .. off[h+1] of hidden [B,T,S] (ONE GEMM for all heads, in front of these
+// kernels) and of v; the offsets travel as a device int32 [n+1] array and are clamped to [0, S] where they are read, so no column index
+// leaves a hidden row whatever it holds.  One head needs no array: a null pointer means the columns [0, S).
 //
-// The single-head kernels (pool_ops.hip) run one workgroup per utterance and would be called once per head: x read n times forward
-// and n times backward, n dx tensors added.  Here x is read once in the forward and twice in the backward for ALL heads, dx is written
-// once, and every pass over x is spread over (channel block | row range, utterance) workgroups:
+// x is read once in the forward and twice in the backward for ALL heads, dx is written once, and every pass over x is spread over
+// (channel block | row range, utterance) workgroups:
 //   forward   mh_energy (one wave per frame: segmented dot products)  ->  mh_softmax (grid (head, utterance), parallel max and sum)
 //             ->  mh_stat (grid (C / 64, utterance) as meanstd_kernel; alpha staged in LDS chunk by chunk; 2n accumulators per channel)
 //   backward  mh_dalpha (grid (row range, utterance); dm | g_q | m of all heads in LDS)  ->  mh_softmax_bwd (grid (head, utterance))
@@ -22,8 +22,9 @@ constexpr int kAlphaChunk = 256;                // frames of alpha staged in LDS
 constexpr size_t kMaxLds = 160 * 1024;          // LDS of one gfx950 workgroup
 constexpr int kRowGridCap = 256 * 16;           // workgroups of the one-wave-per-frame passes, grid-stride the rest
 
-// columns [lo, hi) of head h, inside [0, S] whatever the array holds
+// columns [lo, hi) of head h, inside [0, S] whatever the array holds; no array (n == 1 only, the entry points see to it): [0, S)
 __device__ __forceinline__ void mh_head_range(const int32_t* __restrict__ off, int h, int S, int& lo, int& hi) {
+  if (off == nullptr) { lo = 0; hi = S; return; }
   const int a = off[h], b = off[h + 1];
   lo = a < 0 ? 0 : (a > S ? S : a);
   hi = b < lo ? lo : (b > S ? S : b);
@@ -82,7 +83,8 @@ __device__ __forceinline__ void mh_stage_alpha(float (*sa)[kAlphaChunk], const f
   __syncthreads();
 }
 
-// y[b, h 2C + c] = m_h[c] = sum_t alpha[b,h,t] x[b,t,c];  y[b, h 2C + C + c] = sqrt(max(sum_t alpha x^2 - m_h^2, 0) + eps).
+// y[b, h 2C + c] = m_h[c] = sum_t alpha[b,h,t] x[b,t,c];  y[b, h 2C + C + c] = sqrt(max(sum_t alpha x^2 - m_h^2, 0) + eps), or with
+// eps == 0 the reference's unfloored sqrt(sum_t alpha x^2 - m_h^2) (pooling.py:106), NaN where rounding takes the difference below zero.
 // One workgroup per (64-channel block, utterance) as meanstd_kernel: 16 lanes x float4 span the block, 16 row groups split the frames;
 // every x element is loaded once and feeds the 2 NH fp64 accumulators of all heads; the 16 partial rows meet in LDS head by head.
 template <int NH>
@@ -133,7 +135,7 @@ __global__ __launch_bounds__(256) void mh_stat_kernel(const float* __restrict__ 
       for (int i = 0; i < 16; ++i) { mm += part[i][threadIdx.x][0]; qq += part[i][threadIdx.x][1]; }
       float* yb = y + ((long long)b * NH + h) * 2 * C + c0 + threadIdx.x;
       yb[0] = (float)mm;
-      yb[C] = (float)sqrt(fmax(qq - mm * mm, 0.0) + (double)eps);
+      yb[C] = (float)(eps == 0.f ? sqrt(qq - mm * mm) : sqrt(fmax(qq - mm * mm, 0.0) + (double)eps));
     }
   }
 }
@@ -363,7 +365,7 @@ int mh_bwd_dispatch(int n, const float* x, const float* alpha, const float* y, c
 
 extern "C" int dlip_mh_attn_scores_f32(const float* hidden, const float* v, const float* k, const int32_t* head_off, const int32_t* len,
                                        int32_t len_add, float* alpha, int32_t B, int32_t T, int32_t S, int32_t n, dlip_stream_t stream) {
-  DLIP_CHECK_ARG(hidden && v && k && head_off && alpha);
+  DLIP_CHECK_ARG(hidden && v && k && (head_off || n == 1) && alpha);
   DLIP_CHECK_ARG(n >= 1 && n <= kMaxHeads && B > 0 && B <= 65535 && T > 0 && T <= 16000 && S >= n);
   DlipLen l; l.len = len; l.mul = 1; l.add = len_add;
   hipStream_t st = dlip_hip_stream(stream);
@@ -377,7 +379,7 @@ extern "C" int dlip_mh_attn_scores_f32(const float* hidden, const float* v, cons
 extern "C" int dlip_mh_attn_stat_pool_f32(const float* x, const float* alpha, const int32_t* len, int32_t len_add, float eps, float* y,
                                           int32_t B, int32_t T, int32_t C, int32_t n, dlip_stream_t stream) {
   DLIP_CHECK_ARG(x && alpha && y);
-  DLIP_CHECK_ARG(n >= 1 && n <= kMaxHeads && B > 0 && B <= 65535 && T > 0 && T <= 16000 && C > 0 && (C & 3) == 0 && eps > 0.f);
+  DLIP_CHECK_ARG(n >= 1 && n <= kMaxHeads && B > 0 && B <= 65535 && T > 0 && T <= 16000 && C > 0 && (C & 3) == 0 && eps >= 0.f);
   DLIP_CHECK_ARG((size_t)3 * n * C * sizeof(float) <= kMaxLds);       // the backward's bound: what it could not differentiate is refused here
   DLIP_CHECK_ARG(dlip_aligned16(x));
   DlipLen l; l.len = len; l.mul = 1; l.add = len_add;
@@ -388,9 +390,9 @@ extern "C" int dlip_mh_attn_stat_pool_bwd_f32(const float* x, const float* hidde
                                               const float* alpha, const float* y, const float* dy, const int32_t* len, int32_t len_add,
                                               float eps, float* dx, float* dhidden, float* rde, float* de, float* dek, int32_t B,
                                               int32_t T, int32_t C, int32_t S, int32_t n, dlip_stream_t stream) {
-  DLIP_CHECK_ARG(x && hidden && v && head_off && alpha && y && dy && dx && dhidden && rde && de && dek);
+  DLIP_CHECK_ARG(x && hidden && v && (head_off || n == 1) && alpha && y && dy && dx && dhidden && rde && de && dek);
   DLIP_CHECK_ARG(n >= 1 && n <= kMaxHeads && B > 0 && B <= 65535 && T > 0 && T <= 16000 && C > 0 && (C & 3) == 0 && S >= n);
-  DLIP_CHECK_ARG(eps > 0.f);       // what keeps the std read from y away from zero
+  DLIP_CHECK_ARG(eps >= 0.f);      // > 0 keeps the std read from y away from zero; 0: the reference's 0 / 0 at a frame-constant feature
   DLIP_CHECK_ARG((size_t)3 * n * C * sizeof(float) <= kMaxLds);
   DLIP_CHECK_ARG(dlip_aligned16(x, y, dy, dx));
   DlipLen l; l.len = len; l.mul = 1; l.add = len_add;

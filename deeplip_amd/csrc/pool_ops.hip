@@ -288,190 +288,6 @@ extern "C" int dlip_meanstd_pool_bn_f32(const float* z, const float* mean, const
 }
 
 namespace {
-// AttentiveStatPooling tail (models/audio_models/pooling.py:87-107) on N-T-C activations:
-//   e[t]   = relu(hidden[b,t,:]) . v + k            (hidden = x W^T + b comes from the GEMM kernel)
-//   alpha  = softmax_t(e)
-//   mean_c = sum_t alpha[t] x[b,t,c];  std_c = sqrt(sum_t alpha[t] x[b,t,c]^2 - mean_c^2)
-// One workgroup per utterance: phase 1 one wave per frame for e[t] (LDS), phase 2 softmax over T,
-// phase 3 one thread per channel (coalesced) with fp64 accumulation.
-// FLOOR (ABI 59, the ResNet speech encoder's head: its pooled tensor is post-ReLU, where a feature that is constant over time is
-// ordinary): std_c = sqrt(max(sum_t alpha[t] x^2 - mean_c^2, 0) + eps).  !FLOOR is the reference's expression, instruction for
-// instruction what it was before the template.
-template <bool FLOOR>
-__global__ __launch_bounds__(256) void attentive_stat_kernel(const float* __restrict__ x, const float* __restrict__ hidden,
-                                                             const float* __restrict__ v, const float* __restrict__ kk,
-                                                             float* __restrict__ y, float* __restrict__ alpha_out, int Tpad, int C,
-                                                             int Hd, const DlipLen len, float eps) {
-  extern __shared__ float alpha[];   // [T]
-  __shared__ float red[2];
-  const int b = blockIdx.x;
-  const int T = dlip_valid_rows(len, b, Tpad);          // ragged batches: attention and statistics over the valid frames only
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const float* hb = hidden + (long long)b * Tpad * Hd;
-  for (int t = wave; t < T; t += 4) {
-    double s = 0.0;
-    for (int h = lane; h < Hd; h += 64) s += (double)fmaxf(hb[(long long)t * Hd + h], 0.f) * (double)v[h];
-    s = dlip_wave_sum_f64(s);
-    if (lane == 0) alpha[t] = (float)s + kk[0];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float mx = -__builtin_inff();
-    for (int t = 0; t < T; ++t) mx = fmaxf(mx, alpha[t]);
-    double se = 0.0;
-    for (int t = 0; t < T; ++t) se += exp((double)(alpha[t] - mx));
-    red[0] = mx;
-    red[1] = (float)se;
-  }
-  __syncthreads();
-  const float mx = red[0];
-  const double se = red[1];
-  for (int t = threadIdx.x; t < T; t += 256) alpha[t] = (float)(exp((double)(alpha[t] - mx)) / se);
-  __syncthreads();
-  if (alpha_out != nullptr)          // the attention weights, kept for the backward pass (zeros behind a ragged utterance's end)
-    for (int t = threadIdx.x; t < Tpad; t += 256) alpha_out[(long long)b * Tpad + t] = t < T ? alpha[t] : 0.f;
-  const float* xb = x + (long long)b * Tpad * C;
-  for (int c = threadIdx.x; c < C; c += 256) {
-    double m = 0.0, q = 0.0;
-    for (int t = 0; t < T; ++t) {
-      const double xv = xb[(long long)t * C + c], a = alpha[t];
-      m += a * xv;
-      q += a * xv * xv;
-    }
-    y[(long long)b * 2 * C + c] = (float)m;
-    if constexpr (FLOOR) y[(long long)b * 2 * C + C + c] = (float)sqrt(fmax(q - m * m, 0.0) + (double)eps);
-    else y[(long long)b * 2 * C + C + c] = (float)sqrt(q - m * m);
-  }
-}
-}  // namespace
-
-extern "C" int dlip_attentive_stat_pool_f32(const float* x, const float* hidden, const float* v, const float* k,
-                                            const int32_t* len, int32_t len_add, float* y, float* alpha_out, int32_t B, int32_t T,
-                                            int32_t C, int32_t Hd, dlip_stream_t stream) {
-  DLIP_CHECK_ARG(x && hidden && v && k && y && B > 0 && T > 0 && C > 0 && Hd > 0 && T <= 16000);
-  DlipLen l; l.len = len; l.mul = 1; l.add = len_add;
-  hipLaunchKernelGGL(attentive_stat_kernel<false>, dim3(B), dim3(256), (size_t)T * sizeof(float),
-                     dlip_hip_stream(stream), x, hidden, v, k, y, alpha_out, T, C, Hd, l, 0.f);
-  return dlip_launch_status();
-}
-
-extern "C" int dlip_attentive_stat_pool_eps_f32(const float* x, const float* hidden, const float* v, const float* k,
-                                                const int32_t* len, int32_t len_add, float eps, float* y, float* alpha_out, int32_t B,
-                                                int32_t T, int32_t C, int32_t Hd, dlip_stream_t stream) {
-  DLIP_CHECK_ARG(x && hidden && v && k && y && B > 0 && T > 0 && C > 0 && Hd > 0 && T <= 16000 && eps > 0.f);
-  DlipLen l; l.len = len; l.mul = 1; l.add = len_add;
-  hipLaunchKernelGGL(attentive_stat_kernel<true>, dim3(B), dim3(256), (size_t)T * sizeof(float),
-                     dlip_hip_stream(stream), x, hidden, v, k, y, alpha_out, T, C, Hd, l, eps);
-  return dlip_launch_status();
-}
-
-namespace {
-// Backward of the AttentiveStatPooling tail (models/audio_models/pooling.py:87-107; the forward above) for one utterance per
-// workgroup.  With u = q - m^2, s = sqrt(u):   g_q = ds / (2 s),  g_m = dm - 2 m g_q   (torch's own chain through sqrt and the square)
-//   dx[t,c]     = alpha_t (g_m[c] + 2 x[t,c] g_q[c])                     the statistics' direct path
-//   dalpha_t    = sum_c (g_m[c] x[t,c] + g_q[c] x[t,c]^2)
-//   de_t        = alpha_t (dalpha_t - sum_t' alpha_t' dalpha_t')        softmax over the utterance's valid frames
-//   dhidden[t,j]= de_t v_j [hidden[t,j] > 0]                            -> W, b and the second path into x, through the GEMM's backward
-//   rde[t,j]    = de_t relu(hidden[t,j])                                column sums = dv;  sum(de) = dk
-// fp64 accumulation wherever a sum runs over channels or frames.  LDS: g_m [C] | g_q [C] | dalpha [Tpad].
-// FLOOR (ABI 59): the forward's s = sqrt(max(u, 0) + eps) >= sqrt(eps), so g_q = ds / (2 s) is finite at a feature that is constant
-// over time (u = 0, where the reference's expression divides 0 by 0).  u >= 0 in exact arithmetic (alpha sums to one), so the max is
-// taken as the identity.  There g_q is up to 1 / (2 sqrt(eps)) = 158 ds and g_m = dm - 2 m g_q cancels against 2 x g_q in fp32, so
-// this form keeps dm and m apart (LDS: dm [C] | g_q [C] | dalpha [Tpad] | m [C]) and works on the centred value in fp64:
-//   dx[t,c] = alpha_t (dm[c] + 2 g_q[c] (x - m[c])),   dalpha_t = sum_c x (dm[c] + g_q[c] (x - 2 m[c])).
-template <bool FLOOR>
-__global__ __launch_bounds__(256) void attentive_stat_bwd_kernel(const float* __restrict__ x, const float* __restrict__ hidden,
-                                                                 const float* __restrict__ v, const float* __restrict__ alpha,
-                                                                 const float* __restrict__ y, const float* __restrict__ dy,
-                                                                 float* __restrict__ dx, float* __restrict__ dhidden,
-                                                                 float* __restrict__ rde, float* __restrict__ de_out, int Tpad, int C,
-                                                                 int Hd, const DlipLen len) {
-  extern __shared__ float sm[];
-  float* gm = sm;
-  float* gq = sm + C;
-  float* dal = sm + 2 * C;          // [Tpad]: dalpha, then de
-  float* mm = sm + 2 * C + Tpad;    // [C] (FLOOR only): the mean
-  __shared__ double red[4];
-  const int b = blockIdx.x;
-  const int T = dlip_valid_rows(len, b, Tpad);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const float* xb = x + (long long)b * Tpad * C;
-  const float* ab = alpha + (long long)b * Tpad;
-  for (int c = threadIdx.x; c < C; c += 256) {
-    const double m = y[(long long)b * 2 * C + c], s = y[(long long)b * 2 * C + C + c];
-    const double dm = dy[(long long)b * 2 * C + c], ds = dy[(long long)b * 2 * C + C + c];
-    const double q = ds / (2.0 * s);
-    gq[c] = (float)q;
-    if constexpr (FLOOR) { gm[c] = (float)dm; mm[c] = (float)m; }
-    else gm[c] = (float)(dm - 2.0 * m * q);
-  }
-  __syncthreads();
-  for (int t = wave; t < T; t += 4) {
-    double a = 0.0;
-    for (int c = lane; c < C; c += 64) {
-      const double xv = xb[(long long)t * C + c];
-      if constexpr (FLOOR) a += xv * ((double)gm[c] + (double)gq[c] * (xv - 2.0 * (double)mm[c]));
-      else a += xv * ((double)gm[c] + (double)gq[c] * xv);
-    }
-    a = dlip_wave_sum_f64(a);
-    if (lane == 0) dal[t] = (float)a;
-  }
-  __syncthreads();
-  double dot = 0.0;
-  for (int t = threadIdx.x; t < T; t += 256) dot += (double)ab[t] * (double)dal[t];
-  dot = dlip_block_sum4(dot, red);
-  for (int t = threadIdx.x; t < Tpad; t += 256) {
-    const float de = t < T ? (float)((double)ab[t] * ((double)dal[t] - dot)) : 0.f;
-    dal[t] = de;
-    de_out[(long long)b * Tpad + t] = de;
-  }
-  __syncthreads();
-  float* dxb = dx + (long long)b * Tpad * C;
-  for (long long i = threadIdx.x; i < (long long)Tpad * C; i += 256) {
-    const int t = (int)(i / C), c = (int)(i - (long long)t * C);
-    if constexpr (FLOOR) dxb[i] = t < T ? (float)((double)ab[t] * ((double)gm[c] + 2.0 * (double)gq[c] * ((double)xb[i] - (double)mm[c]))) : 0.f;
-    else dxb[i] = t < T ? ab[t] * (gm[c] + 2.f * xb[i] * gq[c]) : 0.f;
-  }
-  const float* hb = hidden + (long long)b * Tpad * Hd;
-  float* dhb = dhidden + (long long)b * Tpad * Hd;
-  float* rb = rde + (long long)b * Tpad * Hd;
-  for (long long i = threadIdx.x; i < (long long)Tpad * Hd; i += 256) {
-    const int t = (int)(i / Hd), j = (int)(i - (long long)t * Hd);
-    const float h = hb[i], de = dal[t];
-    dhb[i] = (t < T && h > 0.f) ? de * v[j] : 0.f;
-    rb[i] = t < T ? de * fmaxf(h, 0.f) : 0.f;
-  }
-}
-}  // namespace
-
-extern "C" int dlip_attentive_stat_pool_bwd_f32(const float* x, const float* hidden, const float* v, const float* alpha, const float* y,
-                                                const float* dy, const int32_t* len, int32_t len_add, float* dx, float* dhidden,
-                                                float* rde, float* de, int32_t B, int32_t T, int32_t C, int32_t Hd,
-                                                dlip_stream_t stream) {
-  DLIP_CHECK_ARG(x && hidden && v && alpha && y && dy && dx && dhidden && rde && de && B > 0 && T > 0 && C > 0 && Hd > 0);
-  const size_t lds = ((size_t)2 * C + T) * sizeof(float);
-  DLIP_CHECK_ARG(lds <= 60 * 1024);
-  DlipLen l; l.len = len; l.mul = 1; l.add = len_add;
-  hipLaunchKernelGGL(attentive_stat_bwd_kernel<false>, dim3(B), dim3(256), lds, dlip_hip_stream(stream), x, hidden, v, alpha, y, dy,
-                     dx, dhidden, rde, de, T, C, Hd, l);
-  return dlip_launch_status();
-}
-
-extern "C" int dlip_attentive_stat_pool_eps_bwd_f32(const float* x, const float* hidden, const float* v, const float* alpha,
-                                                    const float* y, const float* dy, const int32_t* len, int32_t len_add, float eps,
-                                                    float* dx, float* dhidden, float* rde, float* de, int32_t B, int32_t T, int32_t C,
-                                                    int32_t Hd, dlip_stream_t stream) {
-  DLIP_CHECK_ARG(x && hidden && v && alpha && y && dy && dx && dhidden && rde && de && B > 0 && T > 0 && C > 0 && Hd > 0);
-  DLIP_CHECK_ARG(eps > 0.f);   // what keeps the std read from y away from zero
-  const size_t lds = ((size_t)3 * C + T) * sizeof(float);
-  DLIP_CHECK_ARG(lds <= 60 * 1024);
-  DlipLen l; l.len = len; l.mul = 1; l.add = len_add;
-  hipLaunchKernelGGL(attentive_stat_bwd_kernel<true>, dim3(B), dim3(256), lds, dlip_hip_stream(stream), x, hidden, v, alpha, y, dy,
-                     dx, dhidden, rde, de, T, C, Hd, l);
-  return dlip_launch_status();
-}
-
-namespace {
 // Finisher of the pooled convolution epilogue (conv_igemm_f16x3_dma.hip, EPI 2): partials [tiles_m][4][Kp] fp64 =
 // per tile the column sums {sum, sumsq} of the rows before the tile's group boundary (segment 0) and after it
 // (segment 1).  Group g = rows [g Gs, (g+1) Gs) touches tiles g Gs / BM .. ((g+1) Gs - 1) / BM; in each it is

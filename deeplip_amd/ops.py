@@ -754,23 +754,8 @@ def time_valid_lengths(lengths: Tensor, shift: int, W: int) -> Tensor:
     return out
 
 
-def attentive_stat_pool_eps(x: Tensor, hidden: Tensor, v: Tensor, k: Tensor, eps: float, lengths: Optional[Tensor] = None,
-                            alpha_out: Optional[Tensor] = None) -> Tensor:
-    """x [B,T,C], hidden [B,T,Hd] (= x W^T + b) -> [B,2C] = cat(sum alpha x, sqrt(max(sum alpha x^2 - mean^2, 0) + eps)), alpha = softmax over
-    the first lengths[b] frames of relu(hidden) v + k (dlip_attentive_stat_pool_eps_f32)."""
-    for t, n in ((x, "x"), (hidden, "hidden"), (v, "v"), (k, "k"), (alpha_out, "alpha_out")):
-        _req(t, n)
-    _req(lengths, "lengths", torch.int32)
-    B, T, Cc = x.shape
-    if tuple(hidden.shape[:2]) != (B, T) or v.numel() != hidden.shape[2] or k.numel() != 1 or (lengths is not None and lengths.numel() != B):
-        raise ValueError("attentive_stat_pool_eps: x [B,T,C], hidden [B,T,Hd], v [Hd], k [1], one length per utterance or none")
-    y = _empty((B, 2 * Cc), x.device)
-    check(lib().dlip_attentive_stat_pool_eps_f32(ptr(x), ptr(hidden), ptr(v), ptr(k), ptr(lengths), 0, float(eps), ptr(y), ptr(alpha_out),
-                                                 B, T, Cc, hidden.shape[2], stream_handle()), "dlip_attentive_stat_pool_eps_f32")
-    return y
-
-
-# ---- multi-head attentive statistics pooling (csrc/mh_attn_pool_ops.hip, ABI 64; DESIGN.md 4h): deeplip_amd.audio.MultiHeadAttention ----
+# ---- attentive statistics pooling, one head or several (csrc/mh_attn_pool_ops.hip, ABI 64 / 67):
+# ---- deeplip_amd.audio.AttentiveStatPooling (n = 1) and deeplip_amd.audio.MultiHeadAttention
 MH_MAX_HEADS = 8
 MH_LDS_BYTES = 160 * 1024        # 3 n C floats of the backward's first pass
 
@@ -778,25 +763,27 @@ MH_LDS_BYTES = 160 * 1024        # 3 n C floats of the backward's first pass
 def mh_attn_check(n: int, T: int, C: int) -> None:
     """The limits of the dlip_mh_attn_* entry points as a ValueError that names them (the library answers DLIP_EINVAL)."""
     if not 1 <= n <= MH_MAX_HEADS:
-        raise ValueError(f"multi-head attentive pooling: 1 <= heads <= {MH_MAX_HEADS}, got {n}")
+        raise ValueError(f"attentive pooling: 1 <= heads <= {MH_MAX_HEADS}, got {n}")
     if T > 16000:
-        raise ValueError(f"multi-head attentive pooling: at most 16000 frames, got {T}")
+        raise ValueError(f"attentive pooling: at most 16000 frames, got {T}")
     if C % 4 or 12 * n * C > MH_LDS_BYTES:
-        raise ValueError(f"multi-head attentive pooling: C % 4 == 0 and 12 heads C <= {MH_LDS_BYTES} bytes of LDS, got heads {n}, C {C}")
+        raise ValueError(f"attentive pooling: C % 4 == 0 and 12 heads C <= {MH_LDS_BYTES} bytes of LDS, got heads {n}, C {C}")
 
 
-def mh_attn_scores(hidden: Tensor, v: Tensor, k: Tensor, head_off: Tensor, lengths: Optional[Tensor] = None, len_add: int = 0) -> Tensor:
-    """hidden [B,T,S] (= x W^T + b of all heads), v [S], k [n], head_off int32 CUDA [n+1] (prefix sums of the head widths) -> alpha [B,n,T]:
-    per head the softmax over the first lengths[b] + len_add frames of relu(hidden[..., head]) v[head] + k[h]; zeros behind
-    (dlip_mh_attn_scores_f32)."""
+def mh_attn_scores(hidden: Tensor, v: Tensor, k: Tensor, head_off: Optional[Tensor], lengths: Optional[Tensor] = None,
+                   len_add: int = 0) -> Tensor:
+    """hidden [B,T,S] (= x W^T + b of all heads), v [S], k [n], head_off int32 CUDA [n+1] (prefix sums of the head widths; None for one
+    head, which owns every column) -> alpha [B,n,T]: per head the softmax over the first lengths[b] + len_add frames of
+    relu(hidden[..., head]) v[head] + k[h]; zeros behind (dlip_mh_attn_scores_f32)."""
     for t, nm in ((hidden, "hidden"), (v, "v"), (k, "k")):
         _req(t, nm)
     _req(head_off, "head_off", torch.int32)
     _req(lengths, "lengths", torch.int32)
     B, T, S = hidden.shape
     n = k.numel()
-    if head_off is None or head_off.numel() != n + 1 or v.numel() != S or (lengths is not None and lengths.numel() != B):
-        raise ValueError("mh_attn_scores: hidden [B,T,S], v [S], k [n], head_off [n+1], one length per utterance or none")
+    if ((head_off is None and n != 1) or (head_off is not None and head_off.numel() != n + 1) or v.numel() != S
+            or (lengths is not None and lengths.numel() != B)):
+        raise ValueError("mh_attn_scores: hidden [B,T,S], v [S], k [n], head_off [n+1] (or None with n = 1), one length per utterance or none")
     alpha = _empty((B, n, T), hidden.device)
     check(lib().dlip_mh_attn_scores_f32(ptr(hidden), ptr(v), ptr(k), ptr(head_off), ptr(lengths), int(len_add), ptr(alpha), B, T, S, n,
                                         stream_handle()), "dlip_mh_attn_scores_f32")
@@ -805,7 +792,7 @@ def mh_attn_scores(hidden: Tensor, v: Tensor, k: Tensor, head_off: Tensor, lengt
 
 def mh_attn_stat_pool(x: Tensor, alpha: Tensor, eps: float, lengths: Optional[Tensor] = None, len_add: int = 0) -> Tensor:
     """x [B,T,C], alpha [B,n,T] -> [B, n 2C] = cat over heads of (sum alpha x | sqrt(max(sum alpha x^2 - mean^2, 0) + eps)), x read once
-    for all heads (dlip_mh_attn_stat_pool_f32)."""
+    for all heads (dlip_mh_attn_stat_pool_f32).  eps = 0: the reference's unfloored sqrt(sum alpha x^2 - mean^2) (pooling.py:106)."""
     _req(x, "x")
     _req(alpha, "alpha")
     _req(lengths, "lengths", torch.int32)

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define DLIP_ABI_VERSION 66
+#define DLIP_ABI_VERSION 67
 #define DLIP_HOST              /* marks a pointer parameter that the CPU dereferences during the call (HOST memory, not device) */
 #define DLIP_LIFT_BCAST 2048
 #define DLIP_LIFT_WORDS 4098   /* a gradient's power-of-two lift: (2^e, 2^-e), then 2^-e repeated DLIP_LIFT_BCAST times (the post_scale
@@ -289,24 +289,8 @@ int dlip_group_mean_f32(const float* x, const int32_t* group_ptr, float* y, int3
 int dlip_meanstd_pool_f32(const float* x, const int32_t* len, int32_t len_add, float* y, int32_t B, int32_t T, int32_t C,
                           int32_t out_split, dlip_stream_t stream);
 
-/* AttentiveStatPooling tail (models/audio_models/pooling.py:87-107) on N-T-C: hidden [B,T,Hd] = x W^T + b
- * (from dlip_conv_nhwc_f32), e = relu(hidden).v + k, alpha = softmax over T, y [B,2C] = weighted mean |
- * sqrt(weighted E[x^2] - mean^2).  len / len_add: as dlip_meanstd_pool_f32 (softmax and statistics over the valid frames). */
-int dlip_attentive_stat_pool_f32(const float* x, const float* hidden, const float* v, const float* k, const int32_t* len,
-                                 int32_t len_add, float* y, float* alpha_out, int32_t B, int32_t T, int32_t C, int32_t Hd,
-                                 dlip_stream_t stream);
-/* (ABI 45) alpha_out (nullable, [B,T]) of the entry point above: the attention weights, kept for the backward pass (zeros behind a
- * ragged utterance's end).  The backward of that tail for a training step (models/audio_models/pooling.py:87-107 under
- * model.train(), selected by the config's `pooling: attentive_statistic`, tdnn.py:66-75; train_audio.py:185-200): from y [B,2C]
- * and dy [B,2C], with g_q = ds / (2 s), g_m = dm - 2 m g_q:
- *   dx [B,T,C]      = alpha_t (g_m + 2 x g_q)                              (the statistics' direct path; zeros in padding frames)
- *   de [B,T]        = alpha_t (dalpha_t - sum_t' alpha_t' dalpha_t'),  dalpha_t = sum_c (g_m x + g_q x^2)
- *   dhidden [B,T,Hd]= de_t v_j [hidden > 0]      (through the GEMM's own backward: dW, db and the second path into x)
- *   rde [B,T,Hd]    = de_t relu(hidden)          (its column sums over B*T rows = dv; the sum of de = dk)
- * One workgroup per utterance, fp64 wherever a sum runs over channels or frames; (2 C + T) * 4 bytes of LDS <= 60 KB. */
-int dlip_attentive_stat_pool_bwd_f32(const float* x, const float* hidden, const float* v, const float* alpha, const float* y,
-                                     const float* dy, const int32_t* len, int32_t len_add, float* dx, float* dhidden, float* rde,
-                                     float* de, int32_t B, int32_t T, int32_t C, int32_t Hd, dlip_stream_t stream);
+/* (AttentiveStatPooling's tail, models/audio_models/pooling.py:87-107, and its backward: the dlip_mh_attn_* entry points below with
+ * n = 1 and eps = 0, ABI 67.) */
 
 /* Layout adapters at the API boundary.
  *   dlip_nct_to_ntc_f32: x [B,C,T] (reference layout, tdnn.py:89) -> y [B,T,Cp] zero-padded to Cp>=C.
@@ -1091,11 +1075,8 @@ int dlip_delta_nct_ragged_f32(const float* x, const int32_t* frame_lengths, floa
  * dlip_swap_axes_nhwc_f32: y[n, b, a, :] = x[n, a, b, :] for x [N,A,B,C] -- the copy [N,H,W,C] -> [N,W,H C] that makes each frame's
  *   D-vector contiguous for the attentive pooling's hidden-layer GEMM; its backward is the same call with A and B exchanged.
  * dlip_time_valid_lengths_i32: valid[n] = Wb as above, on the device -- the frame counts the attentive pooling kernels take as `len`.
- * dlip_attentive_stat_pool_eps_f32 / dlip_attentive_stat_pool_eps_bwd_f32 (pooling.py:87-107): dlip_attentive_stat_pool_f32 and its
- *   backward with std = sqrt(max(sum_t alpha x^2 - mean^2, 0) + eps); the same kernels behind a template argument, the entry
- *   points without eps keep their instruction sequence.  The backward takes the max as the identity (the weighted variance is >= 0
- *   in exact arithmetic) and forms dx from the centred value: dx = alpha_t (dmean + dstd (x - mean) / std), in fp64.  LDS of the
- *   backward: (3 C + T) floats <= 60 KiB.
+ * The attentive pooling itself (pooling.py:87-107 with std = sqrt(max(sum_t alpha x^2 - mean^2, 0) + eps)) is the dlip_mh_attn_* entry
+ *   points below with n = 1 and this eps (ABI 67).
  * ------------------------------------------------------------------------------------------ */
 int dlip_statpool_nhwc_f32(const float* x, const int32_t* lengths, int32_t shift, float eps, float* y, int32_t N, int32_t H, int32_t W,
                            int32_t C, dlip_stream_t stream);
@@ -1103,12 +1084,6 @@ int dlip_statpool_nhwc_bwd_f32(const float* x, const float* y, const float* dy, 
                                int32_t C, dlip_stream_t stream);
 int dlip_swap_axes_nhwc_f32(const float* x, float* y, int32_t N, int32_t A, int32_t B, int32_t C, dlip_stream_t stream);
 int dlip_time_valid_lengths_i32(const int32_t* lengths, int32_t shift, int32_t W, int32_t* valid, int32_t N, dlip_stream_t stream);
-int dlip_attentive_stat_pool_eps_f32(const float* x, const float* hidden, const float* v, const float* k, const int32_t* len,
-                                     int32_t len_add, float eps, float* y, float* alpha_out, int32_t B, int32_t T, int32_t C, int32_t Hd,
-                                     dlip_stream_t stream);
-int dlip_attentive_stat_pool_eps_bwd_f32(const float* x, const float* hidden, const float* v, const float* alpha, const float* y,
-                                         const float* dy, const int32_t* len, int32_t len_add, float eps, float* dx, float* dhidden,
-                                         float* rde, float* de, int32_t B, int32_t T, int32_t C, int32_t Hd, dlip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * (ABI 60) WAVEFORM AUGMENTATION in front of the audio front-end: what an x-vector recipe does to a training utterance before the
@@ -1266,25 +1241,29 @@ int dlip_wave_resample_f32(const float* wave, const int32_t* lengths, const floa
                            int32_t span_words, int32_t tile, dlip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
- * (ABI 64) MULTI-HEAD ATTENTIVE STATISTICS POOLING of both speech encoders (`pooling: multi_head_attention`, conf/audio_config.yaml:71,
- * conf/fusion_config.yaml:58; upstream `MultiHeadAttention(input_size, head=4, hidden_size=[100,200,300,400])` is an empty TODO class,
+ * (ABI 64) ATTENTIVE STATISTICS POOLING of both speech encoders, one head (`pooling: attentive_statistic`, pooling.py:73-107; on these
+ * entry points since ABI 67) or several (`pooling: multi_head_attention`, conf/audio_config.yaml:71, conf/fusion_config.yaml:58;
+ * upstream `MultiHeadAttention(input_size, head=4, hidden_size=[100,200,300,400])` is an empty TODO class,
  * models/audio_models/pooling.py:62-71: deeplip_amd/audio.py and DESIGN.md 4h are the definition).  n heads of widths Hd_h, S = sum Hd_h,
  * head_off = their prefix sums (DEVICE int32 [n + 1], head_off[0] = 0, head_off[n] = S; every value is clamped to [0, S] where it is
- * read, so a wrong array leaves no row).  x [B,T,C] fp32 channels-last, hidden [B,T,S] = x W^T + b for ALL heads (one GEMM in front),
- * v [S], k [n].  With L_b = clamp(len[b] + len_add, 0, T) valid frames (len / len_add as dlip_meanstd_pool_f32; NULL: T):
+ * read, so a wrong array leaves no row; NULL is allowed for n == 1 and means the one head owns the columns [0, S)).  x [B,T,C] fp32
+ * channels-last, hidden [B,T,S] = x W^T + b for ALL heads (one GEMM in front), v [S], k [n].  With L_b = clamp(len[b] + len_add, 0, T) valid frames (len / len_add as dlip_meanstd_pool_f32; NULL: T):
  *     e[b,h,t]     = relu(hidden[b,t,off_h:off_{h+1}]) . v[off_h:off_{h+1}] + k[h]
  *     alpha[b,h,:] = softmax over t < L_b of e[b,h,:]            (zeros for t >= L_b)
  *     m_h[c] = sum_t alpha x,   s_h[c] = sqrt(max(sum_t alpha x^2 - m_h^2, 0) + eps),   y[b] = cat_h [m_h | s_h]       [B, n 2C]
- * -- the concatenation of n dlip_attentive_stat_pool_eps_f32 results, from one read of hidden and one read of x.  Exact fp32 data, fp64
- * wherever a sum runs over frames, channels or hidden units, no atomics, the same bits on every run; padding frames of x and hidden are
- * never loaded.  1 <= n <= 8, T <= 16000, B <= 65535.
+ * -- n attentive statistics poolings (pooling.py:87-107) from one read of hidden and one read of x.  eps == 0 (ABI 67) is the
+ * reference's expression s_h[c] = sqrt(sum_t alpha x^2 - m_h^2) without floor: a feature that is constant over the valid frames gives
+ * 0, or NaN where rounding takes the difference below zero, forward and a non-finite gradient (0 / 0) backward, as in the reference.
+ * Exact fp32 data, fp64 wherever a sum runs over frames, channels or hidden units, no atomics, the same bits on every run; padding
+ * frames of x and hidden are never loaded.  1 <= n <= 8, T <= 16000, B <= 65535.
  *
  * dlip_mh_attn_scores_f32: alpha [B,n,T] from hidden.  One wave per frame reads the row's S floats once (segmented dot products); the
  *   softmax runs on a (head, utterance) grid with its maximum and its sum reduced across the workgroup.  S >= n.
  * dlip_mh_attn_stat_pool_f32: y from x and alpha on a (C / 64, utterance) grid like dlip_meanstd_pool_f32's: alpha is staged in LDS 256
  *   frames at a time, each x element is loaded once and feeds the 2 n accumulators of all heads.  C % 4 == 0, x 16-byte aligned,
- *   eps > 0, and the backward's LDS bound below (what could not be differentiated is refused here already).
- * dlip_mh_attn_stat_pool_bwd_f32: the single-head backward above in its floored, centred form per head, with g_q,h = ds_h / (2 s_h):
+ *   eps >= 0, and the backward's LDS bound below (what could not be differentiated is refused here already).
+ * dlip_mh_attn_stat_pool_bwd_f32: per head the chain through the root and the square on the centred value, with g_q,h = ds_h / (2 s_h)
+ *   (s_h read from y, so the floor of eps > 0 is taken as the identity: the weighted variance is >= 0 in exact arithmetic):
  *     dalpha[b,h,t]   = sum_c x (dm_h + g_q,h (x - 2 m_h))                         pass 1 over x, all heads at once
  *     de [B,n,T]      = alpha (dalpha - sum_t' alpha dalpha)                       (zeros behind L_b);  dek [B,n] = sum_t de (its column
  *                                                                                    sums over B = dk)
@@ -1292,9 +1271,10 @@ int dlip_wave_resample_f32(const float* wave, const int32_t* lengths, const floa
  *                                                                                    zeros in padding frames
  *     dhidden [B,T,S] = de[b,h(j),t] v_j [hidden > 0],   rde [B,T,S] = de[b,h(j),t] relu(hidden)       (column sums of rde = dv)
  *   Pass 1 runs on a (row range, utterance) grid with dm | g_q | m of every head in LDS: 3 n C floats <= 160 KiB (n = 4: C <= 3412, n = 8:
- *   C <= 1704; the E-TDNN's C = 1500 at n = 4 takes 70 KiB).  x, y, dy, dx 16-byte aligned, C % 4 == 0, S >= n, eps > 0 (the forward's;
+ *   C <= 1704; the E-TDNN's C = 1500 at n = 4 takes 70 KiB).  x, y, dy, dx 16-byte aligned, C % 4 == 0, S >= n, eps >= 0 (the forward's;
  *   checked, the std in y holds it).
- * DLIP_EINVAL before any launch: n outside [1, 8], T > 16000, B > 65535, the LDS bound, C % 4, alignment, a null pointer.
+ * DLIP_EINVAL before any launch: n outside [1, 8], T > 16000, B > 65535, the LDS bound, C % 4, alignment, eps < 0, a null pointer
+ *   (head_off with n >= 2 included).
  * ------------------------------------------------------------------------------------------ */
 int dlip_mh_attn_scores_f32(const float* hidden, const float* v, const float* k, const int32_t* head_off, const int32_t* len,
                             int32_t len_add, float* alpha, int32_t B, int32_t T, int32_t S, int32_t n, dlip_stream_t stream);

@@ -133,15 +133,21 @@ def test_ops_refuse_cpu_tensors():
         ops.swap_axes_nhwc(x)
     with pytest.raises(DeepLipHipError):
         ops.time_valid_lengths(lens, 1, 5)
+    with pytest.raises(DeepLipHipError):       # (the attentive head's tail: one head of the multi-head entry points, no offsets array)
+        ops.mh_attn_scores(torch.zeros(2, 5, 3), torch.zeros(3), torch.zeros(1), None)
     with pytest.raises(DeepLipHipError):
-        ops.attentive_stat_pool_eps(torch.zeros(2, 5, 12), torch.zeros(2, 5, 3), torch.zeros(3), torch.zeros(1), 1e-5)
+        ops.mh_attn_stat_pool(torch.zeros(2, 5, 12), torch.zeros(2, 1, 5), 1e-5)
 
 
 def test_library_exports_the_entry_points():
+    import test_abi_cpu as abi
     from deeplip_amd import _lib, build
     lib = ctypes.CDLL(build.build(verbose=False))
     for s in ("dlip_statpool_nhwc_f32", "dlip_statpool_nhwc_bwd_f32", "dlip_swap_axes_nhwc_f32", "dlip_time_valid_lengths_i32",
-              "dlip_attentive_stat_pool_eps_f32", "dlip_attentive_stat_pool_eps_bwd_f32"):
+              "dlip_mh_attn_scores_f32", "dlip_mh_attn_stat_pool_f32", "dlip_mh_attn_stat_pool_bwd_f32"):
         assert hasattr(lib, s), s
         assert s in _lib.SIGNATURES
-    assert lib.dlip_abi_version() == _lib.ABI_VERSION >= 59
+    # (ABI 67) the single-head kernels' four entry points are gone: attentive pooling is one head of the dlip_mh_attn_* family
+    for s in [f"dlip_attentive_stat_{p}_f32" for p in ("pool", "pool_bwd", "pool_eps", "pool_eps_bwd")]:
+        assert not hasattr(lib, s) and s not in _lib.SIGNATURES and s not in abi.header_symbols(), s
+    assert lib.dlip_abi_version() == _lib.ABI_VERSION == 67

@@ -88,16 +88,57 @@ def test_forward_and_backward_vs_fp64(name):
 
 
 def test_one_head_is_the_single_head_kernel():
-    from deeplip_amd import ops
+    """One head against the single-head definition (R.single_head in fp64); AttentiveStatPooling with the same parameters runs the same
+    kernels without an offsets array: the same bits."""
+    from models.audio_models.pooling import AttentiveStatPooling
     B, T, C, widths = CASES["one-head"]
     t, ref, _ = _case("one-head")
     pool = _module(t, C, widths)
     x = t["x"].to(DEV)
-    hidden = ops.linear(x.reshape(B * T, C), pool.W.detach().contiguous(), pool.b.detach().reshape(-1).contiguous()).view(B, T, -1)
-    single = ops.attentive_stat_pool_eps(x, hidden, pool.v.detach().reshape(-1).contiguous(), pool.k.detach().reshape(-1).contiguous(), R.EPS)
+    d = {k: v.double() for k, v in t.items()}
+    single = R.single_head(d["x"], d["W"], d["b"], d["v"], d["k"])
+    one = AttentiveStatPooling(C, widths[0])
     with torch.no_grad():
+        for k in ("W", "b", "v", "k"):
+            getattr(one, k).copy_(t[k])
         y = pool.run_ntc(x)
-    assert rel_err(y.cpu().numpy(), single.cpu().numpy()) < BAR_OUT
+        y1 = one.to(DEV).run_ntc(x, eps=R.EPS)
+    assert rel_err(y.cpu().numpy(), single.numpy()) < BAR_OUT
+    assert torch.equal(y, y1)
+
+
+def test_single_head_ragged_rows_without_floor():
+    """AttentiveStatPooling.run_ntc(x, lengths) with eps = 0 (the reference's unfloored root) on rows [41, 40, 2, 1] of a [4, 41, 64]
+    batch whose padding frames hold NaN and 1e30: every row equals the fp64 restatement of the row alone (a single frame has a zero
+    standard deviation on both sides) and is bit-identical to the row run as a batch of one at its own length."""
+    from models.audio_models.pooling import AttentiveStatPooling
+    B, T, C, H = 4, 41, 64, 16
+    lengths = [T, T - 1, 2, 1]
+    t = R.case_tensors(B, T, C, [H], seed=9)
+    d = {k: v.double() for k, v in t.items()}
+    pool = AttentiveStatPooling(C, H)
+    with torch.no_grad():
+        for k in ("W", "b", "v", "k"):
+            getattr(pool, k).copy_(t[k])
+    pool = pool.to(DEV).eval()
+    x = t["x"].clone()
+    for b, L in enumerate(lengths):
+        x[b, L:] = float("nan") if b % 2 else 1e30
+    with torch.no_grad():
+        y = pool.run_ntc(x.to(DEV), torch.tensor(lengths, dtype=torch.int32, device=DEV))
+        torch.cuda.synchronize()
+        assert bool(torch.isfinite(y).all())
+        for b, L in enumerate(lengths):
+            xr = d["x"][b:b + 1, :L]
+            e = torch.relu(xr.matmul(d["W"].t()) + d["b"]).matmul(d["v"]) + d["k"]
+            alpha = torch.softmax(e, dim=1)
+            m = (alpha * xr).sum(dim=1)
+            want = torch.cat([m, torch.sqrt((alpha * xr * xr).sum(dim=1) - m * m)], dim=1)      # pooling.py:103-106
+            e_b = rel_err(y[b:b + 1].cpu().numpy(), want.numpy())
+            print(f"\nrow {b} (L = {L}): y {e_b:.3e}, smallest std {float(want[0, C:].min()):.3e}", end="")
+            assert e_b < BAR_OUT, (b, L)
+            alone = pool.run_ntc(t["x"][b:b + 1, :L].contiguous().to(DEV))
+            assert torch.equal(alone, y[b:b + 1]), (b, L)
 
 
 def _launch(x, hidden, t, widths, lens):
@@ -179,7 +220,9 @@ def test_limits_are_refused_without_a_launch():
     assert L.dlip_mh_attn_stat_pool_f32(ptr(x), ptr(alpha), None, 0, 1e-5, ptr(y), B, 16001, C, 2, stream_handle()) == -1
     assert L.dlip_mh_attn_stat_pool_f32(ptr(big_x), ptr(big_alpha), None, 0, 1e-5, ptr(big_y), 1, 2, 1708, 8, stream_handle()) == -1   # LDS
     assert L.dlip_mh_attn_stat_pool_f32(ptr(x), ptr(alpha), None, 0, 1e-5, ptr(y), B, T, 6, 2, stream_handle()) == -1                  # C % 4
-    assert L.dlip_mh_attn_stat_pool_f32(ptr(x), ptr(alpha), None, 0, 0.0, ptr(y), B, T, C, 2, stream_handle()) == -1                   # eps
+    for bad in (-1e-5, float("nan")):       # eps < 0 (0 is the unfloored root since ABI 67)
+        assert L.dlip_mh_attn_stat_pool_f32(ptr(x), ptr(alpha), None, 0, bad, ptr(y), B, T, C, 2, stream_handle()) == -1
+    assert L.dlip_mh_attn_scores_f32(ptr(hid), ptr(v), ptr(k), None, None, 0, ptr(alpha), B, T, S, 2, stream_handle()) == -1            # no head_off, n = 2
     dx, dh, rde = torch.full_like(x, 7.0), torch.full_like(hid, 7.0), torch.full_like(hid, 7.0)
     de, dek = torch.full((B, 8, T), 7.0, device=DEV), torch.full((B, 8), 7.0, device=DEV)
     for n, TT in ((0, T), (9, T), (2, 16001)):
@@ -187,6 +230,10 @@ def test_limits_are_refused_without_a_launch():
                                                 ptr(rde), ptr(de), ptr(dek), B, TT, C, S, n, stream_handle()) == -1
     assert L.dlip_mh_attn_stat_pool_bwd_f32(ptr(big_x), ptr(hid), ptr(v), ptr(off), ptr(big_alpha), ptr(big_y), ptr(big_y), None, 0, 1e-5,
                                             ptr(big_x), ptr(dh), ptr(rde), ptr(de), ptr(dek), 1, 2, 1708, S, 8, stream_handle()) == -1
+    assert L.dlip_mh_attn_stat_pool_bwd_f32(ptr(x), ptr(hid), ptr(v), None, ptr(alpha), ptr(y), ptr(y), None, 0, 1e-5, ptr(dx), ptr(dh),
+                                            ptr(rde), ptr(de), ptr(dek), B, T, C, S, 2, stream_handle()) == -1                       # no head_off, n = 2
+    assert L.dlip_mh_attn_stat_pool_bwd_f32(ptr(x), ptr(hid), ptr(v), ptr(off), ptr(alpha), ptr(y), ptr(y), None, 0, -1e-5, ptr(dx), ptr(dh),
+                                            ptr(rde), ptr(de), ptr(dek), B, T, C, S, 2, stream_handle()) == -1                       # eps < 0
     torch.cuda.synchronize()
     for o in (alpha, y, big_y, dx, dh, rde, de, dek):
         assert bool((o == 7.0).all())

@@ -3,10 +3,11 @@
 last tensor, C = 1500 channels, T = 278 frames, head widths [100,200,300,400].
 
   train      B = 256: forward and backward of the pooling STAGE (hidden-layer GEMM + tail) through autograd, the fused route
-             (autograd.mh_attentive_stat_pool: one GEMM, the dlip_mh_attn_* kernels) against the COMPOSITION a user could build before them:
-             one autograd.attentive_stat_pool (the single-head _eps entry points) per head, torch.cat of the results -- autograd adds the
-             heads' dx tensors.  Same parameters, same x, same dy; the two outputs are compared before anything is timed.
-  extract    B = 64, ragged lengths: MultiHeadAttention.run_ntc against per-head ops.linear + ops.attentive_stat_pool_eps + torch.cat.
+             (autograd.mh_attentive_stat_pool: one GEMM, the dlip_mh_attn_* kernels with n heads) against the COMPOSITION of single heads:
+             one autograd.attentive_stat_pool (the same kernels with n = 1) per head, torch.cat of the results -- x is read n times
+             forward and 2 n times backward and autograd adds the heads' dx tensors.  Same parameters, same x, same dy; the two outputs
+             are compared before anything is timed.
+  extract    B = 64, ragged lengths: MultiHeadAttention.run_ntc against one AttentiveStatPooling.run_ntc per head + torch.cat.
   tail       the three entry points alone on preallocated tensors, and the bytes the algorithm needs over their time:
              scores = hidden once; stat = x once; bwd = x twice + dx + hidden + dhidden + rde.
 Device events around each call, interleaved rounds, medians.
@@ -165,12 +166,7 @@ def main():
     xe = (torch.randn((Be, T, C), generator=g) * 0.8 + 0.3).cuda()
 
     def comp_extract():
-        ys = []
-        for s in singles:
-            hid = ops.linear(xe.reshape(Be * T, C), s.W.detach().contiguous(), s.b.detach().reshape(-1).contiguous()).view(Be, T, -1)
-            ys.append(ops.attentive_stat_pool_eps(xe, hid, s.v.detach().reshape(-1).contiguous(), s.k.detach().reshape(-1).contiguous(),
-                                                  POOL_EPS, lengths=lens))
-        return torch.cat(ys, dim=1)
+        return torch.cat([s.run_ntc(xe, lens, eps=POOL_EPS) for s in singles], dim=1)
 
     with torch.no_grad():
         err = rel(pool.run_ntc(xe, lens), comp_extract())
