@@ -33,6 +33,7 @@ import yaml  # noqa: E402
 from deeplip_amd import _lib, arith, weightgen as wg  # noqa: E402
 from deeplip_amd.extract import RaggedExtractor  # noqa: E402
 from deeplip_amd.ragged import pad_stack  # noqa: E402
+from deeplip_amd.trainer_common import encoder_min_frames  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F, LMIN, LMAX = 40, 137, 412
@@ -90,7 +91,7 @@ def extraction(a):
         for mode in ("f32", "f16x3"):
             arith.configure(mode)
             D = net.embedding_dim
-            ex = RaggedExtractor(lambda x, l: net.extract_embedding(x, lengths=l)[0], None, dev, batch=a.batch, audio_min_frames=1)
+            ex = RaggedExtractor(lambda x, l: net.extract_embedding(x, lengths=l)[0], None, dev, batch=a.batch, audio_min_frames=encoder_min_frames(net))
             cache: dict = {}
             rows = torch.empty((n, D), device=dev)
 

@@ -30,6 +30,7 @@ import yaml  # noqa: E402
 
 from deeplip_amd import _lib, arith, weightgen as wg  # noqa: E402
 from deeplip_amd.frontend import AudioFrontend  # noqa: E402
+from deeplip_amd.trainer_common import encoder_min_frames  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -74,7 +75,7 @@ def extraction(a):
             feats, nf = fe(w, l)
             return net.extract_embedding(feats, lengths=nf)[0]
 
-        kw = dict(batch=a.batch, audio_min_frames=net.frames_consumed() + 2)
+        kw = dict(batch=a.batch, audio_min_frames=encoder_min_frames(net))
         ex_w = RaggedExtractor(wave_step, None, dev, wave_geometry=(fe.frame_len, fe.frame_step), **kw)
         ex_f = RaggedExtractor(lambda x, l: net.extract_embedding(x, lengths=l)[0], None, dev, **kw)
         cw, cf = {}, {}

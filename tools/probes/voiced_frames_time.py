@@ -155,6 +155,7 @@ def step(reps, B, NF):
     import yaml
     from deeplip_amd import packing, weightgen as wg
     from deeplip_amd.frontend import AudioFrontend
+    from deeplip_amd.trainer_common import encoder_min_frames
     from deeplip_amd.voiced_frames import VoicedFrames
     from models.audio_models.tdnn import SpeakerEmbNet
     with open(os.path.join(ROOT, "conf", "fusion_config.yaml")) as f:
@@ -173,7 +174,7 @@ def step(reps, B, NF):
     gate = (torch.rand((B, S // 4000 + 1), device="cuda") > 0.3).float().repeat_interleave(4000, dim=1)[:, :S]      # pauses of 0.25 s
     wave = (wave * gate).contiguous()
     # float waveforms around 1 put the log-energy near 4 where 16-bit samples put it near 18: the threshold moves with them
-    st = VoicedFrames(cmn_window=WINDOW, vad=dict(VAD, energy_threshold=-5.0), min_keep=net.frames_consumed() + 2)
+    st = VoicedFrames(cmn_window=WINDOW, vad=dict(VAD, energy_threshold=-5.0), min_keep=encoder_min_frames(net))
     with torch.no_grad():
         feats, nf = fe(wave, slen)
         y, ol = st(feats, nf)

@@ -13,10 +13,12 @@ whole encoder (conv dgrad / wgrad, BN and pooling backward as dlip_* launches --
 SGD over model + criterion parameters, MultiStepLR, margin schedule, per-epoch checkpoints and checkpoint
 averaging.  ``train.freeze_encoder: true`` keeps the older criterion-only step on frozen x-vectors.
 
-Round 6: a batch is cut to ONE crop length drawn from a short ladder over ``train.crop_frames`` (the collate's random crop,
+A batch is cut to ONE crop length drawn from a short ladder over ``train.crop_frames`` (the collate's random crop,
 models/audio_models/datasets.py:112-115) and the optimisation step is recorded once per crop length (and margin) and replayed
 (``train.graph_step``, ``--eager-step``); ragged test lists go through ONE extractor per trainer; ``--arith`` / ``model.arith`` pick the
-arithmetic (deeplip_amd/arith.py: auto = f16x3 with an in-process f32 re-run -- and calibration -- of what leaves its range).
+arithmetic (deeplip_amd/arith.py: auto = f16x3 with an in-process f32 re-run -- and calibration -- of what leaves its range).  The run
+plumbing (config + ``--set``, self-launch, run name, optimizer, ``main()``'s tail) and the speech input chain of extraction (front-end,
+voiced frames, encoder, the kept extractor) are deeplip_amd/trainer_common.py's, shared with train_fusion.py.
 
 Data parallelism (the reference wraps the model in nn.DataParallel over ``gpus_id``, train_audio.py:80-83): launched
 under ``torch.distributed.run`` every rank draws its own batches, replicas start from rank 0's weights, gradients are
@@ -32,14 +34,12 @@ import time
 
 import numpy as np
 import torch
-import yaml
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-from deeplip_amd import _lib, arith, dist as ddist, ops, scoring, weightgen as wg  # noqa: E402
+from deeplip_amd import _lib, arith, dist as ddist, ops, scoring, trainer_common as tc, weightgen as wg  # noqa: E402
 from deeplip_amd.synthetic import SyntheticAVSet, synthetic_trials  # noqa: E402
-from models.audio_models import tdnn  # noqa: E402
 from models.audio_models.loss import AAMSoftmax, ASoftmax, Contrastive, LMCL, CrossEntropy, OnlineTriplet  # noqa: E402
 
 
@@ -88,16 +88,8 @@ def build_criterion(train_opts, embedding_dim, n_spk):
 
 
 def build_model(model_opts, data_opts):
-    """The encoder the ``model`` section names (train_audio.py:60-68).  The ResNet's statistics poolings size their vector by the feature
-    dimension, which the ``data`` section knows: it is filled into the ``resnet`` sub-dict when that leaves ``feat_dim`` out."""
-    arch = model_opts["arch"]
-    if arch in ("tdnn", "etdnn"):
-        return tdnn.SpeakerEmbNet(model_opts)
-    if arch == "resnet":                                                     # train_audio.py:64-66 (`import models.resnet`)
-        import models.resnet as resnet
-        model_opts[arch].setdefault("feat_dim", int(data_opts.get("feat_dim", 40)))
-        return resnet.SpeakerEmbNet(model_opts)
-    raise NotImplementedError("Other models are not implemented!")           # train_audio.py:67-68
+    """The encoder the ``model`` section names, the ResNet's ``feat_dim`` filled in from the ``data`` section when it is left out."""
+    return tc.build_speech_encoder(model_opts, int(data_opts.get("feat_dim", 40)))
 
 
 def parse_wave_training(data_opts):
@@ -125,14 +117,7 @@ def parse_speed_perturb(data_opts):
 
 class Trainer(object):
     def __init__(self, config="conf/audio_config.yaml", overrides=None, arith_mode=None):
-        with open(os.path.join(ROOT, config)) as f:
-            opts = yaml.safe_load(f)
-        for k, v in (overrides or {}).items():
-            d = opts
-            *path, leaf = k.split(".")
-            for p in path:
-                d = d[p]
-            d[leaf] = v
+        opts = tc.load_config(ROOT, config, overrides)
         self.train_opts, self.model_opts = opts["train"], opts["model"]
         self.data_opts, self.test_opts = opts["data"], opts["test"]
         # data.train_from_waves / data.augment (build-owned, off by default): batches of WAVEFORMS, augmented on the device and turned
@@ -185,17 +170,13 @@ class Trainer(object):
         # (deeplip_amd/train_plan.py); a recorded step reads its learning rate from a device tensor, which MultiStepLR updates in
         # place, and takes the fused SGD kernel.  train.graph_step: false keeps the loop of eager launches.
         self.graph_step = bool(self.train_opts.get("graph_step", True)) and os.environ.get("DLIP_GRAPH_STEP", "1") != "0"
-        self.optim = self._make_sgd(groups, o)
+        self.optim = tc.make_optimizer("sgd", groups, o, self.graph_step, self.device)
         self._steps = None          # ShapeKeyedSteps, built with the first recorded step
-        self._extractor = None      # one RaggedExtractor for every list and epoch of this trainer (its recorded plans are kept)
+        self._extractor = tc.ExtractorCache()   # one RaggedExtractor for every list and epoch of this trainer (its recorded plans are kept)
         self._cohort = None         # (key, EmbeddingTable): the score-normalisation cohort of the current weights (build_cohort)
         self.lr_scheduler = torch.optim.lr_scheduler.MultiStepLR(self.optim, milestones=self.train_opts["lr_decay_step"], gamma=0.1)
         self.epoch, self.current_epoch = self.train_opts["epoch"], 0
-        self.log_time = time.asctime(time.localtime(time.time())).replace(" ", "_")[4:]
-        if ddist.active():          # one directory name for the job (rank 0's clock), identical replicas
-            name = [self.log_time]
-            torch.distributed.broadcast_object_list(name, 0)
-            self.log_time = name[0]
+        self.log_time = tc.run_name()
         ddist.broadcast_params(list(self.model.parameters()) + list(self.criterion.parameters()))
         self.buckets = None         # built on the first training step (gradient views need the final placement)
         self._wave_fe, self._augment = self._wave_stages(arch, F_) if self.train_from_waves else (None, None)
@@ -209,18 +190,9 @@ class Trainer(object):
         with as many coefficients as the TDNNs take, fbank with ``feat_dim`` bands for ``arch: resnet`` -- and, with ``data.augment``,
         the waveform augmentation in front of it (train_audio.py:454; a synthetic noise bank and synthetic room responses)."""
         from deeplip_amd.augment import WaveAugment
-        from deeplip_amd.frontend import AudioFrontend
         from deeplip_amd.synthetic import noise_bank, room_responses
         d = self.data_opts
-        feat = d.get("feat_type", "mfcc" if arch != "resnet" else "fbank")
-        geom = dict(rate=int(d.get("rate", 16000)), win_len=float(d.get("win_len", 0.025)), win_shift=float(d.get("win_shift", 0.01)),
-                    nfft=int(d.get("nfft", 512)), device=self.device)
-        if feat == "stft":              # log-magnitude spectrogram (datasets.py:72-76): nfft // 2 + 1 bins, nothing else to choose
-            fe = AudioFrontend("stft", **geom)
-        else:
-            fe = AudioFrontend(feat, num_cep=feat_dim, **geom, **({} if feat == "mfcc" else {"num_bin": feat_dim}))
-        if fe.feat_dim != feat_dim:
-            raise ValueError(f"data.train_from_waves: the front-end yields {fe.feat_dim} features, the encoder takes {feat_dim}")
+        fe = tc.frontend_from_section(d, arch, feat_dim, self.device, where="data.train_from_waves")
         if self.augment_opts is None:
             return fe, None
         import warnings
@@ -229,12 +201,6 @@ class Trainer(object):
             longest = fe.frame_len + (int(d["audio_frames"]) - 1) * fe.frame_step          # samples of the longest crop
             aug = WaveAugment(noise=noise_bank(max(5.0, 1.25 * longest / fe.rate), rate=fe.rate), rirs=room_responses(rate=fe.rate), device=self.device, **self.augment_opts)
         return fe, aug
-
-    def _make_sgd(self, groups, o):
-        if self.graph_step:
-            return torch.optim.SGD(groups, lr=torch.tensor(float(o["init_lr"]), device=self.device), momentum=o["momentum"],
-                                   weight_decay=o["weight_decay"], fused=True)
-        return torch.optim.SGD(groups, o["init_lr"], momentum=o["momentum"], weight_decay=o["weight_decay"])
 
     def crop_ladder(self):
         """The crop lengths of the training batches.  The reference's collate cuts every batch to ONE random length of 200 .. 400
@@ -273,7 +239,7 @@ class Trainer(object):
 
     def _adjust_margin(self):
         if isinstance(self.criterion, (LMCL, AAMSoftmax)):
-            self.criterion.margin = self.init_margin if self.current_epoch <= 5 else self.end_margin
+            tc.scheduled_margin(self.criterion, self.current_epoch, self.init_margin, self.end_margin)
 
     def _train_epoch(self):
         """train_audio.py:167-199 on the synthetic set: full-encoder step (or criterion-only with freeze_encoder)."""
@@ -490,50 +456,25 @@ class Trainer(object):
     def _ragged_extractor(self, batch):
         """The trainer's RaggedExtractor (built on first use, per batch size).  Its recorded plans address the model's packed
         weights: a plan whose weights changed since (training, a checkpoint load) is stale -- the extractor is rebuilt then."""
-        from deeplip_amd import holders
+        from deeplip_amd import holders, packing
         from deeplip_amd.extract import RaggedExtractor
-        from deeplip_amd import packing
-        key = (int(batch), holders.PACK_GEN[0], packing.state_version(self.model, self.device))
-        if self._extractor is not None and self._extractor[0] != key:
-            self._extractor[1].close()
-            self._extractor = None
-        if self._extractor is None:
-            stage = self._voiced_frames_stage()
 
-            def audio_fn(a, l):
-                if stage is not None:   # conf/audio_config.yaml:25: sliding CMN, then the voiced frames alone (a shorter row per utterance)
-                    a, l = stage(a, l)
-                return torch.cat(self.model.extract_embedding(a, lengths=l), dim=1)
-            ex = RaggedExtractor(audio_fn, None, self.device, batch=batch, audio_min_frames=self._min_frames())
-            self._extractor = (key, ex)
-        return self._extractor[1]
+        def build():
+            chain = tc.SpeechChain(self.model, voiced=self._voiced_frames_stage())
+            return RaggedExtractor(lambda a, l: torch.cat(chain(a, l), dim=1), None, self.device, batch=batch,
+                                   audio_min_frames=self._min_frames())
+        return self._extractor.get((int(batch), holders.PACK_GEN[0], packing.state_version(self.model, self.device)), build)
 
     def _voiced_frames_stage(self):
-        """The VoicedFrames stage of data.voiced_frames (None: off).  ``min_keep`` defaults to the encoder's minimum frame count: a row
-        the VAD leaves fewer frames keeps all of its frames, which the extractor has checked on the host."""
-        if self.voiced_frames_opts is None:
-            return None
-        from deeplip_amd.voiced_frames import VoicedFrames
-        o = dict(self.voiced_frames_opts)
-        if o["min_keep"] is None:
-            o["min_keep"] = self._min_frames()
-        if o["min_keep"] < self._min_frames():
-            raise ValueError(f"data.voiced_frames.min_keep: {o['min_keep']} is below the {self._min_frames()} frames the encoder needs")
-        return VoicedFrames(**o)
+        """The VoicedFrames stage of data.voiced_frames (None: off)."""
+        return tc.voiced_frames_stage(self.voiced_frames_opts, self._min_frames(), "data.voiced_frames")
 
     def _min_frames(self) -> int:
-        """The shortest utterance the encoder embeds.  The ResNet says itself (min_frames(): one frame -- zero-padded convolutions --
-        or what leaves two frames on its last map under `pooling: statistic`); for the TDNNs the frames their valid convolutions
-        consume + the two pooled frames the unbiased std needs (pooling.py:24-26)."""
-        if hasattr(self.model, "min_frames"):
-            return int(self.model.min_frames())
-        return self.model.frames_consumed() + 2
+        return tc.encoder_min_frames(self.model)
 
     def close(self):
         """Release the recorded extraction plans (their arenas) and the recorded training steps."""
-        if self._extractor is not None:
-            self._extractor[1].close()
-            self._extractor = None
+        self._extractor.close()
         self._steps = None
 
     def _load_for_extract(self, avg_only=False):
@@ -680,17 +621,9 @@ class Trainer(object):
         self.freeze_encoder = True
         param_groups = [{"params": self.criterion.parameters()}]
         kind = self.train_opts.get("type", "sgd")
-        if kind == "sgd":
-            self.optim = self._make_sgd(param_groups, self.train_opts["sgd"])
-        elif kind == "adam":
-            o = self.train_opts["adam"]
-            if self.graph_step:
-                self.optim = torch.optim.Adam(param_groups, lr=torch.tensor(float(o["init_lr"]), device=self.device),
-                                              weight_decay=o["weight_decay"], capturable=True, fused=True)
-            else:
-                self.optim = torch.optim.Adam(param_groups, o["init_lr"], weight_decay=o["weight_decay"])
-        else:
+        if kind not in ("sgd", "adam"):
             raise NotImplementedError(kind)
+        self.optim = tc.make_optimizer(kind, param_groups, self.train_opts[kind], self.graph_step, self.device)
         self.lr_scheduler = torch.optim.lr_scheduler.MultiStepLR(self.optim, milestones=self.train_opts["lr_decay_step"], gamma=0.1)
         self.buckets = None
         self._steps = None              # the recorded steps addressed the old optimizer's state
@@ -712,24 +645,6 @@ class Trainer(object):
         return scoring.eer_from_scores(y, s.cpu().numpy())
 
 
-def _self_launch(gpus, config, overrides, key="train.gpus_id"):
-    """Outside a torch.distributed job and asked for N > 1 GPUs (--gpus, or the config's gpus_id list): start the N-rank job
-    of this same command and return its exit code (deeplip_amd/launch.py); runs before anything touches the GPU."""
-    from deeplip_amd import launch
-    if launch.in_job():
-        return None
-    if gpus is None:
-        with open(os.path.join(ROOT, config) if not os.path.isabs(config) else config) as f:
-            d = yaml.safe_load(f)
-        ids = overrides.get(key)
-        if ids is None:
-            for part in key.split("."):
-                d = d.get(part, {}) if isinstance(d, dict) else {}
-            ids = d
-        gpus = len(ids) if isinstance(ids, (list, tuple)) else 1
-    return launch.maybe_self_launch(os.path.abspath(__file__), sys.argv[1:], gpus)
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", default="test", choices=["train", "test", "av_test", "av_fusion"])    # reference: hard-coded at :486
@@ -744,28 +659,23 @@ def main():
                          "length (train.graph_step: false)")
     arith.add_argument(ap)
     a = ap.parse_args()
-    rc = _self_launch(a.gpus, a.config, {k: yaml.safe_load(v) for k, v in (kv.split("=", 1) for kv in a.set)})
+    ov = tc.parse_set(a.set)
+    rc = tc.self_launch(__file__, a.gpus, a.config, ov)
     if rc is not None:
         sys.exit(rc)
-    ov = {k: yaml.safe_load(v) for k, v in (kv.split("=", 1) for kv in a.set)}
     if a.eager_step:
         ov["train.graph_step"] = False
     tr = Trainer(a.config, ov, arith_mode=a.arith)
     from models.audio_models import utils           # the scoring entry points, called as train_audio.py:499-543 calls them
 
-    def report(fn):
-        if tr.rank == 0:            # the store is on disk and complete (barrier in _store): one rank scores and prints
-            eer, threshold = fn(tr.log_time)
-            print("EER: {:.6f}%".format(eer * 100))
-
     if a.mode == "train":
         tr()
         tr.model_average(min(4, tr.epoch))
         tr.extract_test_xv()
-        report(utils.eer)
+        tc.report(tr, utils.eer)
     elif a.mode == "test":
         tr.extract_test_xv()
-        report(utils.eer)
+        tc.report(tr, utils.eer)
     else:                           # av_test: cosine / PLDA on the x-vectors (train_audio.py:504-520)
         if a.run:
             tr.log_time = a.run     # av_fusion scores the stores an earlier run left under exp/<run>/ (:521-543: extraction commented out)
@@ -777,15 +687,10 @@ def main():
             if a.mode == "av_test":
                 getattr(tr, "extract_test_xv_" + name)()
             if tr.test_opts.get("use_cos", True):
-                report(getattr(utils, "eer_cos_" + name + ("_featurefusion" if a.mode == "av_fusion" else "")))
+                tc.report(tr, getattr(utils, "eer_cos_" + name + ("_featurefusion" if a.mode == "av_fusion" else "")))
             if tr.test_opts.get("use_plda"):
-                report(getattr(utils, "eer_plda_" + name))
-    if tr.rank == 0 and arith.STATS["f32_reruns"]:
-        print("arith auto: {} batch(es) computed again in exact f32".format(arith.STATS["f32_reruns"]))
-    tr.close()
-    if ddist.active():
-        torch.distributed.barrier()
-        torch.distributed.destroy_process_group()
+                tc.report(tr, getattr(utils, "eer_plda_" + name))
+    tc.finish(tr)
 
 
 if __name__ == "__main__":

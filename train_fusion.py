@@ -16,10 +16,12 @@ three structural changes:
   * data parallel = one process per GPU over RCCL (gradient all-reduce of the trainable tail, one
     all-gather of test embeddings), replacing nn.DataParallel (:91-93).
 
-Round 6: ``--mode train`` runs the frozen encoders as a two-deep recorded pipeline (copies of batch i + 2 behind the encoders' work on
+``--mode train`` runs the frozen encoders as a two-deep recorded pipeline (copies of batch i + 2 behind the encoders' work on
 batch i + 1 behind the head's step on batch i) and the head's forward + backward + all-reduce + SGD as ONE recorded step
 (``train.graph_step``, ``--eager-step``); extraction keeps one RaggedExtractor per trainer (``test.batch``, ``test.frames: u8|f32``);
-``--arith`` / ``model.arith`` pick the arithmetic (auto = the benchmarked f16x3, out-of-range batches computed again in f32).
+``--arith`` / ``model.arith`` pick the arithmetic (auto = the benchmarked f16x3, out-of-range batches computed again in f32).  The run
+plumbing (config + ``--set``, self-launch, run name, optimizer, ``main()``'s tail) and the speech input chain of the test lists (resampler,
+front-end, voiced frames, encoder, the kept extractor) are deeplip_amd/trainer_common.py's, shared with train_audio.py.
 
     python train_fusion.py --mode train            # single GPU
     python train_fusion.py --mode train --gpus 8   # starts its own 8-rank job (deeplip_amd/launch.py); so does a config
@@ -37,16 +39,13 @@ import time
 import numpy as np
 import torch
 import torch.distributed as dist
-import yaml
-from torch import optim
 from torch.optim import lr_scheduler
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-from deeplip_amd import arith, dist as ddist, fusion, ops, scoring  # noqa: E402
+from deeplip_amd import arith, dist as ddist, fusion, ops, scoring, trainer_common as tc  # noqa: E402
 from deeplip_amd.synthetic import SyntheticAVSet, synthetic_trials  # noqa: E402
-from models.audio_models import tdnn  # noqa: E402
 from models.audio_models.loss import LMCL, CrossEntropy  # noqa: E402
 from models.fusion_models import LBP, model_fusion  # noqa: E402
 from models.video_models.model import Lipreading  # noqa: E402
@@ -54,14 +53,7 @@ from models.video_models.model import Lipreading  # noqa: E402
 
 class Trainer(object):
     def __init__(self, mode, config="conf/fusion_config.yaml", overrides=None, dry=False, arith_mode=None):
-        with open(os.path.join(ROOT, config) if not os.path.isabs(config) else config) as f:
-            opts = yaml.safe_load(f)
-        for k, v in (overrides or {}).items():      # e.g. {"train.bs": 8}
-            d = opts
-            *path, leaf = k.split(".")
-            for p in path:
-                d = d.setdefault(p, {}) if p == "python_data_config" else d[p]      # (an optional section: older configs lack it)
-            d[leaf] = v
+        opts = tc.load_config(ROOT, config, overrides)      # e.g. {"train.bs": 8}
         self.train_opts, self.model_opts = opts["train"], opts["model"]
         self.data_opts, self.test_opts = opts["data"], opts["test"]
         self.mode = mode
@@ -87,7 +79,7 @@ class Trainer(object):
             if self.source_rate == int(pdc.get("rate", 16000)):
                 raise ValueError(f"data.python_data_config.source_rate equals rate ({self.source_rate}): nothing to resample (leave the "
                                  "key out instead)")
-        self._extractor = None      # one RaggedExtractor for every list / epoch of this trainer (keeps its recorded plans)
+        self._extractor = tc.ExtractorCache()   # one RaggedExtractor for every list / epoch of this trainer (keeps its recorded plans)
         self._host_cache = {} if self.test_opts.get("cache_host_batches", False) else None
         self._steps = self._enc_pipe = self.buckets = None
         self.graph_step = bool(self.train_opts.get("graph_step", True)) and os.environ.get("DLIP_GRAPH_STEP", "1") != "0" and not dry
@@ -110,9 +102,7 @@ class Trainer(object):
                 raise RuntimeError("train_fusion.py needs a ROCm GPU: the deeplip_amd engine has no CPU path")
             torch.cuda.set_device(local)
             self.device = torch.device("cuda", local)
-            if "RANK" in os.environ and not dist.is_initialized():     # any torch.distributed.run job, a one-rank one included
-                os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-                dist.init_process_group("nccl", device_id=self.device)
+            ddist.init_from_env(self.device)     # any torch.distributed.run job, a one-rank one included
 
         d = self.data_opts
         acfg = self.model_opts["audio_config"]
@@ -139,13 +129,7 @@ class Trainer(object):
         if self.dry:
             return self._init_dry(acfg, n_spk)
 
-        if acfg["arch"] in ("tdnn", "etdnn"):
-            self.model_audio = tdnn.SpeakerEmbNet(acfg)
-        elif acfg["arch"] == "resnet":                                       # train_audio.py:64-66 (`import models.resnet`)
-            import models.resnet as resnet
-            self.model_audio = resnet.SpeakerEmbNet(acfg)
-        else:
-            raise NotImplementedError("Other models are not implemented!")
+        self.model_audio = tc.build_speech_encoder(acfg, feat_dim)
         vcfg = self.model_opts["video_config"]
         if vcfg["arch"] == "tcn":
             t = vcfg["tcn"]
@@ -204,24 +188,14 @@ class Trainer(object):
     def _init_optim(self):
         # constants kept as parameters (the count sketches of compact_bilinear) stay out of the update, weight decay and gradient buckets
         param_groups = [{"params": [p for p in self.model_fusion.parameters() if p.requires_grad]}, {"params": self.criterion.parameters()}]
-        if self.train_opts["optimizer"] == "sgd":
-            o = self.train_opts["sgd"]
-            if self.graph_step:     # a recorded step reads its learning rate from a device tensor (MultiStepLR updates it in place)
-                self.optim = optim.SGD(param_groups, lr=torch.tensor(float(o["init_lr"]), device=self.device), momentum=o["momentum"],
-                                       weight_decay=o["weight_decay"], fused=True)
-            else:
-                self.optim = optim.SGD(param_groups, o["init_lr"], momentum=o["momentum"], weight_decay=o["weight_decay"])
-        else:
+        if self.train_opts["optimizer"] != "sgd":
             raise NotImplementedError(self.train_opts["optimizer"])
+        self.optim = tc.make_optimizer("sgd", param_groups, self.train_opts["sgd"], self.graph_step, self.device)
         self.epoch = self.train_opts["epoch"]
         self.resume_audio = self.train_opts["audio_config"]["resume"]
         self.resume_video = self.train_opts["video_config"]["resume"]
         self.resume_fusion = self.train_opts["resume"]
-        self.log_time = time.asctime(time.localtime(time.time())).replace(" ", "_")[4:]
-        if ddist.active():          # one run directory for the job: rank 0's clock
-            name = [self.log_time]
-            dist.broadcast_object_list(name, 0)
-            self.log_time = name[0]
+        self.log_time = tc.run_name()
         self.lr_scheduler = lr_scheduler.MultiStepLR(self.optim, milestones=self.train_opts["lr_decay_step"], gamma=0.1)
         self.current_epoch = 0
         if not self.dry:
@@ -234,7 +208,7 @@ class Trainer(object):
     # ------------------------------------------------------------------ training
     def _adjust_margin(self):
         if isinstance(self.criterion, LMCL):
-            self.criterion.margin = self.init_margin if self.current_epoch <= 5 else self.end_margin
+            tc.scheduled_margin(self.criterion, self.current_epoch, self.init_margin, self.end_margin)
 
     def _train(self):
         for epoch in range(self.current_epoch + 1, self.epoch + 1):
@@ -482,82 +456,38 @@ class Trainer(object):
         address their packed weights) or the batch size did."""
         from deeplip_amd import holders, packing
         from deeplip_amd.extract import RaggedExtractor
-        key = (int(batch), holders.PACK_GEN[0], packing.state_version(self.model_audio, self.device), packing.state_version(self.model_video, self.device))
-        if self._extractor is not None and self._extractor[0] != key:
-            self._extractor[1].close()
-            self._extractor = None
-        if self._extractor is None:
-            arch = self.model_opts["audio_config"]["arch"]
-            audio_fn = lambda a, l: self.model_audio.extract_embedding(a, lengths=l)[0]                    # train_fusion.py:338
-            geom = {}
-            min_frames = 1 if arch == "resnet" else self.model_audio.frames_consumed() + 2
-            if self.test_from_waves:
-                fe = self._test_frontend(arch)
-                stage = self._voiced_frames_stage(min_frames)
 
-                rs = None
+        def build():
+            arch = self.model_opts["audio_config"]["arch"]
+            min_frames = tc.encoder_min_frames(self.model_audio)
+            chain = tc.SpeechChain(self.model_audio)
+            if self.test_from_waves:     # front-end and encoder in one recorded step
+                chain.frontend, chain.voiced = self._test_frontend(arch), self._voiced_frames_stage(min_frames)
                 if self.source_rate is not None:
                     from deeplip_amd.resample import Resample
-                    rs = Resample(self.source_rate, fe.rate, device=self.device)
-
-                def audio_fn(wave, sample_len):  # front-end and encoder in one recorded step; the frame lengths stay on the device
-                    if rs is not None:           # datasets.py:459-463: the recording's rate -> the configured one (a row of another length)
-                        wave, sample_len = rs(wave, sample_len)
-                    feats, n_frames = fe(wave, sample_len)
-                    if stage is not None:        # conf/audio_config.yaml:25: sliding CMN, then the voiced frames alone (a shorter row)
-                        feats, n_frames = stage(feats, n_frames)
-                    return self.model_audio.extract_embedding(feats, lengths=n_frames)[0]
-                geom = {"wave_geometry": fe if fe.feat_type == "stft" else (fe.frame_len, fe.frame_step)}
-                if rs is not None:               # every sample count the extractor handles is at the source rate
-                    from deeplip_amd.resample import ResampledGeometry
-                    geom = {"wave_geometry": ResampledGeometry(fe, rs)}
-            ex = RaggedExtractor(audio_fn,
-                                 lambda v, l: self.model_video.embed(v, lengths=l),                        # :346-348 (mean over T)
-                                 self.device, batch=batch, audio_min_frames=min_frames,
-                                 max_arena_bytes=int(self.test_opts.get("max_arena_gb", 64)) << 30, **geom)
-            self._extractor = (key, ex)
-        return self._extractor[1]
+                    chain.resample = Resample(self.source_rate, chain.frontend.rate, device=self.device)
+            geom = {"wave_geometry": chain.wave_geometry} if self.test_from_waves else {}
+            return RaggedExtractor(lambda a, l: chain(a, l)[0],                                            # train_fusion.py:338
+                                   lambda v, l: self.model_video.embed(v, lengths=l),                      # :346-348 (mean over T)
+                                   self.device, batch=batch, audio_min_frames=min_frames,
+                                   max_arena_bytes=int(self.test_opts.get("max_arena_gb", 64)) << 30, **geom)
+        return self._extractor.get((int(batch), holders.PACK_GEN[0], packing.state_version(self.model_audio, self.device),
+                                    packing.state_version(self.model_video, self.device)), build)
 
     def _test_frontend(self, arch):
-        """The loaders' feature extraction (data.python_data_config; models/audio_models/datasets.py:65-83) as the GPU front-end, with as
-        many coefficients / bands as the speech encoder takes; ``feat_type: stft`` yields nfft // 2 + 1 bins, which the encoder's
-        feat_dim must equal."""
-        from deeplip_amd.frontend import AudioFrontend
-        o = self.feat_opts
-        feat = o.get("feat_type", "mfcc" if arch != "resnet" else "fbank")
-        # voiced_frames with a CMN window: the sliding mean replaces the whole-utterance CMVN (raw features leave the front-end)
+        """The front-end of the test lists' waveforms (data.python_data_config).  voiced_frames with a CMN window: the sliding mean
+        replaces the whole-utterance CMVN (raw features leave the front-end)."""
         vf = self.voiced_frames_opts
-        norm = {} if vf is None or vf["cmn_window"] is None else {"normalize": False}
-        if feat == "stft":
-            fe = AudioFrontend("stft", rate=int(o.get("rate", 16000)), win_len=float(o.get("win_len", 0.025)),
-                               win_shift=float(o.get("win_shift", 0.01)), nfft=int(o.get("nfft", 512)), device=self.device, **norm)
-            if fe.feat_dim != self.feat_dim:
-                raise ValueError(f"data.python_data_config.test_from_waves: the front-end yields {fe.feat_dim} features, the encoder "
-                                 f"takes {self.feat_dim}")
-            return fe
-        return AudioFrontend(feat, rate=int(o.get("rate", 16000)), win_len=float(o.get("win_len", 0.025)), win_shift=float(o.get("win_shift", 0.01)),
-                             nfft=int(o.get("nfft", 512)), num_cep=self.feat_dim, device=self.device, **norm,
-                             **({} if feat == "mfcc" else {"num_bin": self.feat_dim}))
+        return tc.frontend_from_section(self.feat_opts, arch, self.feat_dim, self.device, normalize=vf is None or vf["cmn_window"] is None,
+                                        where="data.python_data_config.test_from_waves")
 
     def _voiced_frames_stage(self, min_frames):
-        """The VoicedFrames stage of data.python_data_config.voiced_frames (None: off).  ``min_keep`` defaults to the encoder's minimum
-        frame count: a row the VAD leaves fewer frames keeps all of its frames, which the extractor has checked on the host."""
-        if self.voiced_frames_opts is None:
-            return None
-        from deeplip_amd.voiced_frames import VoicedFrames
-        o = dict(self.voiced_frames_opts)
-        if o["min_keep"] is None:
-            o["min_keep"] = int(min_frames)
-        if o["min_keep"] < min_frames:
-            raise ValueError(f"data.python_data_config.voiced_frames.min_keep: {o['min_keep']} is below the {min_frames} frames the "
-                             "speech encoder needs")
-        return VoicedFrames(**o)
+        """The VoicedFrames stage of data.python_data_config.voiced_frames (None: off)."""
+        return tc.voiced_frames_stage(self.voiced_frames_opts, min_frames, "data.python_data_config.voiced_frames")
 
     def close(self):
         """Release the recorded plans (extraction arenas, the training pipeline) this trainer holds."""
-        if self._extractor is not None:
-            self._extractor[1].close()
-            self._extractor = None
+        self._extractor.close()
         if self._enc_pipe is not None:
             self._enc_pipe[1].close()
             self._enc_pipe = None
@@ -697,25 +627,6 @@ class _DryCriterion(torch.nn.Module):
         return torch.nn.functional.cross_entropy(output, labels), output
 
 
-def _self_launch(gpus, config, overrides, key):
-    """One command starts every GPU (the reference: gpus_id -> nn.DataParallel).  Outside a torch.distributed job and asked
-    for N > 1 GPUs -- by --gpus or by the length of the config's gpus_id list -- this process becomes the launcher of an
-    N-rank job of the same command (deeplip_amd/launch.py) and returns its exit code; nothing has touched the GPU yet."""
-    from deeplip_amd import launch
-    if launch.in_job():
-        return None
-    if gpus is None:
-        with open(os.path.join(ROOT, config) if not os.path.isabs(config) else config) as f:
-            d = yaml.safe_load(f)
-        ids = overrides.get(key)
-        if ids is None:
-            for part in key.split("."):
-                d = d.get(part, {}) if isinstance(d, dict) else {}
-            ids = d
-        gpus = len(ids) if isinstance(ids, (list, tuple)) else 1
-    return launch.maybe_self_launch(os.path.abspath(__file__), sys.argv[1:], gpus)
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", default="av_test", choices=["train", "av_test", "av_fusion"])   # reference: hard-coded at :424
@@ -735,15 +646,12 @@ def main():
                          "(data.python_data_config.test_from_waves: true; needs data.test_ragged)")
     arith.add_argument(ap)
     args = ap.parse_args()
-    ov = {}
-    for kv in args.set:
-        k, v = kv.split("=", 1)
-        ov[k] = yaml.safe_load(v)
+    ov = tc.parse_set(args.set)
     if args.eager_step:
         ov["train.graph_step"] = False
     if args.from_waves:
         ov["data.python_data_config.test_from_waves"] = True
-    rc = _self_launch(args.gpus, args.config, ov, "train.gpus_id")
+    rc = tc.self_launch(__file__, args.gpus, args.config, ov)
     if rc is not None:
         sys.exit(rc)
     if args.dry:
@@ -757,19 +665,9 @@ def main():
                    "exp/{}/dry_rank{}.pt".format(trainer.log_time, trainer.rank))
         if trainer.rank == 0:
             print("DRY (stand-in arithmetic, nothing of the engine ran): {} rank(s), run {}".format(trainer.world, trainer.log_time), flush=True)
-        if dist.is_initialized():
-            dist.barrier()
-            dist.destroy_process_group()
-        return
+        return tc.finish(trainer)
     trainer = Trainer(args.mode, args.config, ov, arith_mode=args.arith)
     from models.fusion_models import utils          # the scoring entry points, called as train_fusion.py:430-469 calls them
-
-    def report(fn):
-        # every rank extracted its shard and holds the gathered tables; the store is on disk: rank 0 scores and prints
-        if trainer.rank == 0:
-            eer, threshold = fn(trainer.log_time)
-            print("EER: {:.6f}%".format(eer * 100))
-
     if args.mode == "train":
         trainer()
         if trainer.test_opts.get("model_average", False):      # commented out upstream (train_fusion.py:428)
@@ -777,21 +675,16 @@ def main():
                 dist.barrier()
             trainer.model_average(min(2, trainer.epoch))
         trainer.extract_test_xv_lomgrid()
-        report(utils.eer_cos_lomgrid_featurefusion)
+        tc.report(trainer, utils.eer_cos_lomgrid_featurefusion)
     else:
         sets = [(s, getattr(trainer, "extract_test_xv_" + s)) for s in ("lomgrid", "grid") if trainer.test_opts["eval_" + s]]
         for name, extract in sets:
             extract()
             if trainer.test_opts["use_cos"]:
-                report(getattr(utils, "eer_cos_" + name + ("" if args.mode == "av_test" else "_scorefusion")))
+                tc.report(trainer, getattr(utils, "eer_cos_" + name + ("" if args.mode == "av_test" else "_scorefusion")))
             if trainer.test_opts["use_plda"]:
-                report(getattr(utils, "eer_plda_" + name))
-    if trainer.rank == 0 and arith.STATS["f32_reruns"]:
-        print("arith auto: {} batch(es) computed again in exact f32".format(arith.STATS["f32_reruns"]))
-    trainer.close()
-    if dist.is_initialized():
-        dist.barrier()
-        dist.destroy_process_group()
+                tc.report(trainer, getattr(utils, "eer_plda_" + name))
+    tc.finish(trainer)
 
 
 if __name__ == "__main__":
