@@ -1352,6 +1352,48 @@ int dlip_contrastive_loss_f32(const float* x, const int32_t* labels, float margi
                               dlip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * (ABI 67, added) SPECAUGMENT ON THE FEATURE BATCH (Park et al. 2019): a time warp, then frequency masks, then time masks -- the one
+ * augmentation of a speaker-embedding recipe that acts on the features, and the only one the feature-fed training path can take
+ * (`data.spec_augment` of conf/audio_config.yaml).  Nothing upstream defines the stage: this block and DESIGN.md 4j are the definition.
+ *
+ * dlip_spec_augment_f32: x, y fp32 [B, C, NF] -- the front-end's layout, features by frames, frames contiguous (the ResNet's
+ *   [B, 1, F, T] is the same memory with C = F); y must not be x.  `lengths` (device int32 [B], nullable): row b holds
+ *   n = clamp(lengths[b], 1, NF) frames (NF when NULL); frames t >= n of x are never loaded (the padding may hold NaN), frames t >= n of
+ *   y are exact zeros.  `draws`: device int32 [B, DLIP_SPECAUG_DRAWS], DLIP_SPECAUG_DRAWS = 2 + 4 DLIP_SPECAUG_MAX_MASKS, each word a 31-bit
+ *   uniform integer (negatives are taken as 0) that the DEVICE resolves against the row's length -- the host never sees n behind
+ *   VoicedFrames or in a recorded plan, so it draws length-free integers:  pick(r, m) = (int64(r) m) >> 31, in [0, m).  Per row:
+ *   [0] warp centre, [1] warp shift, then (width, start) of each of the MAX_MASKS frequency masks, then (width, start) of each of the
+ *   MAX_MASKS time masks; slots past n_freq / n_time are ignored.
+ *   Time warp (warp = W >= 0): We = min(W, (n - 3) / 2) (integer division; 0 for n < 3); We < 1: none.  Else c = We + 1 + pick(r0, n - 2 -
+ *   2 We), d = pick(r1, 2 We + 1) - We, c' = c + d (1 <= c, c' <= n - 2).  Output frame t reads the source position s = (t c) / c' for
+ *   t <= c', s = c + ((t - c')(n - 1 - c)) / (n - 1 - c') behind it (integer products in 64 bits, converted to fp64, ONE fp64 division):
+ *   i = min(floor(s), n - 2), a = (float)(s - i), v[f, t] = fmaf(a, x[f, i + 1] - x[f, i], x[f, i]) with the difference in fp32; a == 0
+ *   takes x[f, i] and a == 1 (only frame n - 1) takes x[f, i + 1] as they are, so frames 0, c' and n - 1 hold their sources' bits and
+ *   frames 0 and n - 1 stay in place.  d == 0 leaves the row bit for bit.
+ *   Frequency masks (i < n_freq): w = pick(r, min(freq_width, C) + 1), f0 = pick(r', C - w + 1): features [f0, f0 + w).
+ *   Time masks (j < n_time): cap = min(time_width, (int)floor(time_ratio (double)n)) (the product in fp64), w = pick(r, cap + 1),
+ *   t0 = pick(r', n - w + 1): frames [t0, t0 + w).  time_ratio = 1: no adaptive cap beyond the row itself.
+ *   y[f, t] = the fill value where any mask covers (f, t), else v[f, t]: masks apply after the warp and may overlap.  fill = 0: exact
+ *   zeros (the row's mean after CMVN).  fill = 1: the mean of the row's own INPUT over f < C, t < n -- a first launch of
+ *   DLIP_SPECAUG_MEAN_PARTS fp64 partial sums per row into the workspace, in an order (C, n) alone decide, no atomics; rounded to fp32
+ *   once, every masked entry of the row holds those bits.
+ *   A row has the same bits whatever B, NF, its neighbours and the launch geometry are; full lengths give the bits of lengths == NULL.
+ *   Lanes run along time (one 4-byte access per lane; one 16-byte access where NF % 4 == 0 and x, y are 16-byte aligned); a workgroup
+ *   resolves its frames' (i, a, time-mask bit) once and walks a contiguous range of features with them.  Launches: 1, 2 with fill = 1.
+ *   DLIP_EINVAL before any launch: B, C or NF < 1 (B <= 65535), a negative warp, freq_width or time_width, a mask count outside
+ *   [0, DLIP_SPECAUG_MAX_MASKS], time_ratio outside [0, 1] or NaN, fill outside {0, 1}, y == x, a null pointer (lengths excepted), a
+ *   workspace that is misaligned (8 bytes) or smaller than dlip_spec_augment_workspace_bytes says.
+ * dlip_spec_augment_workspace_bytes (host only, no launch): bytes of the caller-owned workspace; negative on bad sizes.
+ * ------------------------------------------------------------------------------------------ */
+#define DLIP_SPECAUG_MAX_MASKS 8
+#define DLIP_SPECAUG_DRAWS 34      /* 2 + 4 * DLIP_SPECAUG_MAX_MASKS */
+#define DLIP_SPECAUG_MEAN_PARTS 8
+int64_t dlip_spec_augment_workspace_bytes(int32_t B, int32_t C, int32_t NF);
+int dlip_spec_augment_f32(const float* x, const int32_t* lengths, const int32_t* draws, float* y, void* workspace,
+                          int64_t workspace_bytes, int32_t B, int32_t C, int32_t NF, int32_t warp, int32_t n_freq, int32_t freq_width,
+                          int32_t n_time, int32_t time_width, double time_ratio, int32_t fill, dlip_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Step plans. The reference drives its encoders from a Python loop, one utterance and one torch.nn layer
  * at a time (train_fusion.py:338-358 extraction, :262-293 training step); here a step is ~45 short kernels
  * and the host must not sit between them.  A plan records every dlip_* launch made on `stream` between

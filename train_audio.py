@@ -115,6 +115,14 @@ def parse_speed_perturb(data_opts):
     return sp
 
 
+def parse_spec_augment(data_opts):
+    """The keyword arguments of ``deeplip_amd.spec_augment.SpecAugment`` a ``data`` section names (``data.spec_augment``; host only), or
+    None for an absent one.  The stage acts on the feature batch, so it needs no ``data.train_from_waves``: it is the one augmentation
+    the feature-fed path takes.  Unknown keys, counts and widths out of range and a section that would do nothing raise ValueError."""
+    from deeplip_amd.spec_augment import parse_spec_augment_section
+    return parse_spec_augment_section(data_opts.get("spec_augment"))
+
+
 class Trainer(object):
     def __init__(self, config="conf/audio_config.yaml", overrides=None, arith_mode=None):
         opts = tc.load_config(ROOT, config, overrides)
@@ -125,6 +133,9 @@ class Trainer(object):
         self.train_from_waves, self.augment_opts = parse_wave_training(self.data_opts)
         # data.speed_perturb (build-owned, absent = off): each training row resampled at a drawn speed in front of the augmentation
         self.speed_opts = parse_speed_perturb(self.data_opts)
+        # data.spec_augment (build-owned, absent = off): time warp, frequency and time masks on the feature batch in front of the step,
+        # on the feature-fed path and from waves alike; evaluation and extraction never see it
+        self.spec_opts = parse_spec_augment(self.data_opts)
         # data.voiced_frames (build-owned, absent = off): sliding-window CMN + energy-VAD frame selection in front of the encoder on the
         # feature-fed ragged test lists -- the `nn_input` / `plda_input` pipe (conf/audio_config.yaml:21,25; deeplip_amd/voiced_frames.py).
         from deeplip_amd.voiced_frames import parse_voiced_frames_section
@@ -184,6 +195,10 @@ class Trainer(object):
         if self.speed_opts is not None:
             from deeplip_amd.resample import SpeedPerturb
             self._speed = SpeedPerturb(device=self.device, **self.speed_opts)
+        self._spec = None
+        if self.spec_opts is not None:
+            from deeplip_amd.spec_augment import SpecAugment
+            self._spec = SpecAugment(device=self.device, **self.spec_opts)
 
     def _wave_stages(self, arch, feat_dim):
         """data.train_from_waves: the loaders' feature extraction (models/audio_models/datasets.py:65-83) as the GPU front-end -- MFCC
@@ -301,6 +316,8 @@ class Trainer(object):
                 else:
                     t0_ = int(rng.integers(0, Ta - T + 1))
                     xb = np.ascontiguousarray(self.trainset.audio(idx)[:, :, t0_:t0_ + T])   # the batch's one crop (datasets.py:112-115)
+                if self._spec is not None:              # data.spec_augment, drawn last of all: a run without the section keeps its stream
+                    extra += (torch.from_numpy(self._spec.draw(bs, rng)["draws"]).pin_memory(),)
                 hb = (torch.from_numpy(xb).pin_memory(), torch.from_numpy(self.trainset.labels(idx)).pin_memory()) + extra
                 if n_cache > 0:
                     cache[k] = hb
@@ -330,10 +347,15 @@ class Trainer(object):
             cur = torch.cuda.current_stream(self.device)
             cur.wait_event(ev)
             x.record_stream(cur); lab.record_stream(cur)
+            for t in extra:
+                t.record_stream(cur)
+            if self._spec is not None:
+                *extra, spec_draws = extra
             if self.train_from_waves:
-                for t in extra:
-                    t.record_stream(cur)
                 x = features(x, extra)
+            if self._spec is not None:   # on the feature batch, directly in front of the step and outside the recorded graph
+                with torch.no_grad():
+                    x = self._spec(x, params={"draws": spec_draws})
             if anneal is not None:
                 anneal()                 # ASoftmax: lambda of this step, written on the device in front of the step, outside the recorded graph
             if recorded:
@@ -360,6 +382,8 @@ class Trainer(object):
             self.last_epoch_stats.update(from_waves=True, augment=None if self.augment_opts is None else dict(self.augment_opts))
             if self.speed_opts is not None:
                 self.last_epoch_stats.update(speed_perturb=dict(self.speed_opts))
+        if self.spec_opts is not None:
+            self.last_epoch_stats.update(spec_augment=dict(self.spec_opts))
         self.model.eval()
         return tot / n
 
