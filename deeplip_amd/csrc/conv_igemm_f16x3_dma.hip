@@ -120,10 +120,15 @@ __device__ __forceinline__ int sk_group_tiles(const StreamK&) { return 0; }
 template <bool GROUPED> struct StreamKOf { typedef StreamK type; };
 template <> struct StreamKOf<true> { typedef StreamKG type; };
 
-template <int BM, int BN, int WAVES_M, int WAVES_N, int EPI, int NSTAGE, int OCC, bool DUAL, int VAR = 0, bool GROUPED = false>
+template <int BM, int BN, int WAVES_M, int WAVES_N, int EPI, int NSTAGE, int OCC, bool DUAL, int VAR = 0, bool GROUPED = false, int HEAD = 0>
 __global__ __launch_bounds__(64 * WAVES_M* WAVES_N, OCC) void conv_igemm_f16x3_dma_kernel(const ConvArgs a, const typename StreamKOf<GROUPED>::type sk) {
   constexpr bool OSPLIT = EPI == 1;
   static_assert(!GROUPED || (BM == 256 && BN == 128 && NSTAGE == 3 && VAR == 0 && EPI != 2), "border groups: the 256 x 128 product tile, fp32 / split rows");
+  // HEAD: what happens between two slice loops of the ping-pong 256 x 128 tile with split-format output (launch_one, ring_head_route):
+  //   0  the LDS-staged epilogue, then the next segment's set-up and ring fill;  1  the epilogue from the accumulators;
+  //   2  ... and the next segment's head issued in front of it (behind the slice loop)
+  static_assert(HEAD == 0 || (HEAD <= 2 && BM == 256 && BN == 128 && WAVES_M * WAVES_N == 8 && NSTAGE == 3 && VAR == 0 && EPI == 1),
+                "register epilogue / early head: the ping-pong tile, split-format rows");
   constexpr int NW = WAVES_M * WAVES_N, NT = 64 * NW;
   constexpr int RPP = NT / 8;   // rows one pass of the workgroup covers (8 lanes x 16 B per row)
   static_assert(BM % RPP == 0 && BN % RPP == 0, "tile rows must be whole passes");
@@ -216,7 +221,19 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N, OCC) void conv_igemm_f16x3_d
   // replayed step plan cannot give the host (no event can be read back from a graph) the kernel notes itself.
   dlip_span_enter(sk.span, g);
   DLIP_LAB_WG_STAMP(8, true);
-  for (long long it = it_begin; it < it_end;) {
+  // A SEGMENT = the slices of one tile inside this workgroup's range.  Its head comes in two steps, seg_decode (which tile, which
+  // slices) and seg_fill (row state, walk, parameter table, the first two slices into the ring), written as lambdas over state that
+  // is declared here: the HEAD 2 instances run them for the NEXT segment between a segment's slice loop and its hand-off / epilogue
+  // (below, behind the loop); every other instance runs them at the top of the segment, as one text.  Both are forced inline.
+  struct Seg { int grp, nk, tile, k0, kn, tile_m, tile_n; };
+  int a_off[AQ];
+  uint32_t a_mask[AQ];         // after set-up: INVERTED (bit tap set = that tap falls outside the image, or the row is past M)
+  int a_h0[BIGTAPS ? AQ : 1], a_w0[BIGTAPS ? AQ : 1];   // (BIGTAPS) window origin of the row; rows past M: far outside
+  uint32_t a2_off[DUAL ? AQ : 1];   // second source: byte offset of the row's pixel; the out-of-range offset itself past M
+  uint32_t b_off[BQ];
+  int seg_nt = ntaps, seg_S = a.S, seg_nk1 = nk1, w_dr = 0, w_sub0 = 0;
+  int c0 = 0, tap = 0, s_pos = 0, x_row = 0, w_row = 0, tap_dh = 0, tap_dw = 0, x_tap = 0, w_tap = 0;
+  auto seg_decode = [&](const long long it) __attribute__((always_inline)) -> Seg {
     // (GROUPED) the segment's group: at most 8 compares on the groups' first slices, then the division by that group's nk.  Of what
     // the entry holds only the sub-filter's width and tap count stay live in the main loop (the walk needs them); everything the
     // hand-off and the epilogue use is read again behind the loop through an opaque copy of the group's index (cf. the paired lanes).
@@ -255,19 +272,98 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N, OCC) void conv_igemm_f16x3_d
       tile_m = tile / a.tiles_n;
       tile_n = tile - tile_m * a.tiles_n;
     }
-    // every wave is done reading the previous segment's last stage (and the ticket word) before the ring is refilled
-    if (it != it_begin) __syncthreads();
-    DLIP_STAMP(0);
-    DLIP_LAB_WG_STAMP(7, it == it_begin);
-
-    f32x4 acc[MI][NI];
+    return Seg{grp_i, seg_nk, tile, k0, kn, tile_m, tile_n};
+  };
 #define DLIP_FENCE() __builtin_amdgcn_sched_barrier(0)
+  // Reduction walk: 32-channel slice OUTER, filter tap INNER (conv_igemm_f16x3.hip), entered at slice k0 (seg_fill).
+  // DUAL: c0 runs on past the a.Cw channels of the first source -- slice nk1 + i is channels 32 i .. of x2,
+  // whose weights sit behind the R S Cw tap weights of each output channel's row.
+  // (GROUPED) the walk runs over the group's sub-filter: tap (r', s') of it is tap (r_lo + r') S + (s_lo + s') of the packed row, so
+  // the weight offset follows the FULL filter's row pitch (w_row) behind the group's first tap (folded into b_off)
+  auto advance = [&]() {
+    if (DUAL && c0 >= a.Cw) {          // second source: one slice per 32 channels
+      c0 += BK;
+    } else {
+      ++tap;
+      if (++s_pos == seg_S) { s_pos = 0; x_row += x_dr; if constexpr (BIGTAPS) tap_dh += a.dh; if constexpr (GROUPED) w_row += w_dr; }
+      if (tap == seg_nt) { tap = 0; s_pos = 0; x_row = 0; c0 += BK; if constexpr (BIGTAPS) tap_dh = 0; if constexpr (GROUPED) w_row = 0; }
+      if constexpr (BIGTAPS) tap_dw = s_pos * a.dw;
+    }
+    x_tap = x_row + s_pos * x_ds + c0 * 4;
+    if constexpr (GROUPED) w_tap = w_row + (s_pos * a.Cw + c0) * 4;
+    else w_tap = (tap * a.Cw + c0) * 4;
+    if constexpr (BIGTAPS) { x_tap = x_row + s_pos * x_ds + (c0 / BK) * a.cs_x; w_tap = tap * a.wt + (c0 / BK) * a.cs_w; }
+    if (DUAL && c0 >= a.Cw) { x_tap = (c0 - a.Cw) * 4; w_tap = (ntaps * a.Cw + c0 - a.Cw) * 4 - w_sub0; }
+  };
+  auto tap_ok = [&](int j) -> bool {
+    if constexpr (BIGTAPS) return (unsigned)(a_h0[j] + tap_dh) < (unsigned)a.H && (unsigned)(a_w0[j] + tap_dw) < (unsigned)a.W;
+    else return ((a_mask[j] >> tap) & 1u) == 0u;
+  };
+  // this wave's A_PER + B_PER pieces of the slice the walk stands on -> ring stage `stage`
+  auto issue_a = [&](int stage) {
+    const uint32_t base = piece0 + stage * STAGE_B;
+    if (DUAL && c0 >= a.Cw) {          // (wave-uniform)
+#pragma unroll
+      for (int j = 0; j < A_PER; ++j)
+        dma_piece(x2r, a2_off[DUAL ? j : 0] + (uint32_t)x_tap, base + j * RPP * ROWB);
+      return;
+    }
+#pragma unroll
+    for (int j = 0; j < A_PER; ++j) {
+      if constexpr (BIGTAPS) {
+        dma_piece(xr, tap_ok(j) ? (uint32_t)(a_off[j] + x_tap) : DLIP_OOB_OFFSET, base + j * RPP * ROWB);
+      } else {
+        // a tap outside the image: its bit of the inverted mask, shifted to bit 31, ORed into the offset -- beyond every buffer
+        // whatever the sum was (add, shift, and-or: the compare + select form was five vector instructions per piece in the
+        // load phase, which is the long pole of a ping-pong slice)
+        const uint32_t oob = (a_mask[j] << (31 - tap)) & 0x80000000u;
+        dma_piece(xr, (uint32_t)(a_off[j] + x_tap) | oob, base + j * RPP * ROWB);
+      }
+    }
+  };
+  auto issue_b = [&](int stage) {
+    const uint32_t base = piece0 + stage * STAGE_B + BM * ROWB;
+#pragma unroll
+    for (int j = 0; j < B_PER; ++j)
+      dma_piece(wr, b_off[j] + (uint32_t)w_tap, base + j * RPP * ROWB);
+  };
+  constexpr int TAB_F = 5 * BN;   // floats of one epilogue parameter table (HEAD 2: two of them behind the ring, then the hand-off's word)
+  // (HEAD 1, 2) the parameter table in two steps: the fetch into registers, and -- as late as the table's first reader allows -- the
+  // arithmetic on the fetched values and the LDS stores.  Same values as the one-step form in seg_fill.
+  float tab_v[HEAD >= 1 ? 5 : 1] = {};
+  (void)tab_v;
+  auto tab_fetch = [&](const int tile_n) __attribute__((always_inline)) {
+    if constexpr (HEAD >= 1) {
+      const int k = tile_n * BN + tid;
+      if (tid < BN && k < a.K) {
+        tab_v[0] = a.wscale[k];
+        tab_v[1] = a.bias ? a.bias[k] : 0.f;
+        tab_v[2] = a.slope ? a.slope[k] : 1.f;
+        tab_v[3] = a.pscale ? a.pscale[k] : 1.f;
+        tab_v[4] = a.pshift ? a.pshift[k] : 0.f;
+      }
+    }
+  };
+  auto tab_store = [&](const int tab_i, const int tile_n) __attribute__((always_inline)) {
+    if constexpr (HEAD >= 1) {
+      if (tid < BN) {
+        const bool kok = tile_n * BN + tid < a.K;
+        float* tab = smem + RING / 4 + tab_i * TAB_F;
+        tab[tid] = kok ? 1.f / tab_v[0] : 0.f;   // power of two: exact
+        tab[BN + tid] = kok ? tab_v[1] : 0.f;
+        tab[2 * BN + tid] = kok ? tab_v[2] : 1.f;
+        tab[3 * BN + tid] = kok ? tab_v[3] : 1.f;
+        tab[4 * BN + tid] = kok ? tab_v[4] : 0.f;
+      }
+    }
+  };
+  // seg_fill: segment sg -> the row state, the walk at its slice k0, its epilogue parameters (HEAD 0: into the table; HEAD 1, 2: the
+  // fetch), its first slices in flight.  `first`: the workgroup's first segment (the only one the lab build's stamps follow).
+  auto seg_fill = [&](const Seg& sg, const bool first) __attribute__((always_inline)) {
+    const int grp_i = sg.grp, seg_nk = sg.nk, k0 = sg.k0, kn = sg.kn, tile_m = sg.tile_m, tile_n = sg.tile_n;
+    tab_fetch(tile_n);
     // Per-row gather state, branch-free: byte offset of the row's window origin and a bit per filter tap
     // that stays inside the image (columns and rows tested separately: R + S steps, not R x S).
-    int a_off[AQ];
-    uint32_t a_mask[AQ];         // after set-up: INVERTED (bit tap set = that tap falls outside the image, or the row is past M)
-    int a_h0[BIGTAPS ? AQ : 1], a_w0[BIGTAPS ? AQ : 1];   // (BIGTAPS) window origin of the row; rows past M: far outside
-    uint32_t a2_off[DUAL ? AQ : 1];   // second source: byte offset of the row's pixel; the out-of-range offset itself past M
     auto row_of = [&](int j) { return rbase + RPP * j; };
     {
       int hi0[AQ], wi0[AQ];
@@ -325,7 +421,6 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N, OCC) void conv_igemm_f16x3_d
       }
     }
     // (a weight row past K carries the out-of-range offset itself: 2^31 plus any tap offset stays out of range -- one add per piece)
-    uint32_t b_off[BQ];
 #pragma unroll
     for (int j = 0; j < BQ; ++j) {
       const int n = tile_n * BN + rbase + RPP * j;
@@ -333,12 +428,8 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N, OCC) void conv_igemm_f16x3_d
       if constexpr (GROUPED) b_off[j] += (uint32_t)sk.grp.g[grp_i].w0;   // the sub-filter's first tap (weights stay as packed)
     }
 
-    // Reduction walk: 32-channel slice OUTER, filter tap INNER (conv_igemm_f16x3.hip), entered at slice k0.
-    // DUAL: c0 runs on past the a.Cw channels of the first source -- slice nk1 + i is channels 32 i .. of x2,
-    // whose weights sit behind the R S Cw tap weights of each output channel's row.
-    // (GROUPED) the walk runs over the group's sub-filter: tap (r', s') of it is tap (r_lo + r') S + (s_lo + s') of the packed row, so
-    // the weight offset follows the FULL filter's row pitch (w_row) behind the group's first tap (folded into b_off)
-    int seg_nt = ntaps, seg_S = a.S, seg_nk1 = nk1, w_dr = 0, w_sub0 = 0;
+    // the walk (advance, above) at slice k0
+    seg_nt = ntaps; seg_S = a.S; seg_nk1 = nk1; w_dr = 0; w_sub0 = 0;
     if constexpr (GROUPED) {
       seg_nt = sk.grp.g[grp_i].ntaps;
       seg_S = sk.grp.g[grp_i].S;
@@ -346,68 +437,25 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N, OCC) void conv_igemm_f16x3_d
       w_dr = a.S * a.Cw * 4;
       if constexpr (DUAL) w_sub0 = sk.grp.g[grp_i].w0;
     }
-    int c0 = (k0 / seg_nt) * BK, tap = k0 % seg_nt;
+    c0 = (k0 / seg_nt) * BK; tap = k0 % seg_nt;
     if constexpr (DUAL) {
       if (k0 >= seg_nk1) { c0 = a.Cw + (k0 - seg_nk1) * BK; tap = 0; }
     }
-    int s_pos = tap % seg_S, x_row = (tap / seg_S) * x_dr;
-    int w_row = GROUPED ? (tap / seg_S) * w_dr : 0;
-    int tap_dh = (tap / a.S) * a.dh, tap_dw = s_pos * a.dw;   // (BIGTAPS) the tap's row / column offset in pixels
-    int x_tap = x_row + s_pos * x_ds + c0 * 4, w_tap = GROUPED ? w_row + (s_pos * a.Cw + c0) * 4 : (tap * a.Cw + c0) * 4;
+    s_pos = tap % seg_S; x_row = (tap / seg_S) * x_dr;
+    w_row = GROUPED ? (tap / seg_S) * w_dr : 0;
+    tap_dh = (tap / a.S) * a.dh; tap_dw = s_pos * a.dw;   // (BIGTAPS) the tap's row / column offset in pixels
+    x_tap = x_row + s_pos * x_ds + c0 * 4; w_tap = GROUPED ? w_row + (s_pos * a.Cw + c0) * 4 : (tap * a.Cw + c0) * 4;
     if constexpr (BIGTAPS) { x_tap = x_row + s_pos * x_ds + (c0 / BK) * a.cs_x; w_tap = tap * a.wt + (c0 / BK) * a.cs_w; }
     if constexpr (DUAL) {   // (the second source's weights sit behind the FULL R S Cw taps)
       if (c0 >= a.Cw) { x_tap = (c0 - a.Cw) * 4; w_tap = (ntaps * a.Cw + c0 - a.Cw) * 4 - w_sub0; }
     }
-    auto advance = [&]() {
-      if (DUAL && c0 >= a.Cw) {          // second source: one slice per 32 channels
-        c0 += BK;
-      } else {
-        ++tap;
-        if (++s_pos == seg_S) { s_pos = 0; x_row += x_dr; if constexpr (BIGTAPS) tap_dh += a.dh; if constexpr (GROUPED) w_row += w_dr; }
-        if (tap == seg_nt) { tap = 0; s_pos = 0; x_row = 0; c0 += BK; if constexpr (BIGTAPS) tap_dh = 0; if constexpr (GROUPED) w_row = 0; }
-        if constexpr (BIGTAPS) tap_dw = s_pos * a.dw;
-      }
-      x_tap = x_row + s_pos * x_ds + c0 * 4;
-      if constexpr (GROUPED) w_tap = w_row + (s_pos * a.Cw + c0) * 4;
-      else w_tap = (tap * a.Cw + c0) * 4;
-      if constexpr (BIGTAPS) { x_tap = x_row + s_pos * x_ds + (c0 / BK) * a.cs_x; w_tap = tap * a.wt + (c0 / BK) * a.cs_w; }
-      if (DUAL && c0 >= a.Cw) { x_tap = (c0 - a.Cw) * 4; w_tap = (ntaps * a.Cw + c0 - a.Cw) * 4 - w_sub0; }
-    };
-    auto tap_ok = [&](int j) -> bool {
-      if constexpr (BIGTAPS) return (unsigned)(a_h0[j] + tap_dh) < (unsigned)a.H && (unsigned)(a_w0[j] + tap_dw) < (unsigned)a.W;
-      else return ((a_mask[j] >> tap) & 1u) == 0u;
-    };
-    // this wave's A_PER + B_PER pieces of the slice the walk stands on -> ring stage `stage`
-    auto issue_a = [&](int stage) {
-      const uint32_t base = piece0 + stage * STAGE_B;
-      if (DUAL && c0 >= a.Cw) {          // (wave-uniform)
-#pragma unroll
-        for (int j = 0; j < A_PER; ++j)
-          dma_piece(x2r, a2_off[DUAL ? j : 0] + (uint32_t)x_tap, base + j * RPP * ROWB);
-        return;
-      }
-#pragma unroll
-      for (int j = 0; j < A_PER; ++j) {
-        if constexpr (BIGTAPS) {
-          dma_piece(xr, tap_ok(j) ? (uint32_t)(a_off[j] + x_tap) : DLIP_OOB_OFFSET, base + j * RPP * ROWB);
-        } else {
-          // a tap outside the image: its bit of the inverted mask, shifted to bit 31, ORed into the offset -- beyond every buffer
-          // whatever the sum was (add, shift, and-or: the compare + select form was five vector instructions per piece in the
-          // load phase, which is the long pole of a ping-pong slice)
-          const uint32_t oob = (a_mask[j] << (31 - tap)) & 0x80000000u;
-          dma_piece(xr, (uint32_t)(a_off[j] + x_tap) | oob, base + j * RPP * ROWB);
-        }
-      }
-    };
-    auto issue_b = [&](int stage) {
-      const uint32_t base = piece0 + stage * STAGE_B + BM * ROWB;
-#pragma unroll
-      for (int j = 0; j < B_PER; ++j)
-        dma_piece(wr, b_off[j] + (uint32_t)w_tap, base + j * RPP * ROWB);
-    };
 
-    // ---- prologue: put the first NSTAGE-1 slices in flight, then initialise the accumulators ----
-    DLIP_STAMP(1);
+    // ---- prologue: put the first NSTAGE-1 slices in flight ----
+    {
+      const long long it = first ? it_begin : it_begin - 1;   // (the lab build's stamp macro names the segment `it`)
+      (void)it;
+      DLIP_STAMP(1);
+    }
     issue_a(0);
     issue_b(0);
     if (PF > 1 && kn > 1) {
@@ -415,18 +463,12 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N, OCC) void conv_igemm_f16x3_d
       issue_a(1);
       issue_b(1);
     }
-
-    // Accumulators hold the TRANSPOSED tile (rows = output channels, columns = pixels: the weight
-    // fragment is the MFMA's A operand), so a lane owns 4 consecutive channels of one pixel per
-    // register quad: 8-B (hi) + 8-B (lo) pieces of an output row for the LDS-staged epilogue.
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[mi][ni][e] = 0.f;
     // Per-channel epilogue parameters of this tile's BN channels -> the LDS table behind the ring (read back
     // as 16-B quads): 1/wscale, bias, slope, post scale, post shift.
+    // (HEAD 1, 2: the head only FETCHES them -- tab_fetch, first thing -- and tab_store puts them into the table behind the slice
+    // loop's first wait, which they have passed by then: in-kernel stamps showed the two waves that own the table sitting out the
+    // fetch's latency here, 4 - 6 k of a segment's "issue + init" cycles, and in front of their epilogue when the head went out early)
+    if constexpr (HEAD == 0)
     if (tid < BN) {
       const int k = tile_n * BN + tid;
       const bool kok = k < a.K;
@@ -437,6 +479,32 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N, OCC) void conv_igemm_f16x3_d
       tab[3 * BN + tid] = (kok && a.pscale) ? a.pscale[k] : 1.f;
       tab[4 * BN + tid] = (kok && a.pshift) ? a.pshift[k] : 0.f;
     }
+  };
+
+  Seg seg_cur = {};
+  bool headed = false;   // (HEAD 2) the head of the segment at `it` went out behind the previous segment's slice loop
+  int tab_cur = 0;       // (HEAD 2) the parameter table of the segment at `it`
+  for (long long it = it_begin; it < it_end;) {
+    if (HEAD < 2 || !headed) {
+      seg_cur = seg_decode(it);
+      // every wave is done reading the previous segment's last stage (and the ticket word) before the ring is refilled
+      if (it != it_begin) __syncthreads();
+      DLIP_STAMP(0);
+      DLIP_LAB_WG_STAMP(7, it == it_begin);
+      seg_fill(seg_cur, it == it_begin);
+    }
+    const int grp_i = seg_cur.grp, tile = seg_cur.tile, kn = seg_cur.kn, tile_m = seg_cur.tile_m, tile_n = seg_cur.tile_n;
+
+    // Accumulators hold the TRANSPOSED tile (rows = output channels, columns = pixels: the weight
+    // fragment is the MFMA's A operand), so a lane owns 4 consecutive channels of one pixel per
+    // register quad: 8-B (hi) + 8-B (lo) pieces of an output row for the LDS-staged epilogue.
+    f32x4 acc[MI][NI];
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+      for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[mi][ni][e] = 0.f;
 
     // ---- main loop: per slice 3 groups of MI x NI instructions.  Group order lo*hi, hi*hi, hi*lo:
     // the last group needs neither the activation-lo nor the weight-hi fragments, so the NEXT slice's first
@@ -511,7 +579,10 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N, OCC) void conv_igemm_f16x3_d
         if (s + 1 < kn) { if (s + 2 < kn) wait_vmcnt<NL>(); else wait_vmcnt<0>(); }
       };
       DLIP_STAMP(2);
-      if (PF > 1 && kn > 1) wait_vmcnt<NL>(); else wait_vmcnt<0>();
+      // (HEAD 2, a head that went out early: the previous epilogue's stores were issued BEHIND its pieces and share vmcnt with them;
+      // no counted wait across that mix -- everything is waited for, the stores' acknowledgements having passed under the epilogue)
+      if (PF > 1 && kn > 1 && !(HEAD == 2 && headed)) wait_vmcnt<NL>(); else wait_vmcnt<0>();
+      tab_store(tab_cur, tile_n);                    // (HEAD 1, 2; fetched in front of the pieces waited for above; read behind this loop)
       __builtin_amdgcn_s_barrier();                  // slice 0 is complete
       DLIP_STAMP(3);
       if (!half_b) {
@@ -631,8 +702,21 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N, OCC) void conv_igemm_f16x3_d
         st_cur = st_nxt;
       }
     }
-#undef DLIP_FENCE
     DLIP_STAMP(4);
+
+    // (HEAD 2) THE NEXT SEGMENT'S HEAD BEFORE THIS SEGMENT'S TAIL.  Every fragment read of the ping-pong loop lies in front of its
+    // last barrier b(2 kn - 1) -- half A's in front of b(2 kn - 2) even -- and a wave is here only behind that barrier: the ring is
+    // free, no further barrier is needed.  The next segment is decoded, its row state and walk go into the registers this segment's
+    // no longer needs, its parameters are fetched (they go into the OTHER table at the top of its loop: this segment's epilogue still
+    // reads tab_cur in other waves; the other one was last read by the epilogue before this segment's loop), and its slices 0 and 1
+    // go out; then the hand-off / epilogue below runs with those pieces in flight, and the fetches' and pieces' latency passes under
+    // it.  A two-stage pipeline at the boundary: nothing of it lives across the slice loop.
+    // The last segment of a range has no successor and keeps the old order.
+    const bool head_next = HEAD == 2 && it + kn < it_end;   // (workgroup-uniform)
+    if (head_next) {
+      seg_cur = seg_decode(it + kn);
+      seg_fill(seg_cur, false);
+    }
 
     // Lane coordinates re-derived behind an opaque asm: otherwise the compiler hoists every address of the
     // hand-off and epilogue code (invariant across segments) out of the segment loop and carries ~100
@@ -654,7 +738,8 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N, OCC) void conv_igemm_f16x3_d
     bool finish = true;
     if (kn != tile_nk) {   // split tile (workgroup-uniform branch)
       constexpr int SLAB = BM * BN;   // floats
-      volatile int* bcast = reinterpret_cast<volatile int*>(smem);
+      // (HEAD 2: stage 0 may already hold the next segment's first slice -- the word sits behind the two parameter tables)
+      volatile int* bcast = reinterpret_cast<volatile int*>(smem + (HEAD == 2 ? RING / 4 + 2 * TAB_F : 0));
       // (GROUPED) the tile's ABSOLUTE first slice and its launch-wide number (the ticket word): column block, group, row tile
       const long long t0 = GROUPED ? (long long)tile_n * sk_group_slices(sk) + ge.it0 + (long long)tile * ge.nk : (long long)tile * a.nk;
       // (paired lanes) this lane's workgroup index / grid / slice space, and the tile's ticket word = its number in tile_m-major order
@@ -752,6 +837,101 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N, OCC) void conv_igemm_f16x3_d
       }   // (!reduce_later)
     }
 
+    if constexpr (HEAD >= 1) {
+      // ---- (HEAD 1, 2) epilogue straight from the accumulators: the window kernel's (conv_win_f16x3.hip, itself the rows
+      // kernel's).  A lane exchanges the odd 16-lane rows of one accumulator with the even rows of its neighbour in the channel
+      // direction (v_permlane16_swap_b32), holds 8 consecutive channels of its pixel and stores one 16-B piece of hi halves and one
+      // of lo halves; the residual arrives in the same shape by two 16-B loads per pixel block, all issued first.  No barrier, no
+      // LDS beside the parameter table -- so the ring can already hold the next segment's head (HEAD 2).  Arithmetic and order per
+      // value are the LDS epilogue's below: same bits.  y may alias the residual: a lane loads exactly the pieces it stores, and
+      // loads them first. ----
+      if (finish) {
+        typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+        static_assert(OSPLIT && PINGPONG && NI % 2 == 0, "register epilogue: split-format rows of the ping-pong tile");
+        const f32x4* tab = reinterpret_cast<const f32x4*>(smem + RING / 4 + tab_cur * TAB_F);
+        const __amdgpu_buffer_rsrc_t rr = dlip_make_rsrc(a.res, a.res ? a.r_bytes : 0u);
+        const __amdgpu_buffer_rsrc_t yr = dlip_make_rsrc(a.y, a.y_bytes);
+        const bool post = a.pscale != nullptr;
+        const int kcol0 = tile_n * BN;
+        const int rows_e = GROUPED ? ge.M : a.M;
+        const int cs = ((half_e & 1) << 4) | ((half_e & 2) << 2);   // after the swap: channels 32 p + {0, 16, 8, 24}[half] + 0..7
+        // this lane's MI pixels: row of y / the residual ((GROUPED) through the group's sub-rectangle), or -1 past the rows
+        int orow[MI];
+#pragma unroll
+        for (int mi = 0; mi < MI; ++mi) {
+          const int m = tile_m * BM + wm * WM + mi * FR + lrow_e;
+          int r = m;
+          if constexpr (GROUPED) {
+            const int mc = m < ge.M ? m : ge.M - 1;
+            const int n = dlip_div(mc, ge.div_howo);
+            const int rem = mc - n * ge.HoWo;
+            const int ho = dlip_div(rem, ge.div_wo);
+            r = n * a.HoWo + (ge.ho0 + ho) * a.Wo + ge.wo0 + (rem - ho * ge.Wo);
+          }
+          orow[mi] = m < rows_e ? r : -1;
+        }
+        // The residual: MI pixel blocks (one 32-channel pair) in flight -- block (p + 1, mi) is fetched when block (p, mi) has been
+        // consumed.  (All NI / 2 x MI blocks at once, as the window kernel holds them, are 64 registers beside 64 of accumulators
+        // and, HEAD 2, the next segment's row state: the instance sat at the 256-register limit with a spill.)
+        h8 rh[MI] = {}, rl[MI] = {};
+        auto res_fetch = [&](int p, int mi) {
+          const int kb = kcol0 + wn * WN + 32 * p;
+          const bool ok = orow[mi] >= 0 && kb < a.K;
+          const uint32_t off = ok ? (uint32_t)((orow[mi] * a.ldr + kb) * 4 + cs * 2) : DLIP_OOB_OFFSET;
+          rh[mi] = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(rr, (int)off, 0, 0));
+          rl[mi] = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(rr, (int)(ok ? off + 64u : DLIP_OOB_OFFSET), 0, 0));
+        };
+        if (a.res) {
+#pragma unroll
+          for (int mi = 0; mi < MI; ++mi) res_fetch(0, mi);
+        }
+        float amax = 0.f;                              // largest |v| this lane converts to fp16
+#pragma unroll
+        for (int p = 0; p < NI / 2; ++p) {
+          const int kl = wn * WN + 32 * p + cs;        // tile-local first channel of this lane's 8
+          float inv[8], bi[8], sl[8], ps[8], pt[8];
+#pragma unroll
+          for (int q = 0; q < 2; ++q) {
+            const f32x4 i4 = tab[(kl >> 2) + q], b4 = tab[((BN + kl) >> 2) + q], l4 = tab[((2 * BN + kl) >> 2) + q];
+            f32x4 p4 = {1.f, 1.f, 1.f, 1.f}, t4 = {0.f, 0.f, 0.f, 0.f};
+            if (post) { p4 = tab[((3 * BN + kl) >> 2) + q]; t4 = tab[((4 * BN + kl) >> 2) + q]; }
+#pragma unroll
+            for (int c = 0; c < 4; ++c) { inv[4 * q + c] = i4[c]; bi[4 * q + c] = b4[c]; sl[4 * q + c] = l4[c]; ps[4 * q + c] = p4[c]; pt[4 * q + c] = t4[c]; }
+          }
+#pragma unroll
+          for (int mi = 0; mi < MI; ++mi) {
+            float v[8];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {   // (scalar copies: see conv_rows_f16x3.hip on __builtin_bit_cast of a vector element)
+              const float xc = acc[mi][2 * p][c], yc = acc[mi][2 * p + 1][c];
+              const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(xc), __float_as_uint(yc), false, false);
+              v[c] = __uint_as_float(r[0]);
+              v[4 + c] = __uint_as_float(r[1]);
+            }
+            const h8 rhv = rh[mi], rlv = rl[mi];
+            if (a.res && p + 1 < NI / 2) res_fetch(p + 1, mi);
+            h8 hi, lo;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+              float t = v[c] * inv[c] + bi[c];
+              if (a.res) t += (float)rhv[c] + (float)rlv[c];
+              t = t >= 0.f ? t : t * sl[c];
+              if (post) t = t * ps[c] + pt[c];
+              hi[c] = (_Float16)t;
+              lo[c] = (_Float16)(t - (float)hi[c]);
+              amax = fmaxf(amax, fabsf(t));
+            }
+            const int kb = kcol0 + wn * WN + 32 * p;
+            const bool ok = orow[mi] >= 0 && kb < a.K;
+            const uint32_t off = ok ? (uint32_t)((orow[mi] * a.ldy + kb) * 4 + cs * 2) : DLIP_OOB_OFFSET;
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hi), yr, (int)off, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, lo), yr, (int)(ok ? off + 64u : DLIP_OOB_OFFSET), 0, 0);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        dlip_report_range(amax, a.status);
+      }
+    } else
     if (finish) {
       // ---- epilogue through LDS: y = act(acc / wscale + bias + residual) * post_scale + post_shift ----
       // The ring is free now and stages the output tile in its memory layout (BM rows x BN*4 bytes, in
@@ -955,7 +1135,10 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N, OCC) void conv_igemm_f16x3_d
     }
     DLIP_LAB_SEGMENT_END_STAMPS();
     it += kn;
+    headed = head_next;
+    if (head_next) tab_cur ^= 1;
   }
+#undef DLIP_FENCE
   dlip_span_exit(sk.span);
   DLIP_LAB_WG_END_STAMPS();
 }
@@ -1168,7 +1351,25 @@ inline bool grouped_by_rule(const ConvArgs& a, const ConvGroups& gt) {
 }
 long long g_grouped_launches = 0;   // (dlip_conv_grouped_query: lets a test see which route a launch took)
 
-template <int BM, int BN, int WAVES_M, int WAVES_N, int NSTAGE, int OCC, int EPI, bool DUAL, int VAR = 0, bool GROUPED = false>
+// Which order a launch of the ping-pong 256 x 128 tile with split-format output takes at its segment boundaries (kernel comment at
+// HEAD; dlip_debug_set(11, 0 | 1 | 2) forces one).  Measured per layer at B = 64, the three routes alternating in one process
+// (tools/bench_ring_head.py, profiles/r20/ring_head_layers_ab.txt; medians in us, route 0 | 1 | 2, spread of the route-0 rounds):
+//   2.0.conv1         130.2 | 122.7 | 123.1   (2.6)        3.1.x (twice)     192.3 | 175.2 | 176.6   (12.9)
+//   2.0.conv2 dual    200.7 | 191.7 | 199.9   (15.8)       4.0.conv1         100.7 |  93.8 |  95.2   (18.6)
+//   3.0.conv1         113.3 | 109.2 | 107.5   (10.7)       4.0.conv2 dual    163.2 | 155.2 | 157.3   (12.9)
+//   3.0.conv2 dual    187.9 | 178.0 | 179.5   (11.2)       4.1.conv1         152.1 | 143.1 | 145.2   (12.6)
+// Route 1 wins on every launch (-3.7 ... -8.9 %, -6.2 % of their sum); route 2 is no slower than route 0 anywhere but beats
+// route 1 on one launch only, by less than the spread, and in the replayed step it gave 17 016 clips/s where route 1 gave 17 054
+// and the parent 16 726 (profiles/r20/ring_head_step_ab.txt; EXPERIMENTS.md R20.1 has what is unexplained about it).  So the
+// built-in choice is route 1 for all launches, no per-launch rule; route 2 stays behind the key.
+constexpr int kRingHeadBuiltIn = 1;
+inline int ring_head_route() {
+  const int v = dlip_dbg_value[DLIP_DBG_RING_HEAD];
+  return v >= 0 && v <= 2 ? v : kRingHeadBuiltIn;
+}
+long long g_ring_head_launches[3] = {};   // (dlip_conv_ring_head_query) launches per route
+
+template <int BM, int BN, int WAVES_M, int WAVES_N, int NSTAGE, int OCC, int EPI, bool DUAL, int VAR = 0, bool GROUPED = false, int HEAD = 0>
 int launch_one(const ConvArgs& a, hipStream_t st, const ConvGroups* groups = nullptr) {
   if constexpr (!GROUPED && BM == 256 && BN == 128 && NSTAGE == 3 && VAR == 0 && EPI != 2) {
     // Border groups: the 256 x 128 product tile, padding, <= 32 taps and pixel-major operands (this dispatch branch), no weight-
@@ -1181,6 +1382,13 @@ int launch_one(const ConvArgs& a, hipStream_t st, const ConvGroups* groups = nul
         return launch_one<BM, BN, WAVES_M, WAVES_N, NSTAGE, OCC, EPI, DUAL, VAR, true>(a, st, &gt);
     }
   }
+  if constexpr (HEAD == 0 && BM == 256 && BN == 128 && WAVES_M * WAVES_N == 8 && NSTAGE == 3 && VAR == 0 && EPI == 1) {
+    // Segment boundary of the ping-pong tile (kernel comment at HEAD): plain, DUAL and both GROUPED twins
+    const int route = ring_head_route();
+    if (route == 1) return launch_one<BM, BN, WAVES_M, WAVES_N, NSTAGE, OCC, EPI, DUAL, VAR, GROUPED, 1>(a, st, groups);
+    if (route == 2) return launch_one<BM, BN, WAVES_M, WAVES_N, NSTAGE, OCC, EPI, DUAL, VAR, GROUPED, 2>(a, st, groups);
+  }
+  if constexpr (BM == 256 && BN == 128 && WAVES_M * WAVES_N == 8 && NSTAGE == 3 && VAR == 0 && EPI == 1) ++g_ring_head_launches[HEAD];
   ConvArgs b = a;
   const int tiles_m = (a.M + BM - 1) / BM;
   b.tiles_n = (a.K + BN - 1) / BN;
@@ -1189,10 +1397,11 @@ int launch_one(const ConvArgs& a, hipStream_t st, const ConvGroups* groups = nul
   const double nk_mean = GROUPED ? (double)groups->slices / groups->tiles : (double)a.nk;
   if (tiles <= 0 || tiles > 0x7FFFFFFFll) return DLIP_EINVAL;
   if (EPI == 2 && a.pool_group < BM) return DLIP_EINVAL;   // a tile may contain at most one row-group boundary
-  constexpr size_t lds = (size_t)NSTAGE * (BM + BN) * ROWB + 5 * BN * sizeof(float);   // ring + epilogue parameter table
+  // ring + epilogue parameter table (HEAD 2: + the next segment's table and the hand-off's broadcast word, which leaves stage 0)
+  constexpr size_t lds = (size_t)NSTAGE * (BM + BN) * ROWB + 5 * BN * sizeof(float) + (HEAD == 2 ? 5 * BN * sizeof(float) + 16 : 0);
   constexpr int threads = 64 * WAVES_M * WAVES_N;
   static_assert(lds <= 160 * 1024, "LDS ring exceeds a CU");
-  auto kern = conv_igemm_f16x3_dma_kernel<BM, BN, WAVES_M, WAVES_N, EPI, NSTAGE, OCC, DUAL, VAR, GROUPED>;
+  auto kern = conv_igemm_f16x3_dma_kernel<BM, BN, WAVES_M, WAVES_N, EPI, NSTAGE, OCC, DUAL, VAR, GROUPED, HEAD>;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return DLIP_EINVAL;
   static KernelSlots ks;   // one per instantiation
@@ -1427,6 +1636,16 @@ extern "C" int dlip_conv_grouped_query(const int32_t* geom, int64_t* out) {
   out[2] = gt.n; out[3] = gt.slices; out[4] = gt.tiles; out[5] = gt.useful;
   out[6] = (int64_t)a.R * a.S * a.HoWo;
   out[7] = g_grouped_launches;
+  return DLIP_OK;
+}
+
+// Tests and tools (not part of the public header): which segment-boundary order (kernel comment at HEAD) the launches of the
+// ping-pong 256 x 128 tile with split-format output took so far.  No device call.
+//   out = {launches on route 0, on route 1, on route 2, the built-in route}
+extern "C" int dlip_conv_ring_head_query(int64_t* out) {
+  DLIP_CHECK_ARG(out != nullptr);
+  for (int i = 0; i < 3; ++i) out[i] = g_ring_head_launches[i];
+  out[3] = kRingHeadBuiltIn;
   return DLIP_OK;
 }
 

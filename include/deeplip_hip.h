@@ -862,9 +862,13 @@ int dlip_range_scope_end(dlip_stream_t stream);
  * 9 the rows kernel's short last round (0 = off: every tile the full height);
  * 10 the LDS-DMA kernel's border groups (a padded convolution on the 256 x 128 tile run as its padding-free sub-convolutions in one
  * launch: 0 = never, 1 = whenever the construction applies; built in where a launch's share of padding taps is large enough);
+ * 11 the segment boundary of the LDS-DMA kernel's 256 x 128 tile with split-format output (0 = the output tile staged in LDS, then
+ * the next tile's set-up and ring fill; 1 = the epilogue straight from the accumulators; 2 = ... and the next tile's first slices
+ * issued in front of it);
  * value -1 restores the built-in choice. */
 enum { DLIP_DBG_CONV_TILE = 0, DLIP_DBG_DMA_TILE = 1, DLIP_DBG_DMA_ENABLE = 2, DLIP_DBG_STREAMK = 3, DLIP_DBG_WIN = 4, DLIP_DBG_NINNER = 5,
-       DLIP_DBG_ROWS = 6, DLIP_DBG_ROWS2D = 7, DLIP_DBG_BN_FUSED = 8, DLIP_DBG_ROWS_TAIL = 9, DLIP_DBG_GROUPED = 10, DLIP_DBG_COUNT = 11 };
+       DLIP_DBG_ROWS = 6, DLIP_DBG_ROWS2D = 7, DLIP_DBG_BN_FUSED = 8, DLIP_DBG_ROWS_TAIL = 9, DLIP_DBG_GROUPED = 10, DLIP_DBG_RING_HEAD = 11,
+       DLIP_DBG_COUNT = 12 };
 int dlip_debug_set(int32_t key, int32_t value);
 
 /* ------------------------------------------------------------------------------------------
