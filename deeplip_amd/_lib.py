@@ -93,13 +93,22 @@ def parse_header(text: str):
     return consts, fields, protos
 
 
+def stream_last(text: str) -> frozenset:
+    """Names of the prototypes in such a header whose LAST parameter is a dlip_stream_t: the entry points ``call`` hands the
+    current stream to.  (dlip_span_scope_end and dlip_plan_end take theirs first: their callers pass it like any argument.)"""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    return frozenset(re.findall(r"\b(dlip_\w+)\s*\([^()]*\bdlip_stream_t(?:\s+\w+)?\s*\)", text))
+
+
 if not os.path.exists(HEADER_PATH):
     raise DeepLipHipError(f"{HEADER_PATH} not found: deeplip_amd binds libdeeplip_hip.so from the header it is built from "
                           "(a source tree: include/ beside the package). deeplip_amd has no CPU fallback.")
 with open(HEADER_PATH) as _f:
-    HEADER, ConvDesc._fields_, PROTOTYPES = parse_header(_f.read())
+    _text = _f.read()
+HEADER, ConvDesc._fields_, PROTOTYPES = parse_header(_text)
 # name -> argtypes of every launch entry point (the two that return text are bound from PROTOTYPES like the rest)
 SIGNATURES = {n: a for n, (_, a) in PROTOTYPES.items() if n not in ("dlip_source_sha", "dlip_error_string")}
+STREAM_LAST = stream_last(_text)
 ABI_VERSION = HEADER["DLIP_ABI_VERSION"]
 LIFT_WORDS = HEADER["DLIP_LIFT_WORDS"]
 LIFT_BCAST = HEADER["DLIP_LIFT_BCAST"]
@@ -160,6 +169,34 @@ def stream_handle() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
+_CURRENT = object()     # call(stream=...): not given
+
+
+def call(name: str, *args, stream=_CURRENT, what: str | None = None) -> None:
+    """Launch the entry point ``name`` and raise DeepLipHipError unless it returns 0 (``what``: the error's label where it is not
+    the name).  ``args`` are the header's parameters, exactly as many, tensors standing for their device address (None: NULL) --
+    without the trailing dlip_stream_t of an entry point that has one: that is the current stream (stream_handle()), or
+    ``stream=`` (a handle or None; torch.cuda is not touched then).  For the entry points that return a status."""
+    argtypes = SIGNATURES.get(name)
+    if argtypes is None:
+        raise DeepLipHipError(f"{name}: no such entry point in include/deeplip_hip.h")
+    takes_stream = name in STREAM_LAST
+    if len(args) != len(argtypes) - takes_stream:
+        raise TypeError(f"{name} takes {len(argtypes) - takes_stream} arguments{' and the stream' if takes_stream else ''} "
+                        f"({len(argtypes)} parameters in the header), got {len(args)}")
+    args = [a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args]
+    if takes_stream:
+        args.append(stream_handle() if stream is _CURRENT else stream)
+    elif stream is not _CURRENT:
+        raise TypeError(f"{name} has no trailing dlip_stream_t: stream= is not for it")
+    check(getattr(lib(), name)(*args), what or name)
+
+
+def env_switch(name: str) -> bool:
+    """An A/B switch of the environment: on unless the variable is set to "0"."""
+    return os.environ.get(name, "1") != "0"
+
+
 # Workspace of the conv kernel's balanced work split: one torch-owned block per (device, stream),
 # registered with the library the first time that stream launches a convolution, so the library itself
 # never allocates device memory.
@@ -175,7 +212,7 @@ def ensure_conv_workspace() -> None:
     if nbytes <= 0:
         raise DeepLipHipError("dlip_conv_workspace_bytes failed (no ROCm device?)")
     buf = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
-    check(lib().dlip_conv_set_workspace(buf.data_ptr(), nbytes, st.cuda_stream), "dlip_conv_set_workspace")
+    call("dlip_conv_set_workspace", buf.data_ptr(), nbytes, stream=st.cuda_stream)
     _workspaces[key] = buf
 
 
@@ -187,7 +224,7 @@ DEBUG = {}          # what this process set through debug_set (key -> value; -1 
 
 
 def debug_set(key: int, value: int = -1) -> None:
-    check(lib().dlip_debug_set(key, value), "dlip_debug_set")
+    call("dlip_debug_set", key, value)
     DEBUG[key] = value
 
 
@@ -203,7 +240,7 @@ def status_words():
     global _status, _status_np
     if _status is None:
         t = torch.zeros(8, dtype=torch.int32).pin_memory()
-        check(lib().dlip_set_status_words(t.data_ptr()), "dlip_set_status_words")
+        call("dlip_set_status_words", t.data_ptr())
         _status_np = t.numpy()      # same memory: a forward's check is one numpy read
         _status = t
     return _status
@@ -249,7 +286,7 @@ class StatusBlock:
         @contextlib.contextmanager
         def cm():
             status_words()      # the process-wide block exists before any launch, scoped or not
-            check(lib().dlip_status_scope(self.t.data_ptr()), "dlip_status_scope")
+            call("dlip_status_scope", self.t.data_ptr())
             try:
                 yield self
             finally:
@@ -326,7 +363,7 @@ class range_scope:
                     ring = _rings[key] = [torch.zeros(_RING_CHUNKS * _EVID_WORDS * _SCOPE_SLOTS, dtype=torch.int32, device="cuda"), 0]
                 slots = ring[0][ring[1] * _EVID_WORDS * _SCOPE_SLOTS:(ring[1] + 1) * _EVID_WORDS * _SCOPE_SLOTS]
                 ring[1] = (ring[1] + 1) % _RING_CHUNKS
-        check(lib().dlip_range_scope_begin(slots.data_ptr(), min(_SCOPE_SLOTS, slots.numel() // _EVID_WORDS)), "dlip_range_scope_begin")
+        call("dlip_range_scope_begin", slots.data_ptr(), min(_SCOPE_SLOTS, slots.numel() // _EVID_WORDS))
         _scope_depth.n = d + 1          # only once the scope is really open: a failed begin leaves the thread's depth as it was
         return self
 

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from ._lib import check, lib, ptr, stream_handle
+from ._lib import call, lib
 
 SNR_PASS = 9999                     # preprocess.py:168: the level that means "leave the signal alone"
 AUGMENT_KEYS = ("snr_levels", "p_reverb", "keep_power", "normalize", "max_taps", "reverb")
@@ -145,8 +145,7 @@ class WaveAugment:
                     raise _lib.DeepLipHipError(f"dlip_wave_rir_spectra_bytes refused R = {R}, Lmax = {Lmax}")
                 sp = torch.empty(nbytes // 4, dtype=torch.float32, device=self.device)
                 with torch.cuda.device(self.device):
-                    check(lib().dlip_wave_rir_spectra_f32(ptr(self._dev["rir"]), ptr(self._dev["rir_len"]), ptr(sp), nbytes, R, Lmax,
-                                                          stream_handle()), "dlip_wave_rir_spectra_f32")
+                    call("dlip_wave_rir_spectra_f32", self._dev["rir"], self._dev["rir_len"], sp, nbytes, R, Lmax)
                     torch.cuda.current_stream().synchronize()      # as the copies above: whichever stream calls later finds them made
                 self._dev["spectra"] = sp
         return self._dev
@@ -215,12 +214,11 @@ class WaveAugment:
             y = ops._empty((B, S), dev)
             R, Lmax = d["rir"].shape
             if self.reverb == "fft":
-                check(lib().dlip_wave_reverb_fft_f32(ptr(cur), ptr(lens), ptr(d["spectra"]), ptr(d["rir_len"]), ptr(d["rir_peak"]), ptr(ridx),
-                                                     ptr(y), ptr(ws_fft), nbytes_fft, B, S, R, Lmax, int(self.keep_power), stream_handle()),
-                      "dlip_wave_reverb_fft_f32")
+                call("dlip_wave_reverb_fft_f32", cur, lens, d["spectra"], d["rir_len"], d["rir_peak"], ridx, y, ws_fft, nbytes_fft, B, S, R, Lmax,
+                     int(self.keep_power))
             else:
-                check(lib().dlip_wave_reverb_f32(ptr(cur), ptr(lens), ptr(d["rir"]), ptr(d["rir_len"]), ptr(d["rir_peak"]), ptr(ridx), ptr(y),
-                                                 ptr(ws), nbytes, B, S, R, Lmax, int(self.keep_power), stream_handle()), "dlip_wave_reverb_f32")
+                call("dlip_wave_reverb_f32", cur, lens, d["rir"], d["rir_len"], d["rir_peak"], ridx, y, ws, nbytes, B, S, R, Lmax,
+                     int(self.keep_power))
             cur = y
         snr = self._param(params, "snr_db", torch.float32, B, dev)
         if snr is not None and d["noise"] is not None:
@@ -228,13 +226,11 @@ class WaveAugment:
             if start is None:
                 raise ValueError("WaveAugment: params carry snr_db but no noise_start")
             z = ops._empty((B, S), dev)
-            check(lib().dlip_wave_add_noise_f32(ptr(cur), ptr(lens), ptr(d["noise"]), d["noise"].numel(), ptr(start), ptr(snr), ptr(z),
-                                                ptr(ws), nbytes, B, S, stream_handle()), "dlip_wave_add_noise_f32")
+            call("dlip_wave_add_noise_f32", cur, lens, d["noise"], d["noise"].numel(), start, snr, z, ws, nbytes, B, S)
             cur = z
         if self.normalize:
             out = ops._empty((B, S), dev)
-            check(lib().dlip_wave_normalize_f32(ptr(cur), ptr(lens), ptr(out), ptr(ws), nbytes, B, S, stream_handle()),
-                  "dlip_wave_normalize_f32")
+            call("dlip_wave_normalize_f32", cur, lens, out, ws, nbytes, B, S)
             cur = out
         if cur is wave:
             raise ValueError("WaveAugment: nothing to apply (no noise bank, no room responses, normalize off)")

@@ -11,19 +11,19 @@ import torch
 from torch.autograd import Function
 
 from . import _lib, ops
-from ._lib import LIFT_WORDS, check, lib, ptr, stream_handle
+from ._lib import LIFT_WORDS, call, env_switch, lib
+from ._lib import check, ptr, stream_handle    # noqa: F401  (tests reach the binding through this module)
 
 
 def _gemm(A, B, M, N, K, ta=False, tb=False):
     C_ = torch.empty((M, N), device=A.device, dtype=torch.float32)
-    check(lib().dlip_gemm_small_f32(ptr(A), ptr(B), ptr(C_), M, N, K, int(ta), int(tb), stream_handle()),
-          "dlip_gemm_small_f32")
+    call("dlip_gemm_small_f32", A, B, C_, M, N, K, int(ta), int(tb))
     return C_
 
 
 def _colsum(x):
     y = torch.empty((x.shape[1],), device=x.device, dtype=torch.float32)
-    check(lib().dlip_colsum_f32(ptr(x), ptr(y), x.shape[0], x.shape[1], stream_handle()), "dlip_colsum_f32")
+    call("dlip_colsum_f32", x, y, x.shape[0], x.shape[1])
     return y
 
 
@@ -31,7 +31,7 @@ def _colsum(x):
 # their balanced work split, like every convolution of the step: the exact-fp32 kernels ran them on 32 - 188 tiles with no split of the
 # reduction -- forward 63 us, dx 69 us, dW 44 us (tools/probes: E§R6.17).  An input width that is no multiple of 32 is zero-padded by
 # the pass that splits it (3 000 -> 3 008).
-LINEAR_ON_MATRIX_KERNELS = __import__("os").environ.get("DLIP_LINEAR_F16X3", "1") != "0"      # (the environment switch: same-box A/B runs)
+LINEAR_ON_MATRIX_KERNELS = env_switch("DLIP_LINEAR_F16X3")      # (the environment switch: same-box A/B runs)
 _ONE_PAIR = {}
 
 
@@ -67,8 +67,7 @@ class LinearFn(Function):
             N = w.shape[0]
             Cp = (Cin + 31) // 32 * 32
             xs = torch.empty((M, 1, 1, Cp), device=x.device, dtype=torch.float32)
-            check(lib().dlip_split_pack_scaled_pad_f32(ptr(x), ptr(xs), ptr(_one_pair(x.device)), M, Cin, Cp, stream_handle()),
-                  "dlip_split_pack_scaled_pad_f32")
+            call("dlip_split_pack_scaled_pad_f32", x, xs, _one_pair(x.device), M, Cin, Cp)
             y = av.conv_train(xs, None, b.contiguous() if b is not None else None, w_ref=w.view(N, Cin, 1, 1), xs_ready=xs)   # (xs doubles as the shape holder)
             return y.view(M, N)
         if Cin % 4 == 0:
@@ -109,9 +108,7 @@ class BatchNormActTrainFn(Function):
         y = torch.empty_like(x)
         mean = torch.empty((C_,), device=x.device, dtype=torch.float32)
         invstd = torch.empty_like(mean)
-        check(lib().dlip_bn1d_train_fwd_f32(ptr(x), ptr(gamma), ptr(beta), ptr(y), ptr(mean), ptr(invstd),
-                                            ptr(running_mean), ptr(running_var), M, C_, momentum, eps, slope,
-                                            stream_handle()), "dlip_bn1d_train_fwd_f32")
+        call("dlip_bn1d_train_fwd_f32", x, gamma, beta, y, mean, invstd, running_mean, running_var, M, C_, momentum, eps, slope)
         ctx.save_for_backward(x, y, gamma, mean, invstd)
         ctx.slope = slope
         return y
@@ -123,12 +120,10 @@ class BatchNormActTrainFn(Function):
         M, C_ = x.shape
         if ctx.slope != 1.0:
             g = torch.empty_like(dy)
-            check(lib().dlip_lrelu_bwd_f32(ptr(dy), ptr(y), ptr(g), dy.numel(), ctx.slope, stream_handle()),
-                  "dlip_lrelu_bwd_f32")
+            call("dlip_lrelu_bwd_f32", dy, y, g, dy.numel(), ctx.slope)
             dy = g
         dx = torch.empty_like(x); dg = torch.empty_like(mean); db = torch.empty_like(mean)
-        check(lib().dlip_bn1d_train_bwd_f32(ptr(dy), ptr(x), ptr(mean), ptr(invstd), ptr(gamma), ptr(dx), ptr(dg),
-                                            ptr(db), M, C_, stream_handle()), "dlip_bn1d_train_bwd_f32")
+        call("dlip_bn1d_train_bwd_f32", dy, x, mean, invstd, gamma, dx, dg, db, M, C_)
         return dx, dg, db, None, None, None, None, None
 
 
@@ -146,8 +141,7 @@ class L2NormalizeFn(Function):
     def backward(ctx, dy):
         (x,) = ctx.saved_tensors
         dx = torch.empty_like(x)
-        check(lib().dlip_l2_normalize_bwd_f32(ptr(x), ptr(dy.contiguous()), ptr(dx), x.shape[0], x.shape[1], ctx.eps,
-                                              stream_handle()), "dlip_l2_normalize_bwd_f32")
+        call("dlip_l2_normalize_bwd_f32", x, dy.contiguous(), dx, x.shape[0], x.shape[1], ctx.eps)
         return dx, None
 
 
@@ -166,9 +160,7 @@ class MarginCELossFn(Function):
         logits, labels = ctx.saved_tensors
         g = torch.empty_like(logits)
         dl = dloss.reshape(1).to(torch.float32).contiguous()       # stays on the device: no host read-back per step
-        check(lib().dlip_margin_ce_bwd_f32(ptr(logits), ptr(labels), ptr(g), logits.shape[0], logits.shape[1],
-                                           ctx.scale, ctx.margin, 1.0, ptr(dl), stream_handle()),
-              "dlip_margin_ce_bwd_f32")
+        call("dlip_margin_ce_bwd_f32", logits, labels, g, logits.shape[0], logits.shape[1], ctx.scale, ctx.margin, 1.0, dl)
         return g, None, None, None
 
 
@@ -267,8 +259,7 @@ class AAMMarginFn(Function):
         ctx.save_for_backward(logits, labels)
         ctx.cfg = (float(margin), int(easy))
         y = torch.empty_like(logits)
-        check(lib().dlip_aam_margin_f32(ptr(logits), ptr(labels), None, ptr(y), logits.shape[0], logits.shape[1], float(margin),
-                                        int(easy), 0, stream_handle()), "dlip_aam_margin_f32")
+        call("dlip_aam_margin_f32", logits, labels, None, y, logits.shape[0], logits.shape[1], float(margin), int(easy), 0)
         return y
 
     @staticmethod
@@ -276,8 +267,7 @@ class AAMMarginFn(Function):
         logits, labels = ctx.saved_tensors
         margin, easy = ctx.cfg
         g = torch.empty_like(logits)
-        check(lib().dlip_aam_margin_f32(ptr(logits), ptr(labels), ptr(dy.contiguous()), ptr(g), logits.shape[0], logits.shape[1],
-                                        margin, easy, 1, stream_handle()), "dlip_aam_margin_f32")
+        call("dlip_aam_margin_f32", logits, labels, dy.contiguous(), g, logits.shape[0], logits.shape[1], margin, easy, 1)
         return g, None, None, None
 
 
@@ -300,8 +290,7 @@ class RowNormFn(Function):
     def backward(ctx, dr):
         x, r = ctx.saved_tensors
         dx = torch.empty_like(x)
-        check(lib().dlip_row_norm_bwd_f32(ptr(x), ptr(r), ptr(dr.contiguous()), ptr(dx), x.shape[0], x.shape[1], ctx.eps, stream_handle()),
-              "dlip_row_norm_bwd_f32")
+        call("dlip_row_norm_bwd_f32", x, r, dr.contiguous(), dx, x.shape[0], x.shape[1], ctx.eps)
         return dx, None
 
 
@@ -326,8 +315,7 @@ class ASoftmaxLogitsFn(Function):
         m, r_floor = ctx.cfg
         dc = torch.empty_like(logits)
         dr = torch.empty_like(r)
-        check(lib().dlip_asoftmax_logits_f32(ptr(logits), ptr(r), ptr(labels), ptr(lam), ptr(dz.contiguous()), ptr(dc), ptr(dr),
-                                             logits.shape[0], logits.shape[1], m, r_floor, 1, stream_handle()), "dlip_asoftmax_logits_f32")
+        call("dlip_asoftmax_logits_f32", logits, r, labels, lam, dz.contiguous(), dc, dr, logits.shape[0], logits.shape[1], m, r_floor, 1)
         return dc, dr, None, None, None, None
 
 
@@ -387,10 +375,10 @@ def margin_ce_loss(logits, labels, scale=1.0, margin=0.0):
 # Channels-last [B,T,C] activations throughout; parameters keep the reference layouts.
 # ==========================================================================================
 # Round 5 (both measured on the speech encoder's training step, tools/bench_train_audio.py; False restores round 4's passes):
-BN_STATS_FROM_CONV = __import__("os").environ.get("DLIP_BN_STATS_FROM_CONV", "1") != "0"
+BN_STATS_FROM_CONV = env_switch("DLIP_BN_STATS_FROM_CONV")
 # Round 5: a TDNN block's activated output is not stored when the next block can take it on load (TDNNBlockTrainFn: defer / pending)
-BN_ON_LOAD = __import__("os").environ.get("DLIP_BN_ON_LOAD", "1") != "0"
-ZERO_BIAS_GRAD_BEFORE_BN = __import__("os").environ.get("DLIP_ZERO_BIAS_GRAD", "1") != "0"
+BN_ON_LOAD = env_switch("DLIP_BN_ON_LOAD")
+ZERO_BIAS_GRAD_BEFORE_BN = env_switch("DLIP_ZERO_BIAS_GRAD")
 
 
 def _ws(M: int, C_: int, device):
@@ -406,7 +394,7 @@ class L1NormFn(Function):
     def forward(ctx, w, coef):
         w = w.contiguous()
         out = torch.empty((1,), device=w.device, dtype=torch.float32)
-        check(lib().dlip_l1_sum_f32(ptr(w), ptr(out), w.numel(), stream_handle()), "dlip_l1_sum_f32")
+        call("dlip_l1_sum_f32", w, out, w.numel())
         ctx.save_for_backward(w)
         ctx.coef = float(coef)
         return out[0] * float(coef)
@@ -416,7 +404,7 @@ class L1NormFn(Function):
         (w,) = ctx.saved_tensors
         dw = torch.empty_like(w)
         gs = g.contiguous().view(1)
-        check(lib().dlip_l1_sign_f32(ptr(w), ptr(gs), ptr(dw), ctx.coef, w.numel(), stream_handle()), "dlip_l1_sign_f32")
+        call("dlip_l1_sign_f32", w, gs, dw, ctx.coef, w.numel())
         return dw, None
 
 
@@ -427,8 +415,7 @@ def l1_norm(w, coef=1.0):
 def _permute3(x, perm, flip_axis=-1):
     d0, d1, d2 = x.shape
     y = torch.empty(tuple(x.shape[p] for p in perm), device=x.device, dtype=torch.float32)
-    check(lib().dlip_permute3_f32(ptr(x), ptr(y), d0, d1, d2, perm[0], perm[1], perm[2], flip_axis, stream_handle()),
-          "dlip_permute3_f32")
+    call("dlip_permute3_f32", x, y, d0, d1, d2, perm[0], perm[1], perm[2], flip_axis)
     return y
 
 
@@ -442,9 +429,7 @@ def _bn_rows_fwd(x2, gamma, beta, rm, rv, momentum, eps, slope, act_first, ready
     mean = torch.empty((C_,), device=x2.device, dtype=torch.float32)
     invstd = torch.empty_like(mean)
     ws, chunks = ready if ready is not None else (_ws(M, C_, x2.device), 0)
-    check(lib().dlip_bn_rows_train_fwd_f32(ptr(x2), ptr(gamma), ptr(beta), ptr(y), ptr(mean), ptr(invstd), ptr(rm), ptr(rv),
-                                           ptr(ws), M, C_, momentum, eps, slope, int(act_first), int(chunks), ptr(nbt),
-                                           stream_handle()), "dlip_bn_rows_train_fwd_f32")
+    call("dlip_bn_rows_train_fwd_f32", x2, gamma, beta, y, mean, invstd, rm, rv, ws, M, C_, momentum, eps, slope, int(act_first), int(chunks), nbt)
     return y, mean, invstd
 
 
@@ -455,9 +440,7 @@ def _bn_rows_bwd(dy2, x2, gamma, beta, mean, invstd, slope, act_first):
     dg = torch.empty_like(mean)
     db = torch.empty_like(mean)
     lift = torch.empty((LIFT_WORDS,), device=x2.device, dtype=torch.float32)
-    check(lib().dlip_bn_rows_train_bwd_f32(ptr(dy2), ptr(x2), ptr(gamma), ptr(beta), ptr(mean), ptr(invstd), ptr(dx), ptr(dg),
-                                           ptr(db), ptr(_ws(M, C_, x2.device)), M, C_, slope, int(act_first), ptr(lift), stream_handle()),
-          "dlip_bn_rows_train_bwd_f32")
+    call("dlip_bn_rows_train_bwd_f32", dy2, x2, gamma, beta, mean, invstd, dx, dg, db, _ws(M, C_, x2.device), M, C_, slope, int(act_first), lift)
     dx._dlip_lift = lift      # the power-of-two lift of dx, formed by the pass that wrote it (autograd_video.pow2_lift picks it up)
     return dx, dg, db
 
@@ -465,7 +448,7 @@ def _bn_rows_bwd(dy2, x2, gamma, beta, mean, invstd, slope, act_first):
 # (round 6, ABI 47) conv -> BatchNorm -> activation under backward(): the BatchNorm's input gradient dz is needed only as the operand
 # images of the convolution in front (weight gradient, data gradient), so it is formed PER LOADED VALUE by their producers from dy and z
 # (dlip_wgrad_*_bnbwd_f32) and never stored: the apply pass's write and the producers' read of an activation-sized tensor per layer.
-BN_BWD_ON_LOAD = __import__("os").environ.get("DLIP_BN_BWD_ON_LOAD", "1") != "0"      # (the environment switch: same-box A/B runs)
+BN_BWD_ON_LOAD = env_switch("DLIP_BN_BWD_ON_LOAD")      # (the environment switch: same-box A/B runs)
 BN_SMALL_ROWS = 4096          # (encoder_train_ops.hip: at most this many rows go through the one-launch BatchNorm, which writes dz)
 
 
@@ -479,9 +462,8 @@ def _bn_rows_bwd_sums(dy2, x2, gamma, beta, mean, invstd, slope, act_first, ms=N
     db = torch.empty_like(mean)
     lift = torch.empty((LIFT_WORDS,), device=x2.device, dtype=torch.float32)
     parts = torch.empty((2 * C_ * (int(lib().dlip_bn_rows_chunks(M)) + 1),), device=x2.device, dtype=torch.float32)   # (per part and channel; ABI 50)
-    check(lib().dlip_bn_rows_train_bwd_sums_f32(ptr(dy2), ptr(x2), ptr(gamma), ptr(beta), ptr(mean), ptr(invstd), ptr(dg), ptr(db),
-                                                ptr(_ws(M, C_, x2.device)), ptr(parts), M, C_, slope, int(act_first), ptr(lift), ptr(ms_c),
-                                                int(ms_T), stream_handle()), "dlip_bn_rows_train_bwd_sums_f32")
+    call("dlip_bn_rows_train_bwd_sums_f32", dy2, x2, gamma, beta, mean, invstd, dg, db, _ws(M, C_, x2.device), parts, M, C_, slope, int(act_first),
+         lift, ms_c, int(ms_T))
     return dg, db, lift
 
 
@@ -603,9 +585,8 @@ class TDNNBlockTrainFn(Function):
             dz2 = torch.empty((M, K), device=dev, dtype=torch.float32)
             dgamma, dbeta = torch.empty_like(mean), torch.empty_like(mean)
             lift = torch.empty((LIFT_WORDS,), device=dev, dtype=torch.float32)
-            check(lib().dlip_bn_rows_train_bwd_ms_f32(ptr(coef_ms), int(T_ms), ptr(z), ptr(gamma), ptr(beta), ptr(mean), ptr(invstd),
-                                                      ptr(dz2), ptr(dgamma), ptr(dbeta), ptr(_ws(M, K, dev)), M, K, float(slope), ptr(lift),
-                                                      stream_handle()), "dlip_bn_rows_train_bwd_ms_f32")
+            call("dlip_bn_rows_train_bwd_ms_f32", coef_ms, int(T_ms), z, gamma, beta, mean, invstd, dz2, dgamma, dbeta, _ws(M, K, dev), M, K,
+                 float(slope), lift)
             dz2._dlip_lift = lift
             return TDNNBlockTrainFn._backward_from_dz(ctx, dz2, dgamma, dbeta)
         if fused:
@@ -621,17 +602,14 @@ class TDNNBlockTrainFn(Function):
                 J32 = x.shape[1]
                 gT = torch.empty((K, J32), device=dev, dtype=torch.float32)
                 dzs = torch.empty((B, 1, Tp, Kp), device=dev, dtype=torch.float32) if want_x else None
-                check(lib().dlip_wgrad_operand_split_bnbwd_f32(ptr(dy2), ptr(z2), ptr(gT), J32, M, K, ptr(mean), ptr(invstd), ptr(gamma), ptr(beta),
-                                                               ptr(dgamma), ptr(dbeta), M, sl, int(act_first), ptr(lift), ptr(dzs),
-                                                               Kp if Kp != K else 0, ptr(ms_c), int(ms_T), stream_handle()),
-                      "dlip_wgrad_operand_split_bnbwd_f32")
+                call("dlip_wgrad_operand_split_bnbwd_f32", dy2, z2, gT, J32, M, K, mean, invstd, gamma, beta, dgamma, dbeta, M, sl, int(act_first),
+                     lift, dzs, Kp if Kp != K else 0, ms_c, int(ms_T))
             else:
                 N32 = (B + 31) // 32 * 32
                 gT = torch.empty((K, 1, Tp, N32), device=dev, dtype=torch.float32)
                 dzs = torch.empty((B, 1, Tp, K), device=dev, dtype=torch.float32) if want_x else None
-                check(lib().dlip_wgrad_chwn_bnbwd_f32(ptr(dy2), ptr(z2), ptr(gT), B, 1, Tp, K, N32, ptr(mean), ptr(invstd), ptr(gamma), ptr(beta),
-                                                      ptr(dgamma), ptr(dbeta), M, sl, int(act_first), ptr(lift), ptr(dzs), stream_handle()),
-                      "dlip_wgrad_chwn_bnbwd_f32")
+                call("dlip_wgrad_chwn_bnbwd_f32", dy2, z2, gT, B, 1, Tp, K, N32, mean, invstd, gamma, beta, dgamma, dbeta, M, sl, int(act_first),
+                     lift, dzs)
             dx = None
             if want_x:
                 shape_only = torch.empty((B, 1, Tp, K), device=dev, dtype=torch.float32)      # (address and shape: conv_train reads dzs)
@@ -669,8 +647,7 @@ class TDNNBlockTrainFn(Function):
                 dbias = torch.zeros((K,), device=dev, dtype=torch.float32)
             else:
                 dbias = torch.empty((K,), device=dev, dtype=torch.float32)
-                check(lib().dlip_colsum_rows_f32(ptr(dz2), ptr(dbias), ptr(_ws(B * Tp, K, dev)), B * Tp, K, stream_handle()),
-                      "dlip_colsum_rows_f32")
+                call("dlip_colsum_rows_f32", dz2, dbias, _ws(B * Tp, K, dev), B * Tp, K)
         dz = dz2.view(B, Tp, K)
         dx = None
         from . import autograd_video as av
@@ -684,8 +661,7 @@ class TDNNBlockTrainFn(Function):
             else:
                 J32 = x.shape[1]
                 gT = torch.empty((K, J32), device=dev, dtype=torch.float32)
-                check(lib().dlip_wgrad_operand_f32(ptr(dz2), ptr(gT), J32, B, 1, Tp, K, K, 1, Tp, 1, 1, 1, 1, 1, 1, 0, 0, ptr(lift), stream_handle()),
-                      "dlip_wgrad_operand_f32")
+                call("dlip_wgrad_operand_f32", dz2, gT, J32, B, 1, Tp, K, K, 1, Tp, 1, 1, 1, 1, 1, 1, 0, 0, lift)
         elif mode == 2 and ctx.needs_input_grad[1]:
             gT, dzs = av.wgrad_image(dz2.view(B, 1, Tp, K), lift, also_nhwc_split=ctx.needs_input_grad[0] and K % 32 == 0)
         if ctx.needs_input_grad[0]:
@@ -723,20 +699,20 @@ def _conv1d_wgrad(x, dz, S, dilation, lift=None):
     xf, dzf = x.view(B * T, Cx), dzp.view(B * T, K)
     # reduction-major operands: [rows, J32] with the B*T axis contiguous (zero padded)
     dzT = torch.empty((1, K, J32), device=dev, dtype=torch.float32)
-    check(lib().dlip_nct_to_ntc_f32(ptr(dzf), ptr(dzT), 1, J, K, J32, stream_handle()), "dlip_nct_to_ntc_f32")
+    call("dlip_nct_to_ntc_f32", dzf, dzT, 1, J, K, J32)
     scale2 = torch.empty((2,), device=dev, dtype=torch.float32)
-    check(lib().dlip_pow2_scale_f32(ptr(dzT), ptr(scale2), dzT.numel(), 1024.0, stream_handle()), "dlip_pow2_scale_f32")
+    call("dlip_pow2_scale_f32", dzT, scale2, dzT.numel(), 1024.0)
     dzT_s = torch.empty_like(dzT)
-    check(lib().dlip_split_pack_scaled_f32(ptr(dzT), ptr(dzT_s), ptr(scale2), K, J32, stream_handle()), "dlip_split_pack_scaled_f32")
+    call("dlip_split_pack_scaled_f32", dzT, dzT_s, scale2, K, J32)
     inv = torch.empty((K,), device=dev, dtype=torch.float32)
-    check(lib().dlip_fill_from_scalar_f32(scale2[1:].data_ptr(), ptr(inv), K, stream_handle()), "dlip_fill_from_scalar_f32")
+    call("dlip_fill_from_scalar_f32", scale2[1:].data_ptr(), inv, K)
     ones = torch.ones((K,), device=dev, dtype=torch.float32)
     zeros = torch.zeros((K,), device=dev, dtype=torch.float32)
     dwt = torch.empty((S, Cx, K), device=dev, dtype=torch.float32)
     xT = torch.empty((1, Cx, J32), device=dev, dtype=torch.float32)
     for s in range(S):
         xs = xf[s * dilation: s * dilation + J]                                # contiguous row slice: no copy
-        check(lib().dlip_nct_to_ntc_f32(ptr(xs), ptr(xT), 1, J, Cx, J32, stream_handle()), "dlip_nct_to_ntc_f32")
+        call("dlip_nct_to_ntc_f32", xs, xT, 1, J, Cx, J32)
         xT_s = ops.split_pack(xT.view(Cx, J32))
         ops.conv_nhwc(xT_s.view(1, 1, Cx, J32), dzT_s.view(K, 1, 1, J32), None, w_scale=ones, x_split=True,
                       post_scale=inv, post_shift=zeros, out=dwt[s].view(1, 1, Cx, K))
@@ -757,8 +733,7 @@ class MeanStdPoolFn(Function):
             z, mean, invstd, gamma, beta, slope = pending
             B, T, C_ = x.shape
             y = torch.empty((B, 2 * C_), device=x.device, dtype=torch.float32)
-            check(lib().dlip_meanstd_pool_bn_f32(ptr(z), ptr(mean), ptr(invstd), ptr(gamma), ptr(beta), float(slope), ptr(y), B, T, C_, stream_handle()),
-                  "dlip_meanstd_pool_bn_f32")
+            call("dlip_meanstd_pool_bn_f32", z, mean, invstd, gamma, beta, float(slope), y, B, T, C_)
             ctx.save_for_backward(z, y, mean, invstd, gamma, beta)
             ctx.slope, ctx.on_load = float(slope), True
             return y
@@ -778,17 +753,15 @@ class MeanStdPoolFn(Function):
                 # dlip_bn_rows_train_bwd_ms_f32): dx stays UNWRITTEN and carries what that takes.  TDNNBlockTrainFn.backward raises if the
                 # tensor it receives has lost the attribute (it was told at forward time to expect it).
                 coef = torch.empty_like(y)            # [B, 2C] = (A | K): dy[b,t,c] = A + K y, one launch over the pooled tensors
-                check(lib().dlip_meanstd_bwd_coef_f32(ptr(y), ptr(dy.contiguous()), ptr(coef), B, C_, T, stream_handle()), "dlip_meanstd_bwd_coef_f32")
+                call("dlip_meanstd_bwd_coef_f32", y, dy.contiguous(), coef, B, C_, T)
                 dx._dlip_ms = (coef, T)
                 return dx, None, None
-            check(lib().dlip_meanstd_pool_bwd_bn_f32(ptr(z), ptr(mean), ptr(invstd), ptr(gamma), ptr(beta), ctx.slope, ptr(y), ptr(dy.contiguous()),
-                                                     ptr(dx), B, T, C_, stream_handle()), "dlip_meanstd_pool_bwd_bn_f32")
+            call("dlip_meanstd_pool_bwd_bn_f32", z, mean, invstd, gamma, beta, ctx.slope, y, dy.contiguous(), dx, B, T, C_)
             return dx, None, None
         x, y = ctx.saved_tensors
         B, T, C_ = x.shape
         dx = torch.empty_like(x)
-        check(lib().dlip_meanstd_pool_bwd_f32(ptr(x), ptr(y), ptr(dy.contiguous()), ptr(dx), B, T, C_, stream_handle()),
-              "dlip_meanstd_pool_bwd_f32")
+        call("dlip_meanstd_pool_bwd_f32", x, y, dy.contiguous(), dx, B, T, C_)
         return dx, None, None
 
 
@@ -823,9 +796,8 @@ class MHAttnStatPoolFn(Function):
         rde = torch.empty_like(hidden)
         de = torch.empty((B, n, T), device=x.device, dtype=torch.float32)
         dek = torch.empty((B, n), device=x.device, dtype=torch.float32)
-        check(lib().dlip_mh_attn_stat_pool_bwd_f32(ptr(x), ptr(hidden), ptr(vv), ptr(head_off), ptr(alpha), ptr(y), ptr(dy.contiguous()), None, 0,
-                                                   ctx.eps, ptr(dx), ptr(dh), ptr(rde), ptr(de), ptr(dek), B, T, C_, S, n, stream_handle()),
-              "dlip_mh_attn_stat_pool_bwd_f32")
+        call("dlip_mh_attn_stat_pool_bwd_f32", x, hidden, vv, head_off, alpha, y, dy.contiguous(), None, 0, ctx.eps, dx, dh, rde, de, dek, B, T, C_,
+             S, n)
         dv = _colsum(rde.view(B * T, S)).view(ctx.shapes[0]) if ctx.needs_input_grad[2] else None
         dk = _colsum(dek).view(ctx.shapes[1]) if ctx.needs_input_grad[3] else None
         return dx, dh, dv, dk, None, None
@@ -868,8 +840,7 @@ class StatPoolNHWCFn(Function):
         x, y = ctx.saved_tensors
         N, H, W, C_ = x.shape
         dx = torch.empty_like(x)
-        check(lib().dlip_statpool_nhwc_bwd_f32(ptr(x), ptr(y), ptr(dy.contiguous()), ctx.eps, ptr(dx), N, H, W, C_, stream_handle()),
-              "dlip_statpool_nhwc_bwd_f32")
+        call("dlip_statpool_nhwc_bwd_f32", x, y, dy.contiguous(), ctx.eps, dx, N, H, W, C_)
         return dx, None
 
 
@@ -898,8 +869,7 @@ def materialize_pending(y, pending):
     z, mean, invstd, gamma, beta, slope = pending
     M, C_ = z.numel() // z.shape[-1], z.shape[-1]
     sv, sc = (slope, 0.0) if isinstance(slope, torch.Tensor) else (None, float(slope))
-    check(lib().dlip_bn_apply_rows_f32(ptr(z), ptr(mean), ptr(invstd), ptr(gamma), ptr(beta), ptr(sv), sc, ptr(y), M, C_, stream_handle()),
-          "dlip_bn_apply_rows_f32")
+    call("dlip_bn_apply_rows_f32", z, mean, invstd, gamma, beta, sv, sc, y, M, C_)
 
 
 def tdnn_block_train(x, blk, pending=None, defer=False):
@@ -921,10 +891,10 @@ def bn_rows_act_train(x, bn, slope, act_first):
                              bn.num_batches_tracked)
 
 
-POOL_BN_ON_LOAD = __import__("os").environ.get("DLIP_POOL_BN_ON_LOAD", "1") != "0"      # (the environment switch: same-box A/B runs)
+POOL_BN_ON_LOAD = env_switch("DLIP_POOL_BN_ON_LOAD")      # (the environment switch: same-box A/B runs)
 
 
-POOL_BWD_ON_LOAD = __import__("os").environ.get("DLIP_POOL_BWD_ON_LOAD", "1") != "0"     # (the environment switch: same-box A/B runs)
+POOL_BWD_ON_LOAD = env_switch("DLIP_POOL_BWD_ON_LOAD")     # (the environment switch: same-box A/B runs)
 
 
 def meanstd_pool(x, pending=None, hand_over=False):

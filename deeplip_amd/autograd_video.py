@@ -11,13 +11,14 @@ parameters keep the reference layouts, so the state dict is the reference's.
 """
 from __future__ import annotations
 
+import os
 import weakref
 
 import torch
 from torch.autograd import Function
 
 from . import _lib, ops
-from ._lib import LIFT_BCAST, LIFT_WORDS, check, lib, ptr, stream_handle
+from ._lib import LIFT_BCAST, LIFT_WORDS, call, env_switch, lib
 from .autograd import BNRowsActFn, _permute3, _ws
 
 
@@ -45,41 +46,8 @@ def _colsum_rows(x2):
     M, C_ = x2.shape
     _lib.ensure_conv_workspace()
     y = torch.empty((C_,), device=x2.device, dtype=torch.float32)
-    check(lib().dlip_colsum_rows_f32(ptr(x2), ptr(y), ptr(_ws(M, C_, x2.device)), M, C_, stream_handle()), "dlip_colsum_rows_f32")
+    call("dlip_colsum_rows_f32", x2, y, _ws(M, C_, x2.device), M, C_)
     return y
-
-
-def wgrad_gemm(dz_rows, tap_rows, n_taps):
-    """dW[s, c, k] = sum_j rows_s[j, c] * dz[j, k]: one GEMM per filter tap with the J output positions as the
-    reduction.  Both operands are transposed to reduction-major, split into (hi, lo) fp16 pairs (the gradient
-    after a power-of-two lift into fp16's normal range) and multiplied by the LDS-DMA kernel, whose balanced
-    work split is what fills the chip on a [C x K] product with J ~ 1e5..1e6 (same scheme as the speech
-    encoder's Conv1d weight gradient, autograd._conv1d_wgrad).  ``tap_rows(s)`` -> [J, C] contiguous."""
-    J, K = dz_rows.shape
-    dev = dz_rows.device
-    J32 = (J + 31) // 32 * 32
-    dzT = torch.empty((1, K, J32), device=dev, dtype=torch.float32)
-    check(lib().dlip_nct_to_ntc_f32(ptr(dz_rows), ptr(dzT), 1, J, K, J32, stream_handle()), "dlip_nct_to_ntc_f32")
-    scale2 = torch.empty((2,), device=dev, dtype=torch.float32)
-    check(lib().dlip_pow2_scale_f32(ptr(dzT), ptr(scale2), dzT.numel(), 1024.0, stream_handle()), "dlip_pow2_scale_f32")
-    dzT_s = torch.empty_like(dzT)
-    check(lib().dlip_split_pack_scaled_f32(ptr(dzT), ptr(dzT_s), ptr(scale2), K, J32, stream_handle()), "dlip_split_pack_scaled_f32")
-    inv = lift_inv(scale2, K)
-    ones = const_vec(K, 1.0, dev)
-    zeros = const_vec(K, 0.0, dev)
-    out = None
-    xT = None
-    for s in range(n_taps):
-        rows = tap_rows(s)
-        Cx = rows.shape[1]
-        if out is None:
-            out = torch.empty((n_taps, Cx, K), device=dev, dtype=torch.float32)
-            xT = torch.empty((1, Cx, J32), device=dev, dtype=torch.float32)
-        check(lib().dlip_nct_to_ntc_f32(ptr(rows), ptr(xT), 1, J, Cx, J32, stream_handle()), "dlip_nct_to_ntc_f32")
-        xT_s = ops.split_pack(xT.view(Cx, J32))
-        ops.conv_nhwc(xT_s.view(1, 1, Cx, J32), dzT_s.view(K, 1, 1, J32), None, w_scale=ones, x_split=True,
-                      post_scale=inv, post_shift=zeros, out=out[s].view(1, 1, Cx, K))
-    return out
 
 
 # Arithmetic of the convolutions of a TRAINING step (forward and data gradient).  The weight gradient is a split-fp16 product in BOTH
@@ -89,7 +57,7 @@ def wgrad_gemm(dz_rows, tap_rows, n_taps):
 # "f16x3" = the split-fp16 kernels of the extraction path -- activations split once per convolution (dlip_split_pack_f32; a
 # gradient after its power-of-two lift), the CURRENT weights split on the device (dlip_split_weights_rows_f32), fp32 out: 2.6x the
 # rate of the exact-fp32 MFMA kernel at fp32-grade accuracy -- or "f32", the exact kernel (what the training path used before).
-TRAIN_CONV = "f32" if __import__("os").environ.get("DLIP_ARITH", "auto").strip().lower() == "f32" else "f16x3"    # (deeplip_amd.arith.configure sets it)
+TRAIN_CONV = "f32" if os.environ.get("DLIP_ARITH", "auto").strip().lower() == "f32" else "f16x3"    # (deeplip_amd.arith.configure sets it)
 WGRAD_ODD_PITCH = True
 
 
@@ -100,7 +68,7 @@ def pow2_lift(t):
     if ready is not None:
         return ready
     scale2 = torch.empty((LIFT_WORDS,), device=t.device, dtype=torch.float32)
-    check(lib().dlip_pow2_lift_f32(ptr(t), ptr(scale2), t.numel(), 1024.0, stream_handle()), "dlip_pow2_lift_f32")
+    call("dlip_pow2_lift_f32", t, scale2, t.numel(), 1024.0)
     return scale2
 
 
@@ -110,7 +78,7 @@ def lift_inv(scale2, K):
     if scale2.numel() >= 2 + K and K <= LIFT_BCAST:
         return scale2[2:2 + K]
     inv = torch.empty((K,), device=scale2.device, dtype=torch.float32)
-    check(lib().dlip_fill_from_scalar_f32(scale2[1:].data_ptr(), ptr(inv), K, stream_handle()), "dlip_fill_from_scalar_f32")
+    call("dlip_fill_from_scalar_f32", scale2[1:].data_ptr(), inv, K)
     return inv
 
 
@@ -118,7 +86,7 @@ def lift_fwd(scale2, K):
     """[K] copies of 2^e: what a convolution's accumulator is DIVIDED by when its activation operand carries the lift (the ``w_scale``
     vector of ops.conv_nhwc, whose epilogue forms acc / w_scale -- a power of two: exact)."""
     fwd = torch.empty((K,), device=scale2.device, dtype=torch.float32)
-    check(lib().dlip_fill_from_scalar_f32(scale2.data_ptr(), ptr(fwd), K, stream_handle()), "dlip_fill_from_scalar_f32")
+    call("dlip_fill_from_scalar_f32", scale2.data_ptr(), fwd, K)
     return fwd
 
 
@@ -236,7 +204,7 @@ class _WeightPrep:
             self.side = torch.cuda.Stream(device=d_dev.device)
         self.side.wait_stream(cur)                       # the previous step's last readers of the images are behind us
         with torch.cuda.stream(self.side):
-            check(lib().dlip_split_weights_multi_f32(ptr(d_dev), ptr(b_dev), n, max_row, stream_handle()), "dlip_split_weights_multi_f32")
+            call("dlip_split_weights_multi_f32", d_dev, b_dev, n, max_row)
             self.event = torch.cuda.Event()
             self.event.record(self.side)
         self.joined = set()
@@ -300,13 +268,12 @@ def conv_train(x, w_krsc, bias, stride=(1, 1), pad=(0, 0), dil=(1, 1), lift=Fals
                 scale2 = pow2_lift(x)
             ws = torch.empty((K, R_, S_, pad_x), device=dev, dtype=torch.float32)
             wsc = torch.empty((K,), device=dev, dtype=torch.float32)
-            check(lib().dlip_split_weights_perm_f32(ptr(w_ref.contiguous()), ptr(ws), ptr(wsc), Ko, Ci, R_ * S_, 1, pad_x, stream_handle()),
-                  "dlip_split_weights_perm_f32")
+            call("dlip_split_weights_perm_f32", w_ref.contiguous(), ws, wsc, Ko, Ci, R_ * S_, 1, pad_x)
             if xs_ready is not None:       # (round 6) the padded split operand [N,H,W,pad_x], lifted by scale2, written by the pass that formed the gradient
                 xs = xs_ready
             else:
                 xs = torch.empty((N, H, W, pad_x), device=dev, dtype=torch.float32)
-                check(lib().dlip_split_pack_scaled_pad_f32(ptr(x), ptr(xs), ptr(scale2), N * H * W, Cx, pad_x, stream_handle()), "dlip_split_pack_scaled_pad_f32")
+                call("dlip_split_pack_scaled_pad_f32", x, xs, scale2, N * H * W, Cx, pad_x)
             return ops.conv_nhwc(xs, ws, None, stride=stride, pad=pad, dil=dil, w_scale=wsc, x_split=True, post_scale=lift_inv(scale2, K),
                                  post_shift=const_vec(K, 0.0, dev))
         if TRAIN_CONV != "f16x3" or Cx % 32 or K % 4 or Cw != Cx:
@@ -321,8 +288,7 @@ def conv_train(x, w_krsc, bias, stride=(1, 1), pad=(0, 0), dil=(1, 1), lift=Fals
         else:
             ws = torch.empty((K, R_, S_, Cw), device=dev, dtype=torch.float32)
             wsc = torch.empty((K,), device=dev, dtype=torch.float32)
-            check(lib().dlip_split_weights_perm_f32(ptr(w_ref.contiguous()), ptr(ws), ptr(wsc), Ko, Ci, R_ * S_, 1 if transposed else 0, Cw,
-                                                    stream_handle()), "dlip_split_weights_perm_f32")
+            call("dlip_split_weights_perm_f32", w_ref.contiguous(), ws, wsc, Ko, Ci, R_ * S_, 1 if transposed else 0, Cw)
             if w_ref.is_contiguous():
                 WEIGHT_PREP.register(key, w_ref, Ko, Ci, R_ * S_, 1 if transposed else 0, Cw, ws, wsc)
     else:
@@ -333,7 +299,7 @@ def conv_train(x, w_krsc, bias, stride=(1, 1), pad=(0, 0), dil=(1, 1), lift=Fals
         L = w_krsc.numel() // K
         ws = torch.empty_like(w_krsc)
         wsc = torch.empty((K,), device=dev, dtype=torch.float32)
-        check(lib().dlip_split_weights_rows_f32(ptr(w_krsc), ptr(ws), ptr(wsc), K, L, stream_handle()), "dlip_split_weights_rows_f32")
+        call("dlip_split_weights_rows_f32", w_krsc, ws, wsc, K, L)
     if not lift:
         st = None
         if stats is not None and stats.get("chunks", 0) > 0:
@@ -347,7 +313,7 @@ def conv_train(x, w_krsc, bias, stride=(1, 1), pad=(0, 0), dil=(1, 1), lift=Fals
         xs = xs_ready
     else:
         xs = torch.empty_like(x)
-        check(lib().dlip_split_pack_scaled_f32(ptr(x), ptr(xs), ptr(scale2), x.numel() // Cx, Cx, stream_handle()), "dlip_split_pack_scaled_f32")
+        call("dlip_split_pack_scaled_f32", x, xs, scale2, x.numel() // Cx, Cx)
     inv = lift_inv(scale2, K)
     zeros = const_vec(K, 0.0, dev)
     return ops.conv_nhwc(xs, ws, None, stride=stride, pad=pad, dil=dil, w_scale=wsc, x_split=True, post_scale=inv, post_shift=zeros)
@@ -376,8 +342,7 @@ def wgrad_conv_fused(x, dy, R, S, stride, pad, dil, scale2=None):
     if scale2 is None:
         scale2 = pow2_lift(dy)
     dzT_s = torch.empty((K, J32), device=dev, dtype=torch.float32)
-    check(lib().dlip_wgrad_operand_f32(ptr(dy), ptr(dzT_s), J32, N, Ho, Wo, K, K, Ho, Wo, 1, 1, 1, 1, 1, 1, 0, 0, ptr(scale2), stream_handle()),
-          "dlip_wgrad_operand_f32")
+    call("dlip_wgrad_operand_f32", dy, dzT_s, J32, N, Ho, Wo, K, K, Ho, Wo, 1, 1, 1, 1, 1, 1, 0, 0, scale2)
     # "f32": the layer input may have ANY fp32 magnitude (the forward and the data gradient never split it), so it gets a power-of-two
     # lift of its own, like dy -- one more absmax pass -- and the GEMM's epilogue divides by both powers (exact).  "f16x3" leaves x as
     # it is: there the forward has split the same tensor unlifted already, and the mode's range contract covers both.
@@ -386,8 +351,8 @@ def wgrad_conv_fused(x, dy, R, S, stride, pad, dil, scale2=None):
         x = x.contiguous()
         x_lift = pow2_lift(x)
     xT_s = torch.empty((taps * Cx, J32), device=dev, dtype=torch.float32)
-    check(lib().dlip_wgrad_operand_f32(ptr(x), ptr(xT_s), J32, N, H, W, Cx, _pixel_pitch(x), Ho, Wo, stride[0], stride[1], R, S, dil[0], dil[1],
-                                       pad[0], pad[1], ptr(x_lift), stream_handle()), "dlip_wgrad_operand_f32")
+    call("dlip_wgrad_operand_f32", x, xT_s, J32, N, H, W, Cx, _pixel_pitch(x), Ho, Wo, stride[0], stride[1], R, S, dil[0], dil[1], pad[0], pad[1],
+         x_lift)
     inv = lift_inv(scale2, K)
     ones = const_vec(K, 1.0, dev) if x_lift is None else lift_fwd(x_lift, K)
     zeros = const_vec(K, 0.0, dev)
@@ -410,11 +375,9 @@ def operand_and_split(t2, scale2=None, bn=None):
     if bn is not None:      # t2's values were never written: read the raw convolution output and apply its BatchNorm + activation on load
         z, mean, invstd, gamma, beta, slope = bn
         sv, sc = (slope, 0.0) if isinstance(slope, torch.Tensor) else (None, float(slope))
-        check(lib().dlip_wgrad_operand_split_bn_f32(ptr(z), ptr(opT), J32, J, C_, ptr(mean), ptr(invstd), ptr(gamma), ptr(beta), ptr(sv), sc,
-                                                    ptr(spl), stream_handle()), "dlip_wgrad_operand_split_bn_f32")
+        call("dlip_wgrad_operand_split_bn_f32", z, opT, J32, J, C_, mean, invstd, gamma, beta, sv, sc, spl)
         return opT, spl
-    check(lib().dlip_wgrad_operand_split_f32(ptr(t2), ptr(opT), J32, J, C_, ptr(scale2) if scale2 is not None else None, ptr(spl), stream_handle()),
-          "dlip_wgrad_operand_split_f32")
+    call("dlip_wgrad_operand_split_f32", t2, opT, J32, J, C_, scale2, spl)
     return opT, spl
 
 
@@ -440,7 +403,7 @@ WGRAD = "conv"
 WGRAD_SLICE_MAJOR = True
 # Round 5: the weight-gradient convolution's epilogue stores dW in the reference layout [K, C, R, S] itself (dlip_wgrad_conv_f16x3's
 # R, S): no [C, R', S', K] tensor, slice copy and permute launch behind every one of them.  False: round 4's path (tests compare the two).
-WGRAD_DIRECT_LAYOUT = __import__("os").environ.get("DLIP_WGRAD_DIRECT", "1") != "0"      # (the environment switch: same-box A/B runs)
+WGRAD_DIRECT_LAYOUT = env_switch("DLIP_WGRAD_DIRECT")      # (the environment switch: same-box A/B runs)
 
 
 def _wgrad_conv_launch(xT, gT, inv, C_, H, W, K, Ho, Wo, N32, stride, pad, dil, RS=None):
@@ -450,9 +413,8 @@ def _wgrad_conv_launch(xT, gT, inv, C_, H, W, K, Ho, Wo, N32, stride, pad, dil, 
     Ro = (H + 2 * pad[0] - stride[0] * (Ho - 1) - 1) // dil[0] + 1
     So = (W + 2 * pad[1] - stride[1] * (Wo - 1) - 1) // dil[1] + 1
     out = torch.empty((K, C_, RS[0], RS[1]) if RS is not None else (C_, Ro, So, K), device=dev, dtype=torch.float32)
-    check(lib().dlip_wgrad_conv_f16x3(ptr(xT), ptr(gT), ptr(inv), ptr(const_vec(K, 0.0, dev)), ptr(const_vec(K, 1.0, dev)), ptr(out), C_, H, W, K,
-                                      Ho, Wo, N32, stride[0], stride[1], pad[0], pad[1], dil[0], dil[1], RS[0] if RS else 0, RS[1] if RS else 0,
-                                      stream_handle()), "dlip_wgrad_conv_f16x3")
+    call("dlip_wgrad_conv_f16x3", xT, gT, inv, const_vec(K, 0.0, dev), const_vec(K, 1.0, dev), out, C_, H, W, K, Ho, Wo, N32, stride[0], stride[1],
+         pad[0], pad[1], dil[0], dil[1], RS[0] if RS else 0, RS[1] if RS else 0)
     return out
 
 
@@ -468,11 +430,9 @@ def wgrad_image(t, scale2=None, also_nhwc_split=False, bn=None):
     if bn is not None:      # (see operand_and_split)
         z, mean, invstd, gamma, beta, slope = bn
         sv, sc = (slope, 0.0) if isinstance(slope, torch.Tensor) else (None, float(slope))
-        check(lib().dlip_wgrad_chwn_bn_f32(ptr(z), ptr(img), N, H, W, C_, N32, ptr(mean), ptr(invstd), ptr(gamma), ptr(beta), ptr(sv), sc, ptr(spl),
-                                           stream_handle()), "dlip_wgrad_chwn_bn_f32")
+        call("dlip_wgrad_chwn_bn_f32", z, img, N, H, W, C_, N32, mean, invstd, gamma, beta, sv, sc, spl)
         return img, spl
-    check(lib().dlip_wgrad_chwn_f32(ptr(t), ptr(img), N, H, W, C_, _pixel_pitch(t), N32, ptr(scale2) if scale2 is not None else None,
-                                    1 if WGRAD_SLICE_MAJOR else 0, ptr(spl) if spl is not None else None, stream_handle()), "dlip_wgrad_chwn_f32")
+    call("dlip_wgrad_chwn_f32", t, img, N, H, W, C_, _pixel_pitch(t), N32, scale2, 1 if WGRAD_SLICE_MAJOR else 0, spl)
     return img, spl
 
 
@@ -528,14 +488,13 @@ def _upsample_zero(dy, Hu, Wu, sh, sw, lift, Ci=4):
     src = torch.empty((N, Hu, Wu, K), device=dy.device, dtype=torch.float32)
     if TRAIN_CONV == "f16x3" and K % 32 == 0 and Ci % 4 == 0 and lift is not None and UPSAMPLE_SPLIT_FUSED:   # (conv_train's split-kernel conditions)
         xs = torch.empty_like(src)
-        check(lib().dlip_upsample_zero_split_f32(ptr(dy), ptr(xs), ptr(lift), N, Ho, Wo, Hu, Wu, K, sh, sw, stream_handle()),
-              "dlip_upsample_zero_split_f32")
+        call("dlip_upsample_zero_split_f32", dy, xs, lift, N, Ho, Wo, Hu, Wu, K, sh, sw)
         return src, xs
-    check(lib().dlip_upsample_zero_f32(ptr(dy), ptr(src), N, Ho, Wo, Hu, Wu, K, sh, sw, stream_handle()), "dlip_upsample_zero_f32")
+    call("dlip_upsample_zero_f32", dy, src, N, Ho, Wo, Hu, Wu, K, sh, sw)
     return src, None
 
 
-UPSAMPLE_SPLIT_FUSED = __import__("os").environ.get("DLIP_UPSAMPLE_SPLIT", "1") != "0"
+UPSAMPLE_SPLIT_FUSED = env_switch("DLIP_UPSAMPLE_SPLIT")
 
 
 class ConvTrainFn(Function):
@@ -578,10 +537,7 @@ class ConvTrainFn(Function):
         N, H, W, Cx = ctx.x_shape
         K, _, R, S = weight.shape
         _, Ho, Wo, _ = dy.shape
-        J = N * Ho * Wo
-        dev = dy.device
-        dz_rows = dy.view(J, K)
-        dbias = _colsum_rows(dz_rows) if has_bias and ctx.needs_input_grad[2] else None
+        dbias = _colsum_rows(dy.view(N * Ho * Wo, K)) if has_bias and ctx.needs_input_grad[2] else None
         dx = None
         lift = pow2_lift(dy) if (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]) else None   # zero insertion does not change max|dy|
         if ctx.fused:
@@ -606,20 +562,8 @@ class ConvTrainFn(Function):
                 src, dys = _upsample_zero(dy, H + 2 * ph - dh * (R - 1), W + 2 * pw - dw * (S - 1), sh, sw, lift, weight.shape[1])
             dx = conv_train(src, None, None, (1, 1), (dh * (R - 1) - ph, dw * (S - 1) - pw), (dh, dw), lift=True, scale2=lift,
                             w_ref=weight, transposed=True, xs_ready=dys)
-        dweight = None
-        if ctx.needs_input_grad[1]:
-            # all taps side by side in ONE [J, RS*C] matrix -> one GEMM with RS*C output rows (RS times the
-            # tiles of a per-tap GEMM: a 64-channel layer would otherwise be a single 64x64 tile)
-            taps = R * S
-            if Cx % 4 == 0 and K % 4 == 0:
-                return dx, wgrad_conv(x, dy, R, S, (sh, sw), (ph, pw), (dh, dw), scale2=lift), dbias, None, None, None, None
-            rows = torch.empty((J, taps * Cx), device=dev, dtype=torch.float32)
-            for t in range(taps):
-                r, s = divmod(t, S)
-                check(lib().dlip_tap_gather_f32(ptr(x), rows.data_ptr() + 4 * t * Cx, N, H, W, Cx, Cx, Ho, Wo, sh, sw,
-                                                r * dh - ph, s * dw - pw, taps * Cx, stream_handle()), "dlip_tap_gather_f32")
-            dwt = wgrad_gemm(dz_rows, lambda _: rows, 1).view(taps, Cx, K)  # [RS, C, K]
-            dweight = _permute3(dwt, (2, 1, 0)).view(K, Cx, R, S)
+        # (the forward admits only Cx % 4 == 0 and K % 4 == 0: what wgrad_conv takes)
+        dweight = wgrad_conv(x, dy, R, S, (sh, sw), (ph, pw), (dh, dw), scale2=lift) if ctx.needs_input_grad[1] else None
         return dx, dweight, dbias, None, None, None, None
 
 
@@ -639,7 +583,7 @@ class StemConvTrainFn(Function):
         if TRAIN_CONV == "f16x3" and K == 64:
             img = torch.empty((K * 296,), device=dev, dtype=torch.float32)
             wsc = torch.empty((K,), device=dev, dtype=torch.float32)
-            check(lib().dlip_split_stem_weights_f32(ptr(weight.contiguous()), ptr(img), ptr(wsc), K, stream_handle()), "dlip_split_stem_weights_f32")
+            call("dlip_split_stem_weights_f32", weight.contiguous(), img, wsc, K)
             y = ops.stem3d(x, img, zero, one, w_scale=wsc)
         else:
             wk = torch.zeros((248, K), device=dev, dtype=torch.float32)
@@ -666,9 +610,9 @@ class StemConvTrainFn(Function):
             scale2 = pow2_lift(dy)
             sm = 1 if WGRAD_SLICE_MAJOR else 0
             xT = torch.empty((5, H, W, N32), device=dev, dtype=torch.float32)
-            check(lib().dlip_stem_wgrad_chwn_f32(ptr(x), ptr(xT), B, T, H, W, N32, sm, stream_handle()), "dlip_stem_wgrad_chwn_f32")
+            call("dlip_stem_wgrad_chwn_f32", x, xT, B, T, H, W, N32, sm)
             gT = torch.empty((K, Ho, Wo, N32), device=dev, dtype=torch.float32)
-            check(lib().dlip_wgrad_chwn_f32(ptr(dy), ptr(gT), N, Ho, Wo, K, K, N32, ptr(scale2), sm, None, stream_handle()), "dlip_wgrad_chwn_f32")
+            call("dlip_wgrad_chwn_f32", dy, gT, N, Ho, Wo, K, K, N32, scale2, sm, None)
             inv = lift_inv(scale2, K)
             if sm:
                 out = _wgrad_conv_launch(xT, gT, inv, 5, H, W, K, Ho, Wo, N32, (2, 2), (3, 3), (1, 1))   # [5, 8, 8, K] (even H: a spare row / column)
@@ -683,8 +627,7 @@ class StemConvTrainFn(Function):
             J32 += 32
         scale2 = pow2_lift(dy)
         dzT_s = torch.empty((K, J32), device=dev, dtype=torch.float32)
-        check(lib().dlip_wgrad_operand_f32(ptr(dy), ptr(dzT_s), J32, B * T, Ho, Wo, K, K, Ho, Wo, 1, 1, 1, 1, 1, 1, 0, 0, ptr(scale2), stream_handle()),
-              "dlip_wgrad_operand_f32")
+        call("dlip_wgrad_operand_f32", dy, dzT_s, J32, B * T, Ho, Wo, K, K, Ho, Wo, 1, 1, 1, 1, 1, 1, 0, 0, scale2)
         # "f32": a clip of any fp32 magnitude -- the operand is written from a copy of the clip lifted by its own power of two, and
         # the GEMM's epilogue divides by it (see wgrad_conv_fused)
         w_scale = const_vec(K, 1.0, dev)
@@ -694,7 +637,7 @@ class StemConvTrainFn(Function):
             x = ops.channel_scale(x, lift_fwd(x_lift, W), const_vec(W, 0.0, dev))
             w_scale = lift_fwd(x_lift, K)
         xT_s = torch.empty((248, J32), device=dev, dtype=torch.float32)
-        check(lib().dlip_stem_wgrad_operand_f32(ptr(x), ptr(xT_s), J32, B, T, H, W, stream_handle()), "dlip_stem_wgrad_operand_f32")
+        call("dlip_stem_wgrad_operand_f32", x, xT_s, J32, B, T, H, W)
         inv = lift_inv(scale2, K)
         out = torch.empty((248, K), device=dev, dtype=torch.float32)
         ops.conv_nhwc(xT_s.view(1, 1, 248, J32), dzT_s.view(K, 1, 1, J32), None, w_scale=w_scale, x_split=True,
@@ -712,7 +655,7 @@ class PReLUFn(Function):
         C_ = x.shape[-1]
         M = x.numel() // C_
         y = torch.empty_like(x)
-        check(lib().dlip_prelu_rows_fwd_f32(ptr(x), ptr(slope), ptr(y), M, C_, stream_handle()), "dlip_prelu_rows_fwd_f32")
+        call("dlip_prelu_rows_fwd_f32", x, slope, y, M, C_)
         ctx.save_for_backward(x, slope)
         return y
 
@@ -724,8 +667,7 @@ class PReLUFn(Function):
         M = x.numel() // C_
         dx = torch.empty_like(x)
         terms = torch.empty_like(x)
-        check(lib().dlip_prelu_rows_bwd_f32(ptr(dy), ptr(x), ptr(slope), ptr(dx), ptr(terms), M, C_, stream_handle()),
-              "dlip_prelu_rows_bwd_f32")
+        call("dlip_prelu_rows_bwd_f32", dy, x, slope, dx, terms, M, C_)
         dslope = _colsum_rows(terms.view(M, C_)) if ctx.needs_input_grad[1] else None
         return dx, dslope
 
@@ -746,9 +688,7 @@ class BNPReLUFn(Function):
         mean = torch.empty((C_,), device=x.device, dtype=torch.float32)
         invstd = torch.empty_like(mean)
         ws = torch.empty((int(lib().dlip_bn_rows_chunks(M)) * C_ * 4,), device=x.device, dtype=torch.float64)
-        check(lib().dlip_bn_prelu_rows_train_fwd_f32(ptr(x), ptr(gamma), ptr(beta), ptr(slope), ptr(y), ptr(mean), ptr(invstd),
-                                                     ptr(running_mean), ptr(running_var), ptr(ws), M, C_, momentum, eps, ptr(nbt), stream_handle()),
-              "dlip_bn_prelu_rows_train_fwd_f32")
+        call("dlip_bn_prelu_rows_train_fwd_f32", x, gamma, beta, slope, y, mean, invstd, running_mean, running_var, ws, M, C_, momentum, eps, nbt)
         ctx.save_for_backward(x, gamma, beta, slope, mean, invstd)
         ctx.shape = shape
         if defer:
@@ -768,9 +708,7 @@ class BNPReLUFn(Function):
         dg, db, ds = (torch.empty_like(mean) for _ in range(3))
         ws = torch.empty((int(lib().dlip_bn_rows_chunks(M)) * C_ * 4,), device=x.device, dtype=torch.float64)
         lift = torch.empty((LIFT_WORDS,), device=x.device, dtype=torch.float32)
-        check(lib().dlip_bn_prelu_rows_train_bwd_f32(ptr(dy), ptr(x), ptr(gamma), ptr(beta), ptr(slope), ptr(mean), ptr(invstd), ptr(dx),
-                                                     ptr(dg), ptr(db), ptr(ds), ptr(ws), M, C_, ptr(lift), stream_handle()),
-              "dlip_bn_prelu_rows_train_bwd_f32")
+        call("dlip_bn_prelu_rows_train_bwd_f32", dy, x, gamma, beta, slope, mean, invstd, dx, dg, db, ds, ws, M, C_, lift)
         dx = dx.view(ctx.shape)
         dx._dlip_lift = lift      # see autograd._bn_rows_bwd: travels with the tensor object the convolution backward receives
         return dx, dg, db, (ds if ctx.needs_input_grad[3] else None), None, None, None, None, None, None
@@ -794,9 +732,8 @@ class BNPReLUMaxPoolFn(Function):
         mean = torch.empty((C_,), device=x.device, dtype=torch.float32)
         invstd = torch.empty_like(mean)
         ws = torch.empty((int(lib().dlip_bn_rows_chunks(N * H * W)) * C_ * 2,), device=x.device, dtype=torch.float64)
-        check(lib().dlip_bn_prelu_maxpool_train_fwd_f32(ptr(x), ptr(gamma), ptr(beta), ptr(slope), ptr(y), idx.data_ptr(), ptr(mean), ptr(invstd),
-                                                        ptr(running_mean), ptr(running_var), ptr(ws), N, H, W, C_, momentum, eps, ptr(nbt),
-                                                        stream_handle()), "dlip_bn_prelu_maxpool_train_fwd_f32")
+        call("dlip_bn_prelu_maxpool_train_fwd_f32", x, gamma, beta, slope, y, idx.data_ptr(), mean, invstd, running_mean, running_var, ws, N, H, W,
+             C_, momentum, eps, nbt)
         ctx.save_for_backward(x, gamma, beta, slope, mean, invstd, idx)
         ctx.set_materialize_grads(False)
         return (y, y.detach()) if fork else y
@@ -814,9 +751,8 @@ class BNPReLUMaxPoolFn(Function):
         dg, db, ds = (torch.empty_like(mean) for _ in range(3))
         ws = torch.empty((int(lib().dlip_bn_rows_chunks(N * H * W)) * C_ * 4,), device=x.device, dtype=torch.float64)
         lift = torch.empty((LIFT_WORDS,), device=x.device, dtype=torch.float32)
-        check(lib().dlip_bn_prelu_maxpool_train_bwd_f32(ptr(dy), ptr(dy2), idx.data_ptr(), ptr(x), ptr(gamma), ptr(beta), ptr(slope), ptr(mean), ptr(invstd),
-                                                        ptr(dx), ptr(dg), ptr(db), ptr(ds), ptr(ws), N, H, W, C_, ptr(lift), stream_handle()),
-              "dlip_bn_prelu_maxpool_train_bwd_f32")
+        call("dlip_bn_prelu_maxpool_train_bwd_f32", dy, dy2, idx.data_ptr(), x, gamma, beta, slope, mean, invstd, dx, dg, db, ds, ws, N, H, W, C_,
+             lift)
         dx._dlip_lift = lift
         return dx, dg, db, (ds if ctx.needs_input_grad[3] else None), None, None, None, None, None, None
 
@@ -832,7 +768,7 @@ class AddPReLUFn(Function):
         M = a.numel() // C_
         s_ = torch.empty_like(a)
         y = torch.empty_like(a)
-        check(lib().dlip_add_prelu_rows_fwd_f32(ptr(a), ptr(b), ptr(slope), ptr(s_), ptr(y), M, C_, stream_handle()), "dlip_add_prelu_rows_fwd_f32")
+        call("dlip_add_prelu_rows_fwd_f32", a, b, slope, s_, y, M, C_)
         ctx.save_for_backward(s_, slope)
         return y
 
@@ -844,7 +780,7 @@ class AddPReLUFn(Function):
         M = s_.numel() // C_
         dx = torch.empty_like(s_)
         terms = torch.empty_like(s_)
-        check(lib().dlip_prelu_rows_bwd_f32(ptr(dy), ptr(s_), ptr(slope), ptr(dx), ptr(terms), M, C_, stream_handle()), "dlip_prelu_rows_bwd_f32")
+        call("dlip_prelu_rows_bwd_f32", dy, s_, slope, dx, terms, M, C_)
         dslope = _colsum_rows(terms.view(M, C_)) if ctx.needs_input_grad[2] else None
         return dx, dx, dslope
 
@@ -867,9 +803,8 @@ class BNAddPReLUFn(Function):
         mean = torch.empty((C_,), device=x.device, dtype=torch.float32)
         invstd = torch.empty_like(mean)
         ws = torch.empty((int(lib().dlip_bn_rows_chunks(M)) * C_ * 2,), device=x.device, dtype=torch.float64)
-        check(lib().dlip_bn_add_prelu_rows_train_fwd_f32(ptr(x), ptr(res), ptr(gamma), ptr(beta), ptr(slope), ptr(s_), ptr(y), ptr(mean), ptr(invstd),
-                                                         ptr(running_mean), ptr(running_var), ptr(ws), M, C_, momentum, eps, ptr(nbt),
-                                                         stream_handle()), "dlip_bn_add_prelu_rows_train_fwd_f32")
+        call("dlip_bn_add_prelu_rows_train_fwd_f32", x, res, gamma, beta, slope, s_, y, mean, invstd, running_mean, running_var, ws, M, C_, momentum,
+             eps, nbt)
         ctx.save_for_backward(x, s_, gamma, beta, slope, mean, invstd)
         ctx.shape = shape
         ctx.set_materialize_grads(False)
@@ -892,9 +827,7 @@ class BNAddPReLUFn(Function):
         dg, db, ds = (torch.empty_like(mean) for _ in range(3))
         ws = torch.empty((int(lib().dlip_bn_rows_chunks(M)) * C_ * 4,), device=x.device, dtype=torch.float64)
         lift = torch.empty((LIFT_WORDS,), device=x.device, dtype=torch.float32)
-        check(lib().dlip_bn_add_prelu_rows_train_bwd_f32(ptr(dy), ptr(dy2), ptr(s_), ptr(x), ptr(gamma), ptr(beta), ptr(slope), ptr(mean), ptr(invstd),
-                                                         ptr(dres), ptr(dx), ptr(dg), ptr(db), ptr(ds), ptr(ws), M, C_, ptr(lift), stream_handle()),
-              "dlip_bn_add_prelu_rows_train_bwd_f32")
+        call("dlip_bn_add_prelu_rows_train_bwd_f32", dy, dy2, s_, x, gamma, beta, slope, mean, invstd, dres, dx, dg, db, ds, ws, M, C_, lift)
         dx = dx.view(ctx.shape)
         dx._dlip_lift = lift
         return dx, dres.view(ctx.shape), dg, db, (ds if ctx.needs_input_grad[4] else None), None, None, None, None, None, None
@@ -911,7 +844,7 @@ class MaxPoolFn(Function):
         Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
         y = torch.empty((N, Ho, Wo, C_), device=x.device, dtype=torch.float32)
         idx = torch.empty((N, Ho, Wo, C_ // 4), device=x.device, dtype=torch.int32)
-        check(lib().dlip_maxpool3x3s2_idx_f32(ptr(x), ptr(y), idx.data_ptr(), N, H, W, C_, stream_handle()), "dlip_maxpool3x3s2_idx_f32")
+        call("dlip_maxpool3x3s2_idx_f32", x, y, idx.data_ptr(), N, H, W, C_)
         ctx.save_for_backward(idx)
         ctx.shape = (N, H, W, C_)
         return y
@@ -921,8 +854,7 @@ class MaxPoolFn(Function):
         (idx,) = ctx.saved_tensors
         N, H, W, C_ = ctx.shape
         dx = torch.empty(ctx.shape, device=dy.device, dtype=torch.float32)
-        check(lib().dlip_maxpool3x3s2_bwd_idx_f32(idx.data_ptr(), ptr(dy.contiguous()), ptr(dx), N, H, W, C_, stream_handle()),
-              "dlip_maxpool3x3s2_bwd_idx_f32")
+        call("dlip_maxpool3x3s2_bwd_idx_f32", idx.data_ptr(), dy.contiguous(), dx, N, H, W, C_)
         return dx
 
 
@@ -939,8 +871,7 @@ class AvgPoolFn(Function):
     def backward(ctx, dy):
         N, H, W, C_ = ctx.shape
         dx = torch.empty(ctx.shape, device=dy.device, dtype=torch.float32)
-        check(lib().dlip_row_broadcast_f32(ptr(dy.contiguous()), None, ptr(dx), N, H * W, C_, 1.0 / (H * W), stream_handle()),
-              "dlip_row_broadcast_f32")
+        call("dlip_row_broadcast_f32", dy.contiguous(), None, dx, N, H * W, C_, 1.0 / (H * W))
         return dx
 
 
@@ -959,8 +890,7 @@ class TimeMeanFn(Function):
         (lengths,) = ctx.saved_tensors
         B, T, C_ = ctx.shape
         dx = torch.empty(ctx.shape, device=dy.device, dtype=torch.float32)
-        check(lib().dlip_row_broadcast_f32(ptr(dy.contiguous()), ptr(lengths), ptr(dx), B, T, C_, 0.0, stream_handle()),
-              "dlip_row_broadcast_f32")
+        call("dlip_row_broadcast_f32", dy.contiguous(), lengths, dx, B, T, C_, 0.0)
         return dx, None
 
 
@@ -975,7 +905,7 @@ class DropoutFn(Function):
         ctx.save_for_backward(u)
         ctx.p = float(p)
         y = torch.empty_like(x)
-        check(lib().dlip_dropout_keep_f32(ptr(x), ptr(u), ptr(y), x.numel(), ctx.p, 1.0 / (1.0 - ctx.p), stream_handle()), "dlip_dropout_keep_f32")
+        call("dlip_dropout_keep_f32", x, u, y, x.numel(), ctx.p, 1.0 / (1.0 - ctx.p))
         return y
 
     @staticmethod
@@ -983,7 +913,7 @@ class DropoutFn(Function):
         (u,) = ctx.saved_tensors
         dy = dy.contiguous()
         dx = torch.empty_like(dy)
-        check(lib().dlip_dropout_keep_f32(ptr(dy), ptr(u), ptr(dx), dy.numel(), ctx.p, 1.0 / (1.0 - ctx.p), stream_handle()), "dlip_dropout_keep_f32")
+        call("dlip_dropout_keep_f32", dy, u, dx, dy.numel(), ctx.p, 1.0 / (1.0 - ctx.p))
         return dx, None, None
 
 
@@ -997,7 +927,7 @@ class MulMaskFn(Function):
         ctx.save_for_backward(mask)
         ctx.scale = scale
         y = torch.empty_like(x)
-        check(lib().dlip_mul_mask_f32(ptr(x), ptr(mask), ptr(y), x.numel(), scale, stream_handle()), "dlip_mul_mask_f32")
+        call("dlip_mul_mask_f32", x, mask, y, x.numel(), scale)
         return y
 
     @staticmethod
@@ -1005,7 +935,7 @@ class MulMaskFn(Function):
         (mask,) = ctx.saved_tensors
         dy = dy.contiguous()
         dx = torch.empty_like(dy)
-        check(lib().dlip_mul_mask_f32(ptr(dy), ptr(mask), ptr(dx), dy.numel(), ctx.scale, stream_handle()), "dlip_mul_mask_f32")
+        call("dlip_mul_mask_f32", dy, mask, dx, dy.numel(), ctx.scale)
         return dx, None, None
 
 
@@ -1028,7 +958,7 @@ def batchnorm(x, bn):
 
 
 # (round 5) conv1 -> bn1 + relu1 -> conv2: relu1's output is not stored, conv2's operand producer applies bn1 + relu1 on load
-BN_ON_LOAD = __import__("os").environ.get("DLIP_BN_ON_LOAD", "1") != "0"
+BN_ON_LOAD = env_switch("DLIP_BN_ON_LOAD")
 
 
 def batchnorm_prelu(x, bn, act, defer=False):
@@ -1051,7 +981,7 @@ def batchnorm_prelu(x, bn, act, defer=False):
 
 
 # (round 5) the stem's BatchNorm + PReLU + max-pool as one Function (False: round 4's three: BNPReLUFn, then MaxPoolFn)
-STEM_BN_POOL_FUSED = __import__("os").environ.get("DLIP_STEM_BN_POOL", "1") != "0"
+STEM_BN_POOL_FUSED = env_switch("DLIP_STEM_BN_POOL")
 
 
 def batchnorm_prelu_maxpool(x, bn, act, fork=False):
@@ -1069,7 +999,7 @@ def batchnorm_prelu_maxpool(x, bn, act, fork=False):
 
 
 # (round 5) the end of a BasicBlock as one Function (False: round 4's BNRowsActFn + AddPReLUFn)
-BLOCK_TAIL_FUSED = __import__("os").environ.get("DLIP_BLOCK_TAIL", "1") != "0"
+BLOCK_TAIL_FUSED = env_switch("DLIP_BLOCK_TAIL")
 
 
 def batchnorm_add_prelu(x, bn, res, act, fork=False):
@@ -1136,8 +1066,7 @@ class ConcatChannelsFn(Function):
         out = torch.empty(tuple(lead) + (Ct,), device=xs[0].device, dtype=torch.float32)
         off = 0
         for x, Cb in zip(xs, widths):
-            check(lib().dlip_tap_gather_f32(ptr(x), out.data_ptr() + 4 * off, J, 1, 1, Cb, Cb, 1, 1, 1, 1, 0, 0, Ct, stream_handle()),
-                  "dlip_tap_gather_f32")
+            call("dlip_tap_gather_f32", x, out.data_ptr() + 4 * off, J, 1, 1, Cb, Cb, 1, 1, 1, 1, 0, 0, Ct)
             off += Cb
         ctx.widths = widths
         return out
@@ -1150,8 +1079,7 @@ class ConcatChannelsFn(Function):
         outs, off = [], 0
         for Cb in ctx.widths:
             g = torch.empty(tuple(dy.shape[:-1]) + (Cb,), device=dy.device, dtype=torch.float32)
-            check(lib().dlip_tap_gather_f32(dy.data_ptr() + 4 * off, ptr(g), J, 1, 1, Cb, Ct, 1, 1, 1, 1, 0, 0, Cb, stream_handle()),
-                  "dlip_tap_gather_f32")
+            call("dlip_tap_gather_f32", dy.data_ptr() + 4 * off, g, J, 1, 1, Cb, Ct, 1, 1, 1, 1, 0, 0, Cb)
             outs.append(g)
             off += Cb
         return tuple(outs)
@@ -1182,8 +1110,7 @@ class ChompConcatFn(Function):
             return out
         off = 0
         for z, Cb, L in zip(zs, widths, lens):
-            check(lib().dlip_tap_gather_f32(ptr(z), out.data_ptr() + 4 * off, B, 1, L, Cb, Cb, 1, T, 1, 1, 0, (L - T) // 2, Ct, stream_handle()),
-                  "dlip_tap_gather_f32")
+            call("dlip_tap_gather_f32", z, out.data_ptr() + 4 * off, B, 1, L, Cb, Cb, 1, T, 1, 1, 0, (L - T) // 2, Ct)
             off += Cb
         return out
 
@@ -1199,15 +1126,14 @@ class ChompConcatFn(Function):
         outs, off = [], 0
         for Cb, L in zip(widths, lens):
             g = torch.empty((B, 1, L, Cb), device=dy.device, dtype=torch.float32)
-            check(lib().dlip_tap_gather_f32(dy.data_ptr() + 4 * off, ptr(g), B, 1, T, Cb, Ct, 1, L, 1, 1, 0, -((L - T) // 2), Cb, stream_handle()),
-                  "dlip_tap_gather_f32")
+            call("dlip_tap_gather_f32", dy.data_ptr() + 4 * off, g, B, 1, T, Cb, Ct, 1, L, 1, 1, 0, -((L - T) // 2), Cb)
             outs.append(g)
             off += Cb
         return (None,) + tuple(outs)
 
 
 # (round 5) the MS-TCN stage's chomp + concatenation in one launch, its dropout in two (False: round 4's 3 + 4 launches; A/B runs)
-TCN_FEWER_LAUNCHES = __import__("os").environ.get("DLIP_TCN_FEWER_LAUNCHES", "1") != "0"
+TCN_FEWER_LAUNCHES = env_switch("DLIP_TCN_FEWER_LAUNCHES")
 
 
 def _chomp_concat_launch(branches, lens, widths, cat, B, T, backward):
@@ -1216,7 +1142,7 @@ def _chomp_concat_launch(branches, lens, widths, cat, B, T, backward):
     pa = (C.c_void_p * n)(*[b.data_ptr() for b in branches])
     la = (C.c_int32 * n)(*[int(v) for v in lens])
     wa = (C.c_int32 * n)(*[int(v) for v in widths])
-    check(lib().dlip_chomp_concat_f32(pa, la, wa, n, ptr(cat), B, T, backward, stream_handle()), "dlip_chomp_concat_f32")
+    call("dlip_chomp_concat_f32", pa, la, wa, n, cat, B, T, backward)
 
 
 def chomp_concat(zs, T):

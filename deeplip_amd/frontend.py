@@ -24,7 +24,8 @@ import numpy as np
 import torch
 
 from . import ops
-from ._lib import check, lib, ptr, stream_handle
+from ._lib import call
+from ._lib import lib    # noqa: F401  (a test replaces it to show that nothing reaches the library)
 
 
 def hz2mel(hz):
@@ -184,27 +185,22 @@ class AudioFrontend:
         out = ops._empty((B, C_, NF), wave.device)
         nf = None
         if lens is None:
-            check(lib().dlip_stft_logmag_wave_f32(ptr(wave), ptr(feat), B, S, *geom, stream_handle()), "dlip_stft_logmag_wave_f32")
-            check(lib().dlip_cmvn_nct_f32(ptr(feat), None, ptr(out), B, NF, C_, self.nbp, int(self.normalize), stream_handle()),
-                  "dlip_cmvn_nct_f32")
+            call("dlip_stft_logmag_wave_f32", wave, feat, B, S, *geom)
+            call("dlip_cmvn_nct_f32", feat, None, out, B, NF, C_, self.nbp, int(self.normalize))
         else:
-            check(lib().dlip_stft_logmag_wave_ragged_f32(ptr(wave), ptr(lens), ptr(feat), B, S, *geom, stream_handle()),
-                  "dlip_stft_logmag_wave_ragged_f32")
+            call("dlip_stft_logmag_wave_ragged_f32", wave, lens, feat, B, S, *geom)
             nf = ops._empty((B,), wave.device, torch.int32)
-            check(lib().dlip_stft_frame_lengths_i32(ptr(lens), ptr(nf), B, S, self.nfft, self.hop, stream_handle()),
-                  "dlip_stft_frame_lengths_i32")
-            check(lib().dlip_cmvn_nct_ragged_f32(ptr(feat), None, ptr(nf), ptr(out), B, NF, C_, self.nbp, int(self.normalize),
-                                                 stream_handle()), "dlip_cmvn_nct_ragged_f32")
+            call("dlip_stft_frame_lengths_i32", lens, nf, B, S, self.nfft, self.hop)
+            call("dlip_cmvn_nct_ragged_f32", feat, None, nf, out, B, NF, C_, self.nbp, int(self.normalize))
         return self._deltas(out, nf, B, C_, NF, lens is None)
 
     def _deltas(self, out, nf, B, C_, NF, rect):
         if self.delta:
             out3 = ops._empty((B, 3 * C_, NF), out.device)
             if rect:
-                check(lib().dlip_delta_nct_f32(ptr(out), ptr(out3), B, C_, NF, 2, stream_handle()), "dlip_delta_nct_f32")
+                call("dlip_delta_nct_f32", out, out3, B, C_, NF, 2)
             else:
-                check(lib().dlip_delta_nct_ragged_f32(ptr(out), ptr(nf), ptr(out3), B, C_, NF, 2, stream_handle()),
-                      "dlip_delta_nct_ragged_f32")
+                call("dlip_delta_nct_ragged_f32", out, nf, out3, B, C_, NF, 2)
             out = out3
         return out if rect else (out, nf)
 
@@ -230,26 +226,20 @@ class AudioFrontend:
         geom = (self.frame_len, self.frame_step, self.nfft)
         if self.dft == "fft64":
             if lens is None:
-                check(lib().dlip_powspec_wave_fft64_f32(ptr(wave), ptr(pw), ptr(energy), B, S, NF, *geom, float(self.preemph), self.nb,
-                                                        self.nbp, stream_handle()), "dlip_powspec_wave_fft64_f32")
+                call("dlip_powspec_wave_fft64_f32", wave, pw, energy, B, S, NF, *geom, float(self.preemph), self.nb, self.nbp)
             else:
-                check(lib().dlip_powspec_wave_fft64_ragged_f32(ptr(wave), ptr(lens), ptr(pw), ptr(energy), B, S, NF, *geom, float(self.preemph),
-                                                               self.nb, self.nbp, stream_handle()), "dlip_powspec_wave_fft64_ragged_f32")
+                call("dlip_powspec_wave_fft64_ragged_f32", wave, lens, pw, energy, B, S, NF, *geom, float(self.preemph), self.nb, self.nbp)
         else:
             frames = ops._empty((R, self.nfft), wave.device)
             if lens is None:
-                check(lib().dlip_frame_preemph_f32(ptr(wave), ptr(frames), B, S, NF, *geom, self.preemph, stream_handle()),
-                      "dlip_frame_preemph_f32")
+                call("dlip_frame_preemph_f32", wave, frames, B, S, NF, *geom, self.preemph)
             else:
-                check(lib().dlip_frame_preemph_ragged_f32(ptr(wave), ptr(lens), ptr(frames), B, S, NF, *geom, self.preemph, stream_handle()),
-                      "dlip_frame_preemph_ragged_f32")
+                call("dlip_frame_preemph_ragged_f32", wave, lens, frames, B, S, NF, *geom, self.preemph)
             if self.dft == "direct64":
-                check(lib().dlip_powspec_dft64_f32(ptr(frames), ptr(pw), ptr(energy), R, self.nb, self.nbp, self.nfft, stream_handle()),
-                      "dlip_powspec_dft64_f32")
+                call("dlip_powspec_dft64_f32", frames, pw, energy, R, self.nb, self.nbp, self.nfft)
             else:
                 spec = ops.linear(frames, self.w_dft)                          # [R, 2*nb]  (DFT as GEMM)
-                check(lib().dlip_powspec_f32(ptr(spec), ptr(pw), ptr(energy), R, self.nb, self.nbp, self.nfft, stream_handle()),
-                      "dlip_powspec_f32")
+                call("dlip_powspec_f32", spec, pw, energy, R, self.nb, self.nbp, self.nfft)
         if lens is None:
             mel = torch.zeros((R, self.nfp), device=wave.device, dtype=torch.float32)
         else:                   # (a buffer of the plan's arena when a step is being recorded: nothing is allocated under capture)
@@ -259,7 +249,7 @@ class AudioFrontend:
         feat, C_, en = mel, self.num_bin, None
         if self.feat_type in ("mfcc", "logfbank"):
             lg = ops._empty(tuple(mel.shape), mel.device)
-            check(lib().dlip_log_floor_f32(ptr(mel), ptr(lg), mel.numel(), stream_handle()), "dlip_log_floor_f32")
+            call("dlip_log_floor_f32", mel, lg, mel.numel())
             feat = lg
         if self.feat_type == "mfcc":
             feat = ops.linear(feat, self.w_dct)                                # [R, num_cep]
@@ -268,14 +258,11 @@ class AudioFrontend:
         out = ops._empty((B, C_, NF), wave.device)
         nf = None
         if lens is None:
-            check(lib().dlip_cmvn_nct_f32(ptr(feat), ptr(en), ptr(out), B, NF, C_, feat.shape[1], int(self.normalize),
-                                          stream_handle()), "dlip_cmvn_nct_f32")
+            call("dlip_cmvn_nct_f32", feat, en, out, B, NF, C_, feat.shape[1], int(self.normalize))
         else:
             nf = ops._empty((B,), wave.device, torch.int32)
-            check(lib().dlip_wave_frame_lengths_i32(ptr(lens), ptr(nf), B, S, self.frame_len, self.frame_step, stream_handle()),
-                  "dlip_wave_frame_lengths_i32")
-            check(lib().dlip_cmvn_nct_ragged_f32(ptr(feat), ptr(en), ptr(nf), ptr(out), B, NF, C_, feat.shape[1], int(self.normalize),
-                                                 stream_handle()), "dlip_cmvn_nct_ragged_f32")
+            call("dlip_wave_frame_lengths_i32", lens, nf, B, S, self.frame_len, self.frame_step)
+            call("dlip_cmvn_nct_ragged_f32", feat, en, nf, out, B, NF, C_, feat.shape[1], int(self.normalize))
         return self._deltas(out, nf, B, C_, NF, lens is None)
 
 
@@ -301,8 +288,7 @@ class VideoFrontend:
             if t is not None and (t.dtype != torch.int32 or not t.is_cuda or tuple(t.shape) != shape or not t.is_contiguous()):
                 raise ValueError(f"VideoFrontend: {n} must be a contiguous int32 CUDA tensor of shape {shape}")
         y = ops._empty((B, 1, T, self.crop, self.crop), frames.device)   # (arena-aware: this may run inside a recorded step plan)
-        check(lib().dlip_crop_normalize_u8(ptr(frames), ptr(clip_params), ptr(lengths), T, ptr(y), B * T, ch, H, W, self.crop,
-                                           stream_handle()), "dlip_crop_normalize_u8")
+        call("dlip_crop_normalize_u8", frames, clip_params, lengths, T, y, B * T, ch, H, W, self.crop)
         return y
 
     def collate(self, clips: Sequence[torch.Tensor]) -> Tuple[torch.Tensor, List[int]]:

@@ -12,7 +12,8 @@ from typing import Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from ._lib import ConvDesc, check, lib, ptr, stream_handle
+from ._lib import ConvDesc, call, lib
+from ._lib import ptr, stream_handle    # noqa: F401  (tests import them from here)
 
 Tensor = torch.Tensor
 
@@ -104,7 +105,7 @@ def conv_nhwc(x: Tensor, w_krsc: Tensor, bias: Optional[Tensor] = None, *, strid
     if hook is not None:
         bm, bn = C.c_int32(), C.c_int32()
         mode = 0 if w_scale is None else (3 if x_split else 1)
-        check(lib().dlip_conv_plan(C.byref(d), mode, C.byref(bm), C.byref(bn)), "dlip_conv_plan")
+        call("dlip_conv_plan", C.byref(d), mode, C.byref(bm), C.byref(bn))
         kname = ("conv_igemm_f32_kernel", "conv_igemm_f16x3_kernel", "", "conv_igemm_f16x3_dma_kernel")[mode]
         kind = lib().dlip_conv_kernel_kind(C.byref(d)) if mode == 3 else 0
         if kind == 1:
@@ -118,18 +119,14 @@ def conv_nhwc(x: Tensor, w_krsc: Tensor, bias: Optional[Tensor] = None, *, strid
         if not (x_split and w_scale is not None) or out_split or residual is not None or post_scale is not None or in_channel_offset or out_channel_offset:
             raise ValueError("conv_nhwc(stats=...): split input, fp32 output, no residual / post-affine / channel slices")
         _lib.ensure_conv_workspace()
-        check(lib().dlip_conv_nhwc_stats_f16x3(C.byref(d), xp, ptr(w_krsc), ptr(w_scale), ptr(bias), ptr(slope), yp, ptr(stats),
-                                               stats.numel() * 8, stream_handle()), "dlip_conv_nhwc_stats_f16x3")
+        call("dlip_conv_nhwc_stats_f16x3", C.byref(d), xp, w_krsc, w_scale, bias, slope, yp, stats, stats.numel() * 8)
     elif w_scale is not None:
         if x_split:
             _lib.ensure_conv_workspace()
-        check(lib().dlip_conv_nhwc_f16x3(C.byref(d), xp, ptr(w_krsc), ptr(w_scale), ptr(bias), ptr(residual),
-                                         ptr(slope), ptr(post_scale), ptr(post_shift), yp,
-                                         int(x_split) | 2 * int(out_split), stream_handle()),
-              "dlip_conv_nhwc_f16x3")
+        call("dlip_conv_nhwc_f16x3", C.byref(d), xp, w_krsc, w_scale, bias, residual, slope, post_scale, post_shift, yp,
+             int(x_split) | 2 * int(out_split))
     else:
-        check(lib().dlip_conv_nhwc_f32(C.byref(d), xp, ptr(w_krsc), ptr(bias), ptr(residual), ptr(slope),
-                                       ptr(post_scale), ptr(post_shift), yp, stream_handle()), "dlip_conv_nhwc_f32")
+        call("dlip_conv_nhwc_f32", C.byref(d), xp, w_krsc, bias, residual, slope, post_scale, post_shift, yp)
     if hook is not None:
         hook.end(tok)
     return out
@@ -172,13 +169,12 @@ def conv2_nhwc(x: Tensor, x2: Tensor, w_split: Tensor, bias: Tensor, w_scale: Te
     hook = LAUNCH_HOOK
     if hook is not None:
         bm, bn = C.c_int32(), C.c_int32()
-        check(lib().dlip_conv_plan(C.byref(d), 3, C.byref(bm), C.byref(bn)), "dlip_conv_plan")
+        call("dlip_conv_plan", C.byref(d), 3, C.byref(bm), C.byref(bn))
         kname = "conv_rows_f16x3_kernel" if lib().dlip_conv_kernel_kind(C.byref(d)) == 2 else "conv_igemm_f16x3_dma_kernel"
         tok = hook.begin(f"{kname}<{bm.value},{bn.value},dual>", 2.0 * N * Ho * Wo * K * (R * S * Cx + C2))
     _lib.ensure_conv_workspace()
-    check(lib().dlip_conv2_nhwc_f16x3(C.byref(d), ptr(x), ptr(x2), H2, W2, C2, C2, stride2[0], stride2[1], ptr(w_split),
-                                      ptr(w_scale), ptr(bias), ptr(residual), ptr(slope), None, None, ptr(out),
-                                      1 | 2 * int(out_split), stream_handle()), "dlip_conv2_nhwc_f16x3")
+    call("dlip_conv2_nhwc_f16x3", C.byref(d), x, x2, H2, W2, C2, C2, stride2[0], stride2[1], w_split, w_scale, bias, residual, slope, None, None, out,
+         1 | 2 * int(out_split))
     if hook is not None:
         hook.end(tok)
     return out
@@ -264,9 +260,8 @@ def conv_pool(x: Tensor, w_krsc: Tensor, bias: Optional[Tensor], w_scale: Tensor
         tok = hook.begin(f"conv_rows_f16x3_kernel<{2 * bm.value},256,pool>" if rows else f"conv_igemm_f16x3_dma_kernel<{bm.value},128,pool>",
                          2.0 * N * Ho * Wo * K * R * S * Cx)
     _lib.ensure_conv_workspace()
-    check(lib().dlip_conv_pool_f16x3(C.byref(d), ptr(x), ptr(w_krsc), ptr(w_scale), ptr(bias), ptr(residual), ptr(slope),
-                                     ptr(post_scale), ptr(post_shift), ptr(part), nbytes, group_rows, ptr(lengths), len_mul, len_add,
-                                     stream_handle()), "dlip_conv_pool_f16x3")
+    call("dlip_conv_pool_f16x3", C.byref(d), x, w_krsc, w_scale, bias, residual, slope, post_scale, post_shift, part, nbytes, group_rows, lengths,
+         len_mul, len_add)
     if hook is not None:
         hook.end(tok)
     M = N * Ho * Wo
@@ -283,8 +278,8 @@ def pool_finish(p: Pooled, mode: str = "mean", out_split: bool = False) -> Tenso
         y = _empty((G, p.K), p.partials.device)
     else:
         y = _empty((G, (2 * p.K + 31) // 32 * 32 if out_split else 2 * p.K), p.partials.device)
-    check(lib().dlip_pool_finish_f32(ptr(p.partials), p.M, p.K, p.tile_rows, p.group_rows, ptr(p.lengths), p.len_mul, p.len_add,
-                                     0 if mode == "mean" else 1, int(out_split), ptr(y), stream_handle()), "dlip_pool_finish_f32")
+    call("dlip_pool_finish_f32", p.partials, p.M, p.K, p.tile_rows, p.group_rows, p.lengths, p.len_mul, p.len_add, 0 if mode == "mean" else 1,
+         int(out_split), y)
     return y
 
 
@@ -324,8 +319,7 @@ def stem3d(x_bthw: Tensor, w_248xk: Tensor, bias: Tensor, slope: Optional[Tensor
         hook = LAUNCH_HOOK
         if hook is not None:
             tok = hook.begin("stem3d_f16x3_kernel", 2.0 * B * T * (H // 2) * (W // 2) * 64 * 245)
-        check(lib().dlip_stem3d_bn_act_f16x3(ptr(x_bthw), ptr(w_248xk), ptr(w_scale), ptr(bias), ptr(slope), ptr(y),
-                                             B, T, H, W, 64, stream_handle()), "dlip_stem3d_bn_act_f16x3")
+        call("dlip_stem3d_bn_act_f16x3", x_bthw, w_248xk, w_scale, bias, slope, y, B, T, H, W, 64)
         if hook is not None:
             hook.end(tok)
         return y
@@ -336,8 +330,7 @@ def stem3d(x_bthw: Tensor, w_248xk: Tensor, bias: Tensor, slope: Optional[Tensor
     hook = LAUNCH_HOOK
     if hook is not None:
         tok = hook.begin("stem3d_f32_kernel", 2.0 * B * T * (H // 2) * (W // 2) * K * 245)
-    check(lib().dlip_stem3d_bn_act_f32(ptr(x_bthw), ptr(w_248xk), ptr(bias), ptr(slope), ptr(y), B, T, H, W, K,
-                                       stream_handle()), "dlip_stem3d_bn_act_f32")
+    call("dlip_stem3d_bn_act_f32", x_bthw, w_248xk, bias, slope, y, B, T, H, W, K)
     if hook is not None:
         hook.end(tok)
     return y
@@ -360,8 +353,7 @@ def stem3d_pool(x_bthw: Tensor, w_img: Tensor, bias: Tensor, slope: Optional[Ten
     hook = LAUNCH_HOOK
     if hook is not None:
         tok = hook.begin("stem3d_pool_f16x3_kernel", 2.0 * B * T * Ho * Wo * 64 * 245)
-    check(lib().dlip_stem3d_pool_f16x3(ptr(x_bthw), ptr(lengths), ptr(ws), ptr(w_img), ptr(w_scale), ptr(bias), ptr(slope), ptr(y),
-                                       B, T, H, W, 64, stream_handle()), "dlip_stem3d_pool_f16x3")
+    call("dlip_stem3d_pool_f16x3", x_bthw, lengths, ws, w_img, w_scale, bias, slope, y, B, T, H, W, 64)
     if hook is not None:
         hook.end(tok)
     return y
@@ -379,8 +371,7 @@ def shuffle_stem24(x_bthw: Tensor, w_248x32: Tensor, bias: Tensor, slope: Option
     hook = LAUNCH_HOOK
     if hook is not None:
         tok = hook.begin("shuffle_stem24_f32_kernel", 2.0 * B * T * (H // 2) * (W // 2) * 24 * 245)
-    check(lib().dlip_shuffle_stem24_f32(ptr(x_bthw), ptr(w_248x32), ptr(bias), ptr(slope), ptr(y), B, T, H, W, stream_handle()),
-          "dlip_shuffle_stem24_f32")
+    call("dlip_shuffle_stem24_f32", x_bthw, w_248x32, bias, slope, y, B, T, H, W)
     if hook is not None:
         hook.end(tok)
     return y
@@ -425,9 +416,8 @@ def shuffle_dwpw(x: Tensor, w: Tensor, bias: Tensor, *, dw_w: Optional[Tensor] =
     hook = LAUNCH_HOOK
     if hook is not None:
         tok = hook.begin("shuffle_dwpw_f32_kernel", 2.0 * N * Ho * Wo * K * Cin + (18.0 * N * Ho * Wo * Cin if dw_w is not None else 0.0))
-    check(lib().dlip_shuffle_dwpw_f32(x.data_ptr() + 4 * in_channel_offset, ptr(dw_w), ptr(dw_b), ptr(w), ptr(bias), ptr(passthrough),
-                                      ptr(out), N, H, W, stride, Cin, K, Kp, Cx, ldp, out.shape[3], hp, par, stream_handle()),
-          "dlip_shuffle_dwpw_f32")
+    call("dlip_shuffle_dwpw_f32", x.data_ptr() + 4 * in_channel_offset, dw_w, dw_b, w, bias, passthrough, out, N, H, W, stride, Cin, K, Kp, Cx, ldp,
+         out.shape[3], hp, par)
     if hook is not None:
         hook.end(tok)
     return out
@@ -474,11 +464,10 @@ def tcn_dw(x: Tensor, ws: Sequence[Tensor], d: int, *, pads: Sequence[int], t_ou
     B, T, Cc = x.shape
     ys = [_empty((B, int(To), Cc), x.device) for To in t_outs]
     n = len(ws)
-    check(lib().dlip_tcn_dw_fwd_f32(ptr(x), n, _arr(C.c_void_p, [w.data_ptr() for w in ws]),
-                                    _arr(C.c_void_p, [b.data_ptr() for b in biases]) if biases is not None else None,
-                                    _arr(C.c_void_p, [s.data_ptr() for s in slopes]) if slopes is not None else None,
-                                    _arr(C.c_void_p, [y.data_ptr() for y in ys]), _arr(C.c_int32, ks), _arr(C.c_int32, list(pads)),
-                                    _arr(C.c_int32, list(t_outs)), B, T, Cc, int(d), stream_handle()), "dlip_tcn_dw_fwd_f32")
+    call("dlip_tcn_dw_fwd_f32", x, n, _arr(C.c_void_p, [w.data_ptr() for w in ws]),
+         _arr(C.c_void_p, [b.data_ptr() for b in biases]) if biases is not None else None,
+         _arr(C.c_void_p, [s.data_ptr() for s in slopes]) if slopes is not None else None, _arr(C.c_void_p, [y.data_ptr() for y in ys]),
+         _arr(C.c_int32, ks), _arr(C.c_int32, list(pads)), _arr(C.c_int32, list(t_outs)), B, T, Cc, int(d))
     return ys
 
 
@@ -497,9 +486,8 @@ def tcn_dw_dgrad(dzs: Sequence[Tensor], ws: Sequence[Tensor], d: int, *, pads: S
         raise ValueError("tcn_dw_dgrad: gradients [B, T_out, C] with one B and C")
     _dw_geometry("tcn_dw_dgrad", (B, T, Cc), ws, ks, pads, t_outs, d)
     dx = _empty((B, T, Cc), dzs[0].device)
-    check(lib().dlip_tcn_dw_dgrad_f32(_arr(C.c_void_p, [g.data_ptr() for g in dzs]), len(dzs), _arr(C.c_void_p, [w.data_ptr() for w in ws]),
-                                      _arr(C.c_int32, ks), _arr(C.c_int32, list(pads)), _arr(C.c_int32, t_outs), ptr(dx), B, T, Cc,
-                                      int(d), stream_handle()), "dlip_tcn_dw_dgrad_f32")
+    call("dlip_tcn_dw_dgrad_f32", _arr(C.c_void_p, [g.data_ptr() for g in dzs]), len(dzs), _arr(C.c_void_p, [w.data_ptr() for w in ws]),
+         _arr(C.c_int32, ks), _arr(C.c_int32, list(pads)), _arr(C.c_int32, t_outs), dx, B, T, Cc, int(d))
     return dx
 
 
@@ -517,10 +505,8 @@ def tcn_dw_wgrad(x: Tensor, dzs: Sequence[Tensor], ks: Sequence[int], d: int, *,
     _dw_geometry("tcn_dw_wgrad", x.shape, dws, list(ks), pads, t_outs, d)
     n_ws = sum(int(lib().dlip_tcn_dw_wgrad_chunks(B * To)) * int(k) * Cc for k, To in zip(ks, t_outs))
     ws = _empty((n_ws,), x.device, torch.float64)
-    check(lib().dlip_tcn_dw_wgrad_f32(ptr(x), len(dzs), _arr(C.c_void_p, [g.data_ptr() for g in dzs]),
-                                      _arr(C.c_void_p, [w.data_ptr() for w in dws]), _arr(C.c_int32, [int(k) for k in ks]),
-                                      _arr(C.c_int32, list(pads)), _arr(C.c_int32, t_outs), B, T, Cc, int(d), ptr(ws), n_ws,
-                                      stream_handle()), "dlip_tcn_dw_wgrad_f32")
+    call("dlip_tcn_dw_wgrad_f32", x, len(dzs), _arr(C.c_void_p, [g.data_ptr() for g in dzs]), _arr(C.c_void_p, [w.data_ptr() for w in dws]),
+         _arr(C.c_int32, [int(k) for k in ks]), _arr(C.c_int32, list(pads)), _arr(C.c_int32, t_outs), B, T, Cc, int(d), ws, n_ws)
     return dws
 
 
@@ -533,8 +519,7 @@ def add_prelu(a: Tensor, b: Tensor, slope: Tensor) -> Tensor:
     Cc = a.shape[-1]
     s_ = _empty(a.shape, a.device)
     y = _empty(a.shape, a.device)
-    check(lib().dlip_add_prelu_rows_fwd_f32(ptr(a), ptr(b), ptr(slope), ptr(s_), ptr(y), a.numel() // Cc, Cc, stream_handle()),
-          "dlip_add_prelu_rows_fwd_f32")
+    call("dlip_add_prelu_rows_fwd_f32", a, b, slope, s_, y, a.numel() // Cc, Cc)
     return y
 
 
@@ -547,7 +532,7 @@ def avgpool3(x: Tensor) -> Tensor:
     if not (3 <= H <= 5 and 3 <= W <= 5):
         raise ValueError(f"avgpool3: AvgPool2d(3) of a {H}x{W} map does not give one pixel per frame")
     y = _empty((N, Cc), x.device)
-    check(lib().dlip_avgpool3_nhwc_f32(ptr(x), ptr(y), N, H, W, Cc, stream_handle()), "dlip_avgpool3_nhwc_f32")
+    call("dlip_avgpool3_nhwc_f32", x, y, N, H, W, Cc)
     return y
 
 
@@ -606,8 +591,7 @@ def stem3d_pool_u8(frames: Tensor, w_img: Tensor, bias: Tensor, slope: Optional[
     hook = LAUNCH_HOOK
     if hook is not None:
         tok = hook.begin("stem3d_pool_f16x3_kernel", 2.0 * B * T * Ho * Wo * 64 * 245)
-    check(lib().dlip_stem3d_pool_u8_f16x3(ptr(frames), ch, Hs, Ws, oy, ox, ptr(clip_params), ptr(lengths), ptr(ws), ptr(w_img), ptr(w_scale), ptr(bias), ptr(slope),
-                                          ptr(y), B, T, H, W, 64, stream_handle()), "dlip_stem3d_pool_u8_f16x3")
+    call("dlip_stem3d_pool_u8_f16x3", frames, ch, Hs, Ws, oy, ox, clip_params, lengths, ws, w_img, w_scale, bias, slope, y, B, T, H, W, 64)
     if hook is not None:
         hook.end(tok)
     return y
@@ -618,7 +602,7 @@ def split_pack(x: Tensor) -> Tensor:
     _req(x, "x")
     y = _empty(x.shape, x.device)
     Cc = x.shape[-1]
-    check(lib().dlip_split_pack_f32(ptr(x), ptr(y), x.numel() // Cc, Cc, stream_handle()), "dlip_split_pack_f32")
+    call("dlip_split_pack_f32", x, y, x.numel() // Cc, Cc)
     return y
 
 
@@ -628,7 +612,7 @@ def split_pack_scaled(x: Tensor, scale: Tensor) -> Tensor:
     _req(x, "x"); _req(scale, "scale")
     y = _empty(x.shape, x.device)
     Cc = x.shape[-1]
-    check(lib().dlip_split_pack_scaled_f32(ptr(x), ptr(y), ptr(scale), x.numel() // Cc, Cc, stream_handle()), "dlip_split_pack_scaled_f32")
+    call("dlip_split_pack_scaled_f32", x, y, scale, x.numel() // Cc, Cc)
     return y
 
 
@@ -644,7 +628,7 @@ def split_unpack(x: Tensor) -> Tensor:
     _req(x, "x")
     y = _empty(x.shape, x.device)
     Cc = x.shape[-1]
-    check(lib().dlip_split_unpack_f32(ptr(x), ptr(y), x.numel() // Cc, Cc, stream_handle()), "dlip_split_unpack_f32")
+    call("dlip_split_unpack_f32", x, y, x.numel() // Cc, Cc)
     return y
 
 
@@ -652,8 +636,7 @@ def maxpool3x3s2(x: Tensor, out_split: bool = False) -> Tensor:
     _req(x, "x")
     N, H, W, Cc = x.shape
     y = _empty((N, (H - 1) // 2 + 1, (W - 1) // 2 + 1, Cc), x.device)
-    check(lib().dlip_maxpool3x3s2_nhwc_f32(ptr(x), ptr(y), N, H, W, Cc, int(out_split), stream_handle()),
-          "dlip_maxpool3x3s2_nhwc_f32")
+    call("dlip_maxpool3x3s2_nhwc_f32", x, y, N, H, W, Cc, int(out_split))
     return y
 
 
@@ -661,7 +644,7 @@ def avgpool(x: Tensor) -> Tensor:
     _req(x, "x")
     N, H, W, Cc = x.shape
     y = _empty((N, Cc), x.device)
-    check(lib().dlip_avgpool_nhwc_f32(ptr(x), ptr(y), N, H * W, Cc, stream_handle()), "dlip_avgpool_nhwc_f32")
+    call("dlip_avgpool_nhwc_f32", x, y, N, H * W, Cc)
     return y
 
 
@@ -671,7 +654,7 @@ def time_mean(x: Tensor, lengths: Optional[Tensor] = None, len_add: int = 0) -> 
     _req(lengths, "lengths", torch.int32)
     B, T, Cc = x.shape
     y = _empty((B, Cc), x.device)
-    check(lib().dlip_time_mean_f32(ptr(x), ptr(lengths), len_add, ptr(y), B, T, Cc, Cc, stream_handle()), "dlip_time_mean_f32")
+    call("dlip_time_mean_f32", x, lengths, len_add, y, B, T, Cc, Cc)
     return y
 
 
@@ -683,7 +666,7 @@ def mask_frames(x: Tensor, lengths: Tensor) -> Tensor:
     if lengths.numel() != B or E % 4:
         raise ValueError("mask_frames: one length per row of x [B,T,E], E % 4 == 0")
     y = _empty(x.shape, x.device)
-    check(lib().dlip_mask_frames_f32(ptr(x), ptr(lengths), ptr(y), B, T, E, stream_handle()), "dlip_mask_frames_f32")
+    call("dlip_mask_frames_f32", x, lengths, y, B, T, E)
     return y
 
 
@@ -700,7 +683,7 @@ def time_tail_zero(x: Tensor, lengths: Tensor, shift: int = 0) -> Tensor:
     + 1 of image n become zeros -- the padding of a ragged batch behind ``shift`` stride-2 stages (dlip_time_tail_zero_f32: store-only,
     the lengths stay on the device).  Returns x."""
     N, H, W, Cc = _time_ragged_args(x, lengths, shift, "time_tail_zero")
-    check(lib().dlip_time_tail_zero_f32(ptr(x), ptr(lengths), int(shift), N, H, W, Cc, stream_handle()), "dlip_time_tail_zero_f32")
+    call("dlip_time_tail_zero_f32", x, lengths, int(shift), N, H, W, Cc)
     return x
 
 
@@ -709,8 +692,7 @@ def avgpool_time_ragged(x: Tensor, lengths: Tensor, shift: int = 0) -> Tensor:
     of each utterance at its own length (dlip_avgpool_time_ragged_f32)."""
     N, H, W, Cc = _time_ragged_args(x, lengths, shift, "avgpool_time_ragged")
     y = _empty((N, Cc), x.device)
-    check(lib().dlip_avgpool_time_ragged_f32(ptr(x), ptr(lengths), int(shift), ptr(y), N, H, W, Cc, stream_handle()),
-          "dlip_avgpool_time_ragged_f32")
+    call("dlip_avgpool_time_ragged_f32", x, lengths, int(shift), y, N, H, W, Cc)
     return y
 
 
@@ -726,8 +708,7 @@ def statpool_nhwc(x: Tensor, lengths: Optional[Tensor] = None, shift: int = 0, e
     if W < 2:
         raise ValueError(f"statpool_nhwc: the unbiased standard deviation needs >= 2 frames, the map has {W}")
     y = _empty((N, 2 * H * Cc), x.device)
-    check(lib().dlip_statpool_nhwc_f32(ptr(x), ptr(lengths), int(shift), float(eps), ptr(y), N, H, W, Cc, stream_handle()),
-          "dlip_statpool_nhwc_f32")
+    call("dlip_statpool_nhwc_f32", x, lengths, int(shift), float(eps), y, N, H, W, Cc)
     return y
 
 
@@ -738,7 +719,7 @@ def swap_axes_nhwc(x: Tensor) -> Tensor:
         raise ValueError("swap_axes_nhwc: x [N,A,B,C] with C % 4 == 0")
     N, A, B, Cc = x.shape
     y = _empty((N, B, A, Cc), x.device)
-    check(lib().dlip_swap_axes_nhwc_f32(ptr(x), ptr(y), N, A, B, Cc, stream_handle()), "dlip_swap_axes_nhwc_f32")
+    call("dlip_swap_axes_nhwc_f32", x, y, N, A, B, Cc)
     return y
 
 
@@ -749,8 +730,7 @@ def time_valid_lengths(lengths: Tensor, shift: int, W: int) -> Tensor:
     if lengths is None or not 0 <= int(shift) <= 16 or W < 1:
         raise ValueError("time_valid_lengths: int32 lengths, 0 <= shift <= 16, W >= 1")
     out = _empty((lengths.numel(),), lengths.device, torch.int32)
-    check(lib().dlip_time_valid_lengths_i32(ptr(lengths), int(shift), int(W), ptr(out), lengths.numel(), stream_handle()),
-          "dlip_time_valid_lengths_i32")
+    call("dlip_time_valid_lengths_i32", lengths, int(shift), int(W), out, lengths.numel())
     return out
 
 
@@ -785,8 +765,7 @@ def mh_attn_scores(hidden: Tensor, v: Tensor, k: Tensor, head_off: Optional[Tens
             or (lengths is not None and lengths.numel() != B)):
         raise ValueError("mh_attn_scores: hidden [B,T,S], v [S], k [n], head_off [n+1] (or None with n = 1), one length per utterance or none")
     alpha = _empty((B, n, T), hidden.device)
-    check(lib().dlip_mh_attn_scores_f32(ptr(hidden), ptr(v), ptr(k), ptr(head_off), ptr(lengths), int(len_add), ptr(alpha), B, T, S, n,
-                                        stream_handle()), "dlip_mh_attn_scores_f32")
+    call("dlip_mh_attn_scores_f32", hidden, v, k, head_off, lengths, int(len_add), alpha, B, T, S, n)
     return alpha
 
 
@@ -801,8 +780,7 @@ def mh_attn_stat_pool(x: Tensor, alpha: Tensor, eps: float, lengths: Optional[Te
         raise ValueError("mh_attn_stat_pool: x [B,T,C], alpha [B,n,T], one length per utterance or none")
     n = alpha.shape[1]
     y = _empty((B, n * 2 * Cc), x.device)
-    check(lib().dlip_mh_attn_stat_pool_f32(ptr(x), ptr(alpha), ptr(lengths), int(len_add), float(eps), ptr(y), B, T, Cc, n, stream_handle()),
-          "dlip_mh_attn_stat_pool_f32")
+    call("dlip_mh_attn_stat_pool_f32", x, alpha, lengths, int(len_add), float(eps), y, B, T, Cc, n)
     return y
 
 
@@ -810,7 +788,7 @@ def l1_sum(w: Tensor) -> Tensor:
     """sum |w| as a 0-d device tensor (dlip_l1_sum_f32: fp64 accumulation, fixed order)."""
     _req(w, "w")
     out = torch.empty((1,), device=w.device, dtype=torch.float32)
-    check(lib().dlip_l1_sum_f32(ptr(w.contiguous()), ptr(out), w.numel(), stream_handle()), "dlip_l1_sum_f32")
+    call("dlip_l1_sum_f32", w.contiguous(), out, w.numel())
     return out[0]
 
 
@@ -819,7 +797,7 @@ def group_mean(x: Tensor, group_ptr: Tensor) -> Tensor:
     _req(group_ptr, "group_ptr", torch.int32)
     U = group_ptr.numel() - 1
     y = _empty((U, x.shape[1]), x.device)
-    check(lib().dlip_group_mean_f32(ptr(x), ptr(group_ptr), ptr(y), U, x.shape[1], stream_handle()), "dlip_group_mean_f32")
+    call("dlip_group_mean_f32", x, group_ptr, y, U, x.shape[1])
     return y
 
 
@@ -836,7 +814,7 @@ def meanstd_pool(x: Tensor, out_split: bool = False, lengths: Optional[Tensor] =
         raise ValueError("meanstd_pool: C must be a multiple of 4")
     width = (2 * Cc + 31) // 32 * 32 if out_split else 2 * Cc
     y = _empty((B, width), x.device)
-    check(lib().dlip_meanstd_pool_f32(ptr(x), ptr(lengths), len_add, ptr(y), B, T, Cc, int(out_split), stream_handle()), "dlip_meanstd_pool_f32")
+    call("dlip_meanstd_pool_f32", x, lengths, len_add, y, B, T, Cc, int(out_split))
     return y
 
 
@@ -847,9 +825,9 @@ def nct_to_ntc(x: Tensor, pad_to: Optional[int] = None, out_split: bool = False)
     Cp = Cc if pad_to is None else pad_to
     y = _empty((B, T, Cp), x.device)
     if out_split:
-        check(lib().dlip_nct_to_ntc_split_f32(ptr(x), ptr(y), B, Cc, T, Cp, stream_handle()), "dlip_nct_to_ntc_split_f32")
+        call("dlip_nct_to_ntc_split_f32", x, y, B, Cc, T, Cp)
         return y
-    check(lib().dlip_nct_to_ntc_f32(ptr(x), ptr(y), B, Cc, T, Cp, stream_handle()), "dlip_nct_to_ntc_f32")
+    call("dlip_nct_to_ntc_f32", x, y, B, Cc, T, Cp)
     return y
 
 
@@ -857,7 +835,7 @@ def ntc_to_nct(x: Tensor) -> Tensor:
     _req(x, "x")
     B, T, Cc = x.shape
     y = _empty((B, Cc, T), x.device)
-    check(lib().dlip_ntc_to_nct_f32(ptr(x), ptr(y), B, T, Cc, stream_handle()), "dlip_ntc_to_nct_f32")
+    call("dlip_ntc_to_nct_f32", x, y, B, T, Cc)
     return y
 
 
@@ -868,7 +846,7 @@ def ingest_rgb_u8(frames: Tensor) -> Tensor:
     if three != 3:
         raise ValueError("ingest_rgb_u8: expected [B,T,3,H,W]")
     y = _empty((B, 1, T, H, W), frames.device)
-    check(lib().dlip_ingest_rgb_u8(ptr(frames), ptr(y), B * T, H, W, stream_handle()), "dlip_ingest_rgb_u8")
+    call("dlip_ingest_rgb_u8", frames, y, B * T, H, W)
     return y
 
 
@@ -876,8 +854,7 @@ def affine_act(x: Tensor, scale: Tensor, shift: Tensor, slope: float = 0.2, act_
     """[M,C]: lrelu(x*scale+shift) or lrelu(x)*scale+shift (eval BatchNorm1d + LeakyReLU)."""
     _req(x, "x"); _req(scale, "scale"); _req(shift, "shift")
     y = _empty(x.shape, x.device)
-    check(lib().dlip_affine_act_f32(ptr(x), ptr(scale), ptr(shift), ptr(y), x.numel() // x.shape[-1], x.shape[-1],
-                                    slope, int(act_first), stream_handle()), "dlip_affine_act_f32")
+    call("dlip_affine_act_f32", x, scale, shift, y, x.numel() // x.shape[-1], x.shape[-1], slope, int(act_first))
     return y
 
 
@@ -887,7 +864,7 @@ def znorm_cat(a: Optional[Tensor], v: Optional[Tensor], biased: bool = False) ->
     Da = a.shape[1] if a is not None else 0
     Dv = v.shape[1] if v is not None else 0
     y = _empty((U, Da + Dv), (a if a is not None else v).device)
-    check(lib().dlip_znorm_cat_f32(ptr(a), Da, ptr(v), Dv, ptr(y), U, int(biased), stream_handle()), "dlip_znorm_cat_f32")
+    call("dlip_znorm_cat_f32", a, Da, v, Dv, y, U, int(biased))
     return y
 
 
@@ -899,15 +876,14 @@ def znorm_cat_pooled(a: Optional[Tensor], p: "Pooled", biased: bool = False) -> 
     if a is not None and a.shape[0] != U:
         raise ValueError(f"znorm_cat_pooled: {a.shape[0]} rows of a, {U} pooled groups")
     y = _empty((U, Da + p.K), p.partials.device)
-    check(lib().dlip_znorm_cat_pooled_f32(ptr(a), Da, ptr(p.partials), p.M, p.K, p.tile_rows, p.group_rows, ptr(p.lengths), p.len_mul,
-                                          p.len_add, ptr(y), U, int(biased), stream_handle()), "dlip_znorm_cat_pooled_f32")
+    call("dlip_znorm_cat_pooled_f32", a, Da, p.partials, p.M, p.K, p.tile_rows, p.group_rows, p.lengths, p.len_mul, p.len_add, y, U, int(biased))
     return y
 
 
 def l2_normalize(x: Tensor, eps: float = 1e-12) -> Tensor:
     _req(x, "x")
     y = _empty(x.shape, x.device)
-    check(lib().dlip_l2_normalize_f32(ptr(x), ptr(y), x.shape[0], x.shape[1], eps, stream_handle()), "dlip_l2_normalize_f32")
+    call("dlip_l2_normalize_f32", x, y, x.shape[0], x.shape[1], eps)
     return y
 
 
@@ -919,8 +895,7 @@ def pair_cosine(emb: Tensor, idx_a: Tensor, idx_b: Tensor, mode: int = 0, eps: f
     if out is None:
         out = _empty((n,), emb.device)
     _req(out, "out")
-    check(lib().dlip_pair_cosine_f32(ptr(emb), emb.shape[0], emb.shape[1], ptr(idx_a), ptr(idx_b), ptr(out), n, mode,
-                                     eps, weight, int(acc), stream_handle()), "dlip_pair_cosine_f32")
+    call("dlip_pair_cosine_f32", emb, emb.shape[0], emb.shape[1], idx_a, idx_b, out, n, mode, eps, weight, int(acc))
     return out
 
 
@@ -948,7 +923,7 @@ def topk_stats(s: Tensor, k: int, n: Optional[int] = None) -> Tuple[Tensor, Tens
         raise ValueError("topk_stats: no rows")
     _req(s, "s")                          # behind the shape checks: those are refused the same way on a box without a GPU
     mean, sd = _empty((R,), s.device), _empty((R,), s.device)
-    check(lib().dlip_topk_stats_f32(ptr(s), R, n, ld, int(k), ptr(mean), ptr(sd), stream_handle()), "dlip_topk_stats_f32")
+    call("dlip_topk_stats_f32", s, R, n, ld, int(k), mean, sd)
     return mean, sd
 
 
@@ -971,8 +946,7 @@ def score_norm(scores: Tensor, idx_a: Tensor, idx_b: Tensor, mu: Tensor, sd: Ten
     _req(out, "out")
     if out.numel() != n:
         raise ValueError(f"score_norm: out has {out.numel()} entries for {n} scores")
-    check(lib().dlip_score_norm_f32(ptr(scores), ptr(idx_a), ptr(idx_b), n, ptr(mu), ptr(sd), mu.numel(), SCORE_NORM_MODES[mode],
-                                    eps, weight, int(acc), ptr(out), stream_handle()), "dlip_score_norm_f32")
+    call("dlip_score_norm_f32", scores, idx_a, idx_b, n, mu, sd, mu.numel(), SCORE_NORM_MODES[mode], eps, weight, int(acc), out)
     return out
 
 
@@ -1013,8 +987,7 @@ def cohort_stats(emb: Tensor, cohort: Tensor, top_k: Optional[int] = None, chunk
     for r0 in range(0, U, rows):
         r = min(rows, U - r0)
         linear(e[r0:r0 + r], c, out=scratch[:r].view(1, 1, r, Nc))
-        check(lib().dlip_topk_stats_f32(ptr(scratch), r, Nc, Nc, k, mu.data_ptr() + 4 * r0, sd.data_ptr() + 4 * r0, stream_handle()),
-              "dlip_topk_stats_f32")
+        call("dlip_topk_stats_f32", scratch, r, Nc, Nc, k, mu.data_ptr() + 4 * r0, sd.data_ptr() + 4 * r0)
     return mu, sd
 
 
@@ -1024,16 +997,14 @@ def logits_argmax(e: Tensor, W: Tensor, bias: Optional[Tensor] = None, cosine: b
     K = W.shape[0]
     logits = _empty((B, K), e.device)
     amax = _empty((B,), e.device, torch.int64)
-    check(lib().dlip_logits_argmax_f32(ptr(e), ptr(W), ptr(bias), ptr(logits), ptr(amax), B, D, K, int(cosine),
-                                       stream_handle()), "dlip_logits_argmax_f32")
+    call("dlip_logits_argmax_f32", e, W, bias, logits, amax, B, D, K, int(cosine))
     return logits, amax
 
 
 def margin_ce_loss(logits: Tensor, labels: Tensor, scale: float = 1.0, margin: float = 0.0) -> Tensor:
     _req(logits, "logits"); _req(labels, "labels", torch.int64)
     loss = _empty((1,), logits.device)
-    check(lib().dlip_margin_ce_loss_f32(ptr(logits), ptr(labels), ptr(loss), logits.shape[0], logits.shape[1], scale,
-                                        margin, stream_handle()), "dlip_margin_ce_loss_f32")
+    call("dlip_margin_ce_loss_f32", logits, labels, loss, logits.shape[0], logits.shape[1], scale, margin)
     return loss[0]
 
 
@@ -1041,7 +1012,7 @@ def row_norm(x: Tensor, eps: float = 1e-12) -> Tensor:
     """r [U] = max(|x_u|, eps): the norm ``l2_normalize`` divides by, the same bits."""
     _req(x, "x")
     r = _empty((x.shape[0],), x.device)
-    check(lib().dlip_row_norm_f32(ptr(x), ptr(r), x.shape[0], x.shape[1], eps, stream_handle()), "dlip_row_norm_f32")
+    call("dlip_row_norm_f32", x, r, x.shape[0], x.shape[1], eps)
     return r
 
 
@@ -1050,8 +1021,7 @@ def asoftmax_logits(logits: Tensor, r: Tensor, labels: Tensor, lam: Tensor, m: i
     (dlip_asoftmax_logits_f32, forward mode)."""
     _req(logits, "logits"); _req(r, "r"); _req(labels, "labels", torch.int64); _req(lam, "lam")
     z = _empty(logits.shape, logits.device)
-    check(lib().dlip_asoftmax_logits_f32(ptr(logits), ptr(r), ptr(labels), ptr(lam), None, ptr(z), None, logits.shape[0], logits.shape[1],
-                                         int(m), float(r_floor), 0, stream_handle()), "dlip_asoftmax_logits_f32")
+    call("dlip_asoftmax_logits_f32", logits, r, labels, lam, None, z, None, logits.shape[0], logits.shape[1], int(m), float(r_floor), 0)
     return z
 
 
@@ -1059,7 +1029,7 @@ def lowfer_cat(e1: Tensor, e2: Tensor) -> Tensor:
     _req(e1, "e1"); _req(e2, "e2")
     B, D = e1.shape
     y = _empty((B, 3 * D), e1.device)
-    check(lib().dlip_lowfer_cat_f32(ptr(e1), ptr(e2), ptr(y), B, D, stream_handle()), "dlip_lowfer_cat_f32")
+    call("dlip_lowfer_cat_f32", e1, e2, y, B, D)
     return y
 
 
@@ -1089,8 +1059,7 @@ def bilinear_pool(e1: Tensor, e2: Tensor, U: Tensor, V: Tensor, k: int, save: bo
     z = _empty((B, o), e1.device)
     P = _empty((B, k * o), e1.device) if save else None
     Q = _empty((B, k * o), e1.device) if save else None
-    check(lib().dlip_bilinear_pool_f32(ptr(e1), ptr(e2), ptr(U), ptr(V), ptr(z), ptr(P), ptr(Q), B, d1, d2, o, int(k), stream_handle()),
-          "dlip_bilinear_pool_f32")
+    call("dlip_bilinear_pool_f32", e1, e2, U, V, z, P, Q, B, d1, d2, o, int(k))
     return (z, P, Q) if save else z
 
 
@@ -1101,8 +1070,7 @@ def bilinear_pool_bwd_w(e1: Tensor, e2: Tensor, P: Tensor, Q: Tensor, dz: Tensor
     _req(dz, "dz")
     dU = _empty((d1, k * o), e1.device)
     dV = _empty((d2, k * o), e1.device)
-    check(lib().dlip_bilinear_pool_bwd_w_f32(ptr(e1), ptr(e2), ptr(P), ptr(Q), ptr(dz), ptr(dU), ptr(dV), B, d1, d2, o, int(k),
-                                             stream_handle()), "dlip_bilinear_pool_bwd_w_f32")
+    call("dlip_bilinear_pool_bwd_w_f32", e1, e2, P, Q, dz, dU, dV, B, d1, d2, o, int(k))
     return dU, dV
 
 
@@ -1114,8 +1082,7 @@ def bilinear_pool_bwd_x(P: Tensor, Q: Tensor, dz: Tensor, U: Tensor, V: Tensor, 
     de1 = _empty((B, d1), dz.device) if want1 else None
     de2 = _empty((B, d2), dz.device) if want2 else None
     if want1 or want2:
-        check(lib().dlip_bilinear_pool_bwd_x_f32(ptr(P), ptr(Q), ptr(dz), ptr(U), ptr(V), ptr(de1), ptr(de2), B, d1, d2, o, int(k),
-                                                 stream_handle()), "dlip_bilinear_pool_bwd_x_f32")
+        call("dlip_bilinear_pool_bwd_x_f32", P, Q, dz, U, V, de1, de2, B, d1, d2, o, int(k))
     return de1, de2
 
 
@@ -1124,8 +1091,7 @@ def bilinear_finish(z: Tensor, scale: Tensor, shift: Tensor, eps: float = 1e-12)
     _req(z, "z"); _req(scale, "scale"); _req(shift, "shift")
     B, o = z.shape
     out = _empty((B, o), z.device)
-    check(lib().dlip_bilinear_finish_f32(ptr(z), ptr(scale), ptr(shift), ptr(out), B, o, float(eps), stream_handle()),
-          "dlip_bilinear_finish_f32")
+    call("dlip_bilinear_finish_f32", z, scale, shift, out, B, o, float(eps))
     return out
 
 
@@ -1184,9 +1150,8 @@ def compact_bilinear(x1: Tensor, x2: Tensor, p1: dict, p2: dict, sum_pool: bool 
     out = _empty((B, D) if sum_pool or x1.dim() == 2 else (B,) + tuple(x1.shape[2:]) + (D,), x1.device)
     psi1 = _empty((B, P, D), x1.device) if save else None
     psi2 = _empty((B, P, D), x1.device) if save else None
-    check(lib().dlip_compact_bilinear_f32(ptr(x1), ptr(x2), ptr(p1["rowptr"]), ptr(p1["idx"]), ptr(p1["sgn"]), ptr(p2["rowptr"]),
-                                          ptr(p2["idx"]), ptr(p2["sgn"]), ptr(out), ptr(psi1), ptr(psi2), B, C1, C2, P, D,
-                                          int(bool(sum_pool)), stream_handle()), "dlip_compact_bilinear_f32")
+    call("dlip_compact_bilinear_f32", x1, x2, p1["rowptr"], p1["idx"], p1["sgn"], p2["rowptr"], p2["idx"], p2["sgn"], out, psi1, psi2, B, C1, C2, P,
+         D, int(bool(sum_pool)))
     return (out, psi1, psi2) if save else out
 
 
@@ -1202,7 +1167,5 @@ def compact_bilinear_bwd(g: Tensor, psi1: Tensor, psi2: Tensor, p1: dict, p2: di
         raise ValueError(f"compact bilinear pooling: g {tuple(g.shape)} does not fit B = {B}, P = {P}, D = {D}, sum_pool = {sum_pool}")
     dx1 = _empty(tuple(shape1), g.device) if want1 else None
     dx2 = _empty(tuple(shape2), g.device) if want2 else None
-    check(lib().dlip_compact_bilinear_bwd_f32(ptr(g), ptr(psi1), ptr(psi2), ptr(p1["h"]), ptr(p1["s"]), ptr(p2["h"]), ptr(p2["s"]),
-                                              ptr(dx1), ptr(dx2), B, p1["C"], p2["C"], P, D, int(bool(sum_pool)), stream_handle()),
-          "dlip_compact_bilinear_bwd_f32")
+    call("dlip_compact_bilinear_bwd_f32", g, psi1, psi2, p1["h"], p1["s"], p2["h"], p2["s"], dx1, dx2, B, p1["C"], p2["C"], P, D, int(bool(sum_pool)))
     return dx1, dx2

@@ -247,7 +247,7 @@ def calib_note(module, name: str, t: Tensor) -> None:
     ent = CALIB.setdefault(id(module), (module, {}))
     pair = torch.empty(2, device=t.device, dtype=torch.float32)
     tt = t if t.is_contiguous() else t.contiguous()
-    _lib.check(_lib.lib().dlip_pow2_scale_f32(tt.data_ptr(), pair.data_ptr(), tt.numel(), float(ACT_TARGET), _lib.stream_handle()), "dlip_pow2_scale_f32")
+    _lib.call("dlip_pow2_scale_f32", tt.data_ptr(), pair.data_ptr(), tt.numel(), float(ACT_TARGET))
     prev = ent[1].get(name)
     ent[1][name] = pair if prev is None else torch.minimum(prev, pair)      # (a name noted twice in one pass: the hotter tensor rules)
 

@@ -19,7 +19,7 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import triplet as tp
-from ._lib import check, lib, ptr, stream_handle
+from ._lib import call
 
 Tensor = torch.Tensor
 
@@ -54,8 +54,7 @@ def loss_forward(embeddings: Tensor, labels: Tensor, margin: float, mode: int, w
     sel = tp._out((B, B), dev, torch.int32) if want_sel else None
     loss = tp._out((1,), dev)
     n = tp._out((1,), dev, torch.int32)
-    check(lib().dlip_contrastive_loss_f32(ptr(x), ptr(lab), float(margin), int(mode), ptr(g), ptr(rownorm), ptr(rowsum), ptr(rowcnt), ptr(w),
-                                          ptr(sel), ptr(loss), ptr(n), B, E, stream_handle()), "dlip_contrastive_loss_f32")
+    call("dlip_contrastive_loss_f32", x, lab, float(margin), int(mode), g, rownorm, rowsum, rowcnt, w, sel, loss, n, B, E)
     return PairLoss(loss[0], n[0], g, rownorm, w, sel)
 
 

@@ -28,7 +28,7 @@ from typing import Callable, List, Optional, Sequence, Tuple
 import torch
 
 from . import holders, ops
-from ._lib import DeepLipHipError, StatusBlock, check, check_range, lib, range_scope, scope_slots
+from ._lib import DeepLipHipError, StatusBlock, call, check_range, lib, range_scope, scope_slots
 
 Tensor = torch.Tensor
 
@@ -151,7 +151,7 @@ class StepPlan:
             gc_was_on = gc.isenabled()
             gc.disable()
             try:
-                check(lib().dlip_plan_begin(self.stream.cuda_stream), "dlip_plan_begin")
+                call("dlip_plan_begin", stream=self.stream.cuda_stream)
                 try:
                     out = self._pass("replay")
                 except BaseException:
@@ -159,7 +159,7 @@ class StepPlan:
                     lib().dlip_plan_end(self.stream.cuda_stream, C.byref(h))   # leave capture mode before propagating
                     lib().dlip_plan_destroy(h)
                     raise
-                check(lib().dlip_plan_end(self.stream.cuda_stream, C.byref(self._handle)), "dlip_plan_end")
+                call("dlip_plan_end", self.stream.cuda_stream, C.byref(self._handle))
             finally:
                 if gc_was_on:
                     gc.enable()
@@ -182,7 +182,7 @@ class StepPlan:
         try:
             if names is not None:
                 ops.LAUNCH_HOOK = names
-                check(lib().dlip_span_scope_begin(self._spans[0].data_ptr(), self._spans[1].data_ptr(), self._spans[2]), "dlip_span_scope_begin")
+                call("dlip_span_scope_begin", self._spans[0].data_ptr(), self._spans[1].data_ptr(), self._spans[2])
             try:
                 # one low-side range scope per pass over the plan's own evidence words: the verdict kernel is the last launch of
                 # the recorded step, so every replay reports (and re-zeroes) for itself
@@ -214,7 +214,7 @@ class StepPlan:
                                      "weights are stale); record a new plan")
         if check_reports:
             check_range()       # f16x3 overflow reported by an earlier replay (host read, no synchronisation)
-        check(lib().dlip_plan_run(self._handle, torch.cuda.current_stream(self.device).cuda_stream), "dlip_plan_run")
+        call("dlip_plan_run", self._handle, stream=torch.cuda.current_stream(self.device).cuda_stream)
         return self.outputs
 
     def take_range_error(self):

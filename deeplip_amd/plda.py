@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import ops
-from ._lib import check, lib, ptr, stream_handle
+from ._lib import call
 
 
 class PLDA:
@@ -155,8 +155,7 @@ class PLDA:
         _, _, psi = self._device_params(u.device)
         n = idx_a.numel()
         out = torch.empty((n,), device=u.device, dtype=torch.float32)
-        check(lib().dlip_plda_llr_f32(ptr(u), u.shape[0], u.shape[1], ptr(psi), ptr(idx_a), ptr(idx_b), ptr(out), n,
-                                      stream_handle()), "dlip_plda_llr_f32")
+        call("dlip_plda_llr_f32", u, u.shape[0], u.shape[1], psi, idx_a, idx_b, out, n)
         return out
 
     def score_trials(self, emb: torch.Tensor, idx_a: torch.Tensor, idx_b: torch.Tensor) -> torch.Tensor:

@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from ._lib import check, lib, ptr, stream_handle
+from ._lib import call, lib
 
 SPEED_KEYS = ("speeds",)
 SPEED_RANGE = (0.5, 2.0)
@@ -161,9 +161,8 @@ class _Bank:
         tabs, bank = self._upload()
         out = ops._empty((B, S_out), wave.device)
         out_lengths = ops._empty((B,), wave.device, torch.int32)
-        check(lib().dlip_wave_resample_f32(ptr(wave), ptr(lens), ptr(tabs), ptr(bank), ptr(ridx), ptr(out), ptr(out_lengths), B, S, S_out,
-                                           len(self.ratios), self.tab_stride, self.span_words, self.tile, stream_handle()),
-              f"{who}: dlip_wave_resample_f32")
+        call("dlip_wave_resample_f32", wave, lens, tabs, bank, ridx, out, out_lengths, B, S, S_out, len(self.ratios), self.tab_stride,
+             self.span_words, self.tile, what=f"{who}: dlip_wave_resample_f32")
         return out, out_lengths
 
 

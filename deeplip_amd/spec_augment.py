@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from ._lib import check, lib, ptr, stream_handle
+from ._lib import call, lib
 
 SPEC_AUGMENT_KEYS = ("time_warp", "freq_masks", "freq_width", "time_masks", "time_width", "time_ratio", "fill")
 FILLS = ("zero", "mean")            # exact zeros (the row's mean after CMVN) | the mean of the row's own input
@@ -128,7 +128,6 @@ class SpecAugment:
             raise _lib.DeepLipHipError(f"dlip_spec_augment_workspace_bytes refused B = {B}, C = {C}, NF = {NF}")
         ws = ops._empty((nbytes // 8,), dev, torch.float64)
         y = ops._empty(tuple(x.shape), dev)
-        check(lib().dlip_spec_augment_f32(ptr(x), ptr(lens), ptr(v), ptr(y), ptr(ws), nbytes, B, C, NF, self.time_warp,
-                                          self.freq_masks, self.freq_width, self.time_masks, self.time_width, self.time_ratio,
-                                          FILLS.index(self.fill), stream_handle()), "dlip_spec_augment_f32")
+        call("dlip_spec_augment_f32", x, lens, v, y, ws, nbytes, B, C, NF, self.time_warp, self.freq_masks, self.freq_width, self.time_masks,
+             self.time_width, self.time_ratio, FILLS.index(self.fill))
         return y

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import ops
-from ._lib import DeepLipHipError, check, lib, ptr, stream_handle
+from ._lib import DeepLipHipError, call
 
 Tensor = torch.Tensor
 
@@ -109,8 +109,7 @@ def mine(embeddings: Tensor, labels: Tensor, margin: float, mode: int, u: Option
     g = _out((B, B), x.device)
     rownorm = _out((B,), x.device)
     neg = _out((B, B), x.device, torch.int32) if mode != MODE_ALL else None
-    check(lib().dlip_triplet_mine_f32(ptr(x), ptr(lab), float(margin), int(mode), ptr(u), ptr(g), ptr(rownorm), ptr(neg), B, E,
-                                      stream_handle()), "dlip_triplet_mine_f32")
+    call("dlip_triplet_mine_f32", x, lab, float(margin), int(mode), u, g, rownorm, neg, B, E)
     return Mined(g, rownorm, neg, lab, int(mode))
 
 
@@ -123,8 +122,7 @@ def loss_forward(m: Mined, margin: float):
     wcount = _out((B, B), dev, torch.int32)
     loss = _out((1,), dev)
     n = _out((1,), dev, torch.int32)
-    check(lib().dlip_triplet_loss_f32(ptr(m.g), ptr(m.rownorm), ptr(m.labels), ptr(m.neg), float(margin), m.mode, ptr(rowsum),
-                                      ptr(rowcnt), ptr(wcount), ptr(loss), ptr(n), B, stream_handle()), "dlip_triplet_loss_f32")
+    call("dlip_triplet_loss_f32", m.g, m.rownorm, m.labels, m.neg, float(margin), m.mode, rowsum, rowcnt, wcount, loss, n, B)
     return loss[0], n[0], wcount
 
 
@@ -134,8 +132,7 @@ def loss_backward(embeddings: Tensor, m: Mined, wcount: Tensor, n: Tensor, gscal
     B, E = x.shape
     mw = _out((B, (B + 15) // 16 * 16), x.device)
     dx = _out((B, E), x.device)
-    check(lib().dlip_triplet_loss_bwd_f32(ptr(x), ptr(m.g), ptr(m.rownorm), ptr(wcount), ptr(n), ptr(gscale), ptr(mw), ptr(dx), B, E,
-                                          stream_handle()), "dlip_triplet_loss_bwd_f32")
+    call("dlip_triplet_loss_bwd_f32", x, m.g, m.rownorm, wcount, n, gscale, mw, dx, B, E)
     return dx
 
 

@@ -18,7 +18,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib, ops
-from ._lib import check, lib, ptr, stream_handle
+from ._lib import call, ptr
 
 SECTION_KEYS = ("cmn_window", "center", "min_window", "norm_vars", "vad", "energy_row", "min_keep")
 VAD_KEYS = ("energy_threshold", "energy_mean_scale", "frames_context", "proportion_threshold")
@@ -176,9 +176,8 @@ class VoicedFrames:
             pos = ops._empty((B, NF), dev, torch.int32)
             out_len = ops._empty((B,), dev, torch.int32)
             self.last_fallback = ops._empty((B,), dev, torch.int32)
-            check(lib().dlip_vad_energy_select_i32(e_ptr, stride, ptr(voiced), ptr(lens), v["energy_threshold"], v["energy_mean_scale"],
-                                                   v["frames_context"], v["proportion_threshold"], self.min_keep, ptr(pos), ptr(out_len),
-                                                   ptr(self.last_fallback), B, NF, stream_handle()), "dlip_vad_energy_select_i32")
+            call("dlip_vad_energy_select_i32", e_ptr, stride, voiced, lens, v["energy_threshold"], v["energy_mean_scale"], v["frames_context"],
+                 v["proportion_threshold"], self.min_keep, pos, out_len, self.last_fallback, B, NF)
         else:
             # CMN only: every frame stays, the length vector is the input's (clamped like the kernels clamp it)
             out_len = ops._empty((B,), dev, torch.int32)
@@ -188,7 +187,6 @@ class VoicedFrames:
                 torch.clamp(lens, 1, NF, out=out_len)
             self.last_fallback = None
         y = ops._empty((B, C, NF), dev)
-        check(lib().dlip_cmn_sliding_select_f32(ptr(x), ptr(lens), ptr(pos), ptr(out_len) if select else None, ptr(y), B, C, NF, window,
-                                                int(self.center), self.min_window, int(self.norm_vars), stream_handle()),
-              "dlip_cmn_sliding_select_f32")
+        call("dlip_cmn_sliding_select_f32", x, lens, pos, out_len if select else None, y, B, C, NF, window, int(self.center), self.min_window,
+             int(self.norm_vars))
         return y, out_len

@@ -20,7 +20,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from deeplip_amd import ops, packing, weightgen as wg                      # noqa: E402
-from deeplip_amd._lib import check, lib, ptr, stream_handle                # noqa: E402
+from deeplip_amd._lib import call                                           # noqa: E402
 from deeplip_amd.audio_resnet import POOL_EPS                              # noqa: E402
 
 
@@ -72,8 +72,7 @@ def main():
     dx = torch.empty_like(m)
 
     def bwd():          # (the entry point StatPoolNHWCFn.backward calls, on preallocated tensors: a launch, no allocation in the window)
-        check(lib().dlip_statpool_nhwc_bwd_f32(ptr(m), ptr(y), ptr(dy), POOL_EPS, ptr(dx), B, H, W, C, stream_handle()),
-              "dlip_statpool_nhwc_bwd_f32")
+        call("dlip_statpool_nhwc_bwd_f32", m, y, dy, POOL_EPS, dx, B, H, W, C)
 
     med, spread = interleaved({"statpool_fwd_us": lambda: ops.statpool_nhwc(m, None, 0, POOL_EPS), "statpool_bwd_us": bwd,
                                "copy_d2d_us": lambda: dst.copy_(m)}, a.rounds)

@@ -24,7 +24,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from deeplip_amd import autograd as ag, ops                                # noqa: E402
-from deeplip_amd._lib import check, lib, ptr, stream_handle                # noqa: E402
+from deeplip_amd._lib import call                                           # noqa: E402
 from deeplip_amd.audio import AttentiveStatPooling, MultiHeadAttention     # noqa: E402
 from deeplip_amd.audio_resnet import POOL_EPS                              # noqa: E402
 
@@ -145,9 +145,7 @@ def main():
     de, dek = torch.empty((B, n, T), device="cuda"), torch.empty((B, n), device="cuda")
 
     def tail_bwd():
-        check(lib().dlip_mh_attn_stat_pool_bwd_f32(ptr(xd), ptr(hidden), ptr(vv), ptr(pool.head_off), ptr(alpha), ptr(y), ptr(dy), None, 0,
-                                                   POOL_EPS, ptr(dx), ptr(dh), ptr(rde), ptr(de), ptr(dek), B, T, C, S, n, stream_handle()),
-              "dlip_mh_attn_stat_pool_bwd_f32")
+        call("dlip_mh_attn_stat_pool_bwd_f32", xd, hidden, vv, pool.head_off, alpha, y, dy, None, 0, POOL_EPS, dx, dh, rde, de, dek, B, T, C, S, n)
 
     med, spread = interleaved({"scores_us": lambda: ops.mh_attn_scores(hidden, vv, kk, pool.head_off),
                                "stat_us": lambda: ops.mh_attn_stat_pool(xd, alpha, POOL_EPS), "bwd_us": tail_bwd}, a.rounds)

@@ -26,7 +26,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from deeplip_amd import ops  # noqa: E402
-from deeplip_amd._lib import check, lib, ptr, stream_handle  # noqa: E402
+from deeplip_amd._lib import call  # noqa: E402
 from deeplip_amd.frontend import AudioFrontend  # noqa: E402
 
 HBM_PEAK = 8.0e12
@@ -65,8 +65,7 @@ def main():
     rows = ops._empty((B * NF, fe.nbp), x.device)
 
     def kernel():
-        check(lib().dlip_stft_logmag_wave_f32(ptr(x), ptr(rows), B, S, NF, fe.win_length, fe.hop, fe.nfft, fe.nb, fe.nbp, stream_handle()),
-              "dlip_stft_logmag_wave_f32")
+        call("dlip_stft_logmag_wave_f32", x, rows, B, S, NF, fe.win_length, fe.hop, fe.nfft, fe.nb, fe.nbp)
 
     runs = {"stft rect": lambda: fe(x), "stft ragged": lambda: fe(x, lens), "stft kernel": kernel, "logfbank-60": lambda: mel(x)}
     with torch.no_grad():

@@ -49,24 +49,20 @@ def timed(fn, iters):
 
 
 def count_dlip_calls(fn):
-    """dlip_* entry points called by fn (every one goes through _lib.check, imported by name into these modules)."""
-    from deeplip_amd import _lib, autograd, autograd_video, ops
-    mods = (ops, autograd, autograd_video)
+    """dlip_* entry points called by fn (every one goes through _lib.call, which hands the status to _lib.check)."""
+    from deeplip_amd import _lib
     n = [0]
     orig = _lib.check
 
     def counting(rc, what=""):
         n[0] += 1
         return orig(rc, what)
-    saved = [m.check for m in mods]
-    for m in mods:
-        m.check = counting
+    _lib.check = counting
     try:
         fn()
         torch.cuda.synchronize()
     finally:
-        for m, c in zip(mods, saved):
-            m.check = c
+        _lib.check = orig
     return n[0]
 
 
