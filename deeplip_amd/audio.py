@@ -188,25 +188,166 @@ class TDNN_Block(nn.Module):
         return ops.ntc_to_nct(self.run_ntc(h, p))
 
 
+class PackedFTDNN:
+    """The eval pack of an FTDNN_Block: its two convolutions and the bypass scale the stored tensors need (2^(e_out - e_in) s)."""
+
+    def __init__(self, factor: packing.Packed, ctx: packing.Packed, bypass: float):
+        self.factor, self.ctx, self.bypass = factor, ctx, bypass
+
+    @property
+    def wscale(self):
+        return self.ctx.wscale
+
+
+class FTDNN_Block(nn.Module):
+    """One factorized TDNN layer (``arch: ftdnn``, conf/audio_config.yaml:84-92; the definition is the build's own: DESIGN.md 4k).
+    ``factor``: Conv1d(input_dim -> bottleneck_dim, one tap per context offset, dilation as TDNN_Block derives it, no bias), no
+    BatchNorm, no activation -- its weight [Bn, Cin, k] seen as M [Bn, Cin k] is what the semi-orthogonal step constrains;
+    ``context_layer``: Conv1d(bottleneck_dim -> output_dim, 1 tap, bias); ``bn`` and LeakyReLU(0.2) in the order ``bn_first`` says, as
+    TDNN_Block; then, when the widths agree and ``bypass_scale`` != 0, y[b, :, t] += bypass_scale x[b, :, t - context[0]]: the input frame
+    at context offset 0, added behind the activation and the BatchNorm."""
+
+    def __init__(self, input_dim, output_dim, dilation, bottleneck_dim=128, bypass_scale=0.66, bn_first=True):
+        super().__init__()
+        context = [int(c) for c in dilation]
+        kernel_size = len(context)
+        dil = (context[-1] - context[0]) // (kernel_size - 1) if kernel_size > 1 else 1
+        Bn = int(bottleneck_dim)
+        if Bn < 4 or Bn % 4:
+            raise ValueError(f"FTDNN_Block: bottleneck_dim must be a positive multiple of 4 (the convolutions' channel granule), got {Bn}")
+        if Bn > input_dim * kernel_size:
+            raise ValueError(f"FTDNN_Block: bottleneck_dim {Bn} exceeds input_dim * taps = {input_dim * kernel_size}: the factor matrix "
+                             "[Bn, Cin k] cannot have orthonormal rows")
+        if Bn > ops.SEMI_ORTH_MAX_ROWS:
+            raise ValueError(f"FTDNN_Block: bottleneck_dim {Bn} exceeds {ops.SEMI_ORTH_MAX_ROWS}, what the semi-orthogonal step's LDS plan "
+                             "carries (P = M M^T stays in one workgroup's LDS)")
+        self.bypass_scale = float(bypass_scale) if input_dim == output_dim else 0.0
+        if self.bypass_scale != 0.0:
+            if not context[0] <= 0 <= context[-1]:
+                raise ValueError(f"FTDNN_Block: the bypass adds the input frame at context offset 0, which {context} does not span")
+            if input_dim % 4:
+                raise ValueError(f"FTDNN_Block: the bypass moves four channels per lane; width {input_dim} is no multiple of 4")
+        self.bypass_shift = -context[0]
+        self.kernel_size, self.dilation, self.padding = kernel_size, dil, 0
+        self.input_dim, self.output_dim, self.bottleneck_dim = input_dim, output_dim, Bn
+        self.factor = ConvParams(input_dim, Bn, (kernel_size,), bias=False)
+        self.context_layer = ConvParams(Bn, output_dim, (1,), bias=True)
+        self.bn = BatchNormParams(output_dim)
+        self.activation = Marker("LeakyReLU(0.2)")
+        self.bn_first = bn_first
+
+    def pack(self, device, e_in: int = 0, e_out: int = 0) -> PackedFTDNN:
+        """The bottleneck tensor carries exponent 0 (an out-of-range one is arith auto's exact re-run); ``e_in`` / ``e_out`` as TDNN_Block."""
+        pf = packing.pack_conv1d(self.factor.weight, None, None, device, packing.const_slope(self.bottleneck_dim, 1.0, device),
+                                 packing.pad_channels(self.input_dim), e_in, 0)
+        slope = packing.const_slope(self.output_dim, LRELU, device)
+        cp = packing.pad_channels(self.bottleneck_dim)
+        if self.bn_first:
+            pc = packing.pack_conv1d(self.context_layer.weight, self.context_layer.bias, self.bn, device, slope, cp, 0, e_out)
+        else:
+            pc = packing.pack_conv1d(self.context_layer.weight, self.context_layer.bias, None, device, slope, cp, 0, e_out)
+            sc, sh = packing.bn_scale_shift(self.bn)
+            if packing.PRECISION == "f16x3" and e_out:
+                sh = sh * (2.0 ** int(e_out))
+            pc.post_scale, pc.post_shift = sc.float().to(device), sh.float().to(device)
+        f16x3 = packing.PRECISION == "f16x3"
+        return PackedFTDNN(pf, pc, self.bypass_scale * (2.0 ** int(e_out - e_in) if f16x3 else 1.0))
+
+    def run_ntc(self, x: Tensor, p: PackedFTDNN, x_split: bool = False, out_split: bool = False) -> Tensor:
+        """x [B,T,C] -> [B,T',K]; x_split / out_split as TDNN_Block.  The bottleneck travels split when it is whole 32-channel blocks."""
+        f, c = p.factor, p.ctx
+        z_split = f.wscale is not None and self.bottleneck_dim % 32 == 0
+        z = ops.conv1d_ntc(x, f.w, f.b, dilation=self.dilation, pad=0, slope=f.slope, w_scale=f.wscale, x_split=x_split, out_split=z_split)
+        byp = self.bypass_scale != 0.0
+        y = ops.conv1d_ntc(z, c.w, c.b, dilation=1, pad=0, slope=c.slope, post_scale=c.post_scale, post_shift=c.post_shift,
+                           w_scale=c.wscale, x_split=z_split, out_split=out_split and not byp)
+        if byp:
+            y = ops.ftdnn_bypass(y, x, p.bypass, self.bypass_shift, x_split=x_split, out_split=out_split)
+        return y
+
+    def forward(self, x: Tensor) -> Tensor:
+        """[B,C,T] -> [B,K,T'] (reference layout, standalone use)."""
+        _require_eval(self)
+        p = _cached_pack(self, x.device, self.pack)
+        h = ops.nct_to_ntc(x.contiguous(), pad_to=packing.pad_channels(self.input_dim))
+        return ops.ntc_to_nct(self.run_ntc(h, p))
+
+
+def default_factorized_layers(context) -> List[int]:
+    """Every layer i >= 1 whose context has more than one offset (layers 1 and 2 of the reference's five-layer ``ftdnn`` section)."""
+    return [i for i, c in enumerate(context) if i >= 1 and len(c) > 1]
+
+
+class SemiOrthStep(nn.Module):
+    """The semi-orthogonal constraint on every ``factor`` matrix of a model, applied behind the optimizer step: one
+    launch pair for all of them.  ``counter`` (a buffer: it goes into checkpoints and into a recorded step's snapshot) counts the
+    optimizer steps ON THE DEVICE; the launch advances it and applies the step when the count is a multiple of ``every``, so a replayed
+    graph and an eager loop update on the same iterations.  Every rank of a job applies the same deterministic update to identical
+    parameters: no collective."""
+
+    def __init__(self, model, every: int = 4):
+        super().__init__()
+        if isinstance(every, bool) or not isinstance(every, int) or every < 0:
+            raise ValueError(f"train.semi_orth_every is an int >= 0 (0: off), got {every!r}")
+        self.every = every
+        self._mats = [m.factor.weight for m in model.modules() if isinstance(m, FTDNN_Block)]
+        if not self._mats:
+            raise ValueError("SemiOrthStep: the model has no factorized layer")
+        if len(self._mats) > ops.SEMI_ORTH_MAX_MATS:
+            raise ValueError(f"SemiOrthStep: at most {ops.SEMI_ORTH_MAX_MATS} factorized layers, got {len(self._mats)}")
+        dev = self._mats[0].device
+        if dev.type != "cuda":
+            raise _lib.DeepLipHipError("SemiOrthStep: the factor matrices must be on the GPU; deeplip_amd has no CPU path")
+        self.register_buffer("counter", torch.zeros(2, dtype=torch.int32, device=dev))
+        self._ws = ops.semi_orth_workspace(len(self._mats), dev)
+        self._key = self._table = None
+
+    def matrices(self):
+        return list(self._mats)
+
+    def forward(self):
+        key = tuple(m.data_ptr() for m in self._mats)
+        if key != self._key:            # (first call, or the parameters moved: a host-to-device copy, never inside a capture)
+            self._table, self._key = ops.semi_orth_table([m.detach() for m in self._mats]), key
+        tab, max_rows, max_cols = self._table
+        ops.semi_orth_step(tab, len(self._mats), max_rows, max_cols, self.counter, self.every, self._ws)
+
+
 class SpeakerEmbNet(nn.Module):
-    """tdnn.py:45-111.  ``opts`` = model options with sub-dict ``opts[opts['arch']]``."""
+    """tdnn.py:45-111.  ``opts`` = model options with sub-dict ``opts[opts['arch']]``.  ``arch: ftdnn`` (conf/audio_config.yaml:84-92;
+    DESIGN.md 4k) takes the ``tdnn`` keys and three of the build's own: ``bottleneck_dim`` (128), ``bypass_scale`` (0.66) and
+    ``factorized_layers`` (default_factorized_layers); the layers it lists are FTDNN_Blocks."""
 
     def __init__(self, opts):
         super().__init__()
-        opts = opts[opts["arch"]]
+        arch = opts["arch"]
+        opts = opts[arch]
         context = opts["context"]
         input_dim = opts["input_dim"]
         hidden_dim = opts["hidden_dim"]
         layers_num = opts["tdnn_layers"]
         embedding_dim = opts["embedding_dim"]
-        attention_hidden_size = opts["attention_hidden_size"]
+        attention_hidden_size = opts.get("attention_hidden_size", 64)     # (upstream's ftdnn section leaves it out)
         self.bn_first = opts["bn_first"]
         self.input_dim = input_dim
         self.embedding_dim = embedding_dim
         self.activation = Marker("LeakyReLU(0.2)")
+        factorized = ()
+        if arch == "ftdnn":
+            factorized = opts.get("factorized_layers")
+            factorized = default_factorized_layers(context[:layers_num]) if factorized is None else [int(i) for i in factorized]
+            bad = [i for i in factorized if not 1 <= i < layers_num]
+            if bad or len(set(factorized)) != len(factorized):
+                raise ValueError(f"model.ftdnn.factorized_layers: distinct layer indices in [1, {layers_num - 1}] (layer 0 reads the "
+                                 f"features and stays a plain TDNN layer), got {factorized}")
+        self.factorized_layers = tuple(sorted(factorized))
         layers = []
         for i in range(layers_num):
-            layers.append(TDNN_Block(input_dim, hidden_dim[i], dilation=context[i], stride=1, bn_first=self.bn_first))
+            if i in self.factorized_layers:
+                layers.append(FTDNN_Block(input_dim, hidden_dim[i], dilation=context[i], bottleneck_dim=opts.get("bottleneck_dim", 128),
+                                          bypass_scale=opts.get("bypass_scale", 0.66), bn_first=self.bn_first))
+            else:
+                layers.append(TDNN_Block(input_dim, hidden_dim[i], dilation=context[i], stride=1, bn_first=self.bn_first))
             input_dim = hidden_dim[i]
         self.tdnn = nn.Sequential(*layers)
         self.pooling_type = opts["pooling"]
@@ -300,7 +441,11 @@ class SpeakerEmbNet(nn.Module):
             if i + 1 == n and last_on_load:
                 T_out = h.shape[1] - blk.dilation * (blk.kernel_size - 1) + 2 * blk.padding
                 hand_over = ag.POOL_BWD_ON_LOAD and h.shape[0] * T_out > ag.BN_SMALL_ROWS and T_out > 1 and blk.bn_first and ag.BN_ON_LOAD
-            h, pend = ag.tdnn_block_train(h, blk, pending=pend, defer=(2 if hand_over else True) if (i + 1 < n or last_on_load) else False)
+            defer = (2 if hand_over else True) if (i + 1 < n or last_on_load) else False
+            if isinstance(blk, FTDNN_Block):
+                h, pend = ag.ftdnn_block_train(h, blk, pending=pend, defer=defer)
+            else:
+                h, pend = ag.tdnn_block_train(h, blk, pending=pend, defer=defer)
         # (pooling.py:24-26 | :87-107: attention scores, softmax over frames, weighted mean and std, all differentiable)
         if self.pooling_type == "statistic":
             h = ag.meanstd_pool(h, pending=pend, hand_over=hand_over and pend is not None)
@@ -353,7 +498,7 @@ class SpeakerEmbNet(nn.Module):
         for i, (blk, bp) in enumerate(zip(self.tdnn, p["tdnn"])):
             nxt = bp.wscale is not None and i + 1 < n and blk.output_dim % 32 == 0
             if (i + 1 == n and split and FUSE_POOL and taps is None and self.pooling_type == "statistic"
-                    and blk.output_dim % 4 == 0):
+                    and blk.output_dim % 4 == 0 and isinstance(blk, TDNN_Block)):
                 pooled = blk.run_pooled(h, bp, lens, len_add)       # None when an utterance is shorter than a workgroup tile
                 if pooled is not None:
                     break

@@ -886,6 +886,76 @@ def tdnn_block_train(x, blk, pending=None, defer=False):
     return out, None
 
 
+class BypassForkFn(Function):
+    """The fork in front of a factorized block with a bypass: x [B,T,C] -> (x, w) with w = x[:, shift:shift + T'] standing for the
+    bypass term s w, its scale NOT applied (BypassAddFn multiplies per loaded value; nothing is copied).  The backward is the block
+    input's whole gradient in one pass: the factor convolution's data gradient arrives for the first output, the gradient of (s w) --
+    the block's output gradient, as it is -- for the second, and dlip_ftdnn_bypass_bwd_f32 adds s times the latter into the shifted
+    window of the former, in place: no zero-filled [B,T,C] temporary, no pass that scales."""
+
+    @staticmethod
+    def forward(ctx, x, shift, Tp, scale):
+        ctx.cfg = (int(shift), float(scale))
+        return x.view_as(x), x.narrow(1, int(shift), int(Tp))
+
+    @staticmethod
+    def backward(ctx, dx, dw):
+        shift, scale = ctx.cfg
+        if dw is None:
+            return dx, None, None, None
+        dw = dw.contiguous()
+        if dx is None:
+            dx = torch.zeros((dw.shape[0], dw.shape[1] + shift, dw.shape[2]), device=dw.device, dtype=dw.dtype)   # (not met: the factor always reads x)
+        dx = dx.contiguous()
+        if hasattr(dx, "_dlip_lift"):
+            del dx._dlip_lift           # (a lift formed for the convolution's gradient alone does not describe the sum)
+        return ops.ftdnn_bypass_bwd(dw, dx, scale, shift), None, None, None
+
+
+class BypassAddFn(Function):
+    """out = y + s w on [B,T',C] (dlip_ftdnn_bypass_f32), w the window view BypassForkFn made of the block's input x; the gradient of
+    both y and (s w) is the output gradient itself."""
+
+    @staticmethod
+    def forward(ctx, y, w, x, shift, scale):
+        return ops.ftdnn_bypass(y.contiguous(), x, float(scale), int(shift))
+
+    @staticmethod
+    def backward(ctx, dout):
+        return dout, dout, None, None, None
+
+
+class _PointwiseOf:
+    """What tdnn_block_train reads of a block, for the 1-tap half of an FTDNN_Block (whose ``dilation`` is the factor's)."""
+    dilation = 1
+
+    def __init__(self, blk):
+        self.context_layer, self.bn, self.bn_first = blk.context_layer, blk.bn, blk.bn_first
+
+
+def ftdnn_block_train(x, blk, pending=None, defer=False):
+    """blk: deeplip_amd.audio.FTDNN_Block in train mode; x [B,T,C] channels-last -> (y, pending for the next block or None), as
+    tdnn_block_train.  The factor runs through the differentiable convolution of the lip-clip encoder (autograd_video.conv: both
+    TRAIN_CONV modes, its weight images prepared with the step's others), the rest through tdnn_block_train -- so the block hands its
+    BatchNorm over on load like its neighbours when it has no bypass; with one, its output is written (the bypass adds to it) and its
+    input is too (the bypass reads it)."""
+    from . import autograd_video as av
+    B, T, C_ = x.shape
+    byp = blk.bypass_scale != 0.0
+    if pending is not None:
+        materialize_pending(x, pending)           # (the factor has no BatchNorm-on-load producer of its own; the bypass reads values)
+    Tp = T - blk.dilation * (blk.kernel_size - 1)
+    xw = None
+    if byp:
+        x, xw = BypassForkFn.apply(x, blk.bypass_shift, Tp, blk.bypass_scale)
+    z = av.conv(x.view(B, 1, T, C_), blk.factor.weight, None, dil=(1, blk.dilation))
+    z = z.view(B, Tp, blk.bottleneck_dim)
+    y, pend = tdnn_block_train(z, _PointwiseOf(blk), pending=None, defer=False if byp else defer)
+    if byp:
+        y = BypassAddFn.apply(y, xw, x.detach(), blk.bypass_shift, blk.bypass_scale)
+    return y, pend
+
+
 def bn_rows_act_train(x, bn, slope, act_first):
     return BNRowsActFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, slope, act_first,
                              bn.num_batches_tracked)

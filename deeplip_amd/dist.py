@@ -160,6 +160,10 @@ class GradBuckets:
     -- on RCCL's own stream, beside the rest of the backward kernels.  ``finish()`` launches whatever is left
     (parameters a batch did not touch keep their zeros: every rank reduces the same layout), waits, and divides by
     the world size.  Use ``optimizer.zero_grad(set_to_none=False)`` (or ``buckets.zero()``) so the views survive.
+    Per step: zero -> forward -> backward (bucket all-reduces start as gradients land) -> ``finish()`` -> ``optimizer.step()`` ->, for
+    ``arch: ftdnn``, the semi-orthogonal step on the factor matrices (deeplip_amd.audio.SemiOrthStep).  That last step
+    needs NO collective: it is a deterministic function of the parameters and of a step count every rank keeps alike, so ranks
+    that hold identical parameters in front of it hold identical ones behind it.
     xGMI is point-to-point (7 links x ~153 GB/s): a ring all-reduce is bound by one link, so buckets are sized for
     a few hundred microseconds each (default 32 MB ~ 0.5 ms at 8 ranks) -- large enough to be bandwidth- rather than
     latency-bound, small enough that the last one does not stick out behind backward.

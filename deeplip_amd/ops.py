@@ -1169,3 +1169,72 @@ def compact_bilinear_bwd(g: Tensor, psi1: Tensor, psi2: Tensor, p1: dict, p2: di
     dx2 = _empty(tuple(shape2), g.device) if want2 else None
     call("dlip_compact_bilinear_bwd_f32", g, psi1, psi2, p1["h"], p1["s"], p2["h"], p2["s"], dx1, dx2, B, p1["C"], p2["C"], P, D, int(bool(sum_pool)))
     return dx1, dx2
+
+
+# ---- the factorized TDNN (`arch: ftdnn`, conf/audio_config.yaml:84-92) ----
+SEMI_ORTH_MAX_ROWS, SEMI_ORTH_MAX_MATS = _lib.HEADER["DLIP_SEMI_ORTH_MAX_ROWS"], _lib.HEADER["DLIP_SEMI_ORTH_MAX_MATS"]
+
+
+def _bypass_check(y: Tensor, x: Tensor, shift: int, what: str):
+    _req(y, "y"); _req(x, "x")
+    if y.dim() != 3 or x.dim() != 3 or x.shape[0] != y.shape[0] or x.shape[2] != y.shape[2]:
+        raise ValueError(f"{what}: y [B,T',C] and x [B,T,C] of one batch and width, got {tuple(y.shape)} and {tuple(x.shape)}")
+    B, Tp, C_ = y.shape
+    T = x.shape[1]
+    if C_ % 4 or shift < 0 or shift + Tp > T:
+        raise ValueError(f"{what}: C % 4 == 0 and 0 <= shift, shift + T' <= T (C {C_}, shift {shift}, T' {Tp}, T {T})")
+    return B, T, Tp, C_
+
+
+def ftdnn_bypass(y: Tensor, x: Tensor, scale: float, shift: int, x_split: bool = False, out_split: bool = False) -> Tensor:
+    """y [B,T',C] fp32 + scale * x[:, shift:shift + T'] -> [B,T',C]; ``x_split`` / ``out_split``: x is / the result comes in the split
+    activation format (C % 32 == 0)."""
+    B, T, Tp, C_ = _bypass_check(y, x, shift, "ftdnn_bypass")
+    if (x_split or out_split) and C_ % 32:
+        raise ValueError("ftdnn_bypass: the split activation format needs C % 32 == 0")
+    out = _empty((B, Tp, C_), y.device)
+    call("dlip_ftdnn_bypass_f32", y, x, out, B, T, Tp, C_, int(shift), float(scale), int(bool(x_split)) | 2 * int(bool(out_split)))
+    return out
+
+
+def ftdnn_bypass_bwd(dy: Tensor, dx: Tensor, scale: float, shift: int) -> Tensor:
+    """dx[:, shift:shift + T'] += scale * dy, IN PLACE on dx [B,T,C] (the factor convolution's data gradient); returns dx."""
+    B, T, Tp, C_ = _bypass_check(dy, dx, shift, "ftdnn_bypass_bwd")
+    call("dlip_ftdnn_bypass_bwd_f32", dy, dx, B, T, Tp, C_, int(shift), float(scale))
+    return dx
+
+
+def semi_orth_workspace(n_mats: int, device) -> Tensor:
+    """The zeroed workspace dlip_semi_orth_step_f32 keeps for ``n_mats`` matrices (ticket words + partial Gram matrices)."""
+    nbytes = int(lib().dlip_semi_orth_workspace_bytes(int(n_mats)))
+    if nbytes <= 0:
+        raise ValueError(f"semi-orthogonal step: 1 .. {SEMI_ORTH_MAX_MATS} matrices, got {n_mats}")
+    return torch.zeros(nbytes, dtype=torch.uint8, device=device)
+
+
+def semi_orth_table(mats: Sequence[Tensor]) -> Tuple[Tensor, int, int]:
+    """(device table, max rows, max cols) of the matrices ``mats``: each a contiguous fp32 CUDA tensor whose first axis is the rows
+    (a factor weight [Bn, Cin, k] is the matrix [Bn, Cin k])."""
+    import numpy as np
+    if not 1 <= len(mats) <= SEMI_ORTH_MAX_MATS:
+        raise ValueError(f"semi-orthogonal step: 1 .. {SEMI_ORTH_MAX_MATS} matrices, got {len(mats)}")
+    dt = np.dtype([("M", "<u8"), ("rows", "<i4"), ("cols", "<i4")])
+    tab = np.zeros(len(mats), dtype=dt)
+    for i, m in enumerate(mats):
+        _req(m, f"matrix {i}")
+        rows, cols = int(m.shape[0]), int(m.numel() // max(int(m.shape[0]), 1))
+        if m.dim() < 2 or not 1 <= rows <= SEMI_ORTH_MAX_ROWS or cols < rows:
+            raise ValueError(f"semi-orthogonal step: matrix {i} is {rows} x {cols}; 1 <= rows <= {SEMI_ORTH_MAX_ROWS} and rows <= cols")
+        tab[i] = (m.data_ptr(), rows, cols)
+    dev = torch.from_numpy(tab.view(np.uint8).copy()).to(mats[0].device)
+    return dev, int(tab["rows"].max()), int(tab["cols"].max())
+
+
+def semi_orth_step(table: Tensor, n_mats: int, max_rows: int, max_cols: int, counter: Tensor, every: int, workspace: Tensor) -> None:
+    """One call of the semi-orthogonal step (launches only): advances ``counter`` (int32 [2] on the device) and, when the step it then
+    counts is a multiple of ``every`` > 0, updates every matrix of ``table`` in place."""
+    _req(counter, "counter", torch.int32)
+    _req(table, "table", torch.uint8); _req(workspace, "workspace", torch.uint8)
+    if counter.numel() != 2 or table.numel() != 16 * n_mats:
+        raise ValueError("semi-orthogonal step: counter is int32 [2], the table holds 16 bytes per matrix")
+    call("dlip_semi_orth_step_f32", table, int(n_mats), int(max_rows), int(max_cols), counter, int(every), workspace, workspace.numel())

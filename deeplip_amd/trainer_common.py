@@ -94,7 +94,7 @@ def build_speech_encoder(model_cfg, feat_dim=None):
     """The speech encoder ``model_cfg["arch"]`` names (train_audio.py:60-68).  The ResNet's statistics poolings size their vector by
     the feature dimension, which the data section knows: ``feat_dim`` is filled into the ``resnet`` sub-dict when that leaves it out."""
     arch = model_cfg["arch"]
-    if arch in ("tdnn", "etdnn"):
+    if arch in ("tdnn", "etdnn", "ftdnn"):                                   # (ftdnn: conf/audio_config.yaml:84-92, DESIGN.md 4k)
         from models.audio_models import tdnn
         return tdnn.SpeakerEmbNet(model_cfg)
     if arch == "resnet":                                                     # train_audio.py:64-66 (`import models.resnet`)

@@ -1398,6 +1398,50 @@ int dlip_spec_augment_f32(const float* x, const int32_t* lengths, const int32_t*
                           int32_t n_time, int32_t time_width, double time_ratio, int32_t fill, dlip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * (ABI 67, added) THE FACTORIZED TDNN, `arch: ftdnn` (conf/audio_config.yaml:84-92 names the architecture; upstream ships no source
+ * for it: this block and DESIGN.md 4k are the definition).  A factorized block is  factor: Conv1d(Cin -> Bn, k taps, dilated, no bias,
+ * no BatchNorm, no activation) -> context_layer: Conv1d(Bn -> Cout, 1 tap, bias) -> BatchNorm / LeakyReLU(0.2) in the order bn_first
+ * says -> (Cin == Cout and s != 0 only) the bypass y[b, :, t] += s x[b, :, t - context[0]], the input frame at context offset 0.  Both
+ * convolutions are the TDNN's (dlip_conv_nhwc_*); what is new is below.
+ *
+ * dlip_semi_orth_step_f32 (conf/audio_config.yaml:84-92): the semi-orthogonal constraint of Povey et al. 2018 (Kaldi's
+ *   ConstrainOrthonormalInternal with a floating scale) on EVERY factor matrix of a model in one launch pair.  `table`: device array of
+ *   n_mats rows { float* M; int32 rows; int32 cols } (16 bytes each): M row-major [rows, cols] = the factor weight [Bn, Cin, k] seen as
+ *   [Bn, Cin k], 1 <= rows <= max_rows <= DLIP_SEMI_ORTH_MAX_ROWS, rows <= cols <= max_cols (a row outside these is skipped by the
+ *   device, never addressed).  `counter`: device int32[2]; counter[0] = optimizer steps so far.  With n = counter[0] + 1 the step is
+ *   DUE iff every > 0 and n % every == 0; the pair always leaves counter[0] = n (counter[1] is its own scratch), so a recorded and
+ *   replayed pair applies the step on the same iterations as an eager loop, without a host read.  When due, per matrix:
+ *     P = M M^T,  tp = tr P,  tpp = |P|_F^2,  alpha2 = tpp / tp,  ratio = tpp rows / tp^2,
+ *     nu = 1/8, halved if ratio > 1.02, halved again if ratio > 1.1,      M <- M - (4 nu / alpha2) (P - alpha2 I) M
+ *   (tp = 0, an all-zero matrix: left alone).  Exact fp32 products (fma chains on the vector ALUs).  P is a split-K reduction over
+ *   DLIP_SEMI_ORTH_SPLITS workgroups per matrix, the last one to arrive adds the partials in split order (ticket words in the
+ *   workspace, self-resetting); the second launch holds P in LDS (64 KB at 128 rows), derives tp and tpp in fp64 in one fixed order --
+ *   the same alpha2 and nu in every workgroup -- and rewrites a DLIP_SEMI_ORTH_PANEL-column panel of M in place.  No atomics on
+ *   data: the result has the same bits on every run.  `workspace`: dlip_semi_orth_workspace_bytes(n_mats) bytes, 16-byte aligned,
+ *   ZEROED ONCE by the caller before its first use and then left to the launches.  DLIP_EINVAL before any launch: a null pointer,
+ *   n_mats outside [1, DLIP_SEMI_ORTH_MAX_MATS], every < 0, max_rows outside [1, DLIP_SEMI_ORTH_MAX_ROWS], max_cols < max_rows, a
+ *   workspace too small or misaligned.  Launches: 2.
+ * dlip_semi_orth_workspace_bytes (host only, no launch): bytes of that workspace; negative on a bad n_mats.
+ * dlip_ftdnn_bypass_f32: out[b, t, :] = y[b, t, :] + scale x[b, t + shift, :] (one fma per element), y fp32 [B, Tp, C], x [B, T, C], out
+ *   [B, Tp, C]; flags bit 0: x is in the split activation format, bit 1: out is written in it (C % 32 == 0 then; the range report of
+ *   dlip_split_pack_f32).  C % 4 == 0, 0 <= shift, shift + Tp <= T, 16-byte aligned pointers; out may be y unless bit 1 is set, never x.
+ *   Each element depends on its own (b, t, c) alone: a row has the same bits alone and in a ragged batch.
+ * dlip_ftdnn_bypass_bwd_f32: dx[b, t + shift, :] += scale dy[b, t, :] IN PLACE on dx [B, T, C] (the factor convolution's data gradient),
+ *   dy [B, Tp, C]: the block input's whole gradient after one pass, no zero-filled temporary.  Same conditions.
+ * ------------------------------------------------------------------------------------------ */
+#define DLIP_SEMI_ORTH_MAX_ROWS 128
+#define DLIP_SEMI_ORTH_MAX_MATS 64
+#define DLIP_SEMI_ORTH_SPLITS 16
+#define DLIP_SEMI_ORTH_PANEL 64
+int64_t dlip_semi_orth_workspace_bytes(int32_t n_mats);
+int dlip_semi_orth_step_f32(const void* table, int32_t n_mats, int32_t max_rows, int32_t max_cols, int32_t* counter, int32_t every,
+                            void* workspace, int64_t workspace_bytes, dlip_stream_t stream);
+int dlip_ftdnn_bypass_f32(const float* y, const float* x, float* out, int32_t B, int32_t T, int32_t Tp, int32_t C, int32_t shift,
+                          float scale, int32_t flags, dlip_stream_t stream);
+int dlip_ftdnn_bypass_bwd_f32(const float* dy, float* dx, int32_t B, int32_t T, int32_t Tp, int32_t C, int32_t shift, float scale,
+                              dlip_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Step plans. The reference drives its encoders from a Python loop, one utterance and one torch.nn layer
  * at a time (train_fusion.py:338-358 extraction, :262-293 training step); here a step is ~45 short kernels
  * and the host must not sit between them.  A plan records every dlip_* launch made on `stream` between

@@ -182,6 +182,15 @@ class Trainer(object):
         # place, and takes the fused SGD kernel.  train.graph_step: false keeps the loop of eager launches.
         self.graph_step = bool(self.train_opts.get("graph_step", True)) and os.environ.get("DLIP_GRAPH_STEP", "1") != "0"
         self.optim = tc.make_optimizer("sgd", groups, o, self.graph_step, self.device)
+        # arch: ftdnn: the semi-orthogonal step on every factor matrix behind optim.step(), each train.semi_orth_every-th
+        # optimizer step (build-owned, default 4; 0: off), counted on the device so that a recorded step follows the same schedule
+        self.semi_orth = None
+        every = self.train_opts.get("semi_orth_every", 4)
+        if isinstance(every, bool) or not isinstance(every, int) or every < 0:
+            raise ValueError(f"train.semi_orth_every is an int >= 0 (0: off), got {every!r}")
+        if getattr(self.model, "factorized_layers", ()) and every > 0 and not self.freeze_encoder:
+            from deeplip_amd.audio import SemiOrthStep
+            self.semi_orth = SemiOrthStep(self.model, every)
         self._steps = None          # ShapeKeyedSteps, built with the first recorded step
         self._extractor = tc.ExtractorCache()   # one RaggedExtractor for every list and epoch of this trainer (its recorded plans are kept)
         self._cohort = None         # (key, EmbeddingTable): the score-normalisation cohort of the current weights (build_cohort)
@@ -250,6 +259,8 @@ class Trainer(object):
         if self.buckets is not None:
             self.buckets.finish()
         self.optim.step()
+        if self.semi_orth is not None:
+            self.semi_orth()                          # (reads and advances its device counter: due or not is decided by the launch)
         return loss, logits
 
     def _adjust_margin(self):
@@ -272,6 +283,8 @@ class Trainer(object):
         if recorded and self._steps is None:
             from deeplip_amd.train_plan import ShapeKeyedSteps, grad_witness, step_state
             mods = [self.criterion] if self.freeze_encoder else [self.model, self.criterion]
+            if self.semi_orth is not None:
+                mods = mods + [self.semi_orth]         # (its step counter is part of what a step mutates: snapshot / restore cover it)
             # (with GradBuckets the branches of a step stay on one stream: see train_video.py)
             self._steps = ShapeKeyedSteps(self._one_step, eager_steps=1, device=self.device, branch_streams=self.buckets is None,
                                           state=step_state(mods, [self.optim], self.buckets), witness=grad_witness(mods, self.buckets))
@@ -408,7 +421,8 @@ class Trainer(object):
         os.makedirs(os.path.dirname(path), exist_ok=True)
         # keys carry the DataParallel 'module.' prefix like the reference's checkpoints (train_audio.py:262)
         torch.save({"epoch": self.current_epoch, "state_dict": {"module." + k: v for k, v in self.model.state_dict().items()},
-                    "criterion": self.criterion.state_dict(), "optimizer": self.optim.state_dict()}, path)
+                    "criterion": self.criterion.state_dict(), "optimizer": self.optim.state_dict(),
+                    **({"semi_orth": self.semi_orth.state_dict()} if self.semi_orth is not None else {})}, path)
         return path
 
     def load(self, resume):
@@ -432,6 +446,8 @@ class Trainer(object):
             if isinstance(crit, torch.nn.Module):
                 crit = crit.state_dict()
             self.criterion.load_state_dict(crit)
+        if self.semi_orth is not None and ck.get("semi_orth") is not None:
+            self.semi_orth.load_state_dict(ck["semi_orth"])      # the optimizer-step count the constraint's schedule runs on
         self.current_epoch = int(ck.get("epoch", self.current_epoch))
 
     def model_average(self, avg_num=4):
@@ -643,6 +659,7 @@ class Trainer(object):
         for p in self.model.parameters():
             p.requires_grad = False
         self.freeze_encoder = True
+        self.semi_orth = None           # (a frozen encoder's factor matrices stay as the checkpoint holds them)
         param_groups = [{"params": self.criterion.parameters()}]
         kind = self.train_opts.get("type", "sgd")
         if kind not in ("sgd", "adam"):
