@@ -562,16 +562,22 @@ def test_stem3d_pool_f16x3(ops, B, T, H, W, neg_slopes):
 def test_conv_split_input_odd_output_width(ops):
     """Split-format input with an output width the LDS-DMA kernel's 16-byte epilogue cannot write
     (K % 4 != 0): the launch must fall back to the register-staged kernel, not write past rows."""
+    import footprint
     from deeplip_amd import packing
     x = rnd(2, 1, 50, 64, seed=61)
     w = rnd(30, 1, 3, 64, seed=62, scale=1.0 / np.sqrt(192))
     b = rnd(30, seed=63, scale=0.1)
     ws, sc = packing.split_weights(w.double())
     xs = ops.split_pack(x.cuda())
-    y = ops.conv_nhwc(xs, ws.cuda(), b.cuda(), pad=(0, 1), w_scale=sc.cuda(), x_split=True)
+    # the 30 channels go into channels [16, 46) of a poisoned 64-channel tensor between two poisoned fences (tests/footprint.py)
+    out = footprint.wide(torch.empty(2, 1, 50, 30, device="cuda"), 16, 18, footprint.POISON, "y", copy=False)
+    ops.conv_nhwc(xs, ws.cuda(), b.cuda(), pad=(0, 1), w_scale=sc.cuda(), x_split=True, out=out.full, out_channel_offset=16)
     torch.cuda.synchronize()
+    y = out.own.contiguous()
     ref = F.conv2d(ops.split_unpack(xs).cpu().permute(0, 3, 1, 2).double(), w.permute(0, 3, 1, 2).double(), b.double(), padding=(0, 1))
     assert rel_err(y.cpu().permute(0, 3, 1, 2).numpy(), ref.numpy()) < TOL
+    assert not footprint.has_poison(y)      # every element of the slice written ...
+    out.check()                             # ... and nothing past a row's 30 channels, before the first row or behind the last
 
 
 def test_conv_workspace_is_caller_owned(ops):
