@@ -316,12 +316,18 @@ class SemiOrthStep(nn.Module):
 class SpeakerEmbNet(nn.Module):
     """tdnn.py:45-111.  ``opts`` = model options with sub-dict ``opts[opts['arch']]``.  ``arch: ftdnn`` (conf/audio_config.yaml:84-92;
     DESIGN.md 4k) takes the ``tdnn`` keys and three of the build's own: ``bottleneck_dim`` (128), ``bypass_scale`` (0.66) and
-    ``factorized_layers`` (default_factorized_layers); the layers it lists are FTDNN_Blocks."""
+    ``factorized_layers`` (default_factorized_layers); the layers it lists are FTDNN_Blocks.  ``arch: sincnet`` is the
+    TDNN plus ``.sinc``, a SincConv of ``input_dim`` filters built from the build-owned ``sinc:`` sub-dict: the encoder then takes
+    WAVEFORMS [B, S] (``lengths``: sample counts) and the layer trains with the stack."""
 
     def __init__(self, opts):
         super().__init__()
         arch = opts["arch"]
         opts = opts[arch]
+        self.sinc = None
+        if arch == "sincnet":
+            from .sincnet import SincConv, parse_sinc_section
+            self.sinc = SincConv(int(opts["input_dim"]), **parse_sinc_section(opts.get("sinc")))
         context = opts["context"]
         input_dim = opts["input_dim"]
         hidden_dim = opts["hidden_dim"]
@@ -407,14 +413,24 @@ class SpeakerEmbNet(nn.Module):
         return ops.nct_to_ntc(x.contiguous().float(), pad_to=packing.pad_channels(self.input_dim, 32 if (split or pad32) else 4),
                               out_split=split)
 
-    def _to_ntc_padded(self, x: Tensor) -> Tensor:
+    def _train_pad(self) -> int:
+        """Channels of the training step's first tensor: F zero-padded to 32 when the first layer can then run on the split-fp16 kernels."""
         from . import autograd_video as av
+        pad32 = av.TRAIN_CONV == "f16x3" and self.input_dim % 32 != 0 and self.tdnn[0].output_dim % 4 == 0
+        return packing.pad_channels(self.input_dim, 32 if pad32 else 4)
+
+    def _to_ntc_padded(self, x: Tensor) -> Tensor:
         if x.dim() == 4:
             x = x.squeeze(1)
         if x.dim() != 3 or x.shape[1] != self.input_dim:
             raise ValueError(f"SpeakerEmbNet expects [B,{self.input_dim},T] features, got {tuple(x.shape)}")
-        pad32 = av.TRAIN_CONV == "f16x3" and self.input_dim % 32 != 0 and self.tdnn[0].output_dim % 4 == 0
-        return ops.nct_to_ntc(x.contiguous().float(), pad_to=packing.pad_channels(self.input_dim, 32 if pad32 else 4))
+        return ops.nct_to_ntc(x.contiguous().float(), pad_to=self._train_pad())
+
+    def _require_waves(self, x: Tensor) -> Tensor:
+        if x.dim() != 2:
+            raise ValueError(f"SpeakerEmbNet(arch: sincnet): the encoder takes waveforms [B, S] (its first layer is the sinc filter bank), "
+                             f"got a tensor of shape {tuple(x.shape)}")
+        return x.contiguous().float()
 
     def _extract_embedding_train(self, x: Tensor) -> Tuple[Tensor, Tensor]:
         """extract_embedding under model.train() (train_audio.py:167-183): batch-statistics BatchNorm, every
@@ -428,7 +444,11 @@ class SpeakerEmbNet(nn.Module):
             raise ValueError("train-mode encoder: input_dim must be a multiple of 4")
         # [B,T,F] channels-last; F zero-padded to a multiple of 32 when the first layer can then run on the split-fp16 kernels
         # (24 features: the exact-fp32 kernel took 0.55 ms per launch on it, 1.1 of a 15 ms step at B = 256)
-        h = self._to_ntc_padded(x)
+        if self.sinc is not None:
+            # the sinc layer writes that tensor itself, channels-last and padded: no transpose between the layer and the first block
+            h, _ = self.sinc.features(self._require_waves(x), None, channels_last_pad=self._train_pad())
+        else:
+            h = self._to_ntc_padded(x)
         from . import autograd_video as av
         av.prepare_weights(self)                           # the step's split weight images (forward and data-gradient banks): one launch
         pend = None                                        # (a block's activated output is not stored when the next block takes it on load)
@@ -477,8 +497,20 @@ class SpeakerEmbNet(nn.Module):
                 raise NotImplementedError("train mode crops every utterance of a batch to one length (datasets.py:112-115)")
             return self._extract_embedding_train(x)
         _lib.check_range()      # an overflow reported by an earlier f16x3 launch surfaces here (host read, no sync)
-        p = _cached_pack(self, x.device, self._pack)
         shrink = self.frames_consumed()
+        if self.sinc is not None:
+            # arch: sincnet -- x is the waveform batch and ``lengths`` counts samples; the layer (exact fp32 in every arithmetic mode)
+            # hands over [B,F,NF] and the rows' frame counts on the device
+            x = self._require_waves(x)
+            if lengths is not None and not (isinstance(lengths, Tensor) and lengths.is_cuda):
+                short = [int(l) for l in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)
+                         if 1 <= int(l) and self.sinc.frames_for_samples(int(l)) < shrink + 2]
+                if short:
+                    raise ValueError(f"lengths: {min(short)} samples make fewer than the {shrink + 2} frames the encoder needs")
+            with torch.no_grad():
+                x, nf = self.sinc.features(x, lengths)
+            lengths = None if lengths is None else nf
+        p = _cached_pack(self, x.device, self._pack)
         lens = ops.lengths_i32(lengths, x.device, n=x.shape[0], lo=shrink + 2, hi=x.shape[-1])   # >= 2 pooled frames (unbiased std)
         len_add = -shrink
         # f16x3 packing: frame-level activations travel between layers as (hi, lo) fp16 pairs, written

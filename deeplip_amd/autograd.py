@@ -489,6 +489,17 @@ class BNRowsActFn(Function):
         return out, dg, db, None, None, None, None, None, None, None
 
 
+def _pad_input_grad(dx, Cx):
+    """The data gradient [B,T,Cw] of a block whose input carries zero channels up to Cx (24 trained features in a 32-channel tensor:
+    the weight has Cw input channels, so has the gradient its transposed bank yields): the gradient of the padded tensor, whose padding
+    channels are constants of the producer -- zeros.  Cw == Cx: dx itself."""
+    if dx.shape[2] == Cx:
+        return dx
+    out = torch.zeros((dx.shape[0], dx.shape[1], Cx), device=dx.device, dtype=dx.dtype)
+    out[:, :, :dx.shape[2]].copy_(dx)
+    return out
+
+
 class TDNNBlockTrainFn(Function):
     """TDNN_Block under autograd (tdnn.py:35-43): Conv1d(k, dilation, no padding, bias) -> BatchNorm1d (batch
     statistics) -> LeakyReLU (or Conv -> LeakyReLU -> BN when bn_first=False), x [B,T,C] -> [B,T',K].
@@ -614,8 +625,8 @@ class TDNNBlockTrainFn(Function):
             if want_x:
                 shape_only = torch.empty((B, 1, Tp, K), device=dev, dtype=torch.float32)      # (address and shape: conv_train reads dzs)
                 dx = av.conv_train(shape_only, None, None, (1, 1), (0, (S - 1) * dilation), (1, dilation), lift=True, scale2=lift,
-                                   w_ref=weight.view(K, Cx, 1, S), transposed=True, xs_ready=dzs)
-                dx = dx.view(B, dx.shape[2], Cx)
+                                   w_ref=weight.view(K, weight.shape[1], 1, S), transposed=True, xs_ready=dzs)
+                dx = _pad_input_grad(dx.view(B, dx.shape[2], dx.shape[3]), Cx)
             if mode == 1:
                 dweight = _permute3(av.wgrad_gemm_operands(x, gT, lift).view(1, Cx, K), (2, 1, 0)).view(K, Cx, 1)
             else:
@@ -667,8 +678,8 @@ class TDNNBlockTrainFn(Function):
         if ctx.needs_input_grad[0]:
             dzc = dz.contiguous()
             dx = av.conv_train(dzc.view(B, 1, Tp, K), None, None, (1, 1), (0, (S - 1) * dilation), (1, dilation), lift=True, scale2=lift,
-                               w_ref=weight.view(K, Cx, 1, S), transposed=True, xs_ready=dzs)   # [K,C,S] -> rows c of [S reversed][K]
-            dx = dx.view(B, dx.shape[2], Cx)
+                               w_ref=weight.view(K, weight.shape[1], 1, S), transposed=True, xs_ready=dzs)   # [K,C,S] -> rows c of [S reversed][K]
+            dx = _pad_input_grad(dx.view(B, dx.shape[2], dx.shape[3]), Cx)
         dweight = None
         if ctx.needs_input_grad[1]:
             if mode == 1:

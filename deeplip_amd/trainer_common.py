@@ -90,11 +90,24 @@ def finish(trainer):
         torch.distributed.destroy_process_group()
 
 
-def build_speech_encoder(model_cfg, feat_dim=None):
+def build_speech_encoder(model_cfg, feat_dim=None, wave_cfg=None):
     """The speech encoder ``model_cfg["arch"]`` names (train_audio.py:60-68).  The ResNet's statistics poolings size their vector by
-    the feature dimension, which the data section knows: ``feat_dim`` is filled into the ``resnet`` sub-dict when that leaves it out."""
+    the feature dimension, which the data section knows: ``feat_dim`` is filled into the ``resnet`` sub-dict when that leaves it out.
+    ``arch: sincnet`` frames the waveform itself: ``rate`` / ``win_len`` / ``win_shift`` of ``wave_cfg`` (the section that
+    describes the waveforms: ``data`` of train_audio.py, ``data.python_data_config`` of train_fusion.py) are filled into its ``sinc``
+    sub-dict where that leaves them out (16000, 0.025, 0.01 when neither names them)."""
     arch = model_cfg["arch"]
-    if arch in ("tdnn", "etdnn", "ftdnn"):                                   # (ftdnn: conf/audio_config.yaml:84-92, DESIGN.md 4k)
+    if arch == "sincnet":
+        from .sincnet import GEOMETRY_KEYS, parse_sinc_section
+        sinc = model_cfg[arch].get("sinc")
+        sinc = dict(sinc) if isinstance(sinc, dict) else ({} if sinc is None else sinc)
+        if isinstance(sinc, dict):
+            for k in GEOMETRY_KEYS:
+                if k in (wave_cfg or {}):
+                    sinc.setdefault(k, wave_cfg[k])
+        parse_sinc_section(sinc)                                             # (a bad section is a ValueError before any model is built)
+        model_cfg[arch]["sinc"] = sinc
+    if arch in ("tdnn", "etdnn", "ftdnn", "sincnet"):                        # (ftdnn: conf/audio_config.yaml:84-92, DESIGN.md 4k; sincnet: 4l)
         from models.audio_models import tdnn
         return tdnn.SpeakerEmbNet(model_cfg)
     if arch == "resnet":                                                     # train_audio.py:64-66 (`import models.resnet`)
@@ -164,6 +177,8 @@ class SpeechChain:
         """What RaggedExtractor's ``wave_geometry`` takes: None for a feature-fed chain; the front-end itself for ``stft`` (its own
         frame count decides), else (frame_len, frame_step); behind a resampler every sample count is at the source rate."""
         fe = self.frontend
+        if fe is None:                    # (arch: sincnet frames the waveform itself: its layer stands where the front-end stands)
+            fe = getattr(self.encoder, "sinc", None)
         if fe is None:
             return None
         if self.resample is not None:

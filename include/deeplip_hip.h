@@ -1442,6 +1442,57 @@ int dlip_ftdnn_bypass_bwd_f32(const float* dy, float* dx, int32_t B, int32_t T, 
                               dlip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * (ABI 67, added) THE SINC FILTER BANK, `arch: sincnet` (conf/audio_config.yaml names the architecture; upstream ships no source for it:
+ * this block and DESIGN.md 4l are the definition): the SincNet layer (Ravanelli & Bengio 2018) in front of the TDNN stack -- F learnable
+ * band-pass filters of L taps (odd, 3 .. DLIP_SINC_MAX_TAPS) on the raw waveform, squared, averaged per frame, logged.
+ *
+ * dlip_sinc_taps_f32: low_hz, band_hz [F] -> g [F, L].  With m = l - (L - 1) / 2:
+ *     f1 = min_low_hz + |low_hz[f]|,   f2 = clamp(f1 + min_band_hz + |band_hz[f]|, min_low_hz, rate / 2)
+ *     g[f, l] = w[l] (sin(2 pi f2 m / rate) - sin(2 pi f1 m / rate)) / ((pi m / rate) 2 (f2 - f1))  (m != 0),   g[f, (L - 1) / 2] = 1
+ *     w[l] = 0.54 - 0.46 cos(2 pi l / (L - 1))
+ *   formed in fp64 and rounded once; g is EVEN in m by construction (the half m >= 0 is computed and mirrored).  One workgroup.
+ * dlip_sinc_taps_bwd_f32: dg [F, L] -> dlow, dband [F] by the chain rule through that formula (|.| has derivative sign(.), 0 at 0; a
+ *   clamped f2 has derivative 0, as torch.clamp), summed over l in fp64 in one fixed order.  One workgroup.
+ * dlip_sinc_features_f32: wave [B, S] (+ lengths int32 [B] or NULL: S; clamped to [1, S] on the device) and g -> y and frame_lengths
+ *   int32 [B] (may be NULL).  x~ = the row on [0, len), zero outside -- never the neighbour row's bytes or the padding's:
+ *     z[b, f, p] = sum_l g[f, l] x~[b, p + l - (L - 1) / 2]
+ *     e[b, t, f] = (1 / frame_len) sum_{j < frame_len, t frame_step + j < len} z[b, f, t frame_step + j]^2,     y = log(e + eps)
+ *   Frames per row: sigproc.framesig's count (1 for len <= frame_len, else 1 + ceil((len - frame_len) / frame_step)); NF is that count
+ *   for S; frames at or past a row's count are zeros.  layout 0: y [B, F, NF] (Fp = F), the AudioFrontend contract; layout 1: y [B, NF, Fp]
+ *   channels-last, F <= Fp <= F + 31, channels >= F written zero.  A workgroup owns (row, a tile of frames, 8 or 24 filters); the tile's
+ *   samples + L - 1 halo sit in LDS (frame_len + L - 1 <= DLIP_SINC_LDS_SAMPLES); the pair sums x~[p - m] + x~[p + m] are formed once per
+ *   position and shared by the filters ((L + 1) / 2 fma per filter and position: exact fp32 chains on the vector ALUs, m ascending);
+ *   squares are added per frame on chip in fp64, positions ascending.  z is never stored.  Every row has the bits of the row run alone.
+ * dlip_sinc_features_bwd_f32: y and dy (in `layout`) -> dg [F, L], the gradient on the even taps:
+ *     dz[b, f, p] = z[b, f, p] (2 / frame_len) sum_{frames t of the row that hold p} dy[b, t, f] / (e[b, t, f] + eps)
+ *     D[f, m] = sum_{b, p} dz[b, f, p] (x~[p - m] + x~[p + m])  (m > 0),  D[f, 0] = sum dz x~[p]
+ *     dg[f, (L - 1) / 2 +- m] = D[f, m] / 2,   dg[f, (L - 1) / 2] = D[f, 0]
+ *   (the two halves of an unconstrained tap gradient averaged: g[f, H - m] and g[f, H + m] are one quantity, and dlip_sinc_taps_bwd_f32
+ *   yields the same parameter gradients from either).  z is recomputed, 1 / (e + eps) = exp(-y); rows of dy at or past a row's frame count
+ *   are not read.  The waveform gets no gradient.  Workgroups walk (row, tile) items in a fixed stride and keep D in registers; one
+ *   partial per workgroup goes to `workspace` (dlip_sinc_features_bwd_workspace_bytes, 16-byte aligned, needs no initialisation) and a
+ *   second launch adds the partials in workgroup order in fp64: no atomics, two runs have the same bits.  Launches: 2.
+ * DLIP_EINVAL before any launch: a null pointer (lengths and frame_lengths excepted), B outside [1, 65535], S < 1, F outside
+ *   [1, DLIP_SINC_MAX_FILTERS], an even L or one outside [3, DLIP_SINC_MAX_TAPS], frame_len or frame_step < 1, frame_len + L - 1 >
+ *   DLIP_SINC_LDS_SAMPLES, NF other than the frame count of S, a layout / Fp pair other than the two above, eps <= 0, rate <= 0, a
+ *   negative min_low_hz / min_band_hz, min_low_hz > rate / 2, a workspace too small or misaligned.
+ * ------------------------------------------------------------------------------------------ */
+#define DLIP_SINC_MAX_TAPS 1023
+#define DLIP_SINC_MAX_FILTERS 512
+#define DLIP_SINC_LDS_SAMPLES 4096
+int dlip_sinc_taps_f32(const float* low_hz, const float* band_hz, float* g, int32_t F, int32_t L, double rate, double min_low_hz,
+                       double min_band_hz, dlip_stream_t stream);
+int dlip_sinc_taps_bwd_f32(const float* low_hz, const float* band_hz, const float* dg, float* dlow, float* dband, int32_t F, int32_t L,
+                           double rate, double min_low_hz, double min_band_hz, dlip_stream_t stream);
+int dlip_sinc_features_f32(const float* wave, const int32_t* lengths, const float* g, float* y, int32_t* frame_lengths, int32_t B, int32_t S,
+                           int32_t F, int32_t L, int32_t frame_len, int32_t frame_step, int32_t NF, int32_t layout, int32_t Fp, float eps,
+                           dlip_stream_t stream);
+int64_t dlip_sinc_features_bwd_workspace_bytes(int32_t B, int32_t S, int32_t F, int32_t L, int32_t frame_len, int32_t frame_step);
+int dlip_sinc_features_bwd_f32(const float* wave, const int32_t* lengths, const float* g, const float* y, const float* dy, float* dg,
+                               void* workspace, int64_t workspace_bytes, int32_t B, int32_t S, int32_t F, int32_t L, int32_t frame_len,
+                               int32_t frame_step, int32_t NF, int32_t layout, int32_t Fp, dlip_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Step plans. The reference drives its encoders from a Python loop, one utterance and one torch.nn layer
  * at a time (train_fusion.py:338-358 extraction, :262-293 training step); here a step is ~45 short kernels
  * and the host must not sit between them.  A plan records every dlip_* launch made on `stream` between

@@ -89,7 +89,22 @@ def build_criterion(train_opts, embedding_dim, n_spk):
 
 def build_model(model_opts, data_opts):
     """The encoder the ``model`` section names, the ResNet's ``feat_dim`` filled in from the ``data`` section when it is left out."""
-    return tc.build_speech_encoder(model_opts, int(data_opts.get("feat_dim", 40)))
+    return tc.build_speech_encoder(model_opts, int(data_opts.get("feat_dim", 40)), wave_cfg=data_opts.get("python_data_config") or data_opts)
+
+
+def check_sincnet(model_opts, data_opts):
+    """``arch: sincnet`` (host only): the encoder's first layer reads waveforms and trains, so the step is fed the waveform
+    itself -- ``data.train_from_waves: true`` is required -- and ``data.spec_augment`` has no features in front of the step to act on.
+    The ``sinc`` sub-dict is checked here too (deeplip_amd.sincnet.parse_sinc_section).  Other architectures pass."""
+    if model_opts.get("arch") != "sincnet":
+        return
+    from deeplip_amd.sincnet import parse_sinc_section
+    parse_sinc_section(model_opts["sincnet"].get("sinc"))
+    if not bool(data_opts.get("train_from_waves", False)):
+        raise ValueError("model.arch: sincnet takes waveforms: set data.train_from_waves: true")
+    if data_opts.get("spec_augment") not in (None, False):
+        raise ValueError("data.spec_augment acts on the feature batch in front of the step; with model.arch: sincnet the features are "
+                         "formed inside the step (waveform augmentation, data.augment / data.speed_perturb, still applies)")
 
 
 def parse_wave_training(data_opts):
@@ -136,6 +151,7 @@ class Trainer(object):
         # data.spec_augment (build-owned, absent = off): time warp, frequency and time masks on the feature batch in front of the step,
         # on the feature-fed path and from waves alike; evaluation and extraction never see it
         self.spec_opts = parse_spec_augment(self.data_opts)
+        check_sincnet(self.model_opts, self.data_opts)
         # data.voiced_frames (build-owned, absent = off): sliding-window CMN + energy-VAD frame selection in front of the encoder on the
         # feature-fed ragged test lists -- the `nn_input` / `plda_input` pipe (conf/audio_config.yaml:21,25; deeplip_amd/voiced_frames.py).
         from deeplip_amd.voiced_frames import parse_voiced_frames_section
@@ -162,8 +178,12 @@ class Trainer(object):
         self.lomgridtestset = SyntheticAVSet(d["test_speakers"], d["test_utt_per_spk"], 0, 1, F_, d["audio_frames"], key="alomgrid", **rag)
         self.gridtestset = SyntheticAVSet(d["test_speakers"], d["test_utt_per_spk"], 0, 1, F_, d["audio_frames"], key="agrid", **rag)
         self.resume = self.train_opts.get("resume", "exp/none/net_avg.pth")
-        sd = wg.fill_state_dict({k: tuple(v.shape) for k, v in self.model.state_dict().items()}, prefix="audio.")
-        self.model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+        # (the sinc layer keeps its own initial values, mel-spaced band edges: generated ones would not be a filter bank)
+        sd = wg.fill_state_dict({k: tuple(v.shape) for k, v in self.model.state_dict().items() if not k.startswith("sinc.")}, prefix="audio.")
+        self.model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=arch != "sincnet")
+        if arch == "sincnet" and self.voiced_frames_opts is not None:
+            raise ValueError("data.voiced_frames selects frames of a feature batch in front of the encoder; model.arch: sincnet forms its "
+                             "features inside the encoder")
         self.model.eval().to(self.device)
         E = self.model_opts[arch]["embedding_dim"]
         self.criterion = build_criterion(self.train_opts, E, d["n_spk"]).to(self.device)
@@ -216,7 +236,10 @@ class Trainer(object):
         from deeplip_amd.augment import WaveAugment
         from deeplip_amd.synthetic import noise_bank, room_responses
         d = self.data_opts
-        fe = tc.frontend_from_section(d, arch, feat_dim, self.device, where="data.train_from_waves")
+        if arch == "sincnet":           # the encoder's own first layer frames the waveform: its geometry cuts the crops, the step gets the samples
+            fe = self.model.sinc
+        else:
+            fe = tc.frontend_from_section(d, arch, feat_dim, self.device, where="data.train_from_waves")
         if self.augment_opts is None:
             return fe, None
         import warnings
@@ -349,6 +372,8 @@ class Trainer(object):
                     wave, _ = self._speed(wave, params={"speed_idx": speed_idx}, out_samples=speed_out[wave.shape[1]])
                 if self._augment is not None:
                     wave = self._augment(wave, params=dict(zip(("snr_db", "noise_start", "rir_idx"), extra)))
+                if getattr(self.model, "sinc", None) is not None:      # arch: sincnet -- the layer runs inside the step, on the waveform itself
+                    return wave
                 return self._wave_fe(wave)
 
         anneal = getattr(self.criterion, "anneal", None)
@@ -473,6 +498,10 @@ class Trainer(object):
         self.model.eval()
         if self.voiced_frames_opts is not None and not dataset.ragged:
             raise ValueError("data.voiced_frames needs data.test_ragged: true (the stage hands the encoder one length per utterance)")
+        sinc = getattr(self.model, "sinc", None)
+        if sinc is not None and not dataset.ragged:
+            raise ValueError("model.arch: sincnet extracts from the lists' waveforms: set data.test_ragged: true (the rectangular lists "
+                             "are fed features)")
         with torch.no_grad():
             if dataset.ragged:
                 # utterances at their own lengths (train_audio.py:343-373 feeds them one by one): length-bucketed batches,
@@ -480,7 +509,7 @@ class Trainer(object):
                 # records (a dozen padded shapes x two input sets) serve every list and every epoch's evaluation.
                 D = self.model.embedding_dim
                 ex = self._ragged_extractor(batch)
-                both, _ = ex.run(dataset, 0, len(dataset), 2 * D)
+                both, _ = ex.run(dataset, 0, len(dataset), 2 * D, waves=sinc is not None)
                 self.extract_stats = dict(ex.stats)
                 xv, x_a = both[:, :D].contiguous(), both[:, D:].contiguous()
                 rows.append(x_a if ce else ops.l2_normalize(xv) if normalize else xv)
@@ -501,8 +530,10 @@ class Trainer(object):
 
         def build():
             chain = tc.SpeechChain(self.model, voiced=self._voiced_frames_stage())
+            # (arch: sincnet: run(waves=True) feeds waveforms and sample counts, planned on the layer's frame geometry)
+            geom = {} if chain.wave_geometry is None else {"wave_geometry": chain.wave_geometry}
             return RaggedExtractor(lambda a, l: torch.cat(chain(a, l), dim=1), None, self.device, batch=batch,
-                                   audio_min_frames=self._min_frames())
+                                   audio_min_frames=self._min_frames(), **geom)
         return self._extractor.get((int(batch), holders.PACK_GEN[0], packing.state_version(self.model, self.device)), build)
 
     def _voiced_frames_stage(self):

@@ -129,7 +129,10 @@ class Trainer(object):
         if self.dry:
             return self._init_dry(acfg, n_spk)
 
-        self.model_audio = tc.build_speech_encoder(acfg, feat_dim)
+        if acfg["arch"] == "sincnet" and not self.test_from_waves:
+            raise ValueError("model.audio_config.arch: sincnet takes waveforms: set data.python_data_config.test_from_waves: true "
+                             "(--from-waves)")
+        self.model_audio = tc.build_speech_encoder(acfg, feat_dim, wave_cfg=self.feat_opts)
         vcfg = self.model_opts["video_config"]
         if vcfg["arch"] == "tcn":
             t = vcfg["tcn"]
@@ -437,8 +440,10 @@ class Trainer(object):
             ck = torch.load(self.resume_audio, map_location="cpu")
             self.model_audio.load_state_dict({k.replace("module.", ""): v for k, v in ck["state_dict"].items()})
         else:
-            sd = wg.fill_state_dict({k: tuple(v.shape) for k, v in self.model_audio.state_dict().items()}, prefix="audio.")
-            self.model_audio.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+            # (a sinc layer keeps its own initial values, mel-spaced band edges: generated ones would not be a filter bank)
+            own = self.model_audio.state_dict()
+            sd = wg.fill_state_dict({k: tuple(v.shape) for k, v in own.items() if not k.startswith("sinc.")}, prefix="audio.")
+            self.model_audio.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=len(sd) == len(own))
         if os.path.exists(self.resume_video):
             self.model_video.load_state_dict(torch.load(self.resume_video, map_location="cpu"))
         else:
@@ -462,10 +467,17 @@ class Trainer(object):
             min_frames = tc.encoder_min_frames(self.model_audio)
             chain = tc.SpeechChain(self.model_audio)
             if self.test_from_waves:     # front-end and encoder in one recorded step
-                chain.frontend, chain.voiced = self._test_frontend(arch), self._voiced_frames_stage(min_frames)
+                if arch == "sincnet":    # (the encoder's first layer is the front-end: DESIGN.md 4l)
+                    if self.voiced_frames_opts is not None:
+                        raise ValueError("data.python_data_config.voiced_frames selects frames of a feature batch in front of the encoder; "
+                                         "arch: sincnet forms its features inside the encoder")
+                    rate = self.model_audio.sinc.rate
+                else:
+                    chain.frontend, chain.voiced = self._test_frontend(arch), self._voiced_frames_stage(min_frames)
+                    rate = chain.frontend.rate
                 if self.source_rate is not None:
                     from deeplip_amd.resample import Resample
-                    chain.resample = Resample(self.source_rate, chain.frontend.rate, device=self.device)
+                    chain.resample = Resample(self.source_rate, rate, device=self.device)
             geom = {"wave_geometry": chain.wave_geometry} if self.test_from_waves else {}
             return RaggedExtractor(lambda a, l: chain(a, l)[0],                                            # train_fusion.py:338
                                    lambda v, l: self.model_video.embed(v, lengths=l),                      # :346-348 (mean over T)
