@@ -80,61 +80,57 @@ struct ConvArgs {
 };
 
 
-// Validates a dlip_conv_desc and fills the kernel argument block.  `Cw` = channels per filter tap in
-// the packed weight tensor (== d->C for the fp32 layout).
-inline int dlip_fill_conv_args(const dlip_conv_desc* d, const float* x, const float* w, const float* bias,
-                               const float* residual, const float* slope, const float* post_scale,
-                               const float* post_shift, float* y, int Cw, ConvArgs* out, int max_taps = 32) {
-  DLIP_CHECK_ARG(d && x && w && y);
-  DLIP_CHECK_ARG(d->N > 0 && d->H > 0 && d->W > 0 && d->C > 0 && d->K > 0 && d->R > 0 && d->S > 0);
+// The geometry half of a kernel argument block: validates the numbers of a dlip_conv_desc and fills every derived field -- what the route of a
+// launch is picked from (a reporter stops here).  `Cw` = channels per filter tap in the packed weight tensor (== d->C for the fp32 layout).
+inline int dlip_conv_geometry(const dlip_conv_desc* d, int Cw, ConvArgs* out, int max_taps = 32) {
+  DLIP_CHECK_ARG(d && d->N > 0 && d->H > 0 && d->W > 0 && d->C > 0 && d->K > 0 && d->R > 0 && d->S > 0);
   DLIP_CHECK_ARG(d->stride_h > 0 && d->stride_w > 0 && d->dil_h > 0 && d->dil_w > 0 && d->pad_h >= 0 && d->pad_w >= 0);
   DLIP_CHECK_ARG((d->C & 3) == 0 && (d->ldx & 3) == 0 && d->ldx >= d->C && d->ldy >= d->K && Cw >= d->C);
-  DLIP_CHECK_ARG((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(w) & 15) == 0);
-  DLIP_CHECK_ARG((post_scale == nullptr) == (post_shift == nullptr));
-  DLIP_CHECK_ARG(residual == nullptr || d->ldr >= d->K);
   const int Ho = (d->H + 2 * d->pad_h - d->dil_h * (d->R - 1) - 1) / d->stride_h + 1;
   const int Wo = (d->W + 2 * d->pad_w - d->dil_w * (d->S - 1) - 1) / d->stride_w + 1;
   DLIP_CHECK_ARG(Ho == d->Ho && Wo == d->Wo && Ho > 0 && Wo > 0);
-  DLIP_CHECK_ARG(d->R * d->S <= max_taps);  // per-row tap-validity mask is 32 bits (the LDS-DMA kernel has a mask-free variant)
-
-  const long long in_pix = (long long)d->N * d->H * d->W;
-  const long long x_bytes = ((in_pix - 1) * d->ldx + d->C) * 4;
-  const long long w_bytes = (long long)d->K * d->R * d->S * Cw * 4;
+  DLIP_CHECK_ARG((long long)d->R * d->S <= max_taps);  // per-row tap-validity mask is 32 bits (the LDS-DMA kernel has a mask-free variant)
   const long long M = (long long)d->N * Ho * Wo;
-  const long long y_bytes = ((M - 1) * d->ldy + d->K) * 4;
-  const long long r_bytes = residual ? ((M - 1) * d->ldr + d->K) * 4 : 0;
-  if (x_bytes > DLIP_MAX_BUFFER_BYTES || w_bytes > DLIP_MAX_BUFFER_BYTES || y_bytes > DLIP_MAX_BUFFER_BYTES ||
-      r_bytes > DLIP_MAX_BUFFER_BYTES || M > 0x7FFFFFFFll)
-    return DLIP_ERANGE;
+  if (M > 0x7FFFFFFFll || (long long)d->R * d->S * Cw * 4 > DLIP_MAX_BUFFER_BYTES) return DLIP_ERANGE;   // (rsc below fits an int)
 
   ConvArgs& a = *out;
-  a.x = x; a.w = w; a.bias = bias; a.res = residual; a.slope = slope;
-  a.pscale = post_scale; a.pshift = post_shift; a.y = y;
+  a = ConvArgs{};
   a.H = d->H; a.W = d->W; a.C = d->C; a.K = d->K; a.R = d->R; a.S = d->S;
   a.sh = d->stride_h; a.sw = d->stride_w; a.ph = d->pad_h; a.pw = d->pad_w; a.dh = d->dil_h; a.dw = d->dil_w;
   a.Wo = Wo; a.HoWo = Ho * Wo;
   a.ldx = d->ldx; a.ldy = d->ldy; a.ldr = d->ldr;
   a.M = (int)M;
-  a.tiles_n = 0;
   a.cchunks = (d->C + BK - 1) / BK;
   a.nk = d->R * d->S * a.cchunks;
   a.rsc = d->R * d->S * Cw;
-  a.x_bytes = (uint32_t)x_bytes; a.w_bytes = (uint32_t)w_bytes;
-  a.r_bytes = (uint32_t)r_bytes; a.y_bytes = (uint32_t)y_bytes;
-  a.wscale = nullptr;
   a.Cw = Cw;
-  a.x2 = nullptr; a.x2_bytes = 0; a.H2 = a.W2 = a.ldx2 = a.s2h = a.s2w = a.nk2 = 0;
-  a.pool = nullptr; a.pool_group = 0; a.pool_len = DlipLen{};
-  a.status = DlipRange{};
   a.div_howo = dlip_fastdiv((uint32_t)a.HoWo);
   a.div_wo = dlip_fastdiv((uint32_t)a.Wo);
-  a.n_inner = 0;
   a.Hs = d->H; a.cs_x = 128; a.wt = Cw * 4; a.cs_w = 128;
-  a.span = nullptr;
-  a.wg_R = a.wg_S = 0;
-  a.stats = nullptr;
   return DLIP_OK;
 }
+
+// The buffer half: pointers, byte extents and alignment of a launch whose geometry `a` already holds.
+inline int dlip_conv_buffers(const dlip_conv_desc* d, const float* x, const float* w, const float* bias, const float* residual,
+                             const float* slope, const float* post_scale, const float* post_shift, float* y, ConvArgs* out) {
+  ConvArgs& a = *out;
+  DLIP_CHECK_ARG(x && w && y && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(w) & 15) == 0);
+  DLIP_CHECK_ARG((post_scale == nullptr) == (post_shift == nullptr) && (residual == nullptr || d->ldr >= d->K));
+  const long long x_bytes = (((long long)d->N * d->H * d->W - 1) * d->ldx + d->C) * 4;
+  const long long w_bytes = (long long)d->K * a.rsc * 4;
+  const long long y_bytes = ((long long)(a.M - 1) * d->ldy + d->K) * 4;
+  const long long r_bytes = residual ? ((long long)(a.M - 1) * d->ldr + d->K) * 4 : 0;
+  if (x_bytes > DLIP_MAX_BUFFER_BYTES || w_bytes > DLIP_MAX_BUFFER_BYTES || y_bytes > DLIP_MAX_BUFFER_BYTES || r_bytes > DLIP_MAX_BUFFER_BYTES)
+    return DLIP_ERANGE;
+  a.x = x; a.w = w; a.bias = bias; a.res = residual; a.slope = slope;
+  a.pscale = post_scale; a.pshift = post_shift; a.y = y;
+  a.x_bytes = (uint32_t)x_bytes; a.w_bytes = (uint32_t)w_bytes;
+  a.r_bytes = (uint32_t)r_bytes; a.y_bytes = (uint32_t)y_bytes;
+  return DLIP_OK;
+}
+
+// Diagnostic switch (dlip_debug_set DLIP_DBG_DMA_ENABLE = 0): keeps split-format launches on the register-staged kernel.
+inline bool dlip_conv_dma_enabled() { return dlip_dbg_value[DLIP_DBG_DMA_ENABLE] != 0; }
 
 // Tile menu / picker shared by both kernels (see conv_igemm.hip for the rationale).
 struct TileCfg { int bm, bn; };

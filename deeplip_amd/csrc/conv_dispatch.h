@@ -9,19 +9,32 @@
 
 #define DLIP_INTERNAL extern "C" __attribute__((visibility("hidden")))
 
-// conv_igemm_f16x3.hip: diagnostic switch (dlip_debug_set DLIP_DBG_DMA_ENABLE = 0 keeps split-format launches off the LDS-DMA kernels)
-DLIP_INTERNAL int dlip_conv_dma_enabled(void);
-// conv_igemm_f16x3_dma.hip: the ring kernel's tile for a launch, its launch (epi: 0 fp32 y, 1 split y, 2 pooled partials), and the
-// per-stream workspace of the balanced split (slabs + ticket words); 0 = none / too small
-DLIP_INTERNAL void dlip_conv_dma_tile(long long M, int K, int nk, int epi, int* bm, int* bn);
-DLIP_INTERNAL int dlip_conv_f16x3_dma_launch(const void* args, void* stream, int epi);
+enum { CONV_EPI_Y = 0, CONV_EPI_POOL = 1, CONV_EPI_STATS = 2 };   // y | pooled partial sums, no y | y and its column sums
+struct ConvAsk {                    // what a launch asks for beyond the geometry in ConvArgs
+  int f16x3, split_in, split_out;   // 0: the fp32 kernel; x and the residual / y in the split activation format
+  int epi, residual, nk2;           // CONV_EPI_*; a residual is added (a reporter: d->ldr != 0); slices of the second source
+  int many_tap, aligned;            // more than 32 taps or slice-major operand images; y and the residual 16-byte aligned
+};
+
+enum { CONV_RING = 0, CONV_WIN = 1, CONV_ROWS = 2, CONV_STAGED = 3, CONV_F32 = 4 };
+struct ConvRoute {     // the answer, which the launches execute and the reporters return: the kernel and the instance that runs
+  int kind, bm, bn;    // CONV_*, workgroup tile
+  int inst;            // ring: index of its tile menu; window: of its geometries (wave layout, workgroups per CU); register-staged, fp32: of kCfg; rows: bm / 32
+  int many_tap, epi;   // ring: the tap-mask-free variant; the instance's epilogue: 0 fp32 y, 1 split y, 2 pooled partials
+  int tail_full, tail_nmi;   // rows: row tiles of full height in front of a SHORT last round, its height / 32 (== inst: none, no TAIL instance)
+  long long tiles_m;   // rows: row tiles, the short last round's included
+  int pool_rows, pool_bn;   // pooled launches: rows of one partial band, column rounding of a band
+};
+
+// conv_igemm_f16x3.hip: the launch of `picked`, or of the route it picks itself (THE route: dlip_conv_route_pick there)
+DLIP_INTERNAL int dlip_conv_dispatch(const void* args, const ConvAsk* ask, void* stream, const ConvRoute* picked);
+// One pair per kernel file: 1 and the instance if the kernel serves the launch, else 0; the launch of the instance a route names
+DLIP_INTERNAL int dlip_conv_win_route(const void* args, const ConvAsk* ask, ConvRoute* route);
+DLIP_INTERNAL int dlip_conv_f16x3_win_launch(const void* args, void* stream, const ConvRoute* route);
+DLIP_INTERNAL int dlip_conv_rows_route(const void* args, const ConvAsk* ask, ConvRoute* route);
+DLIP_INTERNAL int dlip_conv_f16x3_rows_launch(const void* args, void* stream, const ConvRoute* route);
+DLIP_INTERNAL int dlip_conv_ring_route(const void* args, const ConvAsk* ask, ConvRoute* route);
+DLIP_INTERNAL int dlip_conv_f16x3_dma_launch(const void* args, void* stream, const ConvRoute* route);
+DLIP_INTERNAL int dlip_conv_f32_launch(const void* args, void* stream, const ConvRoute* route);
+// conv_igemm_f16x3_dma.hip: the per-stream workspace of the balanced split (slabs + ticket words); 0 = none / too small
 DLIP_INTERNAL int dlip_conv_split_workspace(void* stream, size_t slab_floats, float** slabs, int** counters, int* counter_words);
-// conv_win_f16x3.hip: the window kernel
-DLIP_INTERNAL int dlip_conv_win_ok(const void* args);
-DLIP_INTERNAL int dlip_conv_f16x3_win_launch(const void* args, void* stream, int out_split);
-// conv_rows_f16x3.hip: the rows kernel
-DLIP_INTERNAL int dlip_conv_rows_ok(const void* args);
-DLIP_INTERNAL int dlip_conv_f16x3_rows_launch(const void* args, void* stream, int epi);
-DLIP_INTERNAL int dlip_conv_rows_plan(const dlip_conv_desc* d, int* bm);
-DLIP_INTERNAL long long dlip_conv_rows_tiles(const dlip_conv_desc* d);
-DLIP_INTERNAL int dlip_conv_rows_pool_plan(const dlip_conv_desc* d, int* bm);

@@ -285,13 +285,17 @@ int launch(const ConvArgs& a, hipStream_t st) {
   return dlip_launch_status();
 }
 
-// Tile menu.  {BM, BN, WAVES_M, WAVES_N}: the 2x2 wave layouts give each wave a (BM/2)x(BN/2)
+}  // namespace
+
+// Tile menu (route->inst).  {BM, BN, WAVES_M, WAVES_N}: the 2x2 wave layouts give each wave a (BM/2)x(BN/2)
 // block; the 1x4 layouts give each wave all BM rows of a 32-channel column, which makes BM any
 // multiple of 32 -- used to fight tile quantisation: a launch takes ceil(tiles / 256 CUs) "rounds"
 // of one tile per CU, so for the short-M layers (layer3/4, TDNN) BM is chosen so the tile count
 // lands just under a multiple of 256.
-int launch_cfg(int cfg, const ConvArgs& a, hipStream_t st) {
-  switch (cfg) {
+extern "C" __attribute__((visibility("hidden"))) int dlip_conv_f32_launch(const void* args, void* stream, const ConvRoute* route) {
+  const ConvArgs& a = *static_cast<const ConvArgs*>(args);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  switch (route->inst) {
     case 0: return launch<128, 128, 2, 2>(a, st);
     case 1: return launch<128, 64, 2, 2>(a, st);
     case 2: return launch<64, 64, 2, 2>(a, st);
@@ -300,30 +304,14 @@ int launch_cfg(int cfg, const ConvArgs& a, hipStream_t st) {
   }
 }
 
-}  // namespace
-
 extern "C" int dlip_conv_nhwc_f32(const dlip_conv_desc* d, const float* x, const float* w_krsc,
                                   const float* bias, const float* residual, const float* slope,
                                   const float* post_scale, const float* post_shift, float* y,
                                   dlip_stream_t stream) {
   ConvArgs a;
-  const int rc = dlip_fill_conv_args(d, x, w_krsc, bias, residual, slope, post_scale, post_shift, y, d ? d->C : 0, &a);
+  int rc = dlip_conv_geometry(d, d ? d->C : 0, &a);
+  if (rc == DLIP_OK) rc = dlip_conv_buffers(d, x, w_krsc, bias, residual, slope, post_scale, post_shift, y, &a);
   if (rc != DLIP_OK) return rc;
-  const long long M = a.M;
-  hipStream_t st = dlip_hip_stream(stream);
-  return launch_cfg(pick_tile(M, d->K), a, st);
-}
-
-extern "C" int dlip_conv_plan(const dlip_conv_desc* d, int32_t split_f16, int32_t* bm, int32_t* bn) {
-  DLIP_CHECK_ARG(d && bm && bn && d->N > 0 && d->Ho > 0 && d->Wo > 0 && d->K > 0);
-  if ((split_f16 & 3) == 3 && dlip_conv_dma_enabled()) {   // split-format activations: the LDS-DMA kernel's menu
-    int rbm = 0;
-    if (dlip_conv_rows_plan(d, &rbm)) { *bm = rbm; *bn = 256; return DLIP_OK; }   // conv_rows_f16x3_kernel<BM / 32, ..>: BM x 256
-    dlip_conv_dma_tile((long long)d->N * d->Ho * d->Wo, d->K, d->R * d->S * ((d->C + 31) / 32), 0, bm, bn);
-    return DLIP_OK;
-  }
-  const int t = pick_tile((long long)d->N * d->Ho * d->Wo, d->K, split_f16 ? kEffF16x3 : kEffF32);
-  *bm = kCfg[t].bm;
-  *bn = kCfg[t].bn;
-  return DLIP_OK;
+  const ConvAsk q = {0, 0, 0, CONV_EPI_Y, residual != nullptr, 0, 0, 1};
+  return dlip_conv_dispatch(&a, &q, stream, nullptr);
 }

@@ -327,14 +327,58 @@ int launch(const ConvArgs& a, hipStream_t st, int flags) {
   }
 }
 
+int staged_launch(const ConvArgs& a, hipStream_t st, const ConvRoute& r, int flags) {
+  switch (r.inst) {
+    case 0: return launch<128, 128, 2, 2>(a, st, flags);
+    case 1: return launch<128, 64, 2, 2>(a, st, flags);
+    case 2: return launch<64, 64, 2, 2>(a, st, flags);
+    case 3: return launch<64, 128, 1, 4>(a, st, flags);
+    default: return launch<96, 128, 1, 4>(a, st, flags);
+  }
+}
+
+thread_local struct { ConvRoute r; long long n; } g_last = {};    // this thread's most recent convolution launch and how many it has made
+
 }  // namespace
 
-// Diagnostic switch (dlip_debug_set DLIP_DBG_DMA_ENABLE = 0): keeps split-format launches on the register-staged kernel.
-extern "C" __attribute__((visibility("hidden"))) int dlip_conv_dma_enabled(void) { return dlip_dbg_value[DLIP_DBG_DMA_ENABLE] != 0; }
+// THE route of a convolution launch: which kernel, which instance (the order and every condition: DESIGN.md section 3).  The LDS-DMA
+// kernels' epilogues leave in 16-byte chunks; filters with more than 32 taps (a weight gradient run as a convolution: the "filter" is
+// the output-gradient map) exist on the ring kernel only, split input, fp32 output, no residual; the statistics epilogue on the rows kernel.
+static int dlip_conv_route_pick(const void* args, const ConvAsk* ask, ConvRoute* route) {
+  const ConvArgs& a = *static_cast<const ConvArgs*>(args);
+  const ConvAsk& q = *ask;
+  if (q.many_tap) DLIP_CHECK_ARG(q.split_in && !q.split_out && q.epi == CONV_EPI_Y && !q.residual && q.nk2 == 0);
+  const bool ring_only = q.nk2 != 0 || q.epi == CONV_EPI_POOL;   // (these entry points never asked dlip_conv_dma_enabled)
+  const bool out_ok = q.split_out || q.epi == CONV_EPI_POOL || ((a.K & 3) == 0 && (a.ldy & 3) == 0);
+  if (q.f16x3 && q.split_in && out_ok && q.aligned && (ring_only || dlip_conv_dma_enabled())) {
+    if (q.many_tap || (!dlip_conv_win_route(args, ask, route) && !dlip_conv_rows_route(args, ask, route))) dlip_conv_ring_route(args, ask, route);
+    return q.epi == CONV_EPI_STATS && route->kind != CONV_ROWS ? DLIP_EINVAL : DLIP_OK;
+  }
+  if (q.many_tap || ring_only || q.epi == CONV_EPI_STATS) return DLIP_EINVAL;
+  const int t = pick_tile(a.M, a.K, q.f16x3 ? kEffF16x3 : kEffF32);
+  *route = ConvRoute{q.f16x3 ? CONV_STAGED : CONV_F32, kCfg[t].bm, kCfg[t].bn, t, 0, q.split_out};
+  return DLIP_OK;
+}
+
+// What every convolution entry point ends in: the launch of `picked` (an entry point that had to look at it first) or of the route picked here.
+extern "C" __attribute__((visibility("hidden"))) int dlip_conv_dispatch(const void* args, const ConvAsk* ask, void* stream, const ConvRoute* picked) {
+  ConvRoute r;
+  if (picked != nullptr) r = *picked;
+  else if (const int rc = dlip_conv_route_pick(args, ask, &r); rc != DLIP_OK) return rc;
+  g_last.r = r;
+  ++g_last.n;
+  switch (r.kind) {
+    case CONV_WIN: return dlip_conv_f16x3_win_launch(args, stream, &r);
+    case CONV_ROWS: return dlip_conv_f16x3_rows_launch(args, stream, &r);
+    case CONV_RING: return dlip_conv_f16x3_dma_launch(args, stream, &r);
+    case CONV_F32: return dlip_conv_f32_launch(args, stream, &r);
+    default: return staged_launch(*static_cast<const ConvArgs*>(args), static_cast<hipStream_t>(stream), r, ask->split_in | 2 * ask->split_out);
+  }
+}
 
 namespace {
 
-// Shared argument checks of the three split-fp16 entry points; fills `a`.
+// Shared argument checks of the split-fp16 entry points; fills `a`.
 int fill_f16x3(const dlip_conv_desc* d, const float* x, const void* w_split, const float* w_scale, const float* bias,
                const float* residual, const float* slope, const float* post_scale, const float* post_shift, float* y,
                int32_t flags, ConvArgs* a, int max_taps = 32) {
@@ -343,13 +387,29 @@ int fill_f16x3(const dlip_conv_desc* d, const float* x, const void* w_split, con
   //        DLIP_SPLIT_OUT (y is written in that format; K, ldy multiples of 32)
   if (flags & 1) DLIP_CHECK_ARG((d->C & 31) == 0 && (d->ldx & 31) == 0 && (residual == nullptr || ((d->ldr & 31) == 0 && (d->K & 31) == 0)));
   if (flags & 2) DLIP_CHECK_ARG((d->K & 31) == 0 && (d->ldy & 31) == 0);
-  const int Cw = (d->C + 31) / 32 * 32;
-  const int rc = dlip_fill_conv_args(d, x, static_cast<const float*>(w_split), bias, residual, slope, post_scale,
-                                     post_shift, y, Cw, a, max_taps);
+  int rc = dlip_conv_geometry(d, (d->C + 31) / 32 * 32, a, max_taps);
+  if (rc == DLIP_OK) rc = dlip_conv_buffers(d, x, static_cast<const float*>(w_split), bias, residual, slope, post_scale, post_shift, y, a);
   if (rc != DLIP_OK) return rc;
   a->wscale = w_scale;
   a->status = dlip_range_for(DLIP_ST_CONV);
   return DLIP_OK;
+}
+
+inline int64_t pool_bytes(long long M, int K, const ConvRoute& r) { return (M + r.pool_rows - 1) / r.pool_rows * 4 * ((K + r.pool_bn - 1) / r.pool_bn * r.pool_bn) * 8; }
+inline int aligned16(const void* y, const void* residual) { return ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(residual)) & 15) == 0; }
+
+// The route of every reporter below (mode, epi: dlip_conv_route's): the geometry half of the argument block and the same dlip_conv_route_pick as the launch.
+int route_of_desc(const dlip_conv_desc* d, int mode, int epi, int C2, int unaligned, ConvRoute* r) {
+  DLIP_CHECK_ARG(d && epi >= 0 && epi <= 3 && C2 >= 0 && (C2 & 31) == 0);
+  dlip_conv_desc dd = *d;
+  if (epi == 2) dd.ldy = d->K;   // no y: the descriptor's output stride is not used
+  ConvArgs a;
+  const int rc = dlip_conv_geometry(&dd, mode ? (d->C + 31) / 32 * 32 : d->C, &a, 65536);
+  if (rc != DLIP_OK) return rc;
+  a.nk += a.nk2 = C2 / 32;
+  const ConvAsk q = {mode != 0, (mode & 3) == 3, epi == 1, epi == 2 ? CONV_EPI_POOL : epi == 3 ? CONV_EPI_STATS : CONV_EPI_Y,
+                     d->ldr != 0, a.nk2, a.R * a.S > 32, !unaligned};
+  return dlip_conv_route_pick(&a, &q, r);
 }
 
 }  // namespace
@@ -359,55 +419,64 @@ extern "C" int dlip_conv_nhwc_f16x3(const dlip_conv_desc* d, const float* x, con
                                     const float* slope, const float* post_scale, const float* post_shift,
                                     float* y, int32_t flags, dlip_stream_t stream) {
   ConvArgs a;
-  // Filters with more than 32 taps (a weight gradient run as a convolution: the "filter" is the output-gradient map) exist on the
-  // LDS-DMA kernel only: split input, fp32 output, no residual.
-  const bool big = d && d->R > 0 && d->S > 0 && (long long)d->R * d->S > 32;
-  if (big) DLIP_CHECK_ARG((flags & 3) == 1 && residual == nullptr && (long long)d->R * d->S <= 65536);
+  const bool big = d && d->R > 0 && d->S > 0 && (long long)d->R * d->S > 32;   // (at most 65536: dlip_conv_geometry)
   const int rc = fill_f16x3(d, x, w_split, w_scale, bias, residual, slope, post_scale, post_shift, y, flags, &a, big ? 65536 : 32);
   if (rc != DLIP_OK) return rc;
-  hipStream_t st = dlip_hip_stream(stream);
-  // Split-format activations go to the LDS-DMA kernel.  Its epilogue leaves in 16-byte chunks, so an fp32
-  // output needs K, ldy in multiples of 4 and a 16-byte aligned y (a split output already has K, ldy % 32 == 0);
-  // anything else stays on the register-staged kernel below.
-  const bool dma_ok = (flags & 2) ? (reinterpret_cast<uintptr_t>(y) & 15) == 0
-                                  : ((d->K & 3) == 0 && (d->ldy & 3) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0);
-  const bool res_ok = residual == nullptr || (reinterpret_cast<uintptr_t>(residual) & 15) == 0;
-  if ((flags & 1) && dma_ok && res_ok && dlip_conv_dma_enabled()) {
-    // narrow same-size 3x3 layers (layer 1: 64 -> 64): one activation window per channel slice instead of nine tap fetches
-    if (dlip_conv_win_ok(&a)) return dlip_conv_f16x3_win_launch(&a, stream, (flags & 2) ? 1 : 0);
-    // the speech encoder's 1-D "valid" convolutions and k = 1 GEMMs over all frames: persistent 160 x 256 tiles, continuous slice stream
-    if (dlip_conv_rows_ok(&a)) return dlip_conv_f16x3_rows_launch(&a, stream, (flags & 2) ? 1 : 0);
-    return dlip_conv_f16x3_dma_launch(&a, stream, (flags & 2) ? 1 : 0);
-  }
-  if (big) return DLIP_EINVAL;
-  switch (pick_tile(a.M, d->K, kEffF16x3)) {
-    case 0: return launch<128, 128, 2, 2>(a, st, flags);
-    case 1: return launch<128, 64, 2, 2>(a, st, flags);
-    case 2: return launch<64, 64, 2, 2>(a, st, flags);
-    case 3: return launch<64, 128, 1, 4>(a, st, flags);
-    default: return launch<96, 128, 1, 4>(a, st, flags);
-  }
+  const ConvAsk q = {1, flags & 1, (flags >> 1) & 1, CONV_EPI_Y, residual != nullptr, 0, big, aligned16(y, residual)};
+  return dlip_conv_dispatch(&a, &q, stream, nullptr);
+}
+
+extern "C" int dlip_conv_route(const dlip_conv_desc* d, int32_t mode, int32_t epilogue, int32_t C2, int32_t unaligned, int32_t* kind,
+                               int32_t* bm, int32_t* bn) {
+  ConvRoute r;
+  const int rc = kind && bm && bn ? route_of_desc(d, mode, epilogue, C2, unaligned, &r) : DLIP_EINVAL;
+  if (rc == DLIP_OK) { *kind = r.kind; *bm = r.bm; *bn = r.bn; }
+  return rc;
+}
+
+extern "C" int dlip_conv_plan(const dlip_conv_desc* d, int32_t split_f16, int32_t* bm, int32_t* bn) {
+  int32_t kind;
+  return dlip_conv_route(d, split_f16, 0, 0, 0, &kind, bm, bn);
+}
+
+extern "C" int dlip_conv_kernel_kind(const dlip_conv_desc* d) {
+  ConvRoute r;
+  return !d ? DLIP_EINVAL : route_of_desc(d, 3, 0, 0, 0, &r) == DLIP_OK && (r.kind == CONV_WIN || r.kind == CONV_ROWS) ? r.kind : 0;
+}
+
+extern "C" int32_t dlip_conv_stats_chunks(const dlip_conv_desc* d) {
+  ConvRoute r;
+  return route_of_desc(d, 3, 3, 0, 0, &r) == DLIP_OK && 2 * r.tiles_m <= 0x7FFFFFFF ? (int32_t)(2 * r.tiles_m) : 0;
+}
+
+extern "C" int64_t dlip_conv_pool_partial_bytes(const dlip_conv_desc* d, int32_t* tile_rows) {
+  ConvRoute r;
+  if (route_of_desc(d, 3, 2, 0, 0, &r) != DLIP_OK) return DLIP_EINVAL;
+  if (tile_rows) *tile_rows = r.pool_rows;
+  return pool_bytes((long long)d->N * d->Ho * d->Wo, d->K, r);
+}
+
+// Tests and tools (not part of the public header), no device call: out = {kind, bm, bn} of this thread's most recent convolution
+// launch, and how many it has made.
+extern "C" int dlip_conv_last_route_query(int64_t* out) {
+  DLIP_CHECK_ARG(out != nullptr);
+  out[0] = g_last.r.kind; out[1] = g_last.r.bm; out[2] = g_last.r.bn; out[3] = g_last.n;
+  return DLIP_OK;
 }
 
 // dlip_conv_nhwc_f16x3 (split input, fp32 output, no residual) that also leaves the column sums of its output (include/deeplip_hip.h).
-extern "C" int32_t dlip_conv_stats_chunks(const dlip_conv_desc* d) {
-  if (!d || d->N <= 0 || d->Ho <= 0 || d->Wo <= 0 || (d->C & 31) != 0 || (d->K & 3) != 0 || (d->ldy & 3) != 0 || !dlip_conv_dma_enabled()) return 0;
-  const long long chunks = 2 * dlip_conv_rows_tiles(d);        // (the window kernel is asked first by the launch: not a rows shape then)
-  return chunks > 0 && chunks <= 0x7FFFFFFF ? (int32_t)chunks : 0;
-}
-
 extern "C" int dlip_conv_nhwc_stats_f16x3(const dlip_conv_desc* d, const float* x, const void* w_split, const float* w_scale,
                                           const float* bias, const float* slope, float* y, double* stats, int64_t stats_bytes,
                                           dlip_stream_t stream) {
   DLIP_CHECK_ARG(d && stats && (reinterpret_cast<uintptr_t>(stats) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0);
-  const int32_t chunks = dlip_conv_stats_chunks(d);
-  DLIP_CHECK_ARG(chunks > 0 && stats_bytes >= (int64_t)chunks * d->K * 2 * 8);
   ConvArgs a;
   const int rc = fill_f16x3(d, x, w_split, w_scale, bias, nullptr, slope, nullptr, nullptr, y, DLIP_SPLIT_IN, &a);
   if (rc != DLIP_OK) return rc;
-  DLIP_CHECK_ARG(!dlip_conv_win_ok(&a) && dlip_conv_rows_ok(&a));
+  const ConvAsk q = {1, 1, 0, CONV_EPI_STATS, 0, 0, 0, 1};
+  ConvRoute r;
+  DLIP_CHECK_ARG(dlip_conv_route_pick(&a, &q, &r) == DLIP_OK && stats_bytes >= 2 * r.tiles_m * d->K * 2 * 8);
   a.stats = stats;
-  return dlip_conv_f16x3_rows_launch(&a, stream, 0);
+  return dlip_conv_dispatch(&a, &q, stream, &r);
 }
 
 // A convolution's weight gradient run as a convolution over SLICE-major operand images (include/deeplip_hip.h).
@@ -442,7 +511,9 @@ extern "C" int dlip_wgrad_conv_f16x3(const float* x_img, const float* g_img, con
     a.wg_R = R; a.wg_S = S;
     a.y_bytes = (uint32_t)((long long)K * C * R * S * 4);
   }
-  return dlip_conv_f16x3_dma_launch(&a, stream, 0);
+  // (slice-major images go to the ring kernel's many-tap instances whatever the shape: every other instance reads pixel-major operands)
+  const ConvAsk q = {1, 1, 0, CONV_EPI_Y, 0, 0, a.R * a.S > 32 || a.cs_x != 128 || a.cs_w != 128 || a.wt != a.Cw * 4 || a.Hs != a.H, 1};
+  return dlip_conv_dispatch(&a, &q, stream, nullptr);
 }
 
 // conv + 1x1 strided shortcut convolution in ONE reduction (include/deeplip_hip.h).
@@ -463,29 +534,15 @@ extern "C" int dlip_conv2_nhwc_f16x3(const dlip_conv_desc* d, const float* x, co
   if (x2_bytes > DLIP_MAX_BUFFER_BYTES || w_bytes > DLIP_MAX_BUFFER_BYTES) return DLIP_ERANGE;
   a.x2 = x2; a.x2_bytes = (uint32_t)x2_bytes;
   a.H2 = H2; a.W2 = W2; a.ldx2 = ldx2; a.s2h = stride2_h; a.s2w = stride2_w;
-  a.nk2 = C2 / 32;
-  a.nk += a.nk2;
+  a.nk += a.nk2 = C2 / 32;
   a.rsc += C2;
   a.w_bytes = (uint32_t)w_bytes;
-  const bool y_ok = (flags & 2) ? true : ((d->K & 3) == 0 && (d->ldy & 3) == 0);
-  DLIP_CHECK_ARG(y_ok && (reinterpret_cast<uintptr_t>(y) & 15) == 0 && (residual == nullptr || (reinterpret_cast<uintptr_t>(residual) & 15) == 0));
-  return dlip_conv_f16x3_dma_launch(&a, stream, (flags & 2) ? 1 : 0);
+  // (an fp32 y with K or ldy off a multiple of 4, a misaligned y or residual: no route, DLIP_EINVAL)
+  const ConvAsk q = {1, 1, (flags >> 1) & 1, CONV_EPI_Y, residual != nullptr, a.nk2, 0, aligned16(y, residual)};
+  return dlip_conv_dispatch(&a, &q, stream, nullptr);
 }
 
 // conv whose epilogue keeps only segmented column sums (include/deeplip_hip.h).
-extern "C" int64_t dlip_conv_pool_partial_bytes(const dlip_conv_desc* d, int32_t* tile_rows) {
-  if (!d || d->N <= 0 || d->Ho <= 0 || d->Wo <= 0 || d->K <= 0) return DLIP_EINVAL;
-  int bm = 0, bn = 0;
-  const long long M = (long long)d->N * d->Ho * d->Wo;
-  dlip_conv_dma_tile(M, d->K, d->R * d->S * ((d->C + 31) / 32), 2, &bm, &bn);
-  // the rows kernel's pooled epilogue (conv_rows_f16x3.hip): one partial row set per WAVE ROW = half of its BM x 256 tile; columns
-  // rounded up to 128 like the ring kernel's, so both feed the same finishers
-  if (int rbm = 0; dlip_conv_rows_pool_plan(d, &rbm)) { bm = rbm / 2; bn = 128; }
-  if (tile_rows) *tile_rows = bm;
-  const long long tiles_m = (M + bm - 1) / bm, Kp = (long long)(d->K + bn - 1) / bn * bn;
-  return tiles_m * 4 * Kp * 8;
-}
-
 extern "C" int dlip_conv_pool_f16x3(const dlip_conv_desc* d, const float* x, const void* w_split, const float* w_scale,
                                     const float* bias, const float* residual, const float* slope, const float* post_scale,
                                     const float* post_shift, double* partials, int64_t partial_bytes, int32_t group_rows,
@@ -497,15 +554,13 @@ extern "C" int dlip_conv_pool_f16x3(const dlip_conv_desc* d, const float* x, con
   float* no_y = reinterpret_cast<float*>(partials);   // (never written: the pooled epilogue has no y stores)
   const int rc = fill_f16x3(&dd, x, w_split, w_scale, bias, residual, slope, post_scale, post_shift, no_y, DLIP_SPLIT_IN, &a);
   if (rc != DLIP_OK) return rc;
-  int32_t bm = 0;
-  const int64_t need = dlip_conv_pool_partial_bytes(d, &bm);
-  DLIP_CHECK_ARG(need > 0 && partial_bytes >= need && group_rows >= bm);
-  DLIP_CHECK_ARG(residual == nullptr || (reinterpret_cast<uintptr_t>(residual) & 15) == 0);
+  const ConvAsk q = {1, 1, 0, CONV_EPI_POOL, residual != nullptr || d->ldr != 0, 0, 0, aligned16(nullptr, residual)};   // (ldr: as dlip_conv_pool_partial_bytes sized the buffer)
+  ConvRoute r;
+  DLIP_CHECK_ARG(dlip_conv_route_pick(&a, &q, &r) == DLIP_OK && partial_bytes >= pool_bytes(a.M, a.K, r) && group_rows >= r.pool_rows);
   a.y = nullptr; a.y_bytes = 0;
   a.pool = partials;
   a.pool_group = group_rows;
   a.pool_len.len = group_len; a.pool_len.mul = len_mul; a.pool_len.add = len_add;
-  if (residual == nullptr && dlip_conv_rows_pool_plan(d, nullptr) && dlip_conv_rows_ok(&a)) return dlip_conv_f16x3_rows_launch(&a, stream, 2);
-  return dlip_conv_f16x3_dma_launch(&a, stream, 2);
+  return dlip_conv_dispatch(&a, &q, stream, &r);
 }
 

@@ -1518,8 +1518,8 @@ int launch_dma(const ConvArgs& a, hipStream_t st, int epi) {
 
 }  // namespace
 
-// Tile menu of the DMA kernel (index = what dlip_conv_plan reports via dlip_conv_dma_tile; dlip_debug_set
-// (DLIP_DBG_DMA_TILE) forces one for tests and A/B runs).
+// Tile menu of the DMA kernel (index = ConvRoute::inst of a ring launch; dlip_debug_set (DLIP_DBG_DMA_TILE) forces one for
+// tests and A/B runs).
 const TileCfg kDmaCfg[] = {{128, 128}, {128, 64}, {64, 128}, {64, 64}, {128, 64}, {256, 128}};
 constexpr int NUM_DMA_ALL = (int)(sizeof(kDmaCfg) / sizeof(kDmaCfg[0]));
 
@@ -1575,32 +1575,28 @@ extern "C" __attribute__((visibility("hidden"))) int dlip_conv_split_workspace(v
   return 1;
 }
 
-// Library-internal entry points (hidden): ConvArgs lives in an unnamed namespace, so it crosses the
-// translation-unit boundary as an opaque pointer.
-extern "C" __attribute__((visibility("hidden"))) void dlip_conv_dma_tile(long long M, int K, int nk, int epi, int* bm, int* bn) {
-  const TileCfg& c = kDmaCfg[dma_pick(M, K, nk, epi)];
-  *bm = c.bm;
-  *bn = c.bn;
+// The ring kernel serves every split-input launch (argument checks done by the entry points): the menu index of its tile.
+// The many-tap instances are also the ONLY ones that honour the slice / tap strides of slice-major operand images
+// (dlip_wgrad_conv_f16x3), so a weight gradient with 32 taps or fewer takes them too (tests/test_train_video_gpu.py's full-size gradient test).
+extern "C" __attribute__((visibility("hidden"))) int dlip_conv_ring_route(const void* args, const ConvAsk* ask, ConvRoute* route) {
+  const ConvArgs& a = *static_cast<const ConvArgs*>(args);
+  const int epi = ask->epi == CONV_EPI_POOL ? 2 : ask->split_out;
+  int t = dma_pick(a.M, a.K, a.nk, epi);
+  if (ask->many_tap) t = (a.K <= 64 || t == 1 || t == 3) ? 1 : t == 5 ? 5 : 0;   // the tap-mask-free variant, on the three tiles long reductions use
+  *route = ConvRoute{CONV_RING, kDmaCfg[t].bm, kDmaCfg[t].bn, t, ask->many_tap, epi, 0, 0, 0, kDmaCfg[t].bm, 128};
+  return 1;
 }
 
-// Called by dlip_conv_nhwc_f16x3 / dlip_conv2_nhwc_f16x3 / dlip_conv_pool_f16x3 for DLIP_SPLIT_IN launches
-// (argument checks done there).  epi: 0 fp32 y, 1 split y, 2 pooled partials (a.pool, a.pool_group).
-extern "C" __attribute__((visibility("hidden"))) int dlip_conv_f16x3_dma_launch(const void* args, void* stream, int epi) {
+extern "C" __attribute__((visibility("hidden"))) int dlip_conv_f16x3_dma_launch(const void* args, void* stream, const ConvRoute* route) {
   const ConvArgs& a = *static_cast<const ConvArgs*>(args);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  // The many-tap instances are also the ONLY ones that honour the slice / tap strides of slice-major operand images
-  // (dlip_wgrad_conv_f16x3: cs_x, wt, cs_w, Hs); a weight gradient with 32 taps or fewer -- layer 4's 3x3 output-gradient maps: 9 taps --
-  // used to fall through to the pixel-major instances below and read its slice-major images as if they were pixel-major: wrong
-  // layer-4 weight gradients whenever the batch had more than 32 images (round 3's default layout; the 2-clip golden has one
-  // slice, where the two layouts coincide; found by tests/test_train_video_gpu.py's full-size gradient test in round 4).
-  const bool slice_major = a.cs_x != 128 || a.cs_w != 128 || a.wt != a.Cw * 4 || a.Hs != a.H;
-  if (a.R * a.S > 32 || slice_major) {   // the tap-mask-free variant, on the three tiles long reductions use
-    const int t = dma_pick(a.M, a.K, a.nk, epi);
-    if (a.K <= 64 || t == 1 || t == 3) return launch_dma<128, 64, 2, 2, 3, 2, 4096>(a, st, epi);
-    if (t == 5) return launch_dma<256, 128, 4, 2, 3, 1, 4096>(a, st, epi);
+  const int epi = route->epi;
+  if (route->many_tap) {
+    if (route->inst == 1) return launch_dma<128, 64, 2, 2, 3, 2, 4096>(a, st, epi);
+    if (route->inst == 5) return launch_dma<256, 128, 4, 2, 3, 1, 4096>(a, st, epi);
     return launch_dma<128, 128, 2, 2, 2, 2, 4096>(a, st, epi);
   }
-  switch (dma_pick(a.M, a.K, a.nk, epi)) {
+  switch (route->inst) {
     case 0: return launch_dma<128, 128, 2, 2, 2, 2>(a, st, epi);
     case 1: return launch_dma<128, 64, 2, 2, 3, 2>(a, st, epi);
     case 2: return launch_dma<64, 128, 2, 2, 3, 2>(a, st, epi);

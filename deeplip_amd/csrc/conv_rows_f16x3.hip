@@ -613,7 +613,7 @@ RowsTail rows_tail(long long M, int tiles_n, int mi, int slots) {
 }
 
 template <int MI, int EPI, bool TAIL = false>
-int launch_rows(const ConvArgs& a, hipStream_t st) {
+int launch_rows(const ConvArgs& a, hipStream_t st, const ConvRoute& r) {
   constexpr int BM = 32 * MI;
   constexpr size_t lds = (size_t)3 * (BM + ROWS_BN) * ROWB + (EPI != 2 ? 3 * ROWS_BN * sizeof(float) : 0);   // ring + the epilogue's parameter table
   static_assert(lds <= 160 * 1024, "LDS ring exceeds a CU");
@@ -627,18 +627,13 @@ int launch_rows(const ConvArgs& a, hipStream_t st) {
   e = ks.resident(reinterpret_cast<const void*>(kern), 512, lds, &slots);   // one workgroup per CU
   if (e != DLIP_OK) return e;
   RowsSched sc;
-  long long tiles_m = ((long long)a.M + BM - 1) / BM;
   sc.item_short0 = sc.t_full = 0x7FFFFFFF; sc.nmi_short = MI; sc.row_short0 = 0;
   if constexpr (TAIL) {
-    // the short last round is laid out for the CUs of the chip -- what dlip_conv_stats_chunks can know without a launch; `slots` is that
-    // number whenever the kernel is resident once per CU (if it ever were not, the layout would still be correct, only less even)
-    const RowsTail t = rows_tail(a.M, b.tiles_n, MI, rows_cus());
-    if (t.nmi < MI) {
-      tiles_m = t.tiles_m;
-      sc.t_full = (int)t.full; sc.item_short0 = (int)(t.full * b.tiles_n); sc.nmi_short = t.nmi; sc.row_short0 = (int)(t.full * BM);
-    }
+    // the route laid the short last round out for the CUs of the chip -- what dlip_conv_stats_chunks can know without a launch; `slots` is
+    // that number whenever the kernel is resident once per CU (if it ever were not, the layout would still be correct, only less even)
+    sc.t_full = r.tail_full; sc.item_short0 = r.tail_full * b.tiles_n; sc.nmi_short = r.tail_nmi; sc.row_short0 = r.tail_full * BM;
   }
-  const long long items = tiles_m * b.tiles_n;
+  const long long items = r.tiles_m * b.tiles_n;
   if (items <= 0 || items > 0x3FFFFFFFll) return DLIP_EINVAL;
   sc.items = (int)items;
   sc.tiles_n = b.tiles_n;
@@ -679,7 +674,7 @@ int launch_rows(const ConvArgs& a, hipStream_t st) {
 // exposed half of the last epilogue, about a slice and a half of a 16-slice tile); the fewest "row units" wins, the taller
 // tile on a tie (fewer bytes per MFMA).
 // (round 5) ... and a launch whose last round is SHORT (rows_tail) pays that round at its own height.
-int rows_pick_mi(long long M, int K, int nk, int cus, bool tail = true) {   // tail = false: a pooled launch (tiles of one height)
+int rows_pick_mi(long long M, int K, int nk, int cus, bool tail) {   // tail = false: a pooled launch (tiles of one height)
   const int tiles_n = (K + ROWS_BN - 1) / ROWS_BN;
   int best = 5;
   double best_cost = 1e300;
@@ -702,79 +697,52 @@ int rows_pick_mi(long long M, int K, int nk, int cus, bool tail = true) {   // t
 
 }  // namespace
 
-// Which launches the rows kernel serves: H = 1, one filter row, stride 1, no padding (every tap of every output row exists: a
-// plain row offset), whole 32-channel slices, no residual / second source / pooled epilogue, and enough rows and columns for its
-// 256-column tiles to be the right shape (the fully connected layers on a batch of utterances stay on the ring kernel's split).
-static bool rows_shape_ok(int H, int R, int S, int sh, int sw, int ph, int pw, int C, int K, long long M) {
+// Which launches the rows kernel serves: every tap of every output row exists (a plain row offset), and there are enough
+// rows and columns for its 256-column tiles to be the right shape (the fully connected layers on a batch of utterances stay on the ring kernel's split).
+// The pooled epilogue on this kernel is correct and tested, and slower than the ring kernel's LDS-staged one (the fp64 column sums
+// straight from the accumulators: tdnn.9 at B = 64 130 us against 96, tools/bench_rows.py): a pooled launch comes here only when FORCED.
+static bool rows_shape_ok(const ConvArgs& a, const ConvAsk& q) {
   const int v = dlip_dbg_value[DLIP_DBG_ROWS];
-  if (v == 0 || !dlip_conv_dma_enabled()) return false;
-  if (!(H == 1 && R == 1 && sw == 1 && sh == 1 && ph == 0 && pw == 0 && (C & 31) == 0 && S <= 32)) return false;
+  if (v == 0 || !dlip_conv_dma_enabled() || (q.epi == CONV_EPI_POOL && v < 0)) return false;
+  if (q.residual || q.nk2 != 0 || a.Cw != a.C) return false;
+  if (!(a.H == 1 && a.R == 1 && a.sw == 1 && a.sh == 1 && a.ph == 0 && a.pw == 0 && (a.C & 31) == 0 && a.S <= 32)) return false;
   if (v > 0) return true;                                  // forced (tests)
-  return K >= 192 && M >= 4096;
+  return a.K >= 192 && a.M >= 4096;
 }
 
-extern "C" __attribute__((visibility("hidden"))) int dlip_conv_rows_ok(const void* args) {
+// The tile height and the row tiles of the launch: the statistics epilogue writes two partial rows per row tile, the pooled one a
+// partial band per WAVE ROW = half of its BM x 256 tile, columns rounded up to 128 like the ring kernel's (the same finishers).
+extern "C" __attribute__((visibility("hidden"))) int dlip_conv_rows_route(const void* args, const ConvAsk* ask, ConvRoute* route) {
   const ConvArgs& a = *static_cast<const ConvArgs*>(args);
-  return a.Cw == a.C && a.res == nullptr && a.x2 == nullptr && a.wscale != nullptr &&
-         rows_shape_ok(a.H, a.R, a.S, a.sh, a.sw, a.ph, a.pw, a.C, a.K, a.M);
-}
-
-// The same decision from a descriptor (dlip_conv_kernel_kind / dlip_conv_plan: which kernel and tile a profiler will show for a
-// split-format launch of `d` without a residual); *bm = the tile height the launch will use.
-static int rows_plan(const dlip_conv_desc* d, int* bm, bool tail) {
-  const long long M = (long long)d->N * d->Ho * d->Wo;
-  if (d->ldr != 0 || !rows_shape_ok(d->H, d->R, d->S, d->stride_h, d->stride_w, d->pad_h, d->pad_w, d->C, d->K, M)) return 0;
-  int mi = rows_pick_mi(M, d->K, d->S * (d->C / 32), rows_cus(), tail);
-  if (const int v = dlip_dbg_value[DLIP_DBG_ROWS]; v >= 3 && v <= 5) mi = v;
-  if (bm) *bm = 32 * mi;
+  if (!rows_shape_ok(a, *ask)) return 0;
+  const bool pooled = ask->epi == CONV_EPI_POOL;           // (tiles of one height)
+  const int cus = rows_cus();
+  int mi = rows_pick_mi(a.M, a.K, a.nk, cus, !pooled);
+  if (const int v = dlip_dbg_value[DLIP_DBG_ROWS]; v >= 3 && v <= 5) mi = v;   // dlip_debug_set: a forced tile height (tests, A/B)
+  const RowsTail t = pooled ? RowsTail{((long long)a.M + 32 * mi - 1) / (32 * mi), 0, mi} : rows_tail(a.M, (a.K + ROWS_BN - 1) / ROWS_BN, mi, cus);
+  // a launch with a short last round (rows_tail) runs the TAIL instance; everything else the instance without that code
+  *route = ConvRoute{CONV_ROWS, 32 * mi, ROWS_BN, mi, 0, pooled ? 2 : ask->split_out, (int)t.full, t.nmi, t.tiles_m, 16 * mi, 128};
   return 1;
 }
 
-extern "C" __attribute__((visibility("hidden"))) int dlip_conv_rows_plan(const dlip_conv_desc* d, int* bm) { return rows_plan(d, bm, true); }
-
-// Row tiles of the fp32 / split-output launch dlip_conv_rows_plan describes (with its short last round, if any): the statistics
-// epilogue writes two partial rows per row tile (dlip_conv_stats_chunks).
-extern "C" __attribute__((visibility("hidden"))) long long dlip_conv_rows_tiles(const dlip_conv_desc* d) {
-  int bm = 0;
-  if (!dlip_conv_rows_plan(d, &bm) || bm <= 0) return 0;
-  const long long M = (long long)d->N * d->Ho * d->Wo;
-  return rows_tail(M, (d->K + ROWS_BN - 1) / ROWS_BN, bm / 32, rows_cus()).tiles_m;
-}
-
-// The pooled epilogue on this kernel is correct and tested, and slower than the ring kernel's LDS-staged one: the fp64 column
-// sums taken straight from the accumulators cost ~13 us per tile in cross-lane work (64 doubles x 4 butterfly steps per channel
-// quad), tdnn.9 at B = 64: 130 us against 96 us on the ring kernel's <128,128,pool> instance (tools/bench_rows.py).  So a
-// pooled launch comes here only when the rows kernel is FORCED (dlip_debug_set(6, 1 | 3 | 4 | 5): tests, A/B runs).
-extern "C" __attribute__((visibility("hidden"))) int dlip_conv_rows_pool_plan(const dlip_conv_desc* d, int* bm) {
-  if (dlip_dbg_value[DLIP_DBG_ROWS] <= 0) return 0;
-  return rows_plan(d, bm, false);
-}
-
-extern "C" __attribute__((visibility("hidden"))) int dlip_conv_f16x3_rows_launch(const void* args, void* stream, int epi) {
+extern "C" __attribute__((visibility("hidden"))) int dlip_conv_f16x3_rows_launch(const void* args, void* stream, const ConvRoute* route) {
   const ConvArgs& a = *static_cast<const ConvArgs*>(args);
   hipStream_t st = dlip_hip_stream(stream);
-  const int cus = rows_cus();
-  int mi = rows_pick_mi(a.M, a.K, a.nk, cus, epi != 2);
-  if (const int v = dlip_dbg_value[DLIP_DBG_ROWS]; v >= 3 && v <= 5) mi = v;   // dlip_debug_set: a forced tile height (tests, A/B)
-  if (epi == 2) {   // pooled: a half tile (16 mi rows) may contain at most one row-group boundary
-    if (a.pool == nullptr || a.pool_group < 16 * mi) return DLIP_EINVAL;
+  const ConvRoute& r = *route;
+  const int mi = r.inst, epi = r.epi;
+  // pooled: a half tile (16 mi rows) may contain at most one row-group boundary
+  if (epi == 2 && (a.pool == nullptr || a.pool_group < 16 * mi)) return DLIP_EINVAL;
+  if (epi == 2) return mi == 3 ? launch_rows<3, 2>(a, st, r) : mi == 4 ? launch_rows<4, 2>(a, st, r) : launch_rows<5, 2>(a, st, r);
+  if (r.tail_nmi < mi) {
     switch (mi) {
-      case 3: return launch_rows<3, 2>(a, st);
-      case 4: return launch_rows<4, 2>(a, st);
-      default: return launch_rows<5, 2>(a, st);
-    }
-  }
-  // a launch with a short last round (rows_tail) runs the TAIL instance; everything else the instance without that code
-  if (rows_tail(a.M, (a.K + ROWS_BN - 1) / ROWS_BN, mi, cus).nmi < mi) {
-    switch (mi) {
-      case 3: return epi ? launch_rows<3, 1, true>(a, st) : launch_rows<3, 0, true>(a, st);
-      case 4: return epi ? launch_rows<4, 1, true>(a, st) : launch_rows<4, 0, true>(a, st);
-      default: return epi ? launch_rows<5, 1, true>(a, st) : launch_rows<5, 0, true>(a, st);
+      case 3: return epi ? launch_rows<3, 1, true>(a, st, r) : launch_rows<3, 0, true>(a, st, r);
+      case 4: return epi ? launch_rows<4, 1, true>(a, st, r) : launch_rows<4, 0, true>(a, st, r);
+      default: return epi ? launch_rows<5, 1, true>(a, st, r) : launch_rows<5, 0, true>(a, st, r);
     }
   }
   switch (mi) {
-    case 3: return epi ? launch_rows<3, 1>(a, st) : launch_rows<3, 0>(a, st);
-    case 4: return epi ? launch_rows<4, 1>(a, st) : launch_rows<4, 0>(a, st);
-    default: return epi ? launch_rows<5, 1>(a, st) : launch_rows<5, 0>(a, st);
+    case 3: return epi ? launch_rows<3, 1>(a, st, r) : launch_rows<3, 0>(a, st, r);
+    case 4: return epi ? launch_rows<4, 1>(a, st, r) : launch_rows<4, 0>(a, st, r);
+    default: return epi ? launch_rows<5, 1>(a, st, r) : launch_rows<5, 0>(a, st, r);
   }
 }

@@ -524,23 +524,29 @@ int launch_win(const ConvArgs& a, hipStream_t st, bool out_split) {
 
 }  // namespace
 
-// The window kernel serves same-size stride-1 3x3 convolutions (the nine taps are unrolled; a wave's window pieces go
-// out one per slice and must be older in the queue than the weights of the next channel slice's first tap), a halo within WIN_SLACK,
-// K <= 128 (ONE column block: layer 1 on the 128x64 instance, layer 2 on the 128x128 one; dlip_debug_set(DLIP_DBG_WIN, 1)
-// keeps it to K <= 64) and no second reduction source / pooled epilogue.
-static bool win_shape_ok(int sh, int sw, int H, int W, int Ho, int Wo, int R, int S, int dh, int dw, int ph, int pw, int K) {
+// The window kernel's launches: the nine taps are unrolled, a wave's window pieces go out one per slice and
+// must be older in the queue than the weights of the next channel slice's first tap; ONE column block (dlip_debug_set(DLIP_DBG_WIN, 1): K <= 64).
+static bool win_shape_ok(const ConvArgs& a, const ConvAsk& q) {
   if (dlip_dbg_value[DLIP_DBG_WIN] == 0) return false;
   // masked taps read past the workgroup's LDS allocation and rely on the hardware returning zeros: probed on gfx950
   // (tests/test_kernels_gpu.py::test_lds_read_beyond_allocation_returns_zero), never assumed elsewhere
   if (!dlip_device_is_gfx950()) return false;
-  return sh == 1 && sw == 1 && Wo == W && Ho == H && R == 3 && S == 3 && K <= (dlip_dbg_value[DLIP_DBG_WIN] == 1 ? 64 : 128) && (K & 3) == 0 &&
-         (R - 1) * dh * W + (S - 1) * dw <= WIN_SLACK && ph * W + pw <= WIN_SLACK;
+  return q.nk2 == 0 && q.epi != CONV_EPI_POOL && (a.C & 31) == 0 && a.sh == 1 && a.sw == 1 && a.Wo == a.W && a.HoWo == a.H * a.W &&
+         a.R == 3 && a.S == 3 && a.K <= (dlip_dbg_value[DLIP_DBG_WIN] == 1 ? 64 : 128) && (a.K & 3) == 0 &&
+         (a.R - 1) * a.dh * a.W + (a.S - 1) * a.dw <= WIN_SLACK && a.ph * a.W + a.pw <= WIN_SLACK;
 }
 
-extern "C" __attribute__((visibility("hidden"))) int dlip_conv_win_ok(const void* args) {
+// The geometries (measurements: DESIGN.md section 3).  K <= 64: four waves, two workgroups per CU; 64 < K <= 128 (layer 2): eight waves on a
+// 128x128 tile, one workgroup per CU (the fp32 epilogue image alone is 64 KB).  dlip_debug_set(DLIP_DBG_WIN, v) picks one for same-box
+// A/B runs: 3 = 128x64, TWO waves of 64x64 (two workgroups per CU); 4 = 256x64, four waves of 64x64; 5 = (K > 64) 128x128, four
+// waves of 64x64; 6 = (K > 64) 256x128, eight waves of 64x64.
+extern "C" __attribute__((visibility("hidden"))) int dlip_conv_win_route(const void* args, const ConvAsk* ask, ConvRoute* route) {
   const ConvArgs& a = *static_cast<const ConvArgs*>(args);
-  return a.x2 == nullptr && a.pool == nullptr &&
-         win_shape_ok(a.sh, a.sw, a.H, a.W, a.HoWo / a.Wo, a.Wo, a.R, a.S, a.dh, a.dw, a.ph, a.pw, a.K);
+  if (!win_shape_ok(a, *ask)) return 0;
+  const int v = dlip_dbg_value[DLIP_DBG_WIN];
+  const int inst = a.K > 64 ? (v == 5 ? 4 : v == 6 ? 5 : 3) : (v == 3 ? 1 : v == 4 ? 2 : 0);   // launch_win's instances below
+  *route = ConvRoute{CONV_WIN, inst == 2 || inst == 5 ? 256 : 128, a.K > 64 ? 128 : 64, inst, 0, ask->split_out};
+  return 1;
 }
 
 // ---- the hardware behaviour the masked taps stand on, as a callable check (tests/test_kernels_gpu.py) ----
@@ -577,33 +583,16 @@ extern "C" int dlip_selftest_lds_oob(int32_t* counts, int32_t blocks, dlip_strea
   return dlip_launch_status();
 }
 
-// Which kernel a split-format launch of `d` goes to (include/deeplip_hip.h): 1 = this one.
-extern "C" int dlip_conv_kernel_kind(const dlip_conv_desc* d) {
-  if (!d) return DLIP_EINVAL;
-  if (d->C % 32 == 0 && dlip_conv_dma_enabled() &&
-      win_shape_ok(d->stride_h, d->stride_w, d->H, d->W, d->Ho, d->Wo, d->R, d->S, d->dil_h, d->dil_w, d->pad_h, d->pad_w, d->K))
-    return 1;
-  return dlip_conv_rows_plan(d, nullptr) ? 2 : 0;
-}
-
-extern "C" __attribute__((visibility("hidden"))) int dlip_conv_f16x3_win_launch(const void* args, void* stream, int out_split) {
+extern "C" __attribute__((visibility("hidden"))) int dlip_conv_f16x3_win_launch(const void* args, void* stream, const ConvRoute* route) {
   const ConvArgs& a = *static_cast<const ConvArgs*>(args);
-  // K <= 64: four waves, two workgroups per CU (eight waves in one workgroup per CU: 258 vs 218 us on layer 1, same box).
-  // 64 < K <= 128 (layer 2, 128 -> 128 channels on 11x11 maps): eight waves on a 128x128 tile, one workgroup per CU (the
-  // fp32 epilogue image alone is 64 KB): 178 us vs 200-210 on the 256x128 ring kernel without a residual, 211-223 vs 241-275 with.
-  // dlip_debug_set(DLIP_DBG_WIN, v) picks a geometry for same-box A/B runs: 3 = 128x64 tile, TWO waves of 64x64 (two workgroups
-  // per CU); 4 = 256x64, four waves of 64x64; 5 = (K > 64) 128x128, four waves of 64x64; 6 = (K > 64) 256x128, eight waves of 64x64;
-  // 7 = round 5's 2 x 2 waves of 64x32 on the 128x64 tile.
   hipStream_t st = dlip_hip_stream(stream);
-  const int v = dlip_dbg_value[DLIP_DBG_WIN];
-  if (a.K > 64) {
-    if (v == 5) return launch_win<128, 128, 2, 2, 1>(a, st, out_split != 0);
-    if (v == 6) return launch_win<256, 128, 4, 2, 1>(a, st, out_split != 0);
-    return launch_win<128, 128, 4, 2, 2>(a, st, out_split != 0);
+  const bool out_split = route->epi != 0;
+  switch (route->inst) {   // (wave layout, workgroups per CU)
+    case 4: return launch_win<128, 128, 2, 2, 1>(a, st, out_split);
+    case 5: return launch_win<256, 128, 4, 2, 1>(a, st, out_split);
+    case 3: return launch_win<128, 128, 4, 2, 2>(a, st, out_split);
+    case 1: return launch_win<128, 64, 2, 1, 1>(a, st, out_split);
+    case 2: return launch_win<256, 64, 4, 1, 1>(a, st, out_split);
+    default: return launch_win<128, 64, 2, 2, 2>(a, st, out_split);
   }
-  // (256x64 with eight waves in ONE workgroup per CU -- the weights fetched once per 256 rows instead of per 128 -- measured
-  // 9-20 % slower than the two independent 128x64 workgroups: 239-249 vs 219-225 us, with a residual 348-357 vs 292-297)
-  if (v == 3) return launch_win<128, 64, 2, 1, 1>(a, st, out_split != 0);
-  if (v == 4) return launch_win<256, 64, 4, 1, 1>(a, st, out_split != 0);
-  return launch_win<128, 64, 2, 2, 2>(a, st, out_split != 0);
 }

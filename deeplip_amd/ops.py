@@ -48,6 +48,19 @@ def conv_out_size(n: int, k: int, stride: int, pad: int, dil: int) -> int:
     return (n + 2 * pad - dil * (k - 1) - 1) // stride + 1
 
 
+def _conv_desc(N, H, W, C, K, R, S, stride, pad, dil, ldx=None, ldy=None, ldr=0) -> ConvDesc:
+    return ConvDesc(N, H, W, C, K, R, S, stride[0], stride[1], pad[0], pad[1], dil[0], dil[1], conv_out_size(H, R, stride[0], pad[0], dil[0]),
+                    conv_out_size(W, S, stride[1], pad[1], dil[1]), C if ldx is None else ldx, K if ldy is None else ldy, ldr)
+
+
+def _conv_label(d: ConvDesc, mode: int, epilogue: int, tag: str = "", C2: int = 0, unaligned: bool = False) -> str:
+    """The kernel instance this launch runs on, as a profiler names it: dlip_conv_route's answer (mode, epilogue: see the header)."""
+    kind, bm, bn = C.c_int32(), C.c_int32(), C.c_int32()
+    call("dlip_conv_route", C.byref(d), mode, epilogue, C2, int(unaligned), C.byref(kind), C.byref(bm), C.byref(bn))
+    name = ("conv_igemm_f16x3_dma_kernel", "conv_win_f16x3_kernel", "conv_rows_f16x3_kernel", "conv_igemm_f16x3_kernel", "conv_igemm_f32_kernel")[kind.value]
+    return f"{name}<{bm.value},{bn.value}{tag}>"
+
+
 def conv_nhwc(x: Tensor, w_krsc: Tensor, bias: Optional[Tensor] = None, *, stride=(1, 1), pad=(0, 0),
               dil=(1, 1), residual: Optional[Tensor] = None, slope: Optional[Tensor] = None,
               post_scale: Optional[Tensor] = None, post_shift: Optional[Tensor] = None,
@@ -97,22 +110,14 @@ def conv_nhwc(x: Tensor, w_krsc: Tensor, bias: Optional[Tensor] = None, *, strid
             raise ValueError("conv_nhwc: split input needs channel counts / offsets in multiples of 32")
         if out_split and (K % 32 or out.shape[3] % 32 or out_channel_offset % 32):
             raise ValueError("conv_nhwc: split output needs channel counts / offsets in multiples of 32")
-    d = ConvDesc(N, H, W, Cin, K, R, S, stride[0], stride[1], pad[0], pad[1], dil[0], dil[1], Ho, Wo,
-                 Cx, out.shape[3], residual.shape[3] if residual is not None else 0)
+    d = _conv_desc(N, H, W, Cin, K, R, S, stride, pad, dil, Cx, out.shape[3], residual.shape[3] if residual is not None else 0)
     xp = x.data_ptr() + 4 * in_channel_offset
     yp = out.data_ptr() + 4 * out_channel_offset
     hook = LAUNCH_HOOK
     if hook is not None:
-        bm, bn = C.c_int32(), C.c_int32()
-        mode = 0 if w_scale is None else (3 if x_split else 1)
-        call("dlip_conv_plan", C.byref(d), mode, C.byref(bm), C.byref(bn))
-        kname = ("conv_igemm_f32_kernel", "conv_igemm_f16x3_kernel", "", "conv_igemm_f16x3_dma_kernel")[mode]
-        kind = lib().dlip_conv_kernel_kind(C.byref(d)) if mode == 3 else 0
-        if kind == 1:
-            kname, bm.value, bn.value = "conv_win_f16x3_kernel", 128, (128 if K > 64 else 64)
-        elif kind == 2:      # the rows kernel (the speech encoder's 1-D valid convolutions and k = 1 layers)
-            kname = "conv_rows_f16x3_kernel"
-        tok = hook.begin(f"{kname}<{bm.value},{bn.value}>", 2.0 * N * Ho * Wo * K * R * S * Cin)
+        unaligned = yp % 16 != 0 or (residual is not None and residual.data_ptr() % 16 != 0)
+        tok = hook.begin(_conv_label(d, 0 if w_scale is None else (3 if x_split else 1), 3 if stats is not None else int(out_split), unaligned=unaligned),
+                         2.0 * N * Ho * Wo * K * R * S * Cin)
     if stats is not None:
         # the convolution's epilogue also leaves the column sums of y (dlip_conv_nhwc_stats_f16x3): conv_stats_chunks(...) said it can
         _req(stats, "stats", torch.float64)
@@ -135,10 +140,7 @@ def conv_nhwc(x: Tensor, w_krsc: Tensor, bias: Optional[Tensor] = None, *, strid
 def conv_stats_chunks(N, H, W, Cin, K, R, S, stride=(1, 1), pad=(0, 0), dil=(1, 1)) -> int:
     """How many partial rows conv_nhwc(..., stats=...) writes for this split-input, fp32-output launch (0: no statistics epilogue
     for the shape -- launch the plain convolution and let the BatchNorm make its own pass)."""
-    Ho = conv_out_size(H, R, stride[0], pad[0], dil[0])
-    Wo = conv_out_size(W, S, stride[1], pad[1], dil[1])
-    d = ConvDesc(N, H, W, Cin, K, R, S, stride[0], stride[1], pad[0], pad[1], dil[0], dil[1], Ho, Wo, Cin, K, 0)
-    return int(lib().dlip_conv_stats_chunks(C.byref(d)))
+    return int(lib().dlip_conv_stats_chunks(C.byref(_conv_desc(N, H, W, Cin, K, R, S, stride, pad, dil))))
 
 
 def conv2_nhwc(x: Tensor, x2: Tensor, w_split: Tensor, bias: Tensor, w_scale: Tensor, *, stride=(1, 1), pad=(0, 0),
@@ -155,8 +157,8 @@ def conv2_nhwc(x: Tensor, x2: Tensor, w_split: Tensor, bias: Tensor, w_scale: Te
     R = S = 3 if (RSC - C2) == 9 * Cx else 1
     if N2 != N or RSC != R * S * Cx + C2 or Cx % 32 or C2 % 32:
         raise ValueError(f"conv2_nhwc: weights {tuple(w_split.shape)} do not match x {tuple(x.shape)} + x2 {tuple(x2.shape)}")
-    Ho = conv_out_size(H, R, stride[0], pad[0], dil[0])
-    Wo = conv_out_size(W, S, stride[1], pad[1], dil[1])
+    d = _conv_desc(N, H, W, Cx, K, R, S, stride, pad, dil, ldr=K if residual is not None else 0)
+    Ho, Wo = d.Ho, d.Wo
     if (Ho - 1) * stride2[0] >= H2 or (Wo - 1) * stride2[1] >= W2:
         raise ValueError("conv2_nhwc: the shortcut source does not cover the output grid")
     if out_split and K % 32:
@@ -164,14 +166,9 @@ def conv2_nhwc(x: Tensor, x2: Tensor, w_split: Tensor, bias: Tensor, w_scale: Te
     out = _empty((N, Ho, Wo, K), x.device)
     if residual is not None and tuple(residual.shape) != (N, Ho, Wo, K):
         raise ValueError("conv2_nhwc: residual shape")
-    d = ConvDesc(N, H, W, Cx, K, R, S, stride[0], stride[1], pad[0], pad[1], dil[0], dil[1], Ho, Wo, Cx, K,
-                 K if residual is not None else 0)
     hook = LAUNCH_HOOK
     if hook is not None:
-        bm, bn = C.c_int32(), C.c_int32()
-        call("dlip_conv_plan", C.byref(d), 3, C.byref(bm), C.byref(bn))
-        kname = "conv_rows_f16x3_kernel" if lib().dlip_conv_kernel_kind(C.byref(d)) == 2 else "conv_igemm_f16x3_dma_kernel"
-        tok = hook.begin(f"{kname}<{bm.value},{bn.value},dual>", 2.0 * N * Ho * Wo * K * (R * S * Cx + C2))
+        tok = hook.begin(_conv_label(d, 3, int(out_split), ",dual", C2), 2.0 * N * Ho * Wo * K * (R * S * Cx + C2))
     _lib.ensure_conv_workspace()
     call("dlip_conv2_nhwc_f16x3", C.byref(d), x, x2, H2, W2, C2, C2, stride2[0], stride2[1], w_split, w_scale, bias, residual, slope, None, None, out,
          1 | 2 * int(out_split))
@@ -214,9 +211,7 @@ def conv_pool_tile_rows(x: Tensor, w_krsc: Tensor, *, stride=(1, 1), pad=(0, 0),
     """Rows of the workgroup tile conv_pool would use for this launch (group_rows must be >= it)."""
     N, H, W, Cx = x.shape
     K, R, S, Cw = w_krsc.shape
-    Ho = conv_out_size(H, R, stride[0], pad[0], dil[0])
-    Wo = conv_out_size(W, S, stride[1], pad[1], dil[1])
-    d = ConvDesc(N, H, W, Cx, K, R, S, stride[0], stride[1], pad[0], pad[1], dil[0], dil[1], Ho, Wo, Cx, K, 0)
+    d = _conv_desc(N, H, W, Cx, K, R, S, stride, pad, dil)
     bm = C.c_int32()
     if int(lib().dlip_conv_pool_partial_bytes(C.byref(d), C.byref(bm))) <= 0:
         raise _lib.DeepLipHipError("dlip_conv_pool_partial_bytes failed")
@@ -240,12 +235,10 @@ def conv_pool(x: Tensor, w_krsc: Tensor, bias: Optional[Tensor], w_scale: Tensor
     K, R, S, Cw = w_krsc.shape
     if Cx % 32 or Cw != Cx:
         raise ValueError("conv_pool: split-format input with C % 32 == 0 and matching split weights required")
-    Ho = conv_out_size(H, R, stride[0], pad[0], dil[0])
-    Wo = conv_out_size(W, S, stride[1], pad[1], dil[1])
+    d = _conv_desc(N, H, W, Cx, K, R, S, stride, pad, dil, ldr=K if residual is not None else 0)
+    Ho, Wo = d.Ho, d.Wo
     if residual is not None and (tuple(residual.shape[:3]) != (N, Ho, Wo) or residual.shape[3] != K or K % 32):
         raise ValueError("conv_pool: residual shape")
-    d = ConvDesc(N, H, W, Cx, K, R, S, stride[0], stride[1], pad[0], pad[1], dil[0], dil[1], Ho, Wo, Cx, K,
-                 K if residual is not None else 0)
     bm = C.c_int32()
     nbytes = int(lib().dlip_conv_pool_partial_bytes(C.byref(d), C.byref(bm)))
     if nbytes <= 0:
@@ -255,10 +248,7 @@ def conv_pool(x: Tensor, w_krsc: Tensor, bias: Optional[Tensor], w_scale: Tensor
     part = _empty((nbytes // 8,), x.device, torch.float64)
     hook = LAUNCH_HOOK
     if hook is not None:
-        # the rows kernel (pooled launches go there only when it is forced: dlip_debug_set) reports HALF its tile as partial rows
-        rows = residual is None and _lib.DEBUG.get(_lib.DBG_ROWS, -1) > 0 and lib().dlip_conv_kernel_kind(C.byref(d)) == 2
-        tok = hook.begin(f"conv_rows_f16x3_kernel<{2 * bm.value},256,pool>" if rows else f"conv_igemm_f16x3_dma_kernel<{bm.value},128,pool>",
-                         2.0 * N * Ho * Wo * K * R * S * Cx)
+        tok = hook.begin(_conv_label(d, 3, 2, ",pool"), 2.0 * N * Ho * Wo * K * R * S * Cx)
     _lib.ensure_conv_workspace()
     call("dlip_conv_pool_f16x3", C.byref(d), x, w_krsc, w_scale, bias, residual, slope, post_scale, post_shift, part, nbytes, group_rows, lengths,
          len_mul, len_add)

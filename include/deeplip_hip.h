@@ -116,8 +116,8 @@ int dlip_conv_nhwc_f16x3(DLIP_HOST const dlip_conv_desc* d, const float* x, cons
  * the y it writes: stats [chunks][K][2] fp64 = per chunk of output rows {sum y, sum y^2} -- the batch statistics of the BatchNorm
  * behind a convolution under model.train() (models/audio_models/tdnn.py:35-43: Conv1d -> BatchNorm1d), without the pass over y that
  * dlip_bn_rows_train_fwd_f32 would otherwise make (hand it `stats` as its workspace and `chunks` as ready_chunks).
- * dlip_conv_stats_chunks(d): how many chunks such a launch of `d` writes, or 0 when this shape has no statistics epilogue (today:
- * the rows kernel's shapes -- 1-D valid convolutions and k = 1 GEMMs; the caller then launches the plain convolution).  Within a
+ * dlip_conv_stats_chunks(d): how many chunks such a launch of `d` writes (two per row tile of its route, dlip_conv_route(d, 3, 3, ..)),
+ * or 0 when this shape has no statistics epilogue (today: all but the rows kernel's; the caller then launches the plain convolution).  Within a
  * chunk (half a tile: <= 80 rows) the sums are fp32 in a fixed order; across chunks the finalize kernel adds in fp64. */
 int32_t dlip_conv_stats_chunks(DLIP_HOST const dlip_conv_desc* d);
 int dlip_conv_nhwc_stats_f16x3(DLIP_HOST const dlip_conv_desc* d, const float* x, const void* w_split, const float* w_scale,
@@ -137,8 +137,8 @@ int dlip_conv2_nhwc_f16x3(DLIP_HOST const dlip_conv_desc* d, const float* x, con
  *           models/video_models/resnet.py:125-126, train_fusion.py:274,348 -- a mean of equal-sized means)
  *   mode 1: mean | unbiased std [G,2K] (MeanStdPooling, models/audio_models/pooling.py:24-26), optionally in the
  *           split activation format ([G, 2K rounded up to 32], what fc1's kernel reads).
- * partials: caller-owned, dlip_conv_pool_partial_bytes(d, &tile_rows) bytes (8-byte aligned); group_rows must be
- * >= tile_rows (a tile then holds at most one group boundary) -- callers fall back to the unfused kernels
+ * partials: caller-owned, dlip_conv_pool_partial_bytes(d, &tile_rows) bytes (8-byte aligned): the partial bands of the launch's route,
+ * dlip_conv_route(d, 3, 2, ..), tile_rows rows each; group_rows must be >= tile_rows (a band then holds at most one group boundary) -- callers fall back to the unfused kernels
  * otherwise.  Sums are formed in a fixed order: results do not depend on scheduling.
  * RAGGED BATCHES (ABI 43).  The reference extracts one utterance / one clip at a time at its own length
  * (train_fusion.py:334-349: audio [1,24,T_i], clips [1,1,T_j,88,88]); a batch of them is the zero-padded tensor +
@@ -180,16 +180,19 @@ int dlip_conv_set_workspace(void* ptr, int64_t bytes, dlip_stream_t stream);
 int dlip_split_pack_f32(const float* x, float* y, int64_t rows, int32_t C, dlip_stream_t stream);
 int dlip_split_unpack_f32(const float* x, float* y, int64_t rows, int32_t C, dlip_stream_t stream);
 
-/* Reports the workgroup tile (BM x BN) dlip_conv_nhwc_f32 (split_f16 = 0), dlip_conv_nhwc_f16x3 on
- * fp32 activations (split_f16 = 1) or on split-format activations (split_f16 = 3: the LDS-DMA
- * kernel) will use for `d` -- i.e. which conv_igemm_*_kernel<BM,BN,..> instance a profiler will
- * show.  Host-only, no launch. */
+/* Which kernel and workgroup tile a convolution launch of `d` runs on -- the instance a profiler will show.  Host-only, no launch:
+ * the launches execute the answer of the same function (the kernels, the order, every condition).
+ *   mode      0 dlip_conv_nhwc_f32, 1 dlip_conv_nhwc_f16x3 on fp32 activations, 3 on split-format activations (DLIP_SPLIT_IN)
+ *   epilogue  0 fp32 y, 1 split-format y, 2 pooled partials (dlip_conv_pool_f16x3), 3 y + column sums (DLIP_EINVAL: the shape has none)
+ *   C2        channels of dlip_conv2_nhwc_f16x3's second source, or 0;  unaligned != 0: y or the residual is off 16 bytes;  d->ldr
+ *             != 0 says that a residual is added (dlip_conv_nhwc_f16x3 goes by the pointer: pass ldr = 0 without one)
+ *   *kind     0 LDS-DMA ring, 1 window, 2 rows, 3 register-staged conv_igemm_f16x3_kernel (also: split input with an fp32 y whose K
+ *             or ldy is no multiple of 4), 4 conv_igemm_f32_kernel;  *bm, *bn: that instance's tile */
+int dlip_conv_route(DLIP_HOST const dlip_conv_desc* d, int32_t mode, int32_t epilogue, int32_t C2, int32_t unaligned,
+                    DLIP_HOST int32_t* kind, DLIP_HOST int32_t* bm, DLIP_HOST int32_t* bn);
+/* dlip_conv_route(d, split_f16, 0, 0, 0, ..)'s tile: of whichever kernel serves the launch (window, register-staged at K % 4 != 0, ..). */
 int dlip_conv_plan(DLIP_HOST const dlip_conv_desc* d, int32_t split_f16, DLIP_HOST int32_t* bm, DLIP_HOST int32_t* bn);
-/* 1 if a split-format (DLIP_SPLIT_IN) launch of `d` runs on the window kernel (conv_win_f16x3_kernel<128,64> for K <= 64, <128,128> above: same-size
- * stride-1 3x3 convolutions with K <= 128 -- one activation window per channel slice in LDS instead of one fetch per
- * tap), 2 if on the rows kernel (conv_rows_f16x3_kernel; dlip_conv_plan then reports its BM x 256 tile): without a residual the
- * speech encoder's 1-D valid convolutions and k = 1 GEMMs over all frames), 0 if on the LDS-DMA ring kernel dlip_conv_plan describes.
- * Host-only. */
+/* dlip_conv_route(d, 3, 0, 0, 0, ..)'s kind where it is 1 (window) or 2 (rows); 0 for every other kernel (so at K % 4 != 0 with an fp32 y). */
 int dlip_conv_kernel_kind(DLIP_HOST const dlip_conv_desc* d);
 
 /* ------------------------------------------------------------------------------------------

@@ -109,7 +109,7 @@ def test_derived_signatures_match_handwritten_expectations():
 HOST_POINTERS = {   # every parameter the CPU dereferences (DLIP_HOST in the header): function -> argument positions
     "dlip_conv_nhwc_f32": [0], "dlip_conv_nhwc_f16x3": [0], "dlip_conv_nhwc_stats_f16x3": [0], "dlip_conv2_nhwc_f16x3": [0],
     "dlip_conv_pool_f16x3": [0], "dlip_conv_pool_partial_bytes": [0, 1], "dlip_conv_stats_chunks": [0], "dlip_conv_plan": [0, 2, 3],
-    "dlip_conv_kernel_kind": [0], "dlip_span_scope_end": [1], "dlip_plan_end": [1], "dlip_chomp_concat_f32": [0, 1, 2],
+    "dlip_conv_kernel_kind": [0], "dlip_conv_route": [0, 5, 6, 7], "dlip_span_scope_end": [1], "dlip_plan_end": [1], "dlip_chomp_concat_f32": [0, 1, 2],
     "dlip_tcn_dw_fwd_f32": [2, 3, 4, 5, 6, 7, 8], "dlip_tcn_dw_dgrad_f32": [0, 2, 3, 4, 5], "dlip_tcn_dw_wgrad_f32": [2, 3, 4, 5, 6],
 }
 
@@ -124,7 +124,7 @@ def test_host_pointers_are_exactly_the_marked_ones():
         if pos:
             got[name] = pos
     assert got == HOST_POINTERS
-    assert sum(len(v) for v in got.values()) == 34
+    assert sum(len(v) for v in got.values()) == 38
 
 
 def _parse(text):
