@@ -1496,6 +1496,56 @@ int dlip_sinc_features_bwd_f32(const float* wave, const int32_t* lengths, const 
                                int32_t frame_step, int32_t NF, int32_t layout, int32_t Fp, dlip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * (ABI 67, added) LIP-CLIP AUGMENTATION ON THE DEVICE: time masks, cutout, mixup -- the training-time stage between the loader's frames
+ * and the stem (train_video.py's --time-masks / --cutouts / --mixup-alpha; deeplip_amd.clip_augment.ClipAugment).  Nothing upstream
+ * defines the stage: this block and DESIGN.md 4m are the definition, tests/clip_augment_ref.py restates it in numpy.
+ *
+ * Sources.  dlip_clip_augment_u8: uint8 frames [B, T, channels, Hs, Ws] (channels 1 gray | 3 RGB) with `crop`, `clip_params` (device
+ *   int32 [B][4] = (oy, ox, flip, 0), clamped into the frame; NULL: the centre crop) and `lengths` exactly as dlip_crop_normalize_u8
+ *   takes them; the base pixel is dlip_crop_normalize_u8's (BT.601 gray, (g / 255 - 0.421) / 0.165, contraction off), so an
+ *   un-augmented pixel has its bits.  dlip_clip_augment_f32: float clips x [B, 1, T, H, W], already normalised, no crop and no flip
+ *   (crop below = H, W).  Output y fp32 [B, 1, T, crop, crop] ([B, 1, T, H, W]); y must not be the source.
+ * The augmented clip.  A_b = the cropped, flipped, normalised clip of row b, n_b = clamp(lengths[b], 1, T) (T when lengths is NULL);
+ *   frames t >= n_b of the source are never loaded and frames t >= n_b of y are exact zeros.  `draws`: device int32
+ *   [B, DLIP_CLIPAUG_DRAWS], DLIP_CLIPAUG_DRAWS = 6 DLIP_CLIPAUG_MAX_MASKS, each word a 31-bit uniform integer (negatives count as 0) the
+ *   DEVICE resolves with pick(r, m) = (int64(r) m) >> 31, in [0, m): words [2 i], [2 i + 1] = (width, start) of time mask i, words
+ *   [2 MAX + 4 j .. + 3] = (height, width, top, left) of cutout j; slots past n_time / n_cut are ignored.
+ *   1. Fill value f_b: 0 for fill = 0; for fill = 1 the mean of A_b over its n_b crop crop pixels before any masking, accumulated in
+ *      fp64 in one fixed order and rounded ONCE to fp32: a first launch writes one fp64 partial per (clip, chunk of
+ *      DLIP_CLIPAUG_MEAN_FRAMES frames) into the workspace, the write pass adds the chunks below ceil(n_b / FRAMES) in index order.  No
+ *      atomics: two runs and a replay have the same bits, and so has the row in any batch.
+ *   2. Time mask i < n_time: cap = min(time_width, (int)floor(time_ratio (double)n_b)) (the product in fp64, as dlip_spec_augment_f32
+ *      forms it), w = pick(r, cap + 1), t0 = pick(r', n_b - w + 1): frames [t0, t0 + w) become f_b.
+ *   3. Cutout j < n_cut: h = min(pick(r, cut_size + 1), crop), w likewise, y0 = pick(r'', crop - h + 1), x0 = pick(r''', crop - w + 1):
+ *      the rectangle [y0, y0 + h) x [x0, x0 + w) in OUTPUT coordinates (after the flip), the same in every frame t < n_b, becomes f_b.
+ *   4. Mixup (perm and lam both non-NULL; both NULL: none): perm device int32 [B], lam device float [1].  p = perm[b]; p outside
+ *      [0, B) or p == b: no partner, row b is A'_b (the result of 1-3) unblended.  Else for t < n_b
+ *        y_b[t] = (lam A'_b[t]) + (mu A'_p[t]),   mu = 1 - lam in fp32,   A'_p[t] = 0 for t >= n_p,
+ *      two fp32 products and one fp32 sum, contraction off (numpy float32 reproduces it bit for bit).  Frames t >= n_b stay zero.
+ *   With mixup off every row has the bits of the row run alone with its own draws; with mixup on each operand has.
+ * Launches: the mean pass (fill = 1 only; grid (chunk, clip)) and the write pass (grid (tile of 256 quads, frame, clip)): a lane
+ *   forms four adjacent output pixels of both operands straight from the source bytes (one 4-byte word per colour plane, reversed
+ *   under a flip, re-aligned for an odd ox) and stores one float4; no intermediate float clip exists; a lane whose quad is filled
+ *   whole reads nothing of that clip.  crop (W) must be a multiple of 4.
+ * DLIP_EINVAL before any launch: B or T outside [1, 65535], crop < 4 or crop % 4 != 0, channels not 1 or 3, Hs or Ws < crop, a mask
+ *   count outside [0, DLIP_CLIPAUG_MAX_MASKS], a negative width or size (cut_size <= 2^30), time_ratio outside [0, 1] or NaN, fill
+ *   outside {0, 1}, exactly one of perm / lam NULL, y == the source, y not 16-byte aligned, a null pointer (clip_params, lengths, perm,
+ *   lam excepted), a workspace that is misaligned (8 bytes) or smaller than dlip_clip_augment_workspace_bytes says.
+ * dlip_clip_augment_workspace_bytes (host only, no launch): bytes of the caller-owned workspace; negative on bad sizes.
+ * ------------------------------------------------------------------------------------------ */
+#define DLIP_CLIPAUG_MAX_MASKS 4
+#define DLIP_CLIPAUG_DRAWS 24      /* 6 * DLIP_CLIPAUG_MAX_MASKS */
+#define DLIP_CLIPAUG_MEAN_FRAMES 1
+int64_t dlip_clip_augment_workspace_bytes(int32_t B, int32_t T);
+int dlip_clip_augment_u8(const uint8_t* frames, const int32_t* clip_params, const int32_t* lengths, const int32_t* draws,
+                         const int32_t* perm, const float* lam, float* y, void* workspace, int64_t workspace_bytes, int32_t B, int32_t T,
+                         int32_t channels, int32_t Hs, int32_t Ws, int32_t crop, int32_t n_time, int32_t time_width, double time_ratio,
+                         int32_t n_cut, int32_t cut_size, int32_t fill, dlip_stream_t stream);
+int dlip_clip_augment_f32(const float* x, const int32_t* lengths, const int32_t* draws, const int32_t* perm, const float* lam, float* y,
+                          void* workspace, int64_t workspace_bytes, int32_t B, int32_t T, int32_t H, int32_t W, int32_t n_time,
+                          int32_t time_width, double time_ratio, int32_t n_cut, int32_t cut_size, int32_t fill, dlip_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Step plans. The reference drives its encoders from a Python loop, one utterance and one torch.nn layer
  * at a time (train_fusion.py:338-358 extraction, :262-293 training step); here a step is ~45 short kernels
  * and the host must not sit between them.  A plan records every dlip_* launch made on `stream` between

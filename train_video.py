@@ -22,6 +22,8 @@ loop of eager launches; deeplip_amd/train_plan.py), the next batch's host-to-dev
 on the device between ``--display`` points; ``--arith auto|f16x3|f32`` (default: $DLIP_ARITH, the config's "arith", auto) picks the
 engine's arithmetic (deeplip_amd/arith.py).  ``--device cpu`` runs the plumbing only (config -> model -> batches -> optimiser/scheduler ->
 checkpoint round trip) because the engine has no CPU arithmetic by design.
+``--time-masks`` / ``--cutouts`` / ``--mixup-alpha`` (with their widths, ``--mask-fill``; all off by default) augment the full-model training
+batches on the device (deeplip_amd/clip_augment.py): time masks, cutout, and mixup with the mixed criterion.
 """
 from __future__ import annotations
 
@@ -86,9 +88,35 @@ def load_args(argv=None):
     p.add_argument("--data-cache", type=int, default=0, metavar="N",
                    help="synthetic source: generate N batches once, keep them in pinned host memory and cycle through them (the numpy "
                         "generator makes ~30 clips/s; a run that measures the TRAINER rather than the generator uses this)")
+    # training-time augmentation of the clips on the device (deeplip_amd/clip_augment.py): all off by default
+    p.add_argument("--time-masks", type=int, default=0, help="time masks per clip (frames replaced by the fill value)")
+    p.add_argument("--time-mask-width", type=int, default=0, help="the widest time mask, in frames")
+    p.add_argument("--time-mask-ratio", type=float, default=1.0, help="a time mask is no wider than this share of its clip")
+    p.add_argument("--cutouts", type=int, default=0, help="cutout rectangles per clip (the same rectangle in every frame)")
+    p.add_argument("--cutout-size", type=int, default=0, help="the largest side of a cutout, in pixels of the 88 x 88 crop")
+    p.add_argument("--mask-fill", type=str, default="mean", choices=["zero", "mean"], help="what a masked pixel holds: 0 or the clip's own mean")
+    p.add_argument("--mixup-alpha", type=float, default=0.0, help="> 0: mixup of clip pairs, lam ~ Beta(alpha, alpha) per batch, mixed criterion")
     from deeplip_amd import arith
     arith.add_argument(p)
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    args.clip_augment = clip_augment_options(args)
+    return args
+
+
+def clip_augment_options(args):
+    """The keyword arguments of ``deeplip_amd.clip_augment.ClipAugment`` the augmentation flags name, or None with every one of them
+    at its off value (the run is then today's, launch for launch).  A set of flags that would do nothing, a value out of range and
+    ``--head-only`` beside them raise ValueError."""
+    if not (args.time_masks or args.time_mask_width or args.cutouts or args.cutout_size or args.mixup_alpha):
+        return None
+    from deeplip_amd.clip_augment import ClipAugment
+    kw = dict(time_masks=args.time_masks, time_width=args.time_mask_width, time_ratio=args.time_mask_ratio, cutouts=args.cutouts,
+              cut_size=args.cutout_size, fill=args.mask_fill, mixup_alpha=args.mixup_alpha, crop=88)
+    ClipAugment(**kw)           # validates
+    if args.head_only:
+        raise ValueError("train_video: the clip augmentation flags apply to full-model training batches; --head-only trains on frozen "
+                         "eval-mode features")
+    return kw
 
 
 def load_json(path):
@@ -131,6 +159,13 @@ def synthetic_batch(args, it, rgb=False):
     return pad_packed_collate(items)
 
 
+def mixed_ce_loss(logits, labels_a, labels_b, lam):
+    """Mixup's criterion: lam CE(logits, a) + (1 - lam) CE(logits, b), ``lam`` a float32 device tensor [1] read on the device (a
+    recorded step follows new draws without being re-recorded)."""
+    from deeplip_amd import autograd as ag
+    return lam[0] * ag.margin_ce_loss(logits, labels_a, 1.0, 0.0) + (1.0 - lam[0]) * ag.margin_ce_loss(logits, labels_b, 1.0, 0.0)
+
+
 def extract_feats(model, clip_thw, device):
     """:99-106: model(FloatTensor(data)[None,None], lengths=[T]) with extract_feats=True."""
     model.eval()
@@ -166,6 +201,11 @@ def train(model, args, device):
     last = None
     aug_rng = random.Random(SEED + rank)      # the train pipeline's crop / flip draws (the reference: the `random` module, preprocess.py)
     frontend = None
+    aug = aug_np = None
+    if full and getattr(args, "clip_augment", None):
+        from deeplip_amd.clip_augment import ClipAugment
+        aug = ClipAugment(**args.clip_augment)     # replaces the VideoFrontend call under --rgb, acts on the float clip otherwise
+        aug_np = np.random.default_rng(SEED + rank)
     if device.type == "cpu" and rank == 0:
         print("[plumbing] --device cpu exercises config / collate / optimizer / scheduler / checkpoint plumbing ONLY (BASELINE config C1): the "
               "engine has no CPU arithmetic path by design, so no forward runs and no loss or logits exist here; the same command on "
@@ -174,25 +214,28 @@ def train(model, args, device):
     if graph_step:
         from deeplip_amd.train_plan import ShapeKeyedSteps, grad_witness, step_state
 
-        def one_step(xb, lb, ln):
+        def one_step(xb, lb, ln, mix=None):
             if buckets is None:
                 optimizer.zero_grad(set_to_none=True)
             else:
                 buckets.zero()                       # the gradients are views into the buckets: cleared in place
             lg = model(xb, lengths=ln)
-            ls = ag.margin_ce_loss(lg, lb, 1.0, 0.0)
+            ls = mixed_ce_loss(lg, lb, *mix) if mix is not None else ag.margin_ce_loss(lg, lb, 1.0, 0.0)
             ls.backward()                            # bucket all-reduces start from the hooks as the gradients land
             if buckets is not None:
                 buckets.finish()
             optimizer.step()
             return ls, lg
 
+        def one_step_mix(xb, la, lb, lam, ln):       # mixup: the mixed criterion, lam read from its device tensor on every replay
+            return one_step(xb, la, ln, mix=(lb, lam))
+
         # One recorded step per batch shape (pad_packed_collate pads to the batch's longest clip, dataset.py:123-139: a run meets a
         # few shapes); a shape's first step runs eagerly, its second records.  In a job of several ranks the first replay is
         # checked against an eager step from the same state and the run falls back to eager steps on any doubt (train_plan.py).
         # (with GradBuckets the branches stay on one stream: a bucket's all-reduce is enqueued behind the CURRENT stream of the hook
         # that completes it, and would not wait for gradients another branch stream is still writing)
-        plan = ShapeKeyedSteps(one_step, eager_steps=1, device=device, branch_streams=buckets is None,
+        plan = ShapeKeyedSteps(one_step_mix if aug is not None and aug.mixup else one_step, eager_steps=1, device=device, branch_streams=buckets is None,
                                state=step_state([model], [optimizer], buckets), witness=grad_witness([model], buckets))
     source = _BatchSource(args, world, rank, device)
     copy_stream = torch.cuda.Stream(device=device) if device.type != "cpu" else None
@@ -210,9 +253,10 @@ def train(model, args, device):
             cp = None
             if args.rgb and full:
                 cp = torch.from_numpy(ops.draw_clip_params(inputs.shape[0], inputs.shape[-2], inputs.shape[-1], 88, rng=aug_rng)).to(device, non_blocking=True)
+            ap = aug.to_device(aug.draw(inputs.shape[0], aug_np), device) if aug is not None else None
             ev = torch.cuda.Event()
             ev.record(copy_stream)
-        return raw, lab, ln, cp, lengths, ev
+        return raw, lab, ln, cp, lengths, ev, ap
 
     total_steps = int(args.maxepoch) * args.steps
     staged = stage(0) if device.type != "cpu" and total_steps > 0 else None
@@ -235,13 +279,19 @@ def train(model, args, device):
             if gi == mark_at:
                 torch.cuda.synchronize(device)
                 t_mark = time.perf_counter()
-            raw, labels, ln, cp, lengths, ev = staged
+            raw, labels, ln, cp, lengths, ev, ap = staged
             cur = torch.cuda.current_stream(device)
             cur.wait_event(ev)
-            for t in (raw, labels, ln, cp):
+            for t in (raw, labels, ln, cp) + tuple((ap or {}).values()):
                 if t is not None:
                     t.record_stream(cur)
-            if args.rgb:
+            mix = None
+            if aug is not None:
+                # time masks, cutout and mixup from the loader's frames (under --rgb with the crop and flip drawn above), one stage
+                x = aug(raw, clip_params=cp, lengths=ln, params=ap) if args.rgb else aug(raw.unsqueeze(1), lengths=ln, params=ap)
+                if aug.mixup:
+                    mix = aug.mix_targets(labels, ap)
+            elif args.rgb:
                 # uint8 frames -> normalised 88 x 88 gray clips on the GPU: RandomCrop + HorizontalFlip per clip while the model
                 # trains (dataloaders.py:13-17), CenterCrop otherwise (:19-24); padding frames = zeros of the normalised clip
                 from deeplip_amd.frontend import VideoFrontend
@@ -250,7 +300,7 @@ def train(model, args, device):
             else:
                 x = raw.unsqueeze(1)                                                                    # :125
             if plan is not None:
-                loss, logits = plan.step(x.contiguous(), labels, ln)
+                loss, logits = plan.step(x.contiguous(), *mix, ln) if mix is not None else plan.step(x.contiguous(), labels, ln)
             else:
                 optimizer.zero_grad(set_to_none=buckets is None)
                 if full:
@@ -259,7 +309,7 @@ def train(model, args, device):
                     with torch.no_grad():
                         pooled = model.classifier_features(x, lengths)         # frozen stem + trunk + MS-TCN
                     logits = ag.linear(pooled, head.weight, head.bias)          # tcn_output (model.py:27)
-                loss = ag.margin_ce_loss(logits, labels, 1.0, 0.0)              # nn.CrossEntropyLoss (:115,143)
+                loss = mixed_ce_loss(logits, *mix) if mix is not None else ag.margin_ce_loss(logits, labels, 1.0, 0.0)   # nn.CrossEntropyLoss (:115,143)
                 loss.backward()
                 if buckets is not None:
                     buckets.finish()                                            # wait for the bucket all-reduces, average
@@ -269,7 +319,10 @@ def train(model, args, device):
             n_b = labels.shape[0]
             _, pred = torch.max(torch.softmax(logits.detach(), 1), 1)           # (:145)
             acc[0] += loss.detach().double() * n_b
-            acc[1] += (pred == labels).sum()
+            if mix is None:
+                acc[1] += (pred == labels).sum()
+            else:           # the mixed criterion's accuracy: lam (pred == a) + (1 - lam) (pred == b)
+                acc[1] += mix[2][0].double() * (pred == mix[0]).sum() + (1.0 - mix[2][0].double()) * (pred == mix[1]).sum()
             acc[2] += n_b
             last_loss, last_shape = loss.detach().clone(), tuple(logits.shape)
             staged = stage(gi + 1) if gi + 1 < total_steps else None            # the next batch's copies run behind this step
