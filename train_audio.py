@@ -18,7 +18,7 @@ models/audio_models/datasets.py:112-115) and the optimisation step is recorded o
 (``train.graph_step``, ``--eager-step``); ragged test lists go through ONE extractor per trainer; ``--arith`` / ``model.arith`` pick the
 arithmetic (deeplip_amd/arith.py: auto = f16x3 with an in-process f32 re-run -- and calibration -- of what leaves its range).  The run
 plumbing (config + ``--set``, self-launch, run name, optimizer, ``main()``'s tail) and the speech input chain of extraction (front-end,
-voiced frames, encoder, the kept extractor) are deeplip_amd/trainer_common.py's, shared with train_fusion.py.
+voiced frames, encoder, the kept extractor) are deeplip_amd/trainer_common.py's, the pieces of the step loop deeplip_amd/train_loop.py's.
 
 Data parallelism (the reference wraps the model in nn.DataParallel over ``gpus_id``, train_audio.py:80-83): launched
 under ``torch.distributed.run`` every rank draws its own batches, replicas start from rank 0's weights, gradients are
@@ -38,7 +38,7 @@ import torch
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-from deeplip_amd import _lib, arith, dist as ddist, ops, scoring, trainer_common as tc, weightgen as wg  # noqa: E402
+from deeplip_amd import _lib, arith, dist as ddist, ops, scoring, train_loop as tl, trainer_common as tc, weightgen as wg  # noqa: E402
 from deeplip_amd.synthetic import SyntheticAVSet, synthetic_trials  # noqa: E402
 from models.audio_models.loss import AAMSoftmax, ASoftmax, Contrastive, LMCL, CrossEntropy, OnlineTriplet  # noqa: E402
 
@@ -228,6 +228,8 @@ class Trainer(object):
         if self.spec_opts is not None:
             from deeplip_amd.spec_augment import SpecAugment
             self._spec = SpecAugment(device=self.device, **self.spec_opts)
+        self._ring, self._prefetch = tl.BatchRing(self._host_batch, self.train_opts.get("data_cache", 0)), tl.Prefetch(self.device)
+        self._speed_out = {}                # data.speed_perturb: width of a staged cut -> samples of its crop
 
     def _wave_stages(self, arch, feat_dim):
         """data.train_from_waves: the loaders' feature extraction (models/audio_models/datasets.py:65-83) as the GPU front-end -- MFCC
@@ -268,132 +270,90 @@ class Trainer(object):
 
     def _one_step(self, x, lab):
         """One optimisation step, launches only (what a recorded step replays): train_audio.py:185-200."""
-        if self.buckets is None:
-            self.optim.zero_grad(set_to_none=True)
-        else:
-            self.buckets.zero()
-        if self.freeze_encoder:
-            with torch.no_grad():
-                emb = self.model(x)
-        else:
-            emb = self.model(x)                       # output of bn2 / LeakyReLU (train_audio.py:187)
-        loss, logits = self.criterion(emb, lab)
-        loss.backward()                               # bucket all-reduces start as the gradients land
-        if self.buckets is not None:
-            self.buckets.finish()
-        self.optim.step()
-        if self.semi_orth is not None:
-            self.semi_orth()                          # (reads and advances its device counter: due or not is decided by the launch)
-        return loss, logits
+        def forward_loss(x, lab):
+            with torch.set_grad_enabled(not self.freeze_encoder):
+                emb = self.model(x)                   # output of bn2 / LeakyReLU (train_audio.py:187)
+            return self.criterion(emb, lab)
+        # (semi_orth behind optim.step() reads and advances its device counter: due or not is decided by the launch)
+        return tl.optim_step(forward_loss, self.optim, lambda: self.buckets, self.semi_orth)(x, lab)
 
     def _adjust_margin(self):
         if isinstance(self.criterion, (LMCL, AAMSoftmax)):
             tc.scheduled_margin(self.criterion, self.current_epoch, self.init_margin, self.end_margin)
 
+    def _host_batch(self, k, rng, ladder):
+        """A pinned host batch by name: ``x`` (one crop length of ``ladder``), ``lab`` and each configured augmentation stage's draws under
+        the names it takes them by.  Drawn from the epoch's ``rng`` in a fixed order, the optional stages last: a run without one keeps its stream."""
+        bs = self.train_opts["bs"]
+        idx = rng.integers(0, len(self.trainset), bs)
+        T = int(ladder[int(rng.integers(0, len(ladder)))])
+        draws = {}
+        if self.train_from_waves:
+            # the same crop as WAVEFORMS: frame_len + (T - 1) frame_step samples (T frames) cut from the zero-padded batch at
+            # an offset that fits the shortest row -- a rectangular batch; the augmentation's choices are drawn beside it.
+            # (feat_type stft: the loader cuts the same samples, datasets.py:113-115, and librosa.stft makes T + 2 frames of them)
+            fl, fs = self._wave_fe.frame_len, self._wave_fe.frame_step
+            Sb = fl + (T - 1) * fs
+            # data.speed_perturb: the cut is as wide as the fastest speed needs to leave Sb samples (_features cuts there)
+            Sc = Sb if self._speed is None else self._speed.in_samples(Sb)
+            wl = self.trainset.wave_len(fl, fs)[idx]
+            wav, _ = self.trainset.waves_padded(idx, S=max(int(wl.max()), Sc), frame_len=fl, frame_step=fs)
+            s0 = int(rng.integers(0, max(int(wl.min()) - Sc, 0) + 1))
+            xb = np.ascontiguousarray(wav[:, s0:s0 + Sc])
+            if self._augment is not None:
+                draws.update(self._augment.draw([Sb] * bs, rng))         # snr_db, noise_start, rir_idx
+            if self._speed is not None:
+                self._speed_out[Sc] = Sb
+                draws["speed_idx"] = self._speed.draw(bs, rng)["speed_idx"]
+        else:
+            t0_ = int(rng.integers(0, int(self.data_opts["audio_frames"]) - T + 1))
+            xb = np.ascontiguousarray(self.trainset.audio(idx)[:, :, t0_:t0_ + T])   # the batch's one crop (datasets.py:112-115)
+        if self._spec is not None:
+            draws["draws"] = self._spec.draw(bs, rng)["draws"]
+        host = {"x": xb, "lab": self.trainset.labels(idx), **draws}
+        return {n: torch.from_numpy(v).pin_memory() for n, v in host.items()}
+
+    def _features(self, b):
+        """data.train_from_waves: speed perturbation and augmentation (when configured) and front-end on the staged batch ``b``, eager
+        launches in front of the step -- Kaldi's order: the row is resampled to exactly the crop's samples, then reverberated / mixed."""
+        wave = b["x"]
+        with torch.no_grad():
+            if self._speed is not None:
+                wave, _ = self._speed(wave, params={"speed_idx": b["speed_idx"]}, out_samples=self._speed_out[wave.shape[1]])
+            if self._augment is not None:
+                wave = self._augment(wave, params={n: b[n] for n in ("snr_db", "noise_start", "rir_idx")})
+            if getattr(self.model, "sinc", None) is not None:      # arch: sincnet -- the layer runs inside the step, on the waveform itself
+                return wave
+            return self._wave_fe(wave)
+
     def _train_epoch(self):
         """train_audio.py:167-199 on the synthetic set: full-encoder step (or criterion-only with freeze_encoder)."""
         bs = self.train_opts["bs"]
         rng = np.random.Generator(np.random.PCG64([self.current_epoch, 5, self.rank]))    # every rank its own batches
-        tot = n = correct = 0.0
         self.model.train(not self.freeze_encoder)
         if ddist.active() and self.buckets is None:
-            params = [p for g in self.optim.param_groups for p in g["params"]]
-            self.buckets = ddist.GradBuckets(params)
+            self.buckets = ddist.GradBuckets([p for g in self.optim.param_groups for p in g["params"]])
         steps = self.train_opts.get("steps_per_epoch", 2)
         ladder = self.crop_ladder()
-        Ta = int(self.data_opts["audio_frames"])
-        recorded = self.graph_step and (self.buckets is None or os.environ.get("DLIP_GRAPH_WITH_BUCKETS", "1") != "0")
+        recorded = self.graph_step and tl.records_with(self.buckets)
         if recorded and self._steps is None:
-            from deeplip_amd.train_plan import ShapeKeyedSteps, grad_witness, step_state
             mods = [self.criterion] if self.freeze_encoder else [self.model, self.criterion]
             if self.semi_orth is not None:
                 mods = mods + [self.semi_orth]         # (its step counter is part of what a step mutates: snapshot / restore cover it)
-            # (with GradBuckets the branches of a step stay on one stream: see train_video.py)
-            self._steps = ShapeKeyedSteps(self._one_step, eager_steps=1, device=self.device, branch_streams=self.buckets is None,
-                                          state=step_state(mods, [self.optim], self.buckets), witness=grad_witness(mods, self.buckets))
-        acc = torch.zeros(3, dtype=torch.float64, device=self.device)          # loss * n, correct, n: read once per epoch
-        # ONE copy stream for the trainer's lifetime: torch's caching allocator keeps a pool per stream, so a stream per epoch left every
-        # epoch's batch buffers reserved for ever (tools/probes/leak_check_eager.py: +22 MiB reserved per 10-step epoch at B = 64, the allocated
-        # bytes flat)
-        copy_stream = self.__dict__.get("_copy_stream")
-        if copy_stream is None:
-            copy_stream = self._copy_stream = torch.cuda.Stream(device=self.device)
-        cache = self.__dict__.setdefault("_batch_cache", {})
-        n_cache = int(self.train_opts.get("data_cache", 0) or 0)
-        speed_out = self.__dict__.setdefault("_speed_out", {})       # data.speed_perturb: width of a staged cut -> samples of its crop
-
-        def stage(i):
-            """Batch i -> the device, copies on their own stream behind the running step.  ``train.data_cache: N``: the synthetic
-            source's first N batches are generated once (pinned) and walked cyclically -- a run that measures the trainer, not numpy."""
-            k = (self.current_epoch, i) if n_cache <= 0 else i % n_cache
-            hb = cache.get(k) if n_cache > 0 else None
-            if hb is None:
-                idx = rng.integers(0, len(self.trainset), bs)
-                T = int(ladder[int(rng.integers(0, len(ladder)))])
-                extra = ()
-                if self.train_from_waves:
-                    # the same crop as WAVEFORMS: frame_len + (T - 1) frame_step samples (T frames) cut from the zero-padded batch at
-                    # an offset that fits the shortest row -- a rectangular batch; the augmentation's choices are drawn beside it.
-                    # (feat_type stft: the loader cuts the same samples, datasets.py:113-115, and librosa.stft makes T + 2 frames of them)
-                    fl, fs = self._wave_fe.frame_len, self._wave_fe.frame_step
-                    Sb = fl + (T - 1) * fs
-                    # data.speed_perturb: the cut is as wide as the fastest speed needs to leave Sb samples (features() cuts there)
-                    Sc = Sb if self._speed is None else self._speed.in_samples(Sb)
-                    wl = self.trainset.wave_len(fl, fs)[idx]
-                    wav, _ = self.trainset.waves_padded(idx, S=max(int(wl.max()), Sc), frame_len=fl, frame_step=fs)
-                    s0 = int(rng.integers(0, max(int(wl.min()) - Sc, 0) + 1))
-                    xb = np.ascontiguousarray(wav[:, s0:s0 + Sc])
-                    if self._augment is not None:
-                        p = self._augment.draw([Sb] * bs, rng)
-                        extra = tuple(torch.from_numpy(p[n]).pin_memory() for n in ("snr_db", "noise_start", "rir_idx"))
-                    if self._speed is not None:         # drawn last: a run without the section keeps its random stream
-                        speed_out[Sc] = Sb
-                        extra += (torch.from_numpy(self._speed.draw(bs, rng)["speed_idx"]).pin_memory(),)
-                else:
-                    t0_ = int(rng.integers(0, Ta - T + 1))
-                    xb = np.ascontiguousarray(self.trainset.audio(idx)[:, :, t0_:t0_ + T])   # the batch's one crop (datasets.py:112-115)
-                if self._spec is not None:              # data.spec_augment, drawn last of all: a run without the section keeps its stream
-                    extra += (torch.from_numpy(self._spec.draw(bs, rng)["draws"]).pin_memory(),)
-                hb = (torch.from_numpy(xb).pin_memory(), torch.from_numpy(self.trainset.labels(idx)).pin_memory()) + extra
-                if n_cache > 0:
-                    cache[k] = hb
-            with torch.cuda.stream(copy_stream):
-                x, lab, *extra = (h.to(self.device, non_blocking=True) for h in hb)
-                ev = torch.cuda.Event()
-                ev.record(copy_stream)
-            return x, lab, ev, extra
-
-        def features(wave, extra):
-            """data.train_from_waves: speed perturbation and augmentation (when configured) and front-end, eager launches in front of
-            the step -- Kaldi's order: the row is resampled to exactly the crop's samples, then reverberated / mixed."""
-            with torch.no_grad():
-                if self._speed is not None:
-                    *extra, speed_idx = extra
-                    wave, _ = self._speed(wave, params={"speed_idx": speed_idx}, out_samples=speed_out[wave.shape[1]])
-                if self._augment is not None:
-                    wave = self._augment(wave, params=dict(zip(("snr_db", "noise_start", "rir_idx"), extra)))
-                if getattr(self.model, "sinc", None) is not None:      # arch: sincnet -- the layer runs inside the step, on the waveform itself
-                    return wave
-                return self._wave_fe(wave)
-
+            self._steps = tl.recorded_steps(self._one_step, mods, [self.optim], self.buckets, self.device, branch_streams=self.buckets is None)
+        meter = tl.EpochMeter(self.device)
         anneal = getattr(self.criterion, "anneal", None)
-        staged = stage(0) if steps > 0 else None
+        staged = self._prefetch.stage(self._ring.get(0, rng, ladder)) if steps > 0 else None
         torch.cuda.synchronize(self.device)
         t0 = time.perf_counter()
         for i in range(steps):
-            x, lab, ev, extra = staged
-            cur = torch.cuda.current_stream(self.device)
-            cur.wait_event(ev)
-            x.record_stream(cur); lab.record_stream(cur)
-            for t in extra:
-                t.record_stream(cur)
-            if self._spec is not None:
-                *extra, spec_draws = extra
+            b = self._prefetch.take(staged)
+            x, lab = b["x"], b["lab"]
             if self.train_from_waves:
-                x = features(x, extra)
+                x = self._features(b)
             if self._spec is not None:   # on the feature batch, directly in front of the step and outside the recorded graph
                 with torch.no_grad():
-                    x = self._spec(x, params={"draws": spec_draws})
+                    x = self._spec(x, params={"draws": b["draws"]})
             if anneal is not None:
                 anneal()                 # ASoftmax: lambda of this step, written on the device in front of the step, outside the recorded graph
             if recorded:
@@ -401,14 +361,12 @@ class Trainer(object):
                 loss, logits = self._steps.step(x, lab, key=float(getattr(self.criterion, "margin", 0.0)))
             else:
                 loss, logits = self._one_step(x, lab)
-            acc[0] += loss.detach().double() * x.shape[0]
             # (OnlineTriplet returns the number of triplets, a device scalar, where the classifiers return logits)
-            acc[1] += logits.detach().double() if self.triplet else (torch.max(logits.detach(), dim=1)[1] == lab).sum()
-            acc[2] += x.shape[0]
-            staged = stage(i + 1) if i + 1 < steps else None
+            meter.add(loss, logits.detach().double() if self.triplet else (torch.max(logits.detach(), dim=1)[1] == lab).sum(), x.shape[0])
+            staged = self._prefetch.stage(self._ring.get(i + 1, rng, ladder)) if i + 1 < steps else None      # copies behind this step
         if recorded:
             self._steps.finish()
-        tot, correct, n = acc.tolist()
+        tot, correct, n = meter.read()
         _lib.check_range(sync=True)                       # f16x3 packing: an overflow in this epoch is an error, not a NaN
         dt = time.perf_counter() - t0
         tot, correct, n = ddist.allreduce_metrics([tot, correct, n], self.device)

@@ -21,7 +21,7 @@ batch i + 1 behind the head's step on batch i) and the head's forward + backward
 (``train.graph_step``, ``--eager-step``); extraction keeps one RaggedExtractor per trainer (``test.batch``, ``test.frames: u8|f32``);
 ``--arith`` / ``model.arith`` pick the arithmetic (auto = the benchmarked f16x3, out-of-range batches computed again in f32).  The run
 plumbing (config + ``--set``, self-launch, run name, optimizer, ``main()``'s tail) and the speech input chain of the test lists (resampler,
-front-end, voiced frames, encoder, the kept extractor) are deeplip_amd/trainer_common.py's, shared with train_audio.py.
+front-end, voiced frames, encoder, the kept extractor) are deeplip_amd/trainer_common.py's, the pieces of the step loop deeplip_amd/train_loop.py's.
 
     python train_fusion.py --mode train            # single GPU
     python train_fusion.py --mode train --gpus 8   # starts its own 8-rank job (deeplip_amd/launch.py); so does a config
@@ -44,7 +44,7 @@ from torch.optim import lr_scheduler
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-from deeplip_amd import arith, dist as ddist, fusion, ops, scoring, trainer_common as tc  # noqa: E402
+from deeplip_amd import arith, dist as ddist, fusion, ops, scoring, train_loop as tl, trainer_common as tc  # noqa: E402
 from deeplip_amd.synthetic import SyntheticAVSet, synthetic_trials  # noqa: E402
 from models.audio_models.loss import LMCL, CrossEntropy  # noqa: E402
 from models.fusion_models import LBP, model_fusion  # noqa: E402
@@ -82,6 +82,7 @@ class Trainer(object):
         self._extractor = tc.ExtractorCache()   # one RaggedExtractor for every list / epoch of this trainer (keeps its recorded plans)
         self._host_cache = {} if self.test_opts.get("cache_host_batches", False) else None
         self._steps = self._enc_pipe = self.buckets = None
+        self._ring = tl.BatchRing(self._host_batch, self.train_opts.get("data_cache", 0))     # the training batches (train.data_cache)
         self.graph_step = bool(self.train_opts.get("graph_step", True)) and os.environ.get("DLIP_GRAPH_STEP", "1") != "0" and not dry
         if not dry:                 # the arithmetic of the engine (--arith > $DLIP_ARITH > model.arith > auto), before the first weight pack
             self.arith = arith.configure(arith_mode, self.model_opts.get("arith"))
@@ -194,6 +195,9 @@ class Trainer(object):
         if self.train_opts["optimizer"] != "sgd":
             raise NotImplementedError(self.train_opts["optimizer"])
         self.optim = tc.make_optimizer("sgd", param_groups, self.train_opts["sgd"], self.graph_step, self.device)
+        # the trainable part of a step (train_fusion.py:291-299): fusion head + criterion forward, backward, gradient all-reduce of the
+        # 3.4 MB head, SGD -- launches only, so that it can be recorded once and replayed (deeplip_amd.train_plan)
+        self._head_step = tl.optim_step(lambda a, v, labels: self.criterion(self._fuse(a, v), labels), self.optim, lambda: self.buckets)
         self.epoch = self.train_opts["epoch"]
         self.resume_audio = self.train_opts["audio_config"]["resume"]
         self.resume_video = self.train_opts["video_config"]["resume"]
@@ -257,32 +261,25 @@ class Trainer(object):
             return
         ddist.allreduce_grads([p for g in self.optim.param_groups for p in g["params"]], self.world)   # one bucket (3.4 MB)
 
-    def _head_step(self, xv_audio, em_video, labels):
-        """The trainable part of a step (train_fusion.py:291-299): fusion head + criterion forward, backward, gradient all-reduce of
-        the 3.4 MB head, SGD -- launches only, so that it can be recorded once and replayed (deeplip_amd.train_plan)."""
-        if self.buckets is None:
-            self.optim.zero_grad(set_to_none=True)
-        else:
-            self.buckets.zero()
-        output = self._fuse(xv_audio, em_video)
-        loss, logits = self.criterion(output, labels)
-        loss.backward()
-        if self.buckets is not None:
-            self.buckets.finish()
-        self.optim.step()
-        return loss, logits
-
     def _train_epoch(self):
         if self.dry or not self.graph_step:
             return self._train_epoch_eager()
         return self._train_epoch_recorded()
 
+    def _host_batch(self, k, glob):
+        """This rank's rows of ``glob`` (what every rank drew) as a pinned host batch (audio, clips, clip-group pointers, labels)."""
+        from deeplip_amd.pipeline import pin
+        bs = self.train_opts["bs"]
+        idx = glob[self.rank * bs:(self.rank + 1) * bs]
+        clips, ptr = self.trainset.video(idx)
+        return (pin(torch.from_numpy(self.trainset.audio(idx))), pin(torch.from_numpy(clips)), pin(torch.from_numpy(ptr)),
+                pin(torch.from_numpy(self.trainset.labels(idx))))
+
     def _train_epoch_recorded(self):
         """_train_epoch (train_fusion.py:241-315) as two replayed pieces per step: the frozen encoders' plan (deeplip_amd.pipeline:
         the batch's host-to-device copies and the encoders run BEHIND the previous step's head; a batch that leaves the f16x3 range is
         computed again in f32 under arith auto) and the head's recorded step (forward + backward + all-reduce + SGD, one HIP graph)."""
-        from deeplip_amd.pipeline import ExtractPipeline, pin
-        from deeplip_amd.train_plan import ShapeKeyedSteps, grad_witness, step_state
+        from deeplip_amd.pipeline import ExtractPipeline
         self.model_fusion.train()
         self.model_audio.eval()
         self.model_video.eval()
@@ -294,24 +291,12 @@ class Trainer(object):
         if ddist.active() and self.buckets is None:
             self.buckets = ddist.GradBuckets([p for g in self.optim.param_groups for p in g["params"]])     # one 3.4 MB bucket
         if self._steps is None:
-            self._steps = ShapeKeyedSteps(self._head_step, eager_steps=1, device=self.device, branch_streams=False,
-                                          state=step_state(heads, [self.optim], self.buckets), witness=grad_witness(heads, self.buckets))
-        cache = self.__dict__.setdefault("_batch_cache", {})
-        n_cache = int(self.train_opts.get("data_cache", 0) or 0)
+            self._steps = tl.recorded_steps(self._head_step, heads, [self.optim], self.buckets, self.device, branch_streams=False)
 
         def host_batch(it):
-            # speaker-balanced sampling as the reference's sampler (datasets.py:161-164): idx % n_spk
-            glob = rng.integers(0, len(self.trainset), bs * self.world)
-            k = it % n_cache if n_cache > 0 else None
-            if k is not None and k in cache:
-                return cache[k]
-            idx = glob[self.rank * bs:(self.rank + 1) * bs]
-            clips, ptr = self.trainset.video(idx)
-            hb = (pin(torch.from_numpy(self.trainset.audio(idx))), pin(torch.from_numpy(clips)), pin(torch.from_numpy(ptr)),
-                  pin(torch.from_numpy(self.trainset.labels(idx))))
-            if k is not None:
-                cache[k] = hb
-            return hb
+            # speaker-balanced sampling as the reference's sampler (datasets.py:161-164): idx % n_spk.  Drawn on every call: a batch
+            # that comes from the ring still advances the epoch's stream
+            return self._ring.get(it, rng.integers(0, len(self.trainset), bs * self.world))
 
         def encoders(audio, clips, ptr, labels):
             xv_audio, _ = self.model_audio.extract_embedding(audio)                      # train_fusion.py:262
@@ -330,7 +315,7 @@ class Trainer(object):
         DEPTH = pipe.depth                                   # batches in flight: one in the encoders, one in its copies
         slots = [(torch.empty((bs, D), device=self.device), torch.empty((bs, D), device=self.device),
                   torch.empty((bs,), dtype=torch.int64, device=self.device)) for _ in range(DEPTH)]
-        acc = torch.zeros(3, dtype=torch.float64, device=self.device)
+        meter = tl.EpochMeter(self.device)
         torch.cuda.synchronize(self.device)
         t0 = time.perf_counter()
         cur = torch.cuda.current_stream(self.device)
@@ -341,9 +326,7 @@ class Trainer(object):
             pipe.wait_next()                                 # batch `it` is through the encoders (and inside the arithmetic's range)
             xv_audio, em_video, labels = slots[it % DEPTH]
             loss, logits = self._steps.step(xv_audio, em_video, labels, key=float(getattr(self.criterion, "margin", 0.0)))
-            acc[0] += loss.detach().double() * bs
-            acc[1] += (torch.max(logits.detach(), dim=1)[1] == labels).sum()
-            acc[2] += bs
+            meter.add(loss, (torch.max(logits.detach(), dim=1)[1] == labels).sum(), bs)
             if it + DEPTH < steps:
                 # batch it + DEPTH takes the input set and the slot batch `it` just left: its copies start now, behind the encoders'
                 # work on batch it + 1; the slot is rewritten only after the head's step above has read it (ordered on `cur`)
@@ -352,9 +335,9 @@ class Trainer(object):
                     pipe.submit(host_batch(it + DEPTH), slots[it % DEPTH], 0)
         pipe.finish()
         self._steps.finish()
-        sum_loss, correct, sum_samples = acc.tolist()
+        sums = meter.read()
         dt = time.perf_counter() - t0
-        tot = ddist.allreduce_metrics([sum_loss, correct, sum_samples], self.device)
+        tot = ddist.allreduce_metrics(sums, self.device)
         self.last_epoch_stats = {"loss": tot[0] / tot[2], "acc": tot[1] / tot[2], "pairs_per_s": tot[2] / dt, "steps": steps,
                                  "step_mode": self._steps.mode, "ms_per_step": 1e3 * dt / max(steps, 1)}
         if self.rank == 0:

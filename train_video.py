@@ -39,7 +39,7 @@ import torch
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-from deeplip_amd import weightgen as wg  # noqa: E402
+from deeplip_amd import ops, train_loop as tl, weightgen as wg  # noqa: E402
 from models.video_models.model import Lipreading  # noqa: E402
 
 SEED = 1
@@ -176,12 +176,10 @@ def extract_feats(model, clip_thw, device):
     return y
 
 
-def train(model, args, device):
-    from deeplip_amd import autograd as ag, dist as ddist, ops
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
+def build_step(model, args, device, full):
+    """-> (Adam over what trains, one optimisation step ``step(x, *targets, lengths)``, its recorded form or None for the eager loop)."""
+    from deeplip_amd import autograd as ag, dist as ddist, trainer_common as tc
     head = model.tcn.tcn_output
-    full = not args.head_only and device.type != "cpu"
     if not full:
         for p in model.parameters():
             p.requires_grad = False
@@ -190,191 +188,150 @@ def train(model, args, device):
     params = [p for p in model.parameters() if p.requires_grad]
     # DP: gradients live in flat buckets whose all-reduces (RCCL) start while backward is still running
     buckets = ddist.GradBuckets(params) if (ddist.active() and device.type != "cpu") else None
-    # (with GradBuckets the recorded step contains the bucket all-reduces -- RCCL collectives captured into the graph: exercised at one
-    # rank by tests/test_rccl_gpu.py; DLIP_GRAPH_WITH_BUCKETS=0 keeps data-parallel runs on the eager loop)
-    graph_step = not bool(getattr(args, "eager_step", False)) and full and (buckets is None or os.environ.get("DLIP_GRAPH_WITH_BUCKETS", "1") != "0")
-    if graph_step:      # a recorded step reads its learning rate from a device tensor (the scheduler updates it in place)
-        optimizer = torch.optim.Adam(params, lr=torch.tensor(float(args.lr), device=device), weight_decay=1e-4, capturable=True, fused=True)
-    else:
-        optimizer = torch.optim.Adam(params, lr=args.lr, weight_decay=1e-4)                  # (:112-113)
-    sched = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max=5, eta_min=4e-08)      # (:114)
-    last = None
-    aug_rng = random.Random(SEED + rank)      # the train pipeline's crop / flip draws (the reference: the `random` module, preprocess.py)
-    frontend = None
-    aug = aug_np = None
-    if full and getattr(args, "clip_augment", None):
+    recorded = not bool(getattr(args, "eager_step", False)) and full and tl.records_with(buckets)
+    optimizer = tc.make_optimizer("adam", params, {"init_lr": args.lr, "weight_decay": 1e-4}, recorded, device)      # (:112-113)
+
+    def forward_loss(x, *targets):      # targets: labels -- mixup: labels_a, labels_b, lam (read on the device by every replay) -- then lengths
+        *targets, lengths = targets
+        if full:
+            logits = model(x, lengths=lengths)                      # (:140) whole graph on the engine
+        else:
+            with torch.no_grad():
+                pooled = model.classifier_features(x, lengths)      # frozen stem + trunk + MS-TCN
+            logits = ag.linear(pooled, head.weight, head.bias)      # tcn_output (model.py:27)
+        loss = mixed_ce_loss(logits, *targets) if len(targets) == 3 else ag.margin_ce_loss(logits, targets[0], 1.0, 0.0)      # (:115,143)
+        return loss, logits
+
+    step = tl.optim_step(forward_loss, optimizer, lambda: buckets)
+    plan = tl.recorded_steps(step, [model], [optimizer], buckets, device, branch_streams=buckets is None) if recorded else None
+    return optimizer, step, plan
+
+
+class _Batches:
+    """The synthetic loader behind train() (``--data-cache N``: its first N batches generated once, pinned, walked cyclically) and its
+    batches' way to the step: ``stage(i)`` starts batch i's copies behind the running step, ``take`` forms the clip the model takes."""
+
+    def __init__(self, args, world, rank, device, full):
         from deeplip_amd.clip_augment import ClipAugment
-        aug = ClipAugment(**args.clip_augment)     # replaces the VideoFrontend call under --rgb, acts on the float clip otherwise
-        aug_np = np.random.default_rng(SEED + rank)
-    if device.type == "cpu" and rank == 0:
-        print("[plumbing] --device cpu exercises config / collate / optimizer / scheduler / checkpoint plumbing ONLY (BASELINE config C1): the "
-              "engine has no CPU arithmetic path by design, so no forward runs and no loss or logits exist here; the same command on "
-              "--device gpu computes them (C1-size run: tests/test_entrypoints.py::test_train_video_gpu_two_steps[c1-size]).")
-    plan = None
-    if graph_step:
-        from deeplip_amd.train_plan import ShapeKeyedSteps, grad_witness, step_state
+        self.args, self.world, self.rank, self.full, self.rgb = args, world, rank, full, args.rgb
+        self.ring, self.prefetch, self.frontend = tl.BatchRing(self.make, getattr(args, "data_cache", 0)), tl.Prefetch(device), None
+        self.pin = self.ring.n > 0 and device.type != "cpu"
+        self.aug = ClipAugment(**args.clip_augment) if full and getattr(args, "clip_augment", None) else None
+        self.crop_rng = random.Random(SEED + rank)     # the train pipeline's crop / flip draws (the reference: the `random` module, preprocess.py)
+        self.aug_rng = np.random.default_rng(SEED + rank)
 
-        def one_step(xb, lb, ln, mix=None):
-            if buckets is None:
-                optimizer.zero_grad(set_to_none=True)
-            else:
-                buckets.zero()                       # the gradients are views into the buckets: cleared in place
-            lg = model(xb, lengths=ln)
-            ls = mixed_ce_loss(lg, lb, *mix) if mix is not None else ag.margin_ce_loss(lg, lb, 1.0, 0.0)
-            ls.backward()                            # bucket all-reduces start from the hooks as the gradients land
-            if buckets is not None:
-                buckets.finish()
-            optimizer.step()
-            return ls, lg
+    def make(self, k):      # (inputs, lengths, labels) as pad_packed_collate hands them over (dataset.py:123-139)
+        b = synthetic_batch(self.args, k * self.world + self.rank, self.rgb)        # (the module's global as it is now: a test swaps it)
+        return (b[0].pin_memory(), b[1], b[2]) if self.pin else b
 
-        def one_step_mix(xb, la, lb, lam, ln):       # mixup: the mixed criterion, lam read from its device tensor on every replay
-            return one_step(xb, la, ln, mix=(lb, lam))
+    def stage(self, i):
+        inputs, lengths, labels = self.ring.get(i)
+        host = {"raw": inputs, "lab": labels, "ln": torch.as_tensor(lengths, dtype=torch.int32), "lengths": lengths}
+        if self.rgb and self.full:
+            host["cp"] = torch.from_numpy(ops.draw_clip_params(inputs.shape[0], inputs.shape[-2], inputs.shape[-1], 88, rng=self.crop_rng))
+        if self.aug is not None:            # its draws travel under their own names: draws, and perm and lam under mixup
+            host.update((k, torch.from_numpy(v)) for k, v in self.aug.draw(inputs.shape[0], self.aug_rng).items())
+        return self.prefetch.stage(host)
 
-        # One recorded step per batch shape (pad_packed_collate pads to the batch's longest clip, dataset.py:123-139: a run meets a
-        # few shapes); a shape's first step runs eagerly, its second records.  In a job of several ranks the first replay is
-        # checked against an eager step from the same state and the run falls back to eager steps on any doubt (train_plan.py).
-        # (with GradBuckets the branches stay on one stream: a bucket's all-reduce is enqueued behind the CURRENT stream of the hook
-        # that completes it, and would not wait for gradients another branch stream is still writing)
-        plan = ShapeKeyedSteps(one_step_mix if aug is not None and aug.mixup else one_step, eager_steps=1, device=device, branch_streams=buckets is None,
-                               state=step_state([model], [optimizer], buckets), witness=grad_witness([model], buckets))
-    source = _BatchSource(args, world, rank, device)
-    copy_stream = torch.cuda.Stream(device=device) if device.type != "cpu" else None
+    def take(self, staged):
+        """-> (x [B,1,T,88,88], the targets: (labels,) or mixup's (labels_a, labels_b, lam), lengths on the device, on the host)."""
+        b = self.prefetch.take(staged)
+        raw, ln, targets = b["raw"], b["ln"], (b["lab"],)
+        if self.aug is not None:
+            # time masks, cutout and mixup from the loader's frames (under --rgb with the crop and flip drawn in stage), one stage
+            ap = {k: b[k] for k in ("draws", "perm", "lam") if k in b}
+            x = self.aug(raw, clip_params=b["cp"], lengths=ln, params=ap) if self.rgb else self.aug(raw.unsqueeze(1), lengths=ln, params=ap)
+            if self.aug.mixup:
+                targets = self.aug.mix_targets(b["lab"], ap)
+        elif self.rgb:
+            # uint8 frames -> normalised 88 x 88 gray clips on the GPU: RandomCrop + HorizontalFlip per clip while the model
+            # trains (dataloaders.py:13-17), CenterCrop otherwise (:19-24); padding frames = zeros of the normalised clip
+            from deeplip_amd.frontend import VideoFrontend
+            self.frontend = self.frontend or VideoFrontend(88)
+            x = self.frontend(raw, clip_params=b.get("cp"), lengths=ln)
+        else:
+            x = raw.unsqueeze(1)                                                                    # :125
+        return x, targets, ln, b["lengths"]
 
-    def stage(i):
-        """Batch i on the device: host batch (generated, or from the --data-cache ring) -> asynchronous copies on the copy stream,
-        behind the step that is running.  The reference's loop does `.cuda()` in front of every forward (train_video.py:125)."""
-        nonlocal frontend
-        inputs, lengths, labels = source.get(i)
-        cur = torch.cuda.current_stream(device)
-        with torch.cuda.stream(copy_stream):
-            lab = labels.to(device, non_blocking=True)
-            ln = torch.as_tensor(lengths, dtype=torch.int32).to(device, non_blocking=True)
-            raw = inputs.to(device, non_blocking=True)
-            cp = None
-            if args.rgb and full:
-                cp = torch.from_numpy(ops.draw_clip_params(inputs.shape[0], inputs.shape[-2], inputs.shape[-1], 88, rng=aug_rng)).to(device, non_blocking=True)
-            ap = aug.to_device(aug.draw(inputs.shape[0], aug_np), device) if aug is not None else None
-            ev = torch.cuda.Event()
-            ev.record(copy_stream)
-        return raw, lab, ln, cp, lengths, ev, ap
 
-    total_steps = int(args.maxepoch) * args.steps
-    staged = stage(0) if device.type != "cpu" and total_steps > 0 else None
-    acc = torch.zeros(3, dtype=torch.float64, device=device) if device.type != "cpu" else None      # sum loss*n, correct, n: read at display time only
-    last_loss = last_shape = None
-    # throughput of the loop as it runs: counted from the 4th step on (a shape's first step is eager, its second records and replays)
+def run_epochs(model, args, device, rank, full, batches, optimizer, step, plan, sched):
+    """The loop of train() -> ((last loss, logits shape) or None, (steps timed, their seconds) or None): metrics on the device between
+    ``--display`` points, throughput counted from the 4th step on (a shape's first step is eager, its second records)."""
     import time
+    gpu = device.type != "cpu"
+    total_steps = int(args.maxepoch) * args.steps
+    staged = batches.stage(0) if gpu and total_steps > 0 else None
+    last_loss = last_shape = None
     mark_at, t_mark, t_end = min(3, max(total_steps - 1, 0)), None, None
     for epoch in range(int(args.maxepoch)):
-        if acc is not None:
-            acc.zero_()
+        meter = tl.EpochMeter(device)
         model.train() if full else model.eval()                                                # (:129)
         for it in range(args.steps):
             gi = epoch * args.steps + it
-            if device.type == "cpu":
-                inputs, lengths, labels = source.get(gi)
-                print(f"[plumbing] batch {tuple(inputs.shape)} lengths {lengths} labels {labels.tolist()} lr {sched.get_last_lr()}")
+            if not gpu:     # plumbing: the batch as the collate hands it over (the prefetch passes it through), no forward
+                b = batches.prefetch.take(batches.stage(gi))
+                print(f"[plumbing] batch {tuple(b['raw'].shape)} lengths {b['lengths']} labels {b['lab'].tolist()} lr {sched.get_last_lr()}")
                 optimizer.step(); sched.step()
                 continue
             if gi == mark_at:
                 torch.cuda.synchronize(device)
                 t_mark = time.perf_counter()
-            raw, labels, ln, cp, lengths, ev, ap = staged
-            cur = torch.cuda.current_stream(device)
-            cur.wait_event(ev)
-            for t in (raw, labels, ln, cp) + tuple((ap or {}).values()):
-                if t is not None:
-                    t.record_stream(cur)
-            mix = None
-            if aug is not None:
-                # time masks, cutout and mixup from the loader's frames (under --rgb with the crop and flip drawn above), one stage
-                x = aug(raw, clip_params=cp, lengths=ln, params=ap) if args.rgb else aug(raw.unsqueeze(1), lengths=ln, params=ap)
-                if aug.mixup:
-                    mix = aug.mix_targets(labels, ap)
-            elif args.rgb:
-                # uint8 frames -> normalised 88 x 88 gray clips on the GPU: RandomCrop + HorizontalFlip per clip while the model
-                # trains (dataloaders.py:13-17), CenterCrop otherwise (:19-24); padding frames = zeros of the normalised clip
-                from deeplip_amd.frontend import VideoFrontend
-                frontend = frontend or VideoFrontend(88)
-                x = frontend(raw, clip_params=cp, lengths=ln)
-            else:
-                x = raw.unsqueeze(1)                                                                    # :125
+            x, targets, ln, lengths = batches.take(staged)
             if plan is not None:
-                loss, logits = plan.step(x.contiguous(), *mix, ln) if mix is not None else plan.step(x.contiguous(), labels, ln)
+                loss, logits = plan.step(x.contiguous(), *targets, ln)
             else:
-                optimizer.zero_grad(set_to_none=buckets is None)
-                if full:
-                    logits = model(x, lengths=lengths)                          # (:140) whole graph on the engine
-                else:
-                    with torch.no_grad():
-                        pooled = model.classifier_features(x, lengths)         # frozen stem + trunk + MS-TCN
-                    logits = ag.linear(pooled, head.weight, head.bias)          # tcn_output (model.py:27)
-                loss = mixed_ce_loss(logits, *mix) if mix is not None else ag.margin_ce_loss(logits, labels, 1.0, 0.0)   # nn.CrossEntropyLoss (:115,143)
-                loss.backward()
-                if buckets is not None:
-                    buckets.finish()                                            # wait for the bucket all-reduces, average
-                optimizer.step()
+                loss, logits = step(x, *targets, lengths)
             sched.step()                                                        # per-iteration (:147)
-            # metrics stay on the device (a recorded step's outputs are rewritten by the next replay: folded in right behind it)
-            n_b = labels.shape[0]
             _, pred = torch.max(torch.softmax(logits.detach(), 1), 1)           # (:145)
-            acc[0] += loss.detach().double() * n_b
-            if mix is None:
-                acc[1] += (pred == labels).sum()
-            else:           # the mixed criterion's accuracy: lam (pred == a) + (1 - lam) (pred == b)
-                acc[1] += mix[2][0].double() * (pred == mix[0]).sum() + (1.0 - mix[2][0].double()) * (pred == mix[1]).sum()
-            acc[2] += n_b
+            hits = (pred == targets[0]).sum()
+            if len(targets) == 3:       # the mixed criterion's accuracy: lam (pred == a) + (1 - lam) (pred == b)
+                lam = targets[2][0].double()
+                hits = lam * hits + (1.0 - lam) * (pred == targets[1]).sum()
+            meter.add(loss, hits, targets[0].shape[0])
             last_loss, last_shape = loss.detach().clone(), tuple(logits.shape)
-            staged = stage(gi + 1) if gi + 1 < total_steps else None            # the next batch's copies run behind this step
+            staged = batches.stage(gi + 1) if gi + 1 < total_steps else None    # the next batch's copies run behind this step
             if it % args.display == 0 or it + 1 == args.steps:
                 if plan is not None:
                     plan.finish()                                               # waits; a range report of the f16x3 arithmetic surfaces here
-                a0, a1, a2 = acc.tolist()
+                a0, a1, a2 = meter.read()
                 if rank == 0 and it % args.display == 0:
                     print(f"epoch {epoch} it {it} loss {a0 / a2:.4f} acc {a1 / a2:.3f} lr {float(sched.get_last_lr()[0]):.2e}"
                           f"{' (replayed)' if plan is not None and plan.last.recorded else ''}", flush=True)
-        if device.type != "cpu" and epoch + 1 == int(args.maxepoch):
+        if gpu and epoch + 1 == int(args.maxepoch):
             torch.cuda.synchronize(device)
             t_end = time.perf_counter()                                                        # (the checkpoint below is not a step)
         if rank == 0:
             os.makedirs(args.save_path, exist_ok=True)
             torch.save(model.state_dict(), os.path.join(args.save_path, f"{epoch + 1}.pt"))  # (:169)
     last = (float(last_loss), last_shape) if last_loss is not None else None
-    train.last_stats = None
-    if t_mark is not None and total_steps > mark_at and t_end is not None:
-        dt = t_end - t_mark
-        n = (total_steps - mark_at) * args.batch_size * world
-        train.last_stats = {"clips_per_s": n / dt, "ms_per_step": 1e3 * dt / (total_steps - mark_at), "steps_timed": total_steps - mark_at,
+    timed = (total_steps - mark_at, t_end - t_mark) if t_mark is not None and t_end is not None and total_steps > mark_at else None
+    return last, timed
+
+
+def train(model, args, device):
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank = int(os.environ.get("RANK", "0"))
+    full = not args.head_only and device.type != "cpu"
+    batches = _Batches(args, world, rank, device, full)
+    optimizer, step, plan = build_step(model, args, device, full)
+    sched = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max=5, eta_min=4e-08)      # (:114)
+    train.last_stats, train.last_plan = None, plan
+    if device.type == "cpu" and rank == 0:
+        print("[plumbing] --device cpu exercises config / collate / optimizer / scheduler / checkpoint plumbing ONLY (BASELINE config C1): the "
+              "engine has no CPU arithmetic path by design, so no forward runs and no loss or logits exist here; the same command on "
+              "--device gpu computes them (C1-size run: tests/test_entrypoints.py::test_train_video_gpu_two_steps[c1-size]).")
+    last, timed = run_epochs(model, args, device, rank, full, batches, optimizer, step, plan, sched)
+    if timed is not None:
+        steps, dt = timed
+        train.last_stats = {"clips_per_s": steps * args.batch_size * world / dt, "ms_per_step": 1e3 * dt / steps, "steps_timed": steps,
                             "step_mode": plan.mode if plan is not None else "eager", "global_batch": args.batch_size * world}
         if rank == 0:
             print("train: {:.1f} clips/s, {:.2f} ms/step over the last {} steps [{}]".format(
-                train.last_stats["clips_per_s"], train.last_stats["ms_per_step"], total_steps - mark_at, train.last_stats["step_mode"]), flush=True)
+                train.last_stats["clips_per_s"], train.last_stats["ms_per_step"], steps, train.last_stats["step_mode"]), flush=True)
     if rank == 0 and device.type != "cpu":
         how = ("recorded steps: " + str(plan.summary())) if plan is not None else "eager steps"
         print(f"train: {how}", flush=True)
-    train.last_plan = plan
     return last
-
-
-class _BatchSource:
-    """The synthetic loader behind train(): ``get(i)`` -> (inputs, lengths, labels) of iteration i as pad_packed_collate hands them
-    over (dataset.py:123-139).  ``--data-cache N``: the first N batches are generated once, pinned, and walked cyclically."""
-
-    def __init__(self, args, world, rank, device):
-        self.args, self.world, self.rank = args, world, rank
-        self.n = int(getattr(args, "data_cache", 0) or 0)
-        self.cache = {}
-        self.pin = device.type != "cpu"
-
-    def get(self, i):
-        k = i % self.n if self.n > 0 else i
-        if k in self.cache:
-            return self.cache[k]
-        b = synthetic_batch(self.args, k * self.world + self.rank, self.args.rgb)
-        if self.n > 0:
-            b = (b[0].pin_memory() if self.pin else b[0], b[1], b[2])
-            self.cache[k] = b
-        return b
 
 
 def main(argv=None):
